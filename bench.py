@@ -157,7 +157,39 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-soup", action="store_true", help="skip the second figure (config 4's incoherent triangle-soup variant)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end figures (frame into a caller's host buffer, through the plugin's render())")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the image the last timed step "
+                    "computed (rank 0's whole frame) as DIR/<name>.npy, at most 64 MB in all: see dump_outputs")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21      # 24 MB of float32 pixels + 16 MB of float64 indices
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(out_dir, image):
+    """--dump-outputs: the frame a caller of the timed path receives (H x W x D float32, row-major), as .npy files that two builds
+    run with the same arguments can compare array for array.  A frame of at most 48 MB is written whole (image.npy); a larger one
+    as a fixed, seeded sample of whole pixels (image_sample.npy, their row-major pixel indices in image_sample_index.npy) beside
+    float64 sums of every row and every column (image_row_sums.npy, image_col_sums.npy), so that no pixel goes unchecked."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    H, W, D = image.shape
+    if image.nbytes <= 48 << 20:
+        arrays = {"image": image}
+    else:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        idx = np.sort(rng.choice(H * W, size=min(DUMP_SAMPLE_PIXELS, H * W), replace=False))
+        arrays = {"image_sample": image.reshape(H * W, D)[idx],
+                  "image_sample_index": idx.astype(np.float64),
+                  "image_row_sums": image.sum(axis=1, dtype=np.float64),
+                  "image_col_sums": image.sum(axis=0, dtype=np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def build_scene(args):
@@ -374,6 +406,13 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, kernel_s = [float(x) for x in t.tolist()]
+    # what the timed path computed in its last step, read before any later step reuses that slot's buffers (outside the timed region)
+    last_image = None
+    if args.dump_outputs and rank == 0:
+        last = slots[(args.steps - 1) % len(slots)]
+        img = last.image if world > 1 else last.mine
+        assert img.numel() == H * W * D, (img.numel(), H, W, D)
+        last_image = img.view(H, W, D).cpu().numpy()
     if pipelined_choice:
         os.environ.pop("LT_SHADOW_PACKETS", None)     # (what follows runs one step at a time again: the library's own verdict)
 
@@ -463,6 +502,8 @@ def main():
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, scene, program)
         print(json.dumps(out), flush=True)
+        if last_image is not None:
+            dump_outputs(args.dump_outputs, last_image)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

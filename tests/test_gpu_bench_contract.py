@@ -51,11 +51,38 @@ def test_single_gpu_line_has_the_contract_keys():
     assert px <= d["config"]["rays_per_frame"] <= 2 * px
 
 
-def test_two_ranks_on_one_gpu_through_gloo_count_the_same_rays():
-    one = run([sys.executable, "bench.py", "--gpus", "1", "--no-cpu-baseline"] + SMALL)
+def test_dump_outputs_is_the_frame_the_timed_path_computed(tmp_path):
+    """--dump-outputs DIR: the last timed step's frame (small enough to go whole) equals the same frame rendered through the
+    plugin's render() into a host buffer."""
+    import numpy as np
+    from lens_trace_amd import synth
+    from lens_trace_amd.renderer import RendererHIP, RenderPropertiesHIP
+    d = run([sys.executable, "bench.py", "--gpus", "1", "--no-cpu-baseline", "--no-soup", "--no-e2e",
+             "--dump-outputs", str(tmp_path)] + SMALL)
+    assert d["steps"] == 2
+    assert sorted(os.listdir(tmp_path)) == ["image.npy"]
+    got = np.load(tmp_path / "image.npy")
+    assert got.shape == (360, 640, 3) and got.dtype == np.float32
+    scene = synth.heightfield_wall(64).validate()
+    want = np.empty((360, 640, 3), dtype=np.float32)
+    r = RendererHIP(0)
+    try:
+        r.render(RenderPropertiesHIP("accumulator.cl", (640, 360, 3), want, scene, pCamera=scene.camera, frameFirst=1, frameCount=4,
+                                     accumulate=True))
+    finally:
+        r.close()
+    assert np.isfinite(got).all() and got.max() > 0
+    assert np.array_equal(got, want), "%d of %d floats differ" % (int((got != want).sum()), got.size)
+
+
+def test_two_ranks_on_one_gpu_through_gloo_count_the_same_rays(tmp_path):
+    one = run([sys.executable, "bench.py", "--gpus", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "one")] + SMALL)
     two = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-               "--master-port", "29541", "bench.py", "--gpus", "2", "--no-cpu-baseline"] + SMALL,
+               "--master-port", "29541", "bench.py", "--gpus", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "two")] + SMALL,
               env={"LT_BENCH_BACKEND": "gloo", "LT_BENCH_SINGLE_DEVICE": "1"})
+    # the tiles gathered and untiled at the root make the same frame as one rank
+    import numpy as np
+    assert np.array_equal(np.load(tmp_path / "one" / "image.npy"), np.load(tmp_path / "two" / "image.npy"))
     assert two["n_gpus"] == 2 and two["scaling"] == "strong"
     # two steps in flight: the period of finished frames and one frame's own latency are two numbers
     assert two["config"]["steps_in_flight"] == 2 and two["config"]["frame_latency_ms"] > 0 and two["config"]["kernel_only_mrays_per_s"] is None

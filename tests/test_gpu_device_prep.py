@@ -8,6 +8,8 @@ byte for byte -- the own tree node for node, the table, every 64-byte record of 
 random triangle sets, degenerate ones (coincident centroids, coincident triangles), both split rules (LT_RETREE=0 / 1) and a
 height limit with no slack, where the median rule takes over from the planes.  Buffers the device path declines (a leaf shared
 by two parents, a box outside its parent's, unreachable nodes, an index out of range) come out as they always did."""
+import os
+
 import numpy as np
 import pytest
 
@@ -15,7 +17,7 @@ from lens_trace_amd import _capi as C
 from lens_trace_amd import scene as sc
 from lens_trace_amd import synth
 from lens_trace_amd.renderer import RendererHIP
-from tests.conftest import oracle_props as RenderPropertiesHIP
+from tests.conftest import GOLDEN, oracle_props as RenderPropertiesHIP
 
 pytestmark = pytest.mark.gpu
 
@@ -72,7 +74,7 @@ SCENES = {
     "blob": lambda: synth.blob_in_box(5),
     "colonnade": lambda: synth.colonnade(6, 32, 12),
     "mixed": lambda: synth.wall_and_soup(60, 9000),
-    "cornell": lambda: sc.load_ltsb("tests/golden/cornell_box_O0.ltsb"),
+    "cornell": lambda: sc.load_ltsb(os.path.join(GOLDEN, "cornell_box_O0.ltsb")),
 }
 
 
