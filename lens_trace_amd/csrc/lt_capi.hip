@@ -216,6 +216,10 @@ struct ScenePool {
     spare.clear();
     spareBytes = 0;
   }
+  hipError_t upload(void** p, const void* src, size_t bytes) {   // (a buffer from the pool holding a copy of host memory)
+    const hipError_t e = get(p, bytes);
+    return e == hipSuccess ? hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice) : e;
+  }
   static hipError_t get_cb(void* self, void** p, size_t bytes) { return ((ScenePool*)self)->get(p, bytes); }
   static void put_cb(void* self, void* p) { ((ScenePool*)self)->put(p); }
 };
@@ -255,6 +259,7 @@ struct lt_hip_context {
   bool fold_pieced = false;
   hipStream_t copy_stream = nullptr; //     the pieces travel on a stream of their own, each behind its fold
   unsigned long long* d_stats = nullptr;
+  uint32_t* d_prep_flag = nullptr;   // scene preparation's flag word: the slot behind d_stats, which no render launch writes
   uint32_t* d_queues = nullptr;      // persistent mode: 8 per-XCD work counters per launch of a call
   uint32_t queue_frames = 0;
   int shadow_mode[6] = {-1, -1, -1, -1, -1, -1};   // per built-in program: shadow rays as any-hit packets (1) or per lane (0); -1 = not timed yet
@@ -331,7 +336,8 @@ extern "C" int lt_hip_create(int device_index, lt_hip_context** out_ctx) {
   if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
   if ((e = hipEventCreate(&ctx->ev0)) != hipSuccess) return bail("hipEventCreate", e);
   if ((e = hipEventCreate(&ctx->ev1)) != hipSuccess) return bail("hipEventCreate", e);
-  if ((e = hipMalloc((void**)&ctx->d_stats, 8 * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
+  if ((e = hipMalloc((void**)&ctx->d_stats, 9 * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
+  ctx->d_prep_flag = (uint32_t*)(ctx->d_stats + 8);
   {   // float32 denormals must be kept (lt_denormal_probe_kernel)
     const uint32_t in[2] = {1u, 0u};
     uint32_t out[2] = {0u, 0u};
@@ -361,6 +367,8 @@ static void free_scene(lt_hip_context* ctx) {
   }
   ctx->has_scene = false;
   ctx->device_prepared = false;
+  ctx->height2 = 0;
+  ctx->retree_ms = 0.0f;
 }
 
 extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
@@ -509,6 +517,29 @@ extern "C" int lt_hip_resolve_program(lt_hip_context* ctx, const char* path, int
   return compile_user_program(ctx, p, out_program);
 }
 
+// The checks of the primitives' materials and of the light list (validate_scene, the edit path, the device path's pre-check): the
+// error text, or nullptr.
+static const char kTooManyLights[] = "more than 64 emissive triangles";
+static const char* check_material_indices(const uint8_t* prims, uint32_t n_prims, uint32_t n_mats) {
+  for (uint32_t i = 0; i < n_prims; i++) {
+    int32_t m;
+    memcpy(&m, prims + 76 * (size_t)i + 72, 4);
+    if (m < 0 || (uint32_t)m >= n_mats) return "materialIndex out of range";
+  }
+  return nullptr;
+}
+static const char* check_lights(const uint8_t* lights, uint32_t n_prims) {
+  uint32_t lc;
+  memcpy(&lc, lights, 4);
+  if (lc > 64) return kTooManyLights;
+  for (uint32_t i = 0; i < lc; i++) {
+    uint32_t p;
+    memcpy(&p, lights + 4 + 4 * i, 4);
+    if (p >= n_prims) return "light primitive out of range";
+  }
+  return nullptr;
+}
+
 // Host-side validation: nothing with an out-of-range index or a cycle may reach a kernel.
 // Returns the BVH height (max number of interior ancestors of a node) or -1 with msg set.
 static int validate_scene(const uint8_t* nodes, uint32_t n_nodes, const uint8_t* prims, uint32_t n_prims, uint32_t n_mats,
@@ -525,19 +556,9 @@ static int validate_scene(const uint8_t* nodes, uint32_t n_nodes, const uint8_t*
       if (nd[i].axis > 2) { msg = "split axis out of range"; return -1; }
     }
   }
-  for (uint32_t i = 0; i < n_prims; i++) {
-    int32_t m;
-    memcpy(&m, prims + 76 * (size_t)i + 72, 4);
-    if (m < 0 || (uint32_t)m >= n_mats) { msg = "materialIndex out of range"; return -1; }
-  }
-  uint32_t lc;
-  memcpy(&lc, lights, 4);
-  if (lc > 64) { msg = "more than 64 emissive triangles"; return -1; }
-  for (uint32_t i = 0; i < lc; i++) {
-    uint32_t p;
-    memcpy(&p, lights + 4 + 4 * i, 4);
-    if (p >= n_prims) { msg = "light primitive out of range"; return -1; }
-  }
+  const char* why = check_material_indices(prims, n_prims, n_mats);
+  if (!why) why = check_lights(lights, n_prims);
+  if (why) { msg = why; return -1; }
   // height by forward propagation (children always have larger indices than their parent)
   std::vector<int> depth(n_nodes, -1);
   depth[0] = 0;
@@ -680,27 +701,101 @@ extern "C" int lt_hip_own_wide(const void* own_nodes, uint64_t node_bytes, uint3
   return ok ? height : -1;
 }
 
-static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const void* materials,
-                          uint64_t material_bytes, const void* lights, uint64_t light_bytes, const SceneHash* known_hash);
-
-extern "C" int lt_hip_set_scene(lt_hip_context* ctx, const void* nodes, uint64_t node_bytes, const void* prims,
-                                uint64_t prim_bytes, const void* materials, uint64_t material_bytes, const void* lights,
-                                uint64_t light_bytes) {
-  try {
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = set_scene_impl(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, nullptr);
-    if (getenv("LT_DEBUG_SCENE_TIMING"))
-      fprintf(stderr, "[lt set_scene] %-28s %7.2f ms\n", "lt_hip_set_scene, all of it", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    return rc;
-  } catch (const std::exception& e) {   // (std::bad_alloc, std::system_error of a thread: nothing may cross the C ABI)
-    return fail(ctx, LT_ERR_HIP, std::string("lt_hip_set_scene: ") + e.what());
+// The knobs of scene preparation, read once at the top of every set_scene_impl call (tests change them between the calls on one
+// context), and the call's lap timer: LT_DEBUG_SCENE_TIMING prints the host time of every step, and of the whole call, to stderr.
+struct SceneKnobs {
+  int device = -1;          // LT_DEVICE_BUILD=0 / 1: prepare on the device never / whenever possible; unset (-1): by the scene's size
+  bool own_splits = true;   // LT_RETREE=0: the own structures keep the caller's splits
+  int slack = 2;            // LT_RETREE_SLACK: levels the own tree may have beyond the least height possible
+  const bool always_upload = getenv("LT_SCENE_ALWAYS_UPLOAD") != nullptr;
+  const bool timing = getenv("LT_DEBUG_SCENE_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now(), mark = start;
+  SceneKnobs() {
+    if (const char* e = getenv("LT_DEVICE_BUILD")) device = atoi(e) != 0;
+    if (const char* e = getenv("LT_RETREE")) own_splits = atoi(e) != 0;
+    if (const char* e = getenv("LT_RETREE_SLACK")) slack = atoi(e);
   }
+  ~SceneKnobs() { mark = start; lap("lt_hip_set_scene, all of it"); }
+  void lap(const char* what) {
+    const auto now = std::chrono::steady_clock::now();
+    if (timing) fprintf(stderr, "[lt set_scene] %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - mark).count());
+    mark = now;
+  }
+};
+
+// The own structures as either build leaves them, in device memory from the pool: the own tree and the leaf order table, which
+// install_own_structures hands to the context, and collapse_wide's `children` / `groupOf`, which the builder gives back.
+struct OwnBuild {
+  void *d_nodes2, *d_rank8;
+  const void *d_children, *d_groupOf;
+  uint32_t n_nodes2, groups;
+  int height, wide_height;              // of the own tree; of its 4-wide groups (-1: none)
+  const float *root_lo, *root_hi;       // the own tree's root box: the grid of the per-lane walks' records
+};
+
+// Makes the per-lane walks' group records and the own structures resident -- or, when the walks cannot use them, gives all of them
+// back (the renderer takes them all or none): the scene then walks the caller's tree.  The leaf records are remake_leaf_records'.
+static int install_own_structures(lt_hip_context* ctx, const OwnBuild& b, uint32_t n_prims) {
+  ctx->d_nodes2 = b.d_nodes2;
+  ctx->d_rank8 = b.d_rank8;
+  // (the walk's stack: at most three waiting entries per level of groups and the four of the last one; the records' links: 31 bits)
+  bool ok = b.wide_height >= 0 && b.groups > 0 && 3 * b.wide_height + 4 <= kOwnRows + kOwnDeep && (uint64_t)b.groups + n_prims + 1 < 0x7fffffffull;
+  if (ok) {
+    Own16Frame fr;
+    for (int a = 0; a < 3; a++) lt_own16::frame(b.root_lo[a], b.root_hi[a], fr.O[a], fr.S[a]);
+    LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_pairs2, (size_t)b.n_nodes2 * 64));
+    LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_wide, ((size_t)b.groups + n_prims + 1) * 64 + 64));   // (64 bytes in front: the grid, read by the walks themselves)
+    const float head[16] = {0, 0, 0, 0, 0, 0, 0, 0, fr.O[0], fr.O[1], fr.O[2], 0.0f, fr.S[0], fr.S[1], fr.S[2], 0.0f};
+    LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_wide, head, sizeof(head), hipMemcpyHostToDevice, ctx->stream));
+    LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_prep_flag, 0, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(lt_wide_kernel, dim3((4 * b.groups + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2,
+                       (const uint32_t*)b.d_children, (const uint32_t*)b.d_groupOf, (uint4*)ctx->d_wide + 4, b.groups, n_prims, fr, ctx->d_prep_flag);
+    LT_HIP_CHECK(ctx, hipGetLastError());
+    uint32_t bad = 0;
+    LT_HIP_CHECK(ctx, hipMemcpyAsync(&bad, ctx->d_prep_flag, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+    LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    ok = bad == 0;   // (a bound off the grid cannot happen for a grid sized from the root's box)
+  }
+  if (!ok) {
+    for (void** p : {&ctx->d_nodes2, &ctx->d_pairs2, &ctx->d_wide, &ctx->d_rank8}) { ctx->pool.put(*p); *p = nullptr; }
+    return LT_OK;
+  }
+  ctx->n_nodes2 = b.n_nodes2;
+  ctx->height2 = b.height;
+  ctx->n_wide = b.groups;
+  ctx->wide_height = b.wide_height;
+  return LT_OK;
 }
 
-// The shadow-ray walk timed fastest for a scene (render_on_stream) is kept for a scene of the same shape -- the next pose of an
-// animation, an edited material: it is a matter of speed, never of pixels, and timing it again costs five frames -- and forgotten
-// when the sizes change (another scene).
-static void new_scene_walk_verdicts(lt_hip_context* ctx, const uint64_t sizes[4]) {
+// What is made from the resident primitives: the traversal triangles and, with the own structures, the leaf records of both walks
+// (the packet walks' pairs, the per-lane walks' records behind the groups).  Both builds run it, and an edit of the primitives.
+static int remake_leaf_records(lt_hip_context* ctx, uint32_t n_prims) {
+  hipLaunchKernelGGL(lt_retile_kernel, dim3((n_prims + 255) / 256), dim3(256), 0, ctx->stream, (const float*)ctx->d_prims, (float4*)ctx->d_tris, n_prims);
+  if (ctx->d_nodes2 && ctx->d_pairs2 && ctx->d_wide) {
+    const uint32_t n2 = ctx->n_nodes2;
+    hipLaunchKernelGGL(lt_own_pair_kernel, dim3((n2 + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2, (const float*)ctx->d_prims,
+                       (float4*)ctx->d_pairs2, n2);
+    hipLaunchKernelGGL(lt_wide_leaf_kernel, dim3((n2 + 1 + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2, (const float*)ctx->d_prims,
+                       (float4*)((uint4*)ctx->d_wide + 4), n2, ctx->n_wide, n_prims);
+  }
+  LT_HIP_CHECK(ctx, hipGetLastError());
+  return LT_OK;
+}
+
+// The scene is resident: its sizes and hash (what the next call is compared with), the caller's tree's height, who prepared it.
+static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const SceneHash& hash, int bvh_height, bool device_prepared) {
+  ctx->n_nodes = (uint32_t)(sizes[0] / 32);
+  ctx->n_prims = (uint32_t)(sizes[1] / 76);
+  ctx->n_mats = (uint32_t)(sizes[2] / 32);
+  ctx->bvh_height = bvh_height;
+  ctx->has_scene = true;
+  ctx->device_prepared = device_prepared;
+  ctx->scene_hash = hash;
+  memcpy(ctx->scene_sizes, sizes, sizeof(ctx->scene_sizes));
+  ctx->scene_uploads++;
+  // The shadow-ray walk timed fastest for a scene (render_on_stream) is kept for a scene of the same shape -- the next pose of an
+  // animation, an edited material: it is a matter of speed, never of pixels, and timing it again costs five frames -- and forgotten
+  // when the sizes change (another scene).
   if (ctx->verdict_sizes_valid && memcmp(sizes, ctx->verdict_sizes, sizeof(ctx->verdict_sizes)) == 0 && !getenv("LT_RETIME_EVERY_SCENE")) return;
   for (int& m : ctx->shadow_mode) m = -1;
   ctx->shadow_modes.clear();
@@ -710,28 +805,10 @@ static void new_scene_walk_verdicts(lt_hip_context* ctx, const uint64_t sizes[4]
 
 // The device path of lt_hip_set_scene.  kDeviceDeclined: nothing of ctx was touched, the host path decides.
 constexpr int kDeviceDeclined = -1000;
-static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
-                               const void* materials, uint64_t material_bytes, const void* lights, uint64_t light_bytes, const SceneHash& hash,
-                               bool timing) {
-  const uint32_t n_nodes = (uint32_t)(node_bytes / 32), n_prims = (uint32_t)(prim_bytes / 76), n_mats = (uint32_t)(material_bytes / 32);
-  auto tmark = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[lt set_scene] %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tmark).count());
-    tmark = now;
-  };
-  {   // the light list is 260 bytes: checked here
-    uint32_t lc;
-    memcpy(&lc, lights, 4);
-    if (lc > 64) return kDeviceDeclined;
-    for (uint32_t i = 0; i < lc; i++) {
-      uint32_t pi;
-      memcpy(&pi, (const uint8_t*)lights + 4 + 4 * i, 4);
-      if (pi >= n_prims) return kDeviceDeclined;
-    }
-  }
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const void* prims, const void* materials, const void* lights,
+                               const uint64_t sizes[4], const SceneHash& hash, SceneKnobs& k) {
+  const uint32_t n_nodes = (uint32_t)(sizes[0] / 32), n_prims = (uint32_t)(sizes[1] / 76), n_mats = (uint32_t)(sizes[2] / 32);
+  if (check_lights((const uint8_t*)lights, n_prims)) return kDeviceDeclined;   // (the light list is 260 bytes: checked here; the host words the error)
   void *d_nodes = nullptr, *d_prims = nullptr;
   const lt_prep::Allocator al{&ctx->pool, &ScenePool::get_cb, &ScenePool::put_cb};
   struct Guard {   // (whatever is still set when this returns goes back)
@@ -740,108 +817,55 @@ static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, uint64_t 
   };
   lt_prep::Out prep;
   Guard guard{ctx->pool, al, &d_nodes, &d_prims, &prep};
-  LT_HIP_CHECK(ctx, ctx->pool.get(&d_nodes, node_bytes));
-  LT_HIP_CHECK(ctx, ctx->pool.get(&d_prims, prim_bytes));
-  LT_HIP_CHECK(ctx, hipMemcpy(d_nodes, nodes, node_bytes, hipMemcpyHostToDevice));
-  lap("upload nodes");
+  LT_HIP_CHECK(ctx, ctx->pool.upload(&d_nodes, nodes, sizes[0]));
+  LT_HIP_CHECK(ctx, ctx->pool.get(&d_prims, sizes[1]));
+  k.lap("upload nodes");
   // The hierarchy is built from the nodes alone: the primitives (the larger buffer) travel meanwhile, sent by a thread of their
   // own (a copy from pageable memory keeps its caller until it is done) -- or, if that thread cannot be had, right here.
   std::thread primThread;
   hipError_t primError = hipSuccess;
-  bool primSent = false;
   try {
     primThread = std::thread([&]() {
       primError = hipSetDevice(ctx->device);
-      if (primError == hipSuccess) primError = hipMemcpy(d_prims, prims, prim_bytes, hipMemcpyHostToDevice);
+      if (primError == hipSuccess) primError = hipMemcpy(d_prims, prims, sizes[1], hipMemcpyHostToDevice);
     });
-    primSent = true;
   } catch (...) {
+    primError = hipMemcpy(d_prims, prims, sizes[1], hipMemcpyHostToDevice);
   }
   struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{primThread};   // (every exit below waits for it)
-  if (!primSent) LT_HIP_CHECK(ctx, hipMemcpy(d_prims, prims, prim_bytes, hipMemcpyHostToDevice));
-  const char* re = getenv("LT_RETREE");
-  const char* sl = getenv("LT_RETREE_SLACK");
   const auto t0 = std::chrono::steady_clock::now();
   // (height <= 30: the packet walks' stack, one VGPR, holds 2 * height + 2 entries at most; LT_RETREE=0: the caller's splits)
-  LT_HIP_CHECK(ctx, lt_prep::run(d_nodes, n_nodes, nullptr, n_prims, n_mats, 30, sl ? atoi(sl) : 2, !(re && atoi(re) == 0), ctx->stream, al, prep));
-  if (timing) fprintf(stderr, "[lt set_scene] device: checks + leaf order %.2f ms, own hierarchy %.2f ms (%d levels), 4-wide groups %.2f ms, flags %u\n",
-                      prep.ms_check, prep.ms_build, prep.levels, prep.ms_wide, prep.flags);
+  LT_HIP_CHECK(ctx, lt_prep::run(d_nodes, n_nodes, nullptr, n_prims, n_mats, 30, k.slack, k.own_splits, ctx->stream, al, prep));
+  if (k.timing) fprintf(stderr, "[lt set_scene] device: checks + leaf order %.2f ms, own hierarchy %.2f ms (%d levels), 4-wide groups %.2f ms, flags %u\n",
+                        prep.ms_check, prep.ms_build, prep.levels, prep.ms_wide, prep.flags);
   if (prep.flags != 0 || prep.bvh_height > kMaxStack) return kDeviceDeclined;
-  lap("device preparation");
+  k.lap("device preparation");
   if (primThread.joinable()) primThread.join();
   LT_HIP_CHECK(ctx, primError);
   bool primsOk = false;
-  LT_HIP_CHECK(ctx, lt_prep::check_primitives(d_prims, n_prims, n_mats, ctx->stream, (uint32_t*)ctx->d_stats, primsOk));
+  LT_HIP_CHECK(ctx, lt_prep::check_primitives(d_prims, n_prims, n_mats, ctx->stream, ctx->d_prep_flag, primsOk));
   if (!primsOk) return kDeviceDeclined;
-  lap("primitives arrived, checked");
+  k.lap("primitives arrived, checked");
   // from here on the scene is good: it replaces the resident one
   LT_HIP_CHECK(ctx, hipDeviceSynchronize());
   free_scene(ctx);
-  lap("free the resident scene");
   ctx->d_nodes = d_nodes; d_nodes = nullptr;
   ctx->d_prims = d_prims; d_prims = nullptr;
   LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_tris, (size_t)n_prims * 48));
-  LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_mats, material_bytes));
-  LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_lights, light_bytes));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_mats, materials, material_bytes, hipMemcpyHostToDevice, ctx->stream));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_lights, lights, light_bytes, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(lt_retile_kernel, dim3((n_prims + 255) / 256), dim3(256), 0, ctx->stream, (const float*)ctx->d_prims, (float4*)ctx->d_tris, n_prims);
-  LT_HIP_CHECK(ctx, hipGetLastError());
-  ctx->height2 = 0;
-  ctx->retree_ms = 0.0f;
-  const uint32_t n2 = prep.n_own, groups = prep.groups;
-  const int hw = prep.wide_height;
-  bool ownOk = hw >= 0 && groups > 0 && 3 * hw + 4 <= kOwnRows + kOwnDeep && (uint64_t)groups + n_prims + 1 < 0x7fffffffull;
-  if (ownOk) {
-    ctx->d_nodes2 = prep.d_nodes2; prep.d_nodes2 = nullptr;
-    ctx->d_rank8 = prep.d_rank8; prep.d_rank8 = nullptr;
-    LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_pairs2, (size_t)n2 * 64));
-    hipLaunchKernelGGL(lt_own_pair_kernel, dim3((n2 + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2, (const float*)ctx->d_prims,
-                       (float4*)ctx->d_pairs2, n2);
-    LT_HIP_CHECK(ctx, hipGetLastError());
-    Own16Frame fr;
-    for (int a = 0; a < 3; a++) lt_own16::frame(prep.root_lo[a], prep.root_hi[a], fr.O[a], fr.S[a]);
-    const size_t records = (size_t)groups + n_prims + 1;
-    LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_wide, records * 64 + 64));
-    const float head[16] = {0, 0, 0, 0, 0, 0, 0, 0, fr.O[0], fr.O[1], fr.O[2], 0.0f, fr.S[0], fr.S[1], fr.S[2], 0.0f};
-    LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_wide, head, sizeof(head), hipMemcpyHostToDevice, ctx->stream));
-    LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_stats, 0, sizeof(unsigned long long), ctx->stream));
-    uint4* wide = (uint4*)ctx->d_wide + 4;
-    hipLaunchKernelGGL(lt_wide_kernel, dim3((4 * groups + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2,
-                       (const uint32_t*)prep.d_children, (const uint32_t*)prep.d_groupOf, wide, groups, n_prims, fr, (uint32_t*)ctx->d_stats);
-    LT_HIP_CHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(lt_wide_leaf_kernel, dim3((n2 + 1 + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2,
-                       (const float*)ctx->d_prims, (float4*)wide, n2, groups, n_prims);
-    LT_HIP_CHECK(ctx, hipGetLastError());
-    uint32_t bad = 0;
-    LT_HIP_CHECK(ctx, hipMemcpyAsync(&bad, ctx->d_stats, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
-    lap("mallocs, launches");
-    LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    ownOk = bad == 0;
-    lap("retile, pair and wide records");
-  }
-  if (!ownOk) {   // the scene then walks the caller's tree
-    for (void** p : {&ctx->d_nodes2, &ctx->d_pairs2, &ctx->d_wide, &ctx->d_rank8}) { ctx->pool.put(*p); *p = nullptr; }
-  } else {
-    ctx->n_nodes2 = n2;
-    ctx->height2 = prep.own_height;
-    ctx->n_wide = groups;
-    ctx->wide_height = hw;
-  }
-  lt_prep::release(prep, al);
+  LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_mats, sizes[2]));
+  LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_lights, sizes[3]));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_mats, materials, sizes[2], hipMemcpyHostToDevice, ctx->stream));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_lights, lights, sizes[3], hipMemcpyHostToDevice, ctx->stream));
+  const OwnBuild own{prep.d_nodes2, prep.d_rank8, prep.d_children, prep.d_groupOf, prep.n_own, prep.groups, prep.own_height, prep.wide_height,
+                     prep.root_lo, prep.root_hi};
+  prep.d_nodes2 = prep.d_rank8 = nullptr;   // (the context's from here on; the guard gives back the rest)
+  int rc = install_own_structures(ctx, own, n_prims);
+  if (rc == LT_OK) rc = remake_leaf_records(ctx, n_prims);
+  if (rc) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->retree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  lap("release");
-  ctx->n_nodes = n_nodes;
-  ctx->n_prims = n_prims;
-  ctx->n_mats = n_mats;
-  ctx->bvh_height = prep.bvh_height;
-  ctx->has_scene = true;
-  ctx->scene_hash = hash;
-  ctx->scene_sizes[0] = node_bytes; ctx->scene_sizes[1] = prim_bytes; ctx->scene_sizes[2] = material_bytes; ctx->scene_sizes[3] = light_bytes;
-  ctx->scene_uploads++;
-  ctx->device_prepared = true;
-  new_scene_walk_verdicts(ctx, ctx->scene_sizes);
+  k.lap("own structures, leaf records");
+  adopt_scene(ctx, sizes, hash, prep.bvh_height, true);
   return LT_OK;
 }
 
@@ -853,17 +877,17 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
       light_bytes != 260)
     return fail(ctx, LT_ERR_BAD_SCENE, "scene buffer sizes are not whole multiples of LinearBVHNode(32) / Primitive(76) / Material(32) / LightContainer(260)");
   if (node_bytes > 0xffffffffull || prim_bytes / 76 > 0x7fffffffull / 48) return fail(ctx, LT_ERR_BAD_SCENE, "scene too large for 32-bit byte offsets (4 GiB of nodes / 2 GiB of traversal triangles)");
+  SceneKnobs k;
   const uint32_t n_nodes = (uint32_t)(node_bytes / 32), n_prims = (uint32_t)(prim_bytes / 76), n_mats = (uint32_t)(material_bytes / 32);
   // The reference uploads all buffers on every render() (renderer_opencl.cpp:107-120); here the resident copy is kept when the
   // caller hands over the same content again: sizes and a hash of EVERY byte (so an in-place edit of any vertex, node or
   // material is honoured).  LT_SCENE_ALWAYS_UPLOAD=1 turns the shortcut off.
   const uint64_t sizes[4] = {node_bytes, prim_bytes, material_bytes, light_bytes};
   const void* const bufs[4] = {nodes, prims, materials, lights};
-  const auto tHash = std::chrono::steady_clock::now();
   const SceneHash hash = known_hash ? *known_hash : hash_scene(bufs, sizes);
-  if (getenv("LT_DEBUG_SCENE_TIMING"))
-    fprintf(stderr, "[lt set_scene] %-28s %7.2f ms\n", known_hash ? "hash (known)" : "hash", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tHash).count());
-  if (ctx->has_scene && memcmp(sizes, ctx->scene_sizes, sizeof(sizes)) == 0 && !getenv("LT_SCENE_ALWAYS_UPLOAD")) {
+  k.lap(known_hash ? "hash (known)" : "hash");
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (ctx->has_scene && memcmp(sizes, ctx->scene_sizes, sizeof(sizes)) == 0 && !k.always_upload) {
     if (hash == ctx->scene_hash) {
       ctx->scene_reused++;
       return LT_OK;
@@ -873,188 +897,103 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
     // records of both walks) is made again by the kernels that made it: no host-side build, no second copy of the tree.
     if (hash.buf[0] == ctx->scene_hash.buf[0]) {
       const bool primsChanged = hash.buf[1] != ctx->scene_hash.buf[1];
-      std::string why;
-      if (primsChanged) {
-        for (uint32_t i = 0; i < n_prims && why.empty(); i++) {
-          int32_t m;
-          memcpy(&m, (const uint8_t*)prims + 76 * (size_t)i + 72, 4);
-          if (m < 0 || (uint32_t)m >= n_mats) why = "materialIndex out of range";
-        }
-      }
-      uint32_t lc;
-      memcpy(&lc, lights, 4);
-      if (lc > 64) why = "more than 64 emissive triangles";
-      for (uint32_t i = 0; i < lc && i < 64 && why.empty(); i++) {
-        uint32_t pi;
-        memcpy(&pi, (const uint8_t*)lights + 4 + 4 * i, 4);
-        if (pi >= n_prims) why = "light primitive out of range";
-      }
-      if (!why.empty()) return fail(ctx, LT_ERR_BAD_SCENE, why);
-      LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+      // (of several defects, this path has always named a light count over 64 first, then a materialIndex, then a light's primitive)
+      const char* why = check_lights((const uint8_t*)lights, n_prims);
+      const char* badMaterial = primsChanged ? check_material_indices((const uint8_t*)prims, n_prims, n_mats) : nullptr;
+      if (badMaterial && why != kTooManyLights) why = badMaterial;
+      if (why) return fail(ctx, LT_ERR_BAD_SCENE, why);
       LT_HIP_CHECK(ctx, hipDeviceSynchronize());   // (nothing of an earlier call may still be reading what is about to change)
       if (primsChanged) {
         LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_prims, prims, prim_bytes, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(lt_retile_kernel, dim3((n_prims + 255) / 256), dim3(256), 0, ctx->stream, (const float*)ctx->d_prims, (float4*)ctx->d_tris, n_prims);
-        if (ctx->d_nodes2 && ctx->d_pairs2 && ctx->d_wide) {
-          const uint32_t n2 = ctx->n_nodes2;
-          hipLaunchKernelGGL(lt_own_pair_kernel, dim3((n2 + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2, (const float*)ctx->d_prims,
-                             (float4*)ctx->d_pairs2, n2);
-          hipLaunchKernelGGL(lt_wide_leaf_kernel, dim3((n2 + 1 + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2, (const float*)ctx->d_prims,
-                             (float4*)((uint4*)ctx->d_wide + 4), n2, ctx->n_wide, n_prims);
-        }
-        LT_HIP_CHECK(ctx, hipGetLastError());
+        const int rc = remake_leaf_records(ctx, n_prims);
+        if (rc) return rc;
       }
       LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_mats, materials, material_bytes, hipMemcpyHostToDevice));
       LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_lights, lights, light_bytes, hipMemcpyHostToDevice));
       LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      ctx->scene_hash = hash;
-      ctx->scene_uploads++;
-      new_scene_walk_verdicts(ctx, sizes);
+      adopt_scene(ctx, sizes, hash, ctx->bvh_height, ctx->device_prepared);
       return LT_OK;
     }
   }
-  const bool timing = getenv("LT_DEBUG_SCENE_TIMING") != nullptr;
-  auto tmark = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[lt set_scene] %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tmark).count());
-    tmark = now;
-  };
-  std::string msg;
   // Scene preparation on the device (lt_prep.hip): nodes and primitives go up first, kernels check them, make the leaf order
   // table, build the own hierarchy and collapse it; the host passes below are what remains for scenes that path declines
   // (a malformed buffer -- the host words the error --, a tree that is not in the scene builder's pre-order, boxes that do not
-  // nest) and for small ones, where a host build costs less than the launches.  LT_DEVICE_BUILD=0 / 1: never / whenever possible.
-  {
-    const char* db = getenv("LT_DEVICE_BUILD");
-    const bool device = db ? atoi(db) != 0 : n_nodes >= 8192u;
-    if (device) {
-      const int rc = set_scene_on_device(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, hash, timing);
-      if (rc != kDeviceDeclined) return rc;
-      lap("device preparation declined");
-    }
+  // nest) and for small ones, where a host build costs less than the launches.
+  if (k.device < 0 ? n_nodes >= 8192u : k.device != 0) {
+    const int rc = set_scene_on_device(ctx, nodes, prims, materials, lights, sizes, hash, k);
+    if (rc != kDeviceDeclined) return rc;
+    k.lap("device preparation declined");
   }
+  std::string msg;
   const int height = validate_scene((const uint8_t*)nodes, n_nodes, (const uint8_t*)prims, n_prims, n_mats, (const uint8_t*)lights, msg);
-  lap("validate");
+  k.lap("validate");
   if (height < 0) return fail(ctx, LT_ERR_BAD_SCENE, msg);
   if (height > kMaxStack) return fail(ctx, LT_ERR_BAD_SCENE, "BVH deeper than the reference's 64-entry traversal stack");
-
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   LT_HIP_CHECK(ctx, hipDeviceSynchronize());
   free_scene(ctx);
-  LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_nodes, node_bytes));
-  LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_prims, prim_bytes));
+  LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_nodes, nodes, node_bytes));
+  LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_prims, prims, prim_bytes));
   LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_tris, (size_t)n_prims * 48));
-  LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_mats, material_bytes));
-  LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_lights, light_bytes));
-  LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_nodes, nodes, node_bytes, hipMemcpyHostToDevice));
-  LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_prims, prims, prim_bytes, hipMemcpyHostToDevice));
-  LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_mats, materials, material_bytes, hipMemcpyHostToDevice));
-  LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_lights, lights, light_bytes, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(lt_retile_kernel, dim3((n_prims + 255) / 256), dim3(256), 0, ctx->stream, (const float*)ctx->d_prims,
-                     (float4*)ctx->d_tris, n_prims);
-  LT_HIP_CHECK(ctx, hipGetLastError());
-  lap("free, malloc, upload scene");
+  LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_mats, materials, material_bytes));
+  LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_lights, lights, light_bytes));
+  k.lap("free, malloc, upload scene");
   // The backend's own hierarchy over the same leaves (lt_retree.hpp says why the pixels cannot change), for every finite ray of
   // the non-counting kernels.  LT_RETREE=0 keeps the caller's splits (same structures, same walks).  A scene whose boxes do not
   // nest gets none: its rays walk the caller's tree one by one, in the reference's order.
-  ctx->height2 = 0;
-  ctx->retree_ms = 0.0f;
   {
-    const char* re = getenv("LT_RETREE");
-    std::vector<lt_retree::Node> own;
     const auto t0 = std::chrono::steady_clock::now();
-    const char* sl = getenv("LT_RETREE_SLACK");
-    // (height <= 30: the packet walks' stack, one VGPR, holds 2 * height + 2 entries at most; LT_RETREE=0: the caller's splits)
     // (the leaf order table depends on the caller's tree alone: it is made by a thread of its own beside the build -- or, if that
     // thread cannot be had, after it)
     std::vector<uint32_t> rank8;
     std::thread rankThread;
-    bool rankStarted = false;
-    std::atomic<bool> rankFailed{false};
+    std::atomic<bool> rankMade{false};
     try {
       rankThread = std::thread([&]() {
-        try { lt_retree::reference_order(nodes, n_nodes, n_prims, rank8); } catch (...) { rankFailed = true; }   // (nothing escapes a thread)
+        try { lt_retree::reference_order(nodes, n_nodes, n_prims, rank8); rankMade = true; } catch (...) {}   // (nothing escapes a thread)
       });
-      rankStarted = true;
     } catch (...) {
     }
     struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{rankThread};   // (every exit below waits for it)
-    const int h2 = (re && atoi(re) == 0) ? lt_retree::copy(nodes, n_nodes, 30, own) : lt_retree::build(nodes, n_nodes, 30, sl ? atoi(sl) : 2, own);
-    lap("own hierarchy (host build)");
+    std::vector<lt_retree::Node> own;
+    // (height <= 30: the packet walks' stack, one VGPR, holds 2 * height + 2 entries at most; LT_RETREE=0: the caller's splits)
+    const int h2 = k.own_splits ? lt_retree::build(nodes, n_nodes, 30, k.slack, own) : lt_retree::copy(nodes, n_nodes, 30, own);
+    k.lap("own hierarchy (host build)");
     if (h2 >= 0) {
-      ctx->retree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      const uint32_t n2 = (uint32_t)own.size();
-      LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_nodes2, (size_t)n2 * 32));
-      LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_pairs2, (size_t)n2 * 64));
-      LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_nodes2, own.data(), (size_t)n2 * 32, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(lt_own_pair_kernel, dim3((n2 + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2,
-                         (const float*)ctx->d_prims, (float4*)ctx->d_pairs2, n2);
-      LT_HIP_CHECK(ctx, hipGetLastError());
-      // ... and the per-lane walks' 4-wide groups and leaf records, made from the same upload of the tree
-      lap("upload own tree, pair kernel");
       std::vector<uint32_t> children, groupOf;
       const int hw = lt_retree::collapse_wide(own, n_prims, children, groupOf);
-      const uint32_t groups = (uint32_t)(children.size() / 4);
-      lap("collapse into 4-wide groups");
-      // (the walk's stack: at most three waiting entries per level of groups and the four of the last one)
-      bool ownOk = hw >= 0 && 3 * hw + 4 <= kOwnRows + kOwnDeep && (uint64_t)groups + n_prims + 1 < 0x7fffffffull;
-      if (ownOk) {
-        Own16Frame fr;
-        for (int a = 0; a < 3; a++) lt_own16::frame(own[0].lo[a], own[0].hi[a], fr.O[a], fr.S[a]);
-        const size_t records = (size_t)groups + n_prims + 1;
-        void *d_children = nullptr, *d_groupOf = nullptr;
-        LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_wide, records * 64 + 64));   // (64 bytes in front: the grid, read by the walks themselves)
-        LT_HIP_CHECK(ctx, ctx->pool.get(&d_children, children.size() * 4));
-        LT_HIP_CHECK(ctx, ctx->pool.get(&d_groupOf, groupOf.size() * 4));
-        const float head[16] = {0, 0, 0, 0, 0, 0, 0, 0, fr.O[0], fr.O[1], fr.O[2], 0.0f, fr.S[0], fr.S[1], fr.S[2], 0.0f};
-        LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_wide, head, sizeof(head), hipMemcpyHostToDevice));
-        LT_HIP_CHECK(ctx, hipMemcpy(d_children, children.data(), children.size() * 4, hipMemcpyHostToDevice));
-        LT_HIP_CHECK(ctx, hipMemcpy(d_groupOf, groupOf.data(), groupOf.size() * 4, hipMemcpyHostToDevice));
-        LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_stats, 0, sizeof(unsigned long long), ctx->stream));
-        uint4* wide = (uint4*)ctx->d_wide + 4;
-        hipLaunchKernelGGL(lt_wide_kernel, dim3((4 * groups + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2,
-                           (const uint32_t*)d_children, (const uint32_t*)d_groupOf, wide, groups, n_prims, fr, (uint32_t*)ctx->d_stats);
-        LT_HIP_CHECK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(lt_wide_leaf_kernel, dim3((n2 + 1 + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)ctx->d_nodes2,
-                           (const float*)ctx->d_prims, (float4*)wide, n2, groups, n_prims);
-        LT_HIP_CHECK(ctx, hipGetLastError());
-        uint32_t bad = 0;
-        LT_HIP_CHECK(ctx, hipMemcpyAsync(&bad, ctx->d_stats, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
-        LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->pool.put(d_children);
-        ctx->pool.put(d_groupOf);
-        ownOk = bad == 0;   // (a bound off the grid cannot happen for a grid sized from the root's box)
-        lap("wide records (upload, kernels)");
-      }
-      if (!ownOk) {   // the scene then walks the caller's tree
-        for (void** p : {&ctx->d_nodes2, &ctx->d_pairs2, &ctx->d_wide}) { ctx->pool.put(*p); *p = nullptr; }
-      } else {   // (the own tree's 32-byte form stays resident: an edit of the primitives alone re-makes the leaf records from it)
-        ctx->n_nodes2 = n2;
-        ctx->height2 = h2;
-        ctx->n_wide = groups;
-        ctx->wide_height = hw;
-        if (rankThread.joinable()) rankThread.join();
-        if (!rankStarted || rankFailed) lt_retree::reference_order(nodes, n_nodes, n_prims, rank8);
-        LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_rank8, rank8.size() * sizeof(uint32_t)));
-        LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_rank8, rank8.data(), rank8.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        lap("leaf order table (host, upload)");
-      }
+      if (rankThread.joinable()) rankThread.join();
+      if (!rankMade) lt_retree::reference_order(nodes, n_nodes, n_prims, rank8);
+      k.lap("4-wide groups, leaf order");
+      void *d_children = nullptr, *d_groupOf = nullptr;
+      LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_nodes2, own.data(), own.size() * sizeof(lt_retree::Node)));
+      LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_rank8, rank8.data(), rank8.size() * sizeof(uint32_t)));
+      LT_HIP_CHECK(ctx, ctx->pool.upload(&d_children, children.data(), children.size() * sizeof(uint32_t)));
+      LT_HIP_CHECK(ctx, ctx->pool.upload(&d_groupOf, groupOf.data(), groupOf.size() * sizeof(uint32_t)));
+      const OwnBuild b{ctx->d_nodes2, ctx->d_rank8, d_children, d_groupOf, (uint32_t)own.size(), (uint32_t)(children.size() / 4), h2, hw,
+                       own[0].lo, own[0].hi};
+      const int rc = install_own_structures(ctx, b, n_prims);
+      ctx->pool.put(d_children);
+      ctx->pool.put(d_groupOf);
+      if (rc) return rc;
       ctx->retree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      k.lap("own structures (upload, groups)");
     }
   }
+  const int rc = remake_leaf_records(ctx, n_prims);
+  if (rc) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->n_nodes = n_nodes;
-  ctx->n_prims = n_prims;
-  ctx->n_mats = n_mats;
-  ctx->bvh_height = height;
-  ctx->has_scene = true;
-  ctx->scene_hash = hash;
-  memcpy(ctx->scene_sizes, sizes, sizeof(sizes));
-  ctx->scene_uploads++;
-  new_scene_walk_verdicts(ctx, sizes);
+  adopt_scene(ctx, sizes, hash, height, false);
   return LT_OK;
+}
+
+extern "C" int lt_hip_set_scene(lt_hip_context* ctx, const void* nodes, uint64_t node_bytes, const void* prims,
+                                uint64_t prim_bytes, const void* materials, uint64_t material_bytes, const void* lights,
+                                uint64_t light_bytes) {
+  try {
+    return set_scene_impl(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, nullptr);
+  } catch (const std::exception& e) {   // (std::bad_alloc, std::system_error of a thread: nothing may cross the C ABI)
+    return fail(ctx, LT_ERR_HIP, std::string("lt_hip_set_scene: ") + e.what());
+  }
 }
 
 // ---------------------------------------------------------------------------------- render

@@ -114,9 +114,9 @@ def test_buffers_the_device_declines_keep_their_host_verdicts(monkeypatch):
     base = random_triangles(9, 400)
     r = RendererHIP(0)
 
-    def with_nodes(nodes, prims=None):
+    def with_nodes(nodes, prims=None, lights=None):
         s = sc.Scene(nodes=np.ascontiguousarray(nodes).view(np.uint8).reshape(-1), prims=base.prims if prims is None else prims.view(np.uint8).reshape(-1),
-                     materials=base.materials, lights=base.lights, camera=base.camera)
+                     materials=base.materials, lights=base.lights if lights is None else lights.view(np.uint8).reshape(-1), camera=base.camera)
         r.set_scene(s)
         return r.scene_structure(3)
 
@@ -152,8 +152,28 @@ def test_buffers_the_device_declines_keep_their_host_verdicts(monkeypatch):
     p["materialIndex"][11] = 77
     with pytest.raises(C.LensTraceError, match="materialIndex out of range"):
         with_nodes(good.copy(), p)
+    # the light list (the device path declines it before it starts): a first upload (the resident scene has other nodes) ...
+    too_many = base.light_view.copy()
+    too_many["count"] = 65
+    off_the_end = base.light_view.copy()
+    off_the_end["count"] = max(1, int(off_the_end["count"][0]))
+    off_the_end["primitives"][0][0] = base.n_prims
+    bad_lights = ((too_many, "more than 64 emissive triangles"), (off_the_end, "light primitive out of range"))
+    for lights, words in bad_lights:
+        with pytest.raises(C.LensTraceError, match=words):
+            with_nodes(good.copy(), lights=lights)
     # ... and a good scene afterwards is prepared on the device again
     assert with_nodes(good.copy())[3] == 1
+    # ... and an edit of the resident scene (the same nodes, new lights) is refused in the same words
+    uploads = r.stats()["scene_uploads"]
+    for lights, words in bad_lights:
+        with pytest.raises(C.LensTraceError, match=words):
+            with_nodes(good.copy(), lights=lights)
+    assert r.stats()["scene_uploads"] == uploads
+    # ... and a good scene afterwards is still prepared on the device
+    n = good.copy()
+    n["boundsMax"][0] += 1.0   # (a new node buffer: prepared anew)
+    assert with_nodes(n)[3] == 1 and r.stats()["scene_uploads"] == uploads + 1
     r.close()
 
 
@@ -201,4 +221,45 @@ def test_a_deep_callers_tree(monkeypatch):
         r.set_scene(chain_scene(70))
     r.set_scene(chain_scene(64))
     assert r.scene_structure(3)[3] == 1 and r.stats is not None
+    r.close()
+
+
+def test_scene_preparation_leaves_the_counters_of_a_render_in_flight_alone(monkeypatch):
+    """lt_hip_render_device does not wait for its launches, and lt_hip_set_scene's device path checks the primitives and the walk
+    records' grid in a device word of its own: a counting render still running on another stream keeps its counters, and its
+    counts do not make the new scene look malformed (which would send it down the host path)."""
+    import torch
+    from lens_trace_amd.renderer import make_desc
+    monkeypatch.setenv("LT_DEVICE_BUILD", "1")
+    first = synth.wall_and_soup(60, 9000).validate()
+    second = synth.triangle_soup(30000).validate()
+    W, H = 1920, 1080
+    counters = ("rays", "shadow_rays", "node_visits", "tri_tests")
+    buf = torch.zeros(W * H * 3, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+
+    def render(r, frames, stream):
+        d = make_desc(C.PROGRAM_ACCUMULATOR, W, H, 3, first.camera, frame_first=1, frame_count=frames, accumulate=True, stats=True)
+        r.render_device(d, buf.data_ptr(), buf.numel() * 4, stream)
+
+    alone = RendererHIP(0)
+    alone.set_scene(first)
+    for _ in range(2):   # (the second one timed)
+        render(alone, 1, 0)
+        alone.synchronize(0)
+        frame_ms = alone.stats()["kernel_ms"]
+    frames = max(2, min(256, int(np.ceil(60.0 / max(frame_ms, 0.05)))))   # a render of some 60 ms: ten times the preparation
+    render(alone, frames, 0)
+    alone.synchronize(0)
+    want = alone.stats()
+    alone.close()
+    r = RendererHIP(0)
+    r.set_scene(first)
+    stream = torch.cuda.Stream()
+    render(r, frames, stream.cuda_stream)
+    r.set_scene(second)   # (while the render runs)
+    stream.synchronize()
+    assert r.scene_structure(3)[3] == 1
+    got = r.stats()
+    assert {k: got[k] for k in counters} == {k: want[k] for k in counters}, (frames, frame_ms)
     r.close()
