@@ -16,6 +16,7 @@
 #include <chrono>
 #include <exception>
 #include <thread>
+#include <type_traits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -238,7 +239,6 @@ struct lt_hip_context {
   int height2 = 0;                                 // its height
   uint32_t n_nodes2 = 0;
   float retree_ms = 0.0f;                          // host time of its build
-  uint32_t lds_ref_bytes = 0;                      // LDS of a wave whose per-lane stack follows the caller's tree (set per render call)
   uint32_t n_nodes = 0, n_prims = 0, n_mats = 0;
   int bvh_height = 0;
   bool has_scene = false;
@@ -255,13 +255,11 @@ struct lt_hip_context {
   uint64_t h_out_bytes = 0;          //     (a caller's pageable buffer would be read back through the runtime's small bounce buffers)
   hipEvent_t out_ev[8] = {};         // one event per piece
   hipEvent_t fold_ev[8] = {};        // ... and one behind the fold of each piece (launch_running_mean), when the call's last fold is cut into them
-  uint64_t fold_piece_bytes = 0;     //     (set by lt_hip_render around its render: bytes per piece, 0 = one fold launch)
-  bool fold_pieced = false;
   hipStream_t copy_stream = nullptr; //     the pieces travel on a stream of their own, each behind its fold
   unsigned long long* d_stats = nullptr;
   uint32_t* d_prep_flag = nullptr;   // scene preparation's flag word: the slot behind d_stats, which no render launch writes
   uint32_t* d_queues = nullptr;      // persistent mode: 8 per-XCD work counters per launch of a call
-  uint32_t queue_frames = 0;
+  uint64_t queue_frames = 0;
   int shadow_mode[6] = {-1, -1, -1, -1, -1, -1};   // per built-in program: shadow rays as any-hit packets (1) or per lane (0); -1 = not timed yet
   hipEvent_t cal_ev[12] = {};
   std::map<std::vector<uint32_t>, int> shadow_modes;   // (program, W, H, tile geometry) -> the walk timed faster for it on the resident scene
@@ -278,7 +276,6 @@ struct lt_hip_context {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> mean_events;   // pairs around the running-mean kernels of the last call
   uint32_t mean_pairs = 0;
-  hipStream_t last_stream = nullptr;
   bool pending = false, pending_stats = false;
   lt_hip_stats last{};
   // wavefront GI pipeline: path queues, per-pixel direct / indirect / blend, control block (queue lengths, work counters)
@@ -701,21 +698,29 @@ extern "C" int lt_hip_own_wide(const void* own_nodes, uint64_t node_bytes, uint3
   return ok ? height : -1;
 }
 
-// The knobs of scene preparation, read once at the top of every set_scene_impl call (tests change them between the calls on one
-// context), and the call's lap timer: LT_DEBUG_SCENE_TIMING prints the host time of every step, and of the whole call, to stderr.
+// Set, to a number that reads 0: how most switches are turned off.
+static bool env_off(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }
+
+// The knobs of scene preparation, read once at the top of every public call that may install a scene (tests change them between
+// the calls on one context).
 struct SceneKnobs {
   int device = -1;          // LT_DEVICE_BUILD=0 / 1: prepare on the device never / whenever possible; unset (-1): by the scene's size
-  bool own_splits = true;   // LT_RETREE=0: the own structures keep the caller's splits
+  bool own_splits = !env_off("LT_RETREE");   // off: the own structures keep the caller's splits
   int slack = 2;            // LT_RETREE_SLACK: levels the own tree may have beyond the least height possible
-  const bool always_upload = getenv("LT_SCENE_ALWAYS_UPLOAD") != nullptr;
-  const bool timing = getenv("LT_DEBUG_SCENE_TIMING") != nullptr;
-  std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now(), mark = start;
+  bool always_upload = getenv("LT_SCENE_ALWAYS_UPLOAD") != nullptr;   // the resident scene is uploaded again when it is handed over
+  bool retime = getenv("LT_RETIME_EVERY_SCENE") != nullptr;           // every scene forgets the shadow-walk verdicts (adopt_scene)
+  bool timing = getenv("LT_DEBUG_SCENE_TIMING") != nullptr;           // SceneLaps
   SceneKnobs() {
     if (const char* e = getenv("LT_DEVICE_BUILD")) device = atoi(e) != 0;
-    if (const char* e = getenv("LT_RETREE")) own_splits = atoi(e) != 0;
     if (const char* e = getenv("LT_RETREE_SLACK")) slack = atoi(e);
   }
-  ~SceneKnobs() { mark = start; lap("lt_hip_set_scene, all of it"); }
+};
+
+// The lap timer of one set_scene_impl call: LT_DEBUG_SCENE_TIMING prints the host time of every step, and of the whole call, to stderr.
+struct SceneLaps {
+  const bool timing;
+  std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now(), mark = start;
+  ~SceneLaps() { mark = start; lap("lt_hip_set_scene, all of it"); }
   void lap(const char* what) {
     const auto now = std::chrono::steady_clock::now();
     if (timing) fprintf(stderr, "[lt set_scene] %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - mark).count());
@@ -783,7 +788,7 @@ static int remake_leaf_records(lt_hip_context* ctx, uint32_t n_prims) {
 }
 
 // The scene is resident: its sizes and hash (what the next call is compared with), the caller's tree's height, who prepared it.
-static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const SceneHash& hash, int bvh_height, bool device_prepared) {
+static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const SceneHash& hash, int bvh_height, bool device_prepared, const SceneKnobs& k) {
   ctx->n_nodes = (uint32_t)(sizes[0] / 32);
   ctx->n_prims = (uint32_t)(sizes[1] / 76);
   ctx->n_mats = (uint32_t)(sizes[2] / 32);
@@ -796,7 +801,7 @@ static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const Scen
   // The shadow-ray walk timed fastest for a scene (render_on_stream) is kept for a scene of the same shape -- the next pose of an
   // animation, an edited material: it is a matter of speed, never of pixels, and timing it again costs five frames -- and forgotten
   // when the sizes change (another scene).
-  if (ctx->verdict_sizes_valid && memcmp(sizes, ctx->verdict_sizes, sizeof(ctx->verdict_sizes)) == 0 && !getenv("LT_RETIME_EVERY_SCENE")) return;
+  if (ctx->verdict_sizes_valid && memcmp(sizes, ctx->verdict_sizes, sizeof(ctx->verdict_sizes)) == 0 && !k.retime) return;
   for (int& m : ctx->shadow_mode) m = -1;
   ctx->shadow_modes.clear();
   memcpy(ctx->verdict_sizes, sizes, sizeof(ctx->verdict_sizes));
@@ -806,7 +811,7 @@ static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const Scen
 // The device path of lt_hip_set_scene.  kDeviceDeclined: nothing of ctx was touched, the host path decides.
 constexpr int kDeviceDeclined = -1000;
 static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const void* prims, const void* materials, const void* lights,
-                               const uint64_t sizes[4], const SceneHash& hash, SceneKnobs& k) {
+                               const uint64_t sizes[4], const SceneHash& hash, const SceneKnobs& k, SceneLaps& laps) {
   const uint32_t n_nodes = (uint32_t)(sizes[0] / 32), n_prims = (uint32_t)(sizes[1] / 76), n_mats = (uint32_t)(sizes[2] / 32);
   if (check_lights((const uint8_t*)lights, n_prims)) return kDeviceDeclined;   // (the light list is 260 bytes: checked here; the host words the error)
   void *d_nodes = nullptr, *d_prims = nullptr;
@@ -819,7 +824,7 @@ static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const voi
   Guard guard{ctx->pool, al, &d_nodes, &d_prims, &prep};
   LT_HIP_CHECK(ctx, ctx->pool.upload(&d_nodes, nodes, sizes[0]));
   LT_HIP_CHECK(ctx, ctx->pool.get(&d_prims, sizes[1]));
-  k.lap("upload nodes");
+  laps.lap("upload nodes");
   // The hierarchy is built from the nodes alone: the primitives (the larger buffer) travel meanwhile, sent by a thread of their
   // own (a copy from pageable memory keeps its caller until it is done) -- or, if that thread cannot be had, right here.
   std::thread primThread;
@@ -839,13 +844,13 @@ static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const voi
   if (k.timing) fprintf(stderr, "[lt set_scene] device: checks + leaf order %.2f ms, own hierarchy %.2f ms (%d levels), 4-wide groups %.2f ms, flags %u\n",
                         prep.ms_check, prep.ms_build, prep.levels, prep.ms_wide, prep.flags);
   if (prep.flags != 0 || prep.bvh_height > kMaxStack) return kDeviceDeclined;
-  k.lap("device preparation");
+  laps.lap("device preparation");
   if (primThread.joinable()) primThread.join();
   LT_HIP_CHECK(ctx, primError);
   bool primsOk = false;
   LT_HIP_CHECK(ctx, lt_prep::check_primitives(d_prims, n_prims, n_mats, ctx->stream, ctx->d_prep_flag, primsOk));
   if (!primsOk) return kDeviceDeclined;
-  k.lap("primitives arrived, checked");
+  laps.lap("primitives arrived, checked");
   // from here on the scene is good: it replaces the resident one
   LT_HIP_CHECK(ctx, hipDeviceSynchronize());
   free_scene(ctx);
@@ -864,20 +869,20 @@ static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const voi
   if (rc) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->retree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  k.lap("own structures, leaf records");
-  adopt_scene(ctx, sizes, hash, prep.bvh_height, true);
+  laps.lap("own structures, leaf records");
+  adopt_scene(ctx, sizes, hash, prep.bvh_height, true, k);
   return LT_OK;
 }
 
 static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const void* materials,
-                          uint64_t material_bytes, const void* lights, uint64_t light_bytes, const SceneHash* known_hash) {
+                          uint64_t material_bytes, const void* lights, uint64_t light_bytes, const SceneKnobs& k, const SceneHash* known_hash) {
   if (!ctx) return LT_ERR_INVALID_ARGUMENT;
   if (!nodes || !prims || !materials || !lights) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "NULL scene buffer");
   if (node_bytes == 0 || node_bytes % 32 || prim_bytes == 0 || prim_bytes % 76 || material_bytes == 0 || material_bytes % 32 ||
       light_bytes != 260)
     return fail(ctx, LT_ERR_BAD_SCENE, "scene buffer sizes are not whole multiples of LinearBVHNode(32) / Primitive(76) / Material(32) / LightContainer(260)");
   if (node_bytes > 0xffffffffull || prim_bytes / 76 > 0x7fffffffull / 48) return fail(ctx, LT_ERR_BAD_SCENE, "scene too large for 32-bit byte offsets (4 GiB of nodes / 2 GiB of traversal triangles)");
-  SceneKnobs k;
+  SceneLaps laps{k.timing};
   const uint32_t n_nodes = (uint32_t)(node_bytes / 32), n_prims = (uint32_t)(prim_bytes / 76), n_mats = (uint32_t)(material_bytes / 32);
   // The reference uploads all buffers on every render() (renderer_opencl.cpp:107-120); here the resident copy is kept when the
   // caller hands over the same content again: sizes and a hash of EVERY byte (so an in-place edit of any vertex, node or
@@ -885,7 +890,7 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
   const uint64_t sizes[4] = {node_bytes, prim_bytes, material_bytes, light_bytes};
   const void* const bufs[4] = {nodes, prims, materials, lights};
   const SceneHash hash = known_hash ? *known_hash : hash_scene(bufs, sizes);
-  k.lap(known_hash ? "hash (known)" : "hash");
+  laps.lap(known_hash ? "hash (known)" : "hash");
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (ctx->has_scene && memcmp(sizes, ctx->scene_sizes, sizeof(sizes)) == 0 && !k.always_upload) {
     if (hash == ctx->scene_hash) {
@@ -911,7 +916,7 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
       LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_mats, materials, material_bytes, hipMemcpyHostToDevice));
       LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_lights, lights, light_bytes, hipMemcpyHostToDevice));
       LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      adopt_scene(ctx, sizes, hash, ctx->bvh_height, ctx->device_prepared);
+      adopt_scene(ctx, sizes, hash, ctx->bvh_height, ctx->device_prepared, k);
       return LT_OK;
     }
   }
@@ -920,13 +925,13 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
   // (a malformed buffer -- the host words the error --, a tree that is not in the scene builder's pre-order, boxes that do not
   // nest) and for small ones, where a host build costs less than the launches.
   if (k.device < 0 ? n_nodes >= 8192u : k.device != 0) {
-    const int rc = set_scene_on_device(ctx, nodes, prims, materials, lights, sizes, hash, k);
+    const int rc = set_scene_on_device(ctx, nodes, prims, materials, lights, sizes, hash, k, laps);
     if (rc != kDeviceDeclined) return rc;
-    k.lap("device preparation declined");
+    laps.lap("device preparation declined");
   }
   std::string msg;
   const int height = validate_scene((const uint8_t*)nodes, n_nodes, (const uint8_t*)prims, n_prims, n_mats, (const uint8_t*)lights, msg);
-  k.lap("validate");
+  laps.lap("validate");
   if (height < 0) return fail(ctx, LT_ERR_BAD_SCENE, msg);
   if (height > kMaxStack) return fail(ctx, LT_ERR_BAD_SCENE, "BVH deeper than the reference's 64-entry traversal stack");
   LT_HIP_CHECK(ctx, hipDeviceSynchronize());
@@ -936,7 +941,7 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
   LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_tris, (size_t)n_prims * 48));
   LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_mats, materials, material_bytes));
   LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_lights, lights, light_bytes));
-  k.lap("free, malloc, upload scene");
+  laps.lap("free, malloc, upload scene");
   // The backend's own hierarchy over the same leaves (lt_retree.hpp says why the pixels cannot change), for every finite ray of
   // the non-counting kernels.  LT_RETREE=0 keeps the caller's splits (same structures, same walks).  A scene whose boxes do not
   // nest gets none: its rays walk the caller's tree one by one, in the reference's order.
@@ -957,13 +962,13 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
     std::vector<lt_retree::Node> own;
     // (height <= 30: the packet walks' stack, one VGPR, holds 2 * height + 2 entries at most; LT_RETREE=0: the caller's splits)
     const int h2 = k.own_splits ? lt_retree::build(nodes, n_nodes, 30, k.slack, own) : lt_retree::copy(nodes, n_nodes, 30, own);
-    k.lap("own hierarchy (host build)");
+    laps.lap("own hierarchy (host build)");
     if (h2 >= 0) {
       std::vector<uint32_t> children, groupOf;
       const int hw = lt_retree::collapse_wide(own, n_prims, children, groupOf);
       if (rankThread.joinable()) rankThread.join();
       if (!rankMade) lt_retree::reference_order(nodes, n_nodes, n_prims, rank8);
-      k.lap("4-wide groups, leaf order");
+      laps.lap("4-wide groups, leaf order");
       void *d_children = nullptr, *d_groupOf = nullptr;
       LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_nodes2, own.data(), own.size() * sizeof(lt_retree::Node)));
       LT_HIP_CHECK(ctx, ctx->pool.upload(&ctx->d_rank8, rank8.data(), rank8.size() * sizeof(uint32_t)));
@@ -976,13 +981,13 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
       ctx->pool.put(d_groupOf);
       if (rc) return rc;
       ctx->retree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      k.lap("own structures (upload, groups)");
+      laps.lap("own structures (upload, groups)");
     }
   }
   const int rc = remake_leaf_records(ctx, n_prims);
   if (rc) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  adopt_scene(ctx, sizes, hash, height, false);
+  adopt_scene(ctx, sizes, hash, height, false, k);
   return LT_OK;
 }
 
@@ -990,16 +995,57 @@ extern "C" int lt_hip_set_scene(lt_hip_context* ctx, const void* nodes, uint64_t
                                 uint64_t prim_bytes, const void* materials, uint64_t material_bytes, const void* lights,
                                 uint64_t light_bytes) {
   try {
-    return set_scene_impl(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, nullptr);
+    return set_scene_impl(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, SceneKnobs(), nullptr);
   } catch (const std::exception& e) {   // (std::bad_alloc, std::system_error of a thread: nothing may cross the C ABI)
     return fail(ctx, LT_ERR_HIP, std::string("lt_hip_set_scene: ") + e.what());
   }
 }
 
 // ---------------------------------------------------------------------------------- render
+// The render switches, read once at the top of every public render call (tests and bench.py change them between the calls on one
+// context): A/B measurements, tests, debugging.  None of them changes a pixel.
+struct RenderKnobs {
+  int shadow_packets = -1;              // LT_SHADOW_PACKETS=0..3: the shadow-ray walk, forced (choose_shadow_walk); -1: timed or remembered
+  float shadow_spread = 0.02f;          // LT_SHADOW_SPREAD: walk 2's threshold (SceneDev::shadowSpread is its square)
+  bool square_major = !env_off("LT_SQUARE_MAJOR");
+  bool persistent = !env_off("LT_PERSISTENT");       // off: one square per workgroup instead of persistent wavefronts
+  bool square_order = !getenv("LT_NATURAL_ORDER");   // (set to anything, "0" included: the natural hand-out order)
+  int gi_wavefront = -1;                // LT_GI_MEGAKERNEL=1 / =0: the GI programs' one-lane-per-pixel kernel / wavefront pipeline; -1: plan_fusion decides
+  bool gi_lds_scene = !env_off("LT_GI_LDS_SCENE");   // (gi_lds_scene())
+  bool gi_trace = !env_off("LT_GI_TRACE");           // off: a GI bounce stage in one kernel (launch_gi_sample)
+  uint32_t trace_refill = 24;           // LT_TRACE_REFILL=1..64: lt_trace_kernel's TraceParams::refill
+  bool fused_frames = !env_off("LT_FUSED_FRAMES");   // off: one launch per sample (plan_fusion)
+  uint64_t fused_bytes = 16ull << 30;   // LT_FUSED_BYTES: the scratch memory of fused launches
+  uint32_t debug_lds_rows = 0;          // LT_DEBUG_LDS_ROWS=1..160: LDS rows of every render launch (render_on_stream); 0: what it needs
+  bool debug_calibration = getenv("LT_DEBUG_CALIBRATION") != nullptr;   // calibrate_shadow_walk prints its timings to stderr
+  bool pinned_readback = !env_off("LT_PINNED_READBACK");   // off: lt_hip_render reads back in one copy (readback_piece)
+  RenderKnobs() {
+    if (const char* e = getenv("LT_SHADOW_PACKETS")) shadow_packets = std::max(0, std::min(3, atoi(e)));
+    if (const char* e = getenv("LT_SHADOW_SPREAD")) shadow_spread = (float)atof(e);
+    if (const char* e = getenv("LT_GI_MEGAKERNEL")) gi_wavefront = atoi(e) == 0;
+    if (const char* e = getenv("LT_TRACE_REFILL")) trace_refill = (uint32_t)std::max(1, std::min(64, atoi(e)));
+    if (const char* e = getenv("LT_FUSED_BYTES")) fused_bytes = strtoull(e, nullptr, 10);
+    if (const char* e = getenv("LT_DEBUG_LDS_ROWS")) debug_lds_rows = (uint32_t)std::max(1, std::min(160, atoi(e)));
+  }
+};
+
+// Grows a scratch buffer of the context to `need` units (`bytes` bytes): frees the old one, allocates, records the capacity
+// (0 while there is no buffer).
+template <class T>
+static hipError_t grow_scratch(T*& buf, uint64_t& capacity, uint64_t need, uint64_t bytes) {
+  if (capacity >= need) return hipSuccess;
+  hipError_t e = buf ? hipFree(buf) : hipSuccess;
+  if (e != hipSuccess) return e;
+  buf = nullptr;
+  e = hipMalloc((void**)&buf, bytes);
+  capacity = e == hipSuccess ? need : 0;
+  return e;
+}
+
 struct TilePlan {
   uint32_t tileW, tileH, tilesX, tilesY, tileFirst, tileStride, tilesInCall, bptx, bpty;
   uint64_t floats;
+  uint64_t squares() const { return (uint64_t)tilesInCall * (bptx * bpty); }   // 8x8 squares of one frame
 };
 
 static int plan_tiles(const lt_hip_render_desc* d, TilePlan& p, std::string& msg) {
@@ -1026,30 +1072,99 @@ extern "C" int lt_hip_output_floats(const lt_hip_render_desc* desc, uint64_t* ou
   TilePlan p;
   std::string msg;
   if (!out_floats) return LT_ERR_INVALID_ARGUMENT;
-  int rc = plan_tiles(desc, p, msg);
-  if (rc) return rc;
+  if (const int rc = plan_tiles(desc, p, msg)) return rc;
   *out_floats = p.floats;
   return LT_OK;
 }
 
-struct LaunchConfig { bool deep, stats; int devlibm; };   // devlibm: the math flavour, Math<0 / 1 / 2> (lt_device.hpp)
+// Every argument error of a render call past its tile plan, in the order they have always been reported.
+static int check_render_desc(lt_hip_context* ctx, const lt_hip_render_desc* d, const TilePlan& p, const float* out, uint64_t out_bytes) {
+  const bool userProgram = d->program >= LT_PROGRAM_USER_BASE;
+  if (userProgram ? (size_t)(d->program - LT_PROGRAM_USER_BASE) >= ctx->user_programs.size()
+                  : (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL))
+    return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
+  if (userProgram && (d->flags & (LT_RENDER_FLAG_STATS | LT_RENDER_FLAG_PIXEL_COUNTERS)))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "user programs are compiled without the counting variants");
+  if (d->kernel_mode != LT_KERNEL_MODE_LINEAR && d->kernel_mode != LT_KERNEL_MODE_TILE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown kernel mode");
+  if (!out) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "output pointer is NULL");
+  if (out_bytes < p.floats * sizeof(float)) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "output buffer smaller than the image/tile stack");
+  if (d->gi_max_depth < 0 || d->gi_max_depth > 64) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "gi_max_depth out of range");
+  if ((d->flags & LT_RENDER_FLAG_PIXEL_COUNTERS) && d->depth < 4) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PIXEL_COUNTERS needs depth >= 4");
+  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (p.squares() > 0x7fffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "too many workgroups");
+  return LT_OK;
+}
+
+// The resident scene as the kernels see it, no shadow-ray walk chosen yet.  The default math flavour (2) is bit-identical to the
+// reference's OpenCL kernels as RendererOpenCL builds them on this GPU; LT_RENDER_FLAG_STRICT_MATH / _PORTABLE_MATH select the
+// other two (include/lenstrace_hip.h).
+static SceneDev scene_dev(const lt_hip_context* ctx, const RenderKnobs& k, int devlibm) {
+  SceneDev sc{};
+  sc.nodes = (const float4*)ctx->d_nodes;
+  sc.wide = ctx->d_wide ? (const uint4*)ctx->d_wide + 4 : nullptr;   // (behind the 64 bytes that hold the grid)
+  sc.ownPairs = (const float4*)ctx->d_pairs2;
+  sc.rank8 = (const uint32_t*)ctx->d_rank8;
+  sc.nWide = ctx->d_rank8 ? ctx->n_wide : 0u;
+  sc.tris = (const float4*)ctx->d_tris; sc.prims = (const float*)ctx->d_prims;
+  sc.mats = (const Material*)ctx->d_mats; sc.lights = (const Lights*)ctx->d_lights;
+  sc.n_nodes = ctx->n_nodes; sc.n_prims = ctx->n_prims; sc.n_mats = ctx->n_mats;
+  sc.shadowSpread = k.shadow_spread * k.shadow_spread;
+  sc.fastRcp = devlibm == 2 ? 1u : 0u;
+  return sc;
+}
+
+// What is the same for every frame of a call; the frame loop of render_on_stream fills in the rest.
+static FrameParams frame_params(const lt_hip_render_desc* d, const TilePlan& p, const RenderKnobs& k) {
+  float cam[7];
+  memcpy(cam, d->camera, 28);
+  FrameParams fp{};
+  fp.camx = cam[0]; fp.camy = cam[1]; fp.camz = cam[2];
+  fp.apx = 0.0f; fp.apy = 0.0f; fp.apz = 5.0f;
+  fp.cosYaw = (float)std::cos((double)cam[3]);
+  fp.sinYaw = (float)std::sin((double)cam[3]);
+  fp.yaw = cam[3];
+  fp.width = d->width; fp.height = d->height; fp.depth = d->depth;
+  fp.clampOutput = d->kernel_mode == LT_KERNEL_MODE_LINEAR;
+  fp.squareMajor = k.square_major ? 1u : 0u;
+  fp.giMaxDepth = d->gi_max_depth ? d->gi_max_depth : 16;
+  fp.tileW = p.tileW; fp.tileH = p.tileH; fp.tilesX = p.tilesX; fp.tileFirst = p.tileFirst; fp.tileStride = p.tileStride;
+  fp.tilesInCall = p.tilesInCall; fp.totalSquares = (uint32_t)p.squares();
+  fp.blocksPerTileX = p.bptx; fp.blocksPerTile = p.bptx * p.bpty;
+  fp.pixelCounters = (d->flags & LT_RENDER_FLAG_PIXEL_COUNTERS) != 0;
+  fp.persistent = k.persistent;
+  return fp;
+}
+
+// What the launches of one render call share: render_on_stream fills it in once, before its frame loop.
+struct RenderCall {
+  const lt_hip_render_desc* d; const RenderKnobs& k; hipStream_t s;
+  bool deep, stats;       // the counting kernels, in their deep-tree form
+  int devlibm;            // the math flavour, Math<0 / 1 / 2> (lt_device.hpp)
+  uint32_t lds;           // LDS of a render launch's workgroup
+  uint32_t ldsRefBytes;   // LDS of a wave whose per-lane stack follows the caller's tree (the LDS-scene GI launches)
+  uint64_t nblocks;       // 8x8 squares of one frame
+  uint32_t launches;      // lt_hip_stats::kernel_launches
+};
+
+// f(std::integral_constant<int, M>) for the math flavour M of a launch.
+template <class F>
+static auto with_math(int devlibm, F&& f) {
+  return devlibm == 2 ? f(std::integral_constant<int, 2>{}) : devlibm == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+}
 
 template <int PROGRAM>
-static void launch_program(const LaunchConfig& k, dim3 grid, uint32_t lds, hipStream_t s, const SceneDev& sc, const FrameParams& fp,
-                           float* out, unsigned long long* st, uint32_t* queues) {
-#define LT_LAUNCH(D, S, M) hipLaunchKernelGGL((lt_render_kernel<PROGRAM, Config<D, S, M>>), grid, dim3(kBlock), lds, s, sc, fp, out, st, queues)
-  // (DEEP -- LDS stack rows beyond kLdsStack spilled to scratch -- concerns the counting kernels only: the others keep no per-lane
-  // stack in LDS, whatever the height of the caller's tree)
-  if constexpr (PROGRAM == kAccumulatorQueue) {   // (never a counting launch)
-    if (k.devlibm == 2) LT_LAUNCH(false, false, 2); else if (k.devlibm == 1) LT_LAUNCH(false, false, 1); else LT_LAUNCH(false, false, 0);
-  } else if (k.devlibm == 2) {     // the default flavour: the reference kernels as RendererOpenCL builds them
-    if (k.stats) { if (k.deep) LT_LAUNCH(true, true, 2); else LT_LAUNCH(false, true, 2); } else LT_LAUNCH(false, false, 2);
-  } else if (k.devlibm == 1) {   // strict build of the reference kernels
-    if (k.stats) { if (k.deep) LT_LAUNCH(true, true, 1); else LT_LAUNCH(false, true, 1); } else LT_LAUNCH(false, false, 1);
-  } else {
-    if (k.stats) { if (k.deep) LT_LAUNCH(true, true, 0); else LT_LAUNCH(false, true, 0); } else LT_LAUNCH(false, false, 0);
-  }
-#undef LT_LAUNCH
+static void launch_program(const RenderCall& c, const SceneDev& sc, const FrameParams& fp, dim3 grid, float* out, unsigned long long* st, uint32_t* queues) {
+  with_math(c.devlibm, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    auto launch = [&](auto cfg) { hipLaunchKernelGGL((lt_render_kernel<PROGRAM, decltype(cfg)>), grid, dim3(kBlock), c.lds, c.s, sc, fp, out, st, queues); };
+    // (DEEP -- LDS stack rows beyond kLdsStack spilled to scratch -- concerns the counting kernels only: the others keep no per-lane
+    // stack in LDS, whatever the height of the caller's tree; kAccumulatorQueue is never a counting launch)
+    if constexpr (PROGRAM == kAccumulatorQueue) launch(Config<false, false, M>{});
+    else if (c.stats && c.deep) launch(Config<true, true, M>{});
+    else if (c.stats) launch(Config<false, true, M>{});
+    else launch(Config<false, false, M>{});
+  });
 }
 
 // 8 per-XCD square queues, queue lengths, bounce work counters, trace work counters (extension rays, shadow rays), hit-list lengths:
@@ -1066,24 +1181,35 @@ static int ensure_gi_buffers(lt_hip_context* ctx, uint64_t pixels) {
   return LT_OK;
 }
 
+// A scene of a few hundred triangles rides in LDS for the GI bounce stages' per-lane walks (Config::kLdsScene): workgroups of
+// eight waves share one copy.  LT_GI_LDS_SCENE=0 turns it off (A/B measurements).
+static uint64_t scene_lds_bytes(const lt_hip_context* ctx) { return (uint64_t)ctx->n_nodes * 32 + (uint64_t)ctx->n_prims * 48; }
+static bool gi_lds_scene(const lt_hip_context* ctx, const RenderKnobs& k) {
+  return ctx->bvh_height <= kLdsStack && scene_lds_bytes(ctx) <= 16384 && k.gi_lds_scene;   // (its walks keep the LDS stack)
+}
+
 // fp.fusedFrames samples of a global-illumination program through one set of stage launches of the wavefront pipeline
 // (lt_kernel.hpp): frames sample, sample + 1, ... of the single-sample program (blend25Out == nullptr: the resolve stage
 // writes each frame's clamped colour to out + frame * fp.frameStride, or straight to the image when there is one frame), or
 // samples k0 .. k0 + fusedFrames - 1 of ONE frame of the 25-sample variant (blend25Out = the image: the resolve stage
 // writes raw colours to `out`, lt_gi_blend25_kernel blends them in order and finishes the pixel with accumulateN).
 template <class CFG>
-static int launch_gi_sample(lt_hip_context* ctx, hipStream_t s, const SceneDev& sc, const FrameParams& fp, float* out, uint32_t lds,
-                            uint64_t pixels, uint32_t sample, uint32_t k0, float* blend25Out, int32_t accumulateN, uint32_t& launches) {
+static int launch_gi_sample(lt_hip_context* ctx, RenderCall& c, const SceneDev& sc, const FrameParams& fp, float* out, uint64_t pixels,
+                            uint32_t sample, uint32_t k0, float* blend25Out, int32_t accumulateN) {
   // `pixels` = compact output pixels of ONE frame
+  const hipStream_t s = c.s;
   GiParams gp{};
   for (int k = 0; k < 2; k++) {
     gp.q[k].o = (float4*)ctx->d_gi[4 * k + 0]; gp.q[k].d = (float4*)ctx->d_gi[4 * k + 1];
     gp.q[k].n = (float4*)ctx->d_gi[4 * k + 2]; gp.q[k].m = (uint4*)ctx->d_gi[4 * k + 3];
   }
   gp.direct = (float4*)ctx->d_gi[8]; gp.indirect = (float4*)ctx->d_gi[9]; gp.blend = (float4*)ctx->d_gi[10];
+  // the control block behind the 8 square queues: runs of kMaxStack + 2 counters, one per stage (the trace launches' in eights)
+  auto ctl = [&](uint32_t run) { return ctx->d_giCtl + (8 + run * (kMaxStack + 2)) * kQueueStride; };
   uint32_t* queues = ctx->d_giCtl;
-  gp.counts = ctx->d_giCtl + 8 * kQueueStride;
-  gp.work = ctx->d_giCtl + (8 + (kMaxStack + 2)) * kQueueStride;
+  gp.counts = ctl(0); gp.work = ctl(1); gp.hitCount = ctl(2);
+  uint32_t* const traceWork = ctl(3);     // 8 per stage
+  uint32_t* const shadowWork = ctl(11);   // 8 per stage
   gp.sample = sample;
   gp.raw = blend25Out ? 1u : 0u;
   gp.pixels = (uint32_t)pixels;
@@ -1092,38 +1218,27 @@ static int launch_gi_sample(lt_hip_context* ctx, hipStream_t s, const SceneDev& 
   const uint32_t resident = (uint32_t)ctx->cu_count * 4u * LT_GI_STAGE_WAVES;
   const uint32_t gridA = (uint32_t)std::min<uint64_t>((uint64_t)fp.totalSquares * fp.fusedFrames, resident);
   // the primary stage's shadow rays are accumulator's (same light samples from the same camera hits): any-hit packets unless this
-  // scene's accumulator frames were timed faster per lane (render_on_stream) or LT_SHADOW_PACKETS says otherwise; the bounce
+  // scene's accumulator frames were timed faster per lane (calibrate_shadow_walk) or LT_SHADOW_PACKETS says otherwise; the bounce
   // stages' shadow rays start on scattered bounce hits and stay per lane
   SceneDev scPrimary = sc;
   {
-    const char* spe = getenv("LT_SHADOW_PACKETS");
     const int timed = ctx->shadow_mode[LT_PROGRAM_ACCUMULATOR];
-    scPrimary.shadowPackets = spe ? (uint32_t)std::max(0, std::min(3, atoi(spe))) : (timed < 0 ? 1u : (uint32_t)timed);
-    if (scPrimary.shadowPackets == 3u) scPrimary.shadowPackets = 0u;   // (queued is accumulator's own; where it won, the rays are not packets)
+    const int mode = c.k.shadow_packets >= 0 ? c.k.shadow_packets : timed < 0 ? 1 : timed;
+    scPrimary.shadowPackets = mode == 3 ? 0u : (uint32_t)mode;   // (queued is accumulator's own; where it won, the rays are not packets)
   }
-  // A scene of a few hundred triangles rides in LDS for the bounce stages' per-lane walks (Config::kLdsScene): workgroups of
-  // eight waves share one copy.  LT_GI_LDS_SCENE=0 turns it off (A/B measurements).
-  const uint64_t sceneLdsBytes = (uint64_t)ctx->n_nodes * 32 + (uint64_t)ctx->n_prims * 48;
-  const char* le = getenv("LT_GI_LDS_SCENE");
-  const bool ldsScene = ctx->bvh_height <= kLdsStack && sceneLdsBytes <= 16384 && !(le && atoi(le) == 0);   // (its walks keep the LDS stack)
+  const bool ldsScene = gi_lds_scene(ctx, c.k);
   // With a tree of the backend's own to walk, a bounce stage is five launches instead of one (lt_kernel.hpp): its extension rays
   // through lt_trace_kernel, whose lanes take a new ray when theirs is done; the paths sorted into light hits, misses and
   // surface hits; the surface hits' light samples; their shadow rays through lt_trace_kernel; the survivors' next rays.
   // LT_GI_TRACE=0: the one-kernel stage (A/B measurements).
-  const char* te = getenv("LT_GI_TRACE");
-  const bool pretrace = !ldsScene && ctx->d_rank8 != nullptr && !(te && atoi(te) == 0);
-  gp.hitCount = ctx->d_giCtl + (8 + 2 * (kMaxStack + 2)) * kQueueStride;
+  const bool pretrace = !ldsScene && ctx->d_rank8 != nullptr && c.k.gi_trace;
   gp.directQueue = pretrace ? 1u : 0u;
-  hipLaunchKernelGGL((lt_gi_primary_kernel<CFG>), dim3(gridA), dim3(kBlock), lds, s, scPrimary, fp, gp, queues);
+  hipLaunchKernelGGL((lt_gi_primary_kernel<CFG>), dim3(gridA), dim3(kBlock), c.lds, s, scPrimary, fp, gp, queues);
   LT_HIP_CHECK(ctx, hipGetLastError());
-  launches++;
-  gp.ldsRows = ctx->lds_ref_bytes / (kBlock * sizeof(int));   // (read by the multi-wave workgroups of the LDS-scene launches only)
-  uint32_t* traceWork = ctx->d_giCtl + (8 + 3 * (kMaxStack + 2)) * kQueueStride;    // 8 per stage
-  uint32_t* shadowWork = ctx->d_giCtl + (8 + 11 * (kMaxStack + 2)) * kQueueStride;  // 8 per stage
+  c.launches++;
+  gp.ldsRows = c.ldsRefBytes / (kBlock * sizeof(int));   // (read by the multi-wave workgroups of the LDS-scene launches only)
   gp.hitList = (uint32_t*)ctx->d_gi[12];
   gp.so = (float4*)ctx->d_gi[13]; gp.sd = (float4*)ctx->d_gi[14]; gp.sm = (uint4*)ctx->d_gi[15]; gp.sn = (float4*)ctx->d_gi[16];
-  const char* re = getenv("LT_TRACE_REFILL");
-  const uint32_t refill = re ? (uint32_t)std::max(1, std::min(64, atoi(re))) : 24u;
   const uint32_t traceLds = (uint32_t)((kTraceRows + kTraceStage) * kBlock * sizeof(int));
   const dim3 streamGrid((uint32_t)ctx->cu_count * 8u), streamBlock(256);
   for (int d = 0; d < fp.giMaxDepth; d++) {
@@ -1135,7 +1250,7 @@ static int launch_gi_sample(lt_hip_context* ctx, hipStream_t s, const SceneDev& 
       tp.hit = (uint4*)ctx->d_gi[11];
       tp.count = gp.counts + (size_t)d * kQueueStride;
       tp.next = traceWork + (size_t)d * 8 * kQueueStride;
-      tp.refill = refill;
+      tp.refill = c.k.trace_refill;
       tp.dead = d == 0 ? 1u : 0u;
       gp.hits = tp.hit;
       hipLaunchKernelGGL((lt_trace_kernel<kGI, false>), dim3(resident), dim3(kBlock), traceLds, s, sc, tp);
@@ -1150,22 +1265,22 @@ static int launch_gi_sample(lt_hip_context* ctx, hipStream_t s, const SceneDev& 
       hipLaunchKernelGGL((lt_trace_kernel<kGI, true>), dim3(resident), dim3(kBlock), traceLds, s, sc, tp);
       hipLaunchKernelGGL((lt_gi_finish_kernel<CFG>), streamGrid, streamBlock, 0, s, sc, fp, gp, (uint32_t)d);
       LT_HIP_CHECK(ctx, hipGetLastError());
-      launches += 5;
+      c.launches += 5;
       continue;
     }
     if (ldsScene) {
       using CFGL = Config<false, false, CFG::kDevLibm, true>;
       hipLaunchKernelGGL((lt_gi_bounce_kernel<CFGL>), dim3((resident + kLdsSceneWaves - 1) / kLdsSceneWaves), dim3(kBlock * kLdsSceneWaves),
-                         (uint32_t)sceneLdsBytes + kLdsSceneWaves * ctx->lds_ref_bytes, s, sc, fp, gp, (uint32_t)d);
+                         (uint32_t)scene_lds_bytes(ctx) + kLdsSceneWaves * c.ldsRefBytes, s, sc, fp, gp, (uint32_t)d);
     } else {
-      hipLaunchKernelGGL((lt_gi_bounce_kernel<CFG>), dim3(resident), dim3(kBlock), lds, s, sc, fp, gp, (uint32_t)d);
+      hipLaunchKernelGGL((lt_gi_bounce_kernel<CFG>), dim3(resident), dim3(kBlock), c.lds, s, sc, fp, gp, (uint32_t)d);
     }
     LT_HIP_CHECK(ctx, hipGetLastError());
-    launches++;
+    c.launches++;
   }
   hipLaunchKernelGGL((lt_gi_resolve_kernel<CFG>), dim3((uint32_t)((vpixels + 255) / 256)), dim3(256), 0, s, fp, gp, out, (uint32_t)vpixels);
   LT_HIP_CHECK(ctx, hipGetLastError());
-  launches++;
+  c.launches++;
   if (blend25Out) {
     FrameParams fb = fp;
     fb.accumulateN = accumulateN;
@@ -1191,11 +1306,8 @@ static int ensure_square_order(lt_hip_context* ctx, const lt_hip_render_desc* d,
   const uint64_t n = (uint64_t)p.tilesInCall * bpt;
   if (n == 0) return LT_OK;
   const std::vector<uint32_t> key = {d->width, d->height, p.tileW, p.tileH, p.tileFirst, p.tileStride, (uint32_t)cx, (uint32_t)cy};
-  if (key == ctx->order_key) {
-    *order = ctx->d_order;
-    for (int i = 0; i < 8; i++) head[i] = ctx->order_head[i];
-    return LT_OK;
-  }
+  auto hand_out = [&]() { *order = ctx->d_order; for (int i = 0; i < 8; i++) head[i] = ctx->order_head[i]; return LT_OK; };
+  if (key == ctx->order_key) return hand_out();
   std::vector<uint32_t> ord((size_t)n);
   const uint64_t q = n / 8, r = n % 8;
   for (uint32_t xcd = 0; xcd < 8; xcd++) {
@@ -1235,28 +1347,20 @@ static int ensure_square_order(lt_hip_context* ctx, const lt_hip_render_desc* d,
     std::copy(rest.begin(), rest.end(), ord.begin() + pos);
   }
   ctx->order_key.clear();
-  if (ctx->order_capacity < n) {
-    if (ctx->d_order) LT_HIP_CHECK(ctx, hipFree(ctx->d_order));
-    ctx->d_order = nullptr;
-    ctx->order_capacity = 0;
-    LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_order, n * sizeof(uint32_t)));
-    ctx->order_capacity = n;
-  }
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_order, ctx->order_capacity, n, n * sizeof(uint32_t)));
   // (rare path: image size, tiling or camera rotation changed)  No launch of an earlier call, on whatever stream, may still
   // be reading the old order; and `ord` must outlive the copy.
   LT_HIP_CHECK(ctx, hipDeviceSynchronize());
   LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_order, ord.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
   ctx->order_key = key;
-  *order = ctx->d_order;
-  for (int i = 0; i < 8; i++) head[i] = ctx->order_head[i];
-  return LT_OK;
+  return hand_out();
 }
 
 // The wavefront GI pipeline for one iteration of render_on_stream's frame loop: one set of stage launches for the
 // fp.fusedFrames frames of the single-sample program (samplesPerSet == 0; colours go to stageOut), or ceil(25 / samplesPerSet)
 // sets for the 25 samples of the one frame of the 25-sample variant (raw colours to ctx->d_samples, blended into `image`).
-static int launch_gi_sets(lt_hip_context* ctx, hipStream_t s, const SceneDev& sc, const FrameParams& fp, const LaunchConfig& lc, uint32_t lds,
-                          uint64_t giPixels, uint32_t samplesPerSet, uint64_t floats, float* stageOut, float* image, uint32_t& launches) {
+static int launch_gi_sets(lt_hip_context* ctx, RenderCall& c, const SceneDev& sc, const FrameParams& fp, uint64_t giPixels, uint32_t samplesPerSet,
+                          uint64_t floats, float* stageOut, float* image) {
   const bool gi25 = samplesPerSet != 0u;
   const uint32_t sets = gi25 ? (25u + samplesPerSet - 1u) / samplesPerSet : 1u;
   for (uint32_t set = 0; set < sets; set++) {
@@ -1273,19 +1377,30 @@ static int launch_gi_sets(lt_hip_context* ctx, hipStream_t s, const SceneDev& sc
       out = ctx->d_samples;
       sample = fp.frameCount * 32u + k0;
     }
-    int rc;
-#define LT_GI(D, M) launch_gi_sample<Config<D, false, M>>(ctx, s, sc, fs, out, lds, giPixels, sample, k0, blendOut, fp.accumulateN, launches)
-    rc = lc.devlibm == 2 ? LT_GI(false, 2) : lc.devlibm == 1 ? LT_GI(false, 1) : LT_GI(false, 0);   // (never a counting launch: no deep-tree form)
-#undef LT_GI
+    const int rc = with_math(c.devlibm, [&](auto m) {   // (never a counting launch: no deep-tree form)
+      return launch_gi_sample<Config<false, false, decltype(m)::value>>(ctx, c, sc, fs, out, giPixels, sample, k0, blendOut, fp.accumulateN);
+    });
     if (rc) return rc;
   }
   return LT_OK;
 }
 
+// lt_hip_render's read-back of `need` bytes: eight pieces of this many bytes each (enqueue_readback), and the call's last fold cut
+// into the same pieces (launch_running_mean); 0 (LT_PINNED_READBACK=0, a small image): one copy, one fold launch.
+static uint64_t readback_piece(const RenderKnobs& k, uint64_t need) {
+  return k.pinned_readback && need >= (1u << 20) ? ((need + 7) / 8 + 4095) / 4096 * 4096 : 0;
+}
+
+// One lt_hip_render call's read-back of ctx->d_out.
+struct ReadBack {
+  uint64_t need = 0, piece = 0;   // bytes of the image; readback_piece (0 once enqueue_readback has no pinned buffer to stage in)
+  bool foldPieced = false;        // the call's last fold came in the pieces, an event behind each (launch_running_mean)
+};
+
 // Folds the nf sample images a fused launch left in ctx->d_samples into `out` (timed by its own event pair, so that
 // lt_hip_stats::render_ms can leave it out).
 static int launch_running_mean(lt_hip_context* ctx, hipStream_t s, const FrameParams& fp, uint64_t floats, uint32_t nf, int32_t base,
-                               bool paddedTiles, float* out, bool lastOfCall) {
+                               bool paddedTiles, float* out, ReadBack* rb) {
   const uint32_t threads = 256;
   while (ctx->mean_events.size() < 2 * (size_t)(ctx->mean_pairs + 1)) {
     hipEvent_t e;
@@ -1293,12 +1408,11 @@ static int launch_running_mean(lt_hip_context* ctx, hipStream_t s, const FramePa
     ctx->mean_events.push_back(e);
   }
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->mean_events[2 * ctx->mean_pairs], s));
-  ctx->fold_pieced = false;
-  if (lastOfCall && ctx->fold_piece_bytes != 0 && out == ctx->d_out && s == ctx->stream) {
+  if (rb && rb->piece != 0) {
     // lt_hip_render: the call's last fold in the eight pieces of the read-back, an event behind each, so that piece k travels
     // (enqueue_readback, on the copy stream) while piece k + 1 is folded
     for (hipEvent_t& e : ctx->fold_ev) if (!e) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const uint64_t per = ctx->fold_piece_bytes / sizeof(float);
+    const uint64_t per = rb->piece / sizeof(float);
     for (int k = 0; k < 8; k++) {
       const uint64_t lo = std::min(floats, (uint64_t)k * per), hi = std::min(floats, lo + per);
       if (hi > lo)
@@ -1306,7 +1420,7 @@ static int launch_running_mean(lt_hip_context* ctx, hipStream_t s, const FramePa
                                                                                                          paddedTiles ? 1 : 0);
       LT_HIP_CHECK(ctx, hipEventRecord(ctx->fold_ev[k], s));
     }
-    ctx->fold_pieced = true;
+    rb->foldPieced = true;
   } else {
     lt_running_mean_kernel<<<dim3((uint32_t)((floats + threads - 1) / threads)), dim3(threads), 0, s>>>(ctx->d_samples, nf, floats, out, 0ull, floats,
                                                                                                     base, fp, paddedTiles ? 1 : 0);
@@ -1321,14 +1435,14 @@ static int launch_running_mean(lt_hip_context* ctx, hipStream_t s, const FramePa
 // frames (or, for the 25-sample variant, samples of one frame) travel through one launch, and the scratch memory for them.
 struct FusionPlan {
   bool giWavefront = false;     // wavefront pipeline instead of the one-lane-per-pixel kernel
-  bool gi25Sets = false;        // 25-sample variant through the pipeline: samplesPerSet samples per set of stage launches
   uint32_t chunk = 1;           // frames per launch (> 1: fused; lt_running_mean_kernel folds them)
-  uint32_t samplesPerSet = 0;
+  uint32_t samplesPerSet = 0;   // 25-sample variant through the pipeline: samples per set of stage launches (0: another program)
   uint64_t giPixels = 0;        // compact output pixels of one frame
 };
 
-static int plan_fusion(lt_hip_context* ctx, const lt_hip_render_desc* d, const TilePlan& p, uint32_t frames, uint64_t nblocks, bool stats,
-                       bool persistent, int giMaxDepth, FusionPlan& out) {
+static int plan_fusion(lt_hip_context* ctx, const RenderKnobs& k, const lt_hip_render_desc* d, const TilePlan& p, uint32_t frames, bool stats,
+                       int giMaxDepth, FusionPlan& out) {
+  const uint64_t nblocks = p.squares();
   // The global-illumination programs run as a wavefront pipeline with path compaction when the scene is big enough for the
   // traversal to dominate the ~18 launches and the queue traffic per sample (1 M-triangle wall at 4K, 16 bounces: 31 ms
   // against 52 ms for the one-lane-per-pixel kernel; 42-triangle Cornell box at 1080p: 3.5 ms against 2.7 ms), or when the
@@ -1337,15 +1451,12 @@ static int plan_fusion(lt_hip_context* ctx, const lt_hip_render_desc* d, const T
   // 37 against 55 ms at 16 bounces, 27.5 against 21 ms at 4), and never when work is being counted (the counting kernels
   // re-trace like the reference does).  LT_GI_MEGAKERNEL=1 / =0 force one or the other (A/B measurements, tests of both
   // paths on small scenes).
-  const char* ge = getenv("LT_GI_MEGAKERNEL");
   const bool giProgram = d->program == LT_PROGRAM_GLOBAL_ILLUMINATION || d->program == LT_PROGRAM_GLOBAL_ILLUMINATION_25;
   // (a scene small enough to ride in LDS through the bounce stages, launch_gi_sample, takes the pipeline from 2 bounces on:
   // Cornell 1080p, 16 frames per call, 4 bounces: 8.6 against 10.9 ms; 25-sample variant 12.9 against 19.9 ms)
-  const bool ldsScene = ctx->bvh_height <= kLdsStack && (uint64_t)ctx->n_nodes * 32 + (uint64_t)ctx->n_prims * 48 <= 16384 &&
-                        !(getenv("LT_GI_LDS_SCENE") && atoi(getenv("LT_GI_LDS_SCENE")) == 0);
-  const bool giManyLongPaths = giMaxDepth > (ldsScene ? 1 : 8) && (d->program == LT_PROGRAM_GLOBAL_ILLUMINATION_25 ||
-                                                                   (d->program == LT_PROGRAM_GLOBAL_ILLUMINATION && frames > 1 && d->accumulate));
-  const bool giWavefront = giProgram && !stats && nblocks > 0 && (ge ? atoi(ge) == 0 : (ctx->n_prims >= 1024u || giManyLongPaths));
+  const bool giManyLongPaths = giMaxDepth > (gi_lds_scene(ctx, k) ? 1 : 8) && (d->program == LT_PROGRAM_GLOBAL_ILLUMINATION_25 ||
+                                                                               (d->program == LT_PROGRAM_GLOBAL_ILLUMINATION && frames > 1 && d->accumulate));
+  const bool giWavefront = giProgram && !stats && nblocks > 0 && (k.gi_wavefront >= 0 ? k.gi_wavefront != 0 : (ctx->n_prims >= 1024u || giManyLongPaths));
   const uint64_t giPixels = (uint64_t)p.tilesInCall * p.tileW * p.tileH;
   const uint64_t giSlots = std::max<uint64_t>(giPixels, nblocks * kBlock);   // (a direct-mapped path queue has a slot per lane of every square)
   if (giWavefront && giSlots > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "too many pixels for the GI path queues");
@@ -1364,27 +1475,17 @@ static int plan_fusion(lt_hip_context* ctx, const lt_hip_render_desc* d, const T
   uint32_t chunk = 1;
   const bool giFusable = giWavefront && d->program == LT_PROGRAM_GLOBAL_ILLUMINATION;
   const bool gi25Sets = giWavefront && d->program == LT_PROGRAM_GLOBAL_ILLUMINATION_25;
-  if (gi25Sets || ((giFusable || (persistent && !giWavefront)) && !stats && frames > 1 && d->accumulate && nblocks > 0)) {
-    const char* fe = getenv("LT_FUSED_FRAMES");
-    const char* fb = getenv("LT_FUSED_BYTES");
-    const uint64_t cap = fb ? strtoull(fb, nullptr, 10) : (16ull << 30);
+  if (gi25Sets || ((giFusable || (k.persistent && !giWavefront)) && !stats && frames > 1 && d->accumulate && nblocks > 0)) {
     const uint64_t frameBytes = p.floats * sizeof(float);
     const uint64_t scratchPerFrame = frameBytes + (giWavefront ? giSlots * 16 * 17 : 0);
-    if (!(fe && atoi(fe) == 0) && frameBytes > 0)
-      chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)(gi25Sets ? 25u : frames), cap / scratchPerFrame, 0xffffffffull / nblocks,
+    if (k.fused_frames && frameBytes > 0)
+      chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)(gi25Sets ? 25u : frames), k.fused_bytes / scratchPerFrame, 0xffffffffull / nblocks,
                                                                   giWavefront ? 0xffffffffull / std::max<uint64_t>(giSlots, 1) : ~0ull}));
-    if ((chunk > 1 || gi25Sets) && ctx->d_samples_bytes < chunk * frameBytes) {
-      if (ctx->d_samples) LT_HIP_CHECK(ctx, hipFree(ctx->d_samples));
-      ctx->d_samples = nullptr;
-      ctx->d_samples_bytes = 0;
-      // a device that cannot spare the scratch memory gets shorter launches, down to one sample per launch
-      while ((chunk > 1 || gi25Sets) && hipMalloc((void**)&ctx->d_samples, chunk * frameBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->d_samples = nullptr;
-        if (chunk == 1) return fail(ctx, LT_ERR_HIP, "out of device memory for one sample image");
-        chunk /= 2;
-      }
-      ctx->d_samples_bytes = ctx->d_samples ? chunk * frameBytes : 0;
+    // a device that cannot spare the scratch memory gets shorter launches, down to one sample per launch
+    while ((chunk > 1 || gi25Sets) && grow_scratch(ctx->d_samples, ctx->d_samples_bytes, chunk * frameBytes, chunk * frameBytes) != hipSuccess) {
+      (void)hipGetLastError();
+      if (chunk == 1) return fail(ctx, LT_ERR_HIP, "out of device memory for one sample image");
+      chunk /= 2;
     }
   }
   if (giWavefront) {
@@ -1393,301 +1494,210 @@ static int plan_fusion(lt_hip_context* ctx, const lt_hip_render_desc* d, const T
     if (erc) return erc;
   }
   out.giWavefront = giWavefront;
-  out.gi25Sets = gi25Sets;
   out.giPixels = giPixels;
   out.samplesPerSet = gi25Sets ? chunk : 0u;   // 25-sample variant: samples k per set of stage launches
   out.chunk = gi25Sets ? 1u : chunk;           // ... and its frames stay one per iteration of the caller's loop
   return LT_OK;
 }
 
-static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, float* out_device, uint64_t out_bytes, hipStream_t s) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_render before lt_hip_set_scene");
-  TilePlan p;
-  std::string msg;
-  int rc = plan_tiles(d, p, msg);
-  if (rc) return fail(ctx, rc, msg);
-  const bool userProgram = d->program >= LT_PROGRAM_USER_BASE;
-  if (userProgram ? (size_t)(d->program - LT_PROGRAM_USER_BASE) >= ctx->user_programs.size()
-                  : (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL))
-    return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
-  if (userProgram && (d->flags & (LT_RENDER_FLAG_STATS | LT_RENDER_FLAG_PIXEL_COUNTERS)))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "user programs are compiled without the counting variants");
-  if (d->kernel_mode != LT_KERNEL_MODE_LINEAR && d->kernel_mode != LT_KERNEL_MODE_TILE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown kernel mode");
-  if (!out_device) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-  if (out_bytes < p.floats * sizeof(float)) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "output buffer smaller than the image/tile stack");
-  if (d->gi_max_depth < 0 || d->gi_max_depth > 64) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "gi_max_depth out of range");
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-
-  float cam[7];
-  uint32_t camFrame;
-  memcpy(cam, d->camera, 28);
-  memcpy(&camFrame, d->camera + 24, 4);
-
-  SceneDev sc;
-  sc.nodes = (const float4*)ctx->d_nodes;
-  sc.wide = ctx->d_wide ? (const uint4*)ctx->d_wide + 4 : nullptr;   // (behind the 64 bytes that hold the grid)
-  sc.ownPairs = (const float4*)ctx->d_pairs2;
-  sc.rank8 = (const uint32_t*)ctx->d_rank8;
-  sc.nWide = ctx->d_rank8 ? ctx->n_wide : 0u;
-  sc.tris = (const float4*)ctx->d_tris;
-  sc.prims = (const float*)ctx->d_prims;
-  sc.mats = (const Material*)ctx->d_mats;
-  sc.lights = (const Lights*)ctx->d_lights;
-  sc.n_nodes = ctx->n_nodes; sc.n_prims = ctx->n_prims; sc.n_mats = ctx->n_mats;
-  // Shadow rays as any-hit packets, per lane, chosen per wavefront (traverse(), lt_device.hpp) or queued for lt_trace_kernel
-  // (accumulator): which is fastest depends on the scene (wall: packets; soup: the queue), so each (scene, program, image geometry,
-  // frames per launch) is timed once, on the first launch that can be repeated without changing the result, and the fastest
-  // walk kept.  LT_SHADOW_PACKETS=0/1/2/3 forces one (tests, A/B measurements).
-  const char* spe = getenv("LT_SHADOW_PACKETS");
+// Shadow rays as any-hit packets (1), per lane (0), chosen per wavefront (2: traverse(), lt_device.hpp) or queued for
+// lt_trace_kernel (3: accumulator): which is fastest depends on the scene (wall: packets; soup: the queue), so each (scene,
+// program, image geometry, frames per launch) is timed once, on the first launch that can be repeated without changing the
+// result (calibrate_shadow_walk), and the fastest walk kept.  LT_SHADOW_PACKETS=0/1/2/3 forces one (tests, A/B measurements).
+// -1: to be timed.  `queueOk`: the call's launches can queue their shadow rays (or there are none).
+static int choose_shadow_walk(lt_hip_context* ctx, const RenderKnobs& k, const lt_hip_render_desc* d, const std::vector<uint32_t>& key, bool queueOk) {
   const bool hasShadowRays = d->program == LT_PROGRAM_ACCUMULATOR || d->program == LT_PROGRAM_BASIC_LIGHTING;   // (the GI programs' kernels hold the per-lane walk only)
-  // (keyed on the image geometry too: how coherent a wavefront's 64 shadow rays are depends on how large its 8x8 pixels are in
-  // the scene; shadow_mode[program] keeps the most recent verdict for callers without a geometry of their own: the GI pipeline)
-  std::vector<uint32_t> shadowKey = {(uint32_t)d->program, d->width, d->height, p.tileW, p.tileH, p.tileFirst, p.tileStride, 0u};   // (+ frames per launch, below)
-  int shadowMode = 0;   // (looked up once the frames per launch are known, below)
-  sc.shadowPackets = 0u;
-  sc.shadowQueue = nullptr;
-  sc.shadowCap = 0u;
-  {
-    const char* se = getenv("LT_SHADOW_SPREAD");
-    const float thr = se ? (float)atof(se) : 0.02f;
-    sc.shadowSpread = thr * thr;
-  }
-  sc.ldsNodes = sc.ldsTris = 0u;
-  sc.fastRcp = 0u;
+  int mode = k.shadow_packets >= 0 ? k.shadow_packets : hasShadowRays ? -1 : 0;
+  if (mode < 0 && ctx->shadow_modes.count(key)) mode = ctx->shadow_modes[key];
+  if (mode < 0 && (d->flags & LT_RENDER_FLAG_NO_WALK_TIMING))   // the caller wants no timing launches in this call
+    mode = ctx->shadow_mode[d->program] >= 0 ? ctx->shadow_mode[d->program] : 1;
+  if (mode == 3 && d->program != LT_PROGRAM_ACCUMULATOR) mode = 0;   // (queued shadow rays are accumulator's)
+  if (mode == 3 && !queueOk) mode = k.shadow_packets >= 0 ? 0 : -1;   // (a forced or remembered mode 3 where it cannot run)
+  return mode;
+}
 
-  FrameParams fp{};
-  fp.camx = cam[0]; fp.camy = cam[1]; fp.camz = cam[2];
-  fp.apx = 0.0f; fp.apy = 0.0f; fp.apz = 5.0f;
-  fp.cosYaw = (float)std::cos((double)cam[3]);
-  fp.sinYaw = (float)std::sin((double)cam[3]);
-  fp.yaw = cam[3];
-  fp.width = d->width; fp.height = d->height; fp.depth = d->depth;
-  fp.clampOutput = d->kernel_mode == LT_KERNEL_MODE_LINEAR;
-  {
-    const char* sm = getenv("LT_SQUARE_MAJOR");
-    fp.squareMajor = (sm && atoi(sm) == 0) ? 0u : 1u;
+// One launch of a built-in program through the one-lane-per-pixel kernels.
+static void launch_builtin(const RenderCall& c, const SceneDev& sc, const FrameParams& fp, dim3 grid, float* out, unsigned long long* st,
+                           uint32_t* queues) {
+  switch (c.d->program) {
+    case LT_PROGRAM_BASIC: launch_program<kBasic>(c, sc, fp, grid, out, st, queues); break;
+    case LT_PROGRAM_BASIC_LIGHTING: launch_program<kBasicLighting>(c, sc, fp, grid, out, st, queues); break;
+    case LT_PROGRAM_ACCUMULATOR:
+      if (sc.shadowPackets == 3u) launch_program<kAccumulatorQueue>(c, sc, fp, grid, out, st, queues);
+      else launch_program<kAccumulator>(c, sc, fp, grid, out, st, queues);
+      break;
+    case LT_PROGRAM_GLOBAL_ILLUMINATION: launch_program<kGI>(c, sc, fp, grid, out, st, queues); break;
+    case LT_PROGRAM_GLOBAL_ILLUMINATION_25: launch_program<kGI25>(c, sc, fp, grid, out, st, queues); break;
+    default: launch_program<kCustom>(c, sc, fp, grid, out, st, queues); break;
   }
-  fp.giMaxDepth = d->gi_max_depth ? d->gi_max_depth : 16;
-  fp.tileW = p.tileW; fp.tileH = p.tileH; fp.tilesX = p.tilesX; fp.tileFirst = p.tileFirst; fp.tileStride = p.tileStride;
-  fp.tilesInCall = p.tilesInCall;
-  fp.blocksPerTileX = p.bptx; fp.blocksPerTile = p.bptx * p.bpty;
+}
 
-  const bool pixelCounters = (d->flags & LT_RENDER_FLAG_PIXEL_COUNTERS) != 0;
-  if (pixelCounters && d->depth < 4) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PIXEL_COUNTERS needs depth >= 4");
-  fp.pixelCounters = pixelCounters;
-  const bool stats = pixelCounters || (d->flags & LT_RENDER_FLAG_STATS) != 0;
-  const bool deep = ctx->bvh_height > kLdsStack;
-  // The default flavour is bit-identical to the reference's OpenCL kernels as RendererOpenCL builds them on this GPU (Math<2>);
-  // LT_RENDER_FLAG_STRICT_MATH / _PORTABLE_MATH select the other two (include/lenstrace_hip.h).
-  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+// One frame-set of the call with a given shadow-ray walk: the render launch and, when the shadow rays are queued (mode 3:
+// accumulator, a tree of the backend's own, a launch that overwrites what it writes), lt_trace_kernel over the queue and the
+// kernel that blacks out the occluded samples.
+static int launch_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& sc, uint32_t mode, const FrameParams& fp, dim3 grid, float* out, uint32_t* queues) {
+  sc.shadowPackets = mode;
+  if (mode != 3u) {
+    launch_builtin(c, sc, fp, grid, out, ctx->d_stats, queues);
+    return LT_OK;
+  }
+  const uint64_t slots = c.nblocks * fp.fusedFrames * kBlock;
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_shadowq, ctx->shadowq_slots, slots, slots * 52));   // (origin + tmax, direction, pixel / primitive / frame: 48 bytes; its fate: 4)
+  if (!ctx->d_shadowCtl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_shadowCtl, 9 * kQueueStride * sizeof(uint32_t)));
+  LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_shadowCtl, 0, 8 * kQueueStride * sizeof(uint32_t), c.s));
+  LT_HIP_CHECK(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->d_shadowCtl + 8 * kQueueStride), (int)(uint32_t)slots, 1, c.s));
+  sc.shadowQueue = (float4*)ctx->d_shadowq;
+  sc.shadowCap = (uint32_t)ctx->shadowq_slots;
+  launch_builtin(c, sc, fp, grid, out, ctx->d_stats, queues);
+  TraceParams tp{};
+  tp.o = sc.shadowQueue; tp.d = sc.shadowQueue + sc.shadowCap; tp.m = (const uint4*)(sc.shadowQueue + 2 * (size_t)sc.shadowCap);
+  tp.occluded = (uint32_t*)(sc.shadowQueue + 3 * (size_t)sc.shadowCap);
+  tp.count = ctx->d_shadowCtl + 8 * kQueueStride; tp.next = ctx->d_shadowCtl;
+  tp.refill = c.k.trace_refill; tp.dead = 1u;
+  hipLaunchKernelGGL((lt_trace_kernel<kGI, true>), dim3((uint32_t)ctx->cu_count * 32u), dim3(kBlock), (uint32_t)((kTraceRows + kTraceStage) * kBlock * sizeof(int)),
+                     c.s, sc, tp);
+  hipLaunchKernelGGL(lt_shadow_resolve_kernel, dim3((uint32_t)ctx->cu_count * 8u), dim3(256), 0, c.s, tp.m, (const uint32_t*)tp.occluded, (uint32_t)slots, out,
+                     fp.frameStride, fp.depth);
+  LT_HIP_CHECK(ctx, hipGetLastError());
+  c.launches += 2;
+  return LT_OK;
+}
+
+// Times the shadow-ray walks (any-hit packets, per lane, chosen per wavefront, queued for lt_trace_kernel) once per (scene,
+// program, image geometry, frames per launch), ahead of a launch whose output they may scribble on (it overwrites what it
+// writes, as every fused launch does): the launch as it is -- a verdict on fewer frames is another launch's verdict: a
+// launch pays a fixed price for its slowest squares, which the walks share out differently -- once per walk after one
+// untimed run.  The fastest wins, unless the walk an earlier verdict on this scene picked is within 3 % of it: two walks
+// that close must not take turns from call to call.
+static int calibrate_shadow_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& sc, const FrameParams& fp, dim3 grid, float* out, uint32_t* queues,
+                                 bool queueOk, const std::vector<uint32_t>& key, int& mode) {
+  for (hipEvent_t& e : ctx->cal_ev) if (!e) LT_HIP_CHECK(ctx, hipEventCreate(&e));
+  const uint32_t kOrder[4] = {1u, 0u, 2u, 3u};
+  const int candidates = queueOk ? 4 : 3;
+  for (int pass = -1; pass < candidates; pass++) {
+    if (pass >= 0) LT_HIP_CHECK(ctx, hipEventRecord(ctx->cal_ev[2 * pass], c.s));
+    if (const int rc = launch_walk(ctx, c, sc, kOrder[pass < 0 ? 0 : pass], fp, grid, out, queues)) return rc;
+    if (pass >= 0) LT_HIP_CHECK(ctx, hipEventRecord(ctx->cal_ev[2 * pass + 1], c.s));
+    LT_HIP_CHECK(ctx, hipMemsetAsync(queues, 0, 8 * kQueueStride * sizeof(uint32_t), c.s));
+  }
+  float t[4] = {0, 0, 0, 0};
+  LT_HIP_CHECK(ctx, hipEventSynchronize(ctx->cal_ev[2 * candidates - 1]));
+  for (int k = 0; k < candidates; k++) LT_HIP_CHECK(ctx, hipEventElapsedTime(&t[k], ctx->cal_ev[2 * k], ctx->cal_ev[2 * k + 1]));
+  if (c.k.debug_calibration)
+    fprintf(stderr, "shadow-walk timing (ms, %u frames): packets %.3f, per lane %.3f, per wavefront %.3f, queued %.3f\n", fp.fusedFrames, t[0], t[1], t[2], t[3]);
+  int best = 0;
+  for (int k = 1; k < candidates; k++) if (t[k] < t[best]) best = k;
+  mode = (int)kOrder[best];
+  const int earlier = ctx->shadow_mode[c.d->program];
+  for (int k = 0; k < candidates; k++)
+    if ((int)kOrder[k] == earlier && t[k] <= 1.03f * t[best]) mode = earlier;
+  ctx->shadow_modes[key] = mode;
+  ctx->shadow_mode[c.d->program] = mode;
+  c.launches += (uint32_t)candidates + 1u;
+  return LT_OK;
+}
+
+// `rb`: lt_hip_render's read-back of out_device (= ctx->d_out, on ctx->stream), whose pieces the call's last fold follows; null
+// for lt_hip_render_device.
+static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, const TilePlan& p, float* out_device, uint64_t out_bytes,
+                            hipStream_t s, const RenderKnobs& k, ReadBack* rb) {
+  if (const int rc = check_render_desc(ctx, d, p, out_device, out_bytes)) return rc;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool stats = (d->flags & (LT_RENDER_FLAG_STATS | LT_RENDER_FLAG_PIXEL_COUNTERS)) != 0;
   const int devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
-  sc.fastRcp = devlibm == 2 ? 1u : 0u;
-  const LaunchConfig lc{deep, stats, devlibm};
+  SceneDev sc = scene_dev(ctx, k, devlibm);
+  FrameParams fp = frame_params(d, p, k);
+  uint32_t camFrame;
+  memcpy(&camFrame, d->camera + 24, 4);
   const uint32_t frames = d->frame_count ? d->frame_count : 1;
-  const uint64_t nblocks = (uint64_t)p.tilesInCall * fp.blocksPerTile;
-  if (nblocks > 0x7fffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "too many workgroups");
+  const uint64_t nblocks = p.squares();
 
   if (stats) LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_stats, 0, 8 * sizeof(unsigned long long), s));
-  // persistent wavefronts by default; LT_PERSISTENT=0 selects one-square-per-workgroup dispatch (A/B measurements)
-  const char* pe = getenv("LT_PERSISTENT");
-  const bool persistent = !pe || atoi(pe) != 0;
-  if (persistent) {
-    if (ctx->queue_frames < frames) {
-      if (ctx->d_queues) LT_HIP_CHECK(ctx, hipFree(ctx->d_queues));
-      ctx->d_queues = nullptr;
-      ctx->queue_frames = 0;
-      LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_queues, (size_t)frames * 8 * kQueueStride * sizeof(uint32_t)));
-      ctx->queue_frames = frames;
-    }
-    LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_queues, 0, (size_t)frames * 8 * kQueueStride * sizeof(uint32_t), s));
-  }
-  fp.totalSquares = (uint32_t)nblocks;
-  fp.persistent = persistent;
-  fp.order = nullptr;
-  if (persistent && !getenv("LT_NATURAL_ORDER")) {
-    const int orc = ensure_square_order(ctx, d, p, fp.sinYaw == 0.0f, s, &fp.order, fp.orderHead);
-    if (orc) return orc;
+  if (k.persistent) {   // (persistent wavefronts by default; LT_PERSISTENT=0 selects one-square-per-workgroup dispatch: A/B measurements)
+    const uint64_t queueBytes = (uint64_t)frames * 8 * kQueueStride * sizeof(uint32_t);
+    LT_HIP_CHECK(ctx, grow_scratch(ctx->d_queues, ctx->queue_frames, frames, queueBytes));
+    LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_queues, 0, queueBytes, s));
+    if (k.square_order)
+      if (const int rc = ensure_square_order(ctx, d, p, fp.sinYaw == 0.0f, s, &fp.order, fp.orderHead)) return rc;
   }
   FusionPlan fu;
-  {
-    const int frc = plan_fusion(ctx, d, p, frames, nblocks, stats, persistent, fp.giMaxDepth, fu);
-    if (frc) return frc;
-  }
-  const bool giWavefront = fu.giWavefront, gi25Sets = fu.gi25Sets, fused = fu.chunk > 1;
-  const uint32_t chunk = fu.chunk, samplesPerSet = fu.samplesPerSet;
-  const uint64_t giPixels = fu.giPixels;
-  const bool paddedTiles = d->width % p.tileW != 0 || d->height % p.tileH != 0;
-  {   // (frames per launch in three classes: a launch pays a fixed price for its slowest squares, which the walks share out differently)
-    const uint32_t lf = fused ? std::min(chunk, frames) : 1u;
-    shadowKey[7] = lf == 1u ? 1u : lf < 8u ? 2u : 8u;
-  }
-  if (spe) shadowMode = std::max(0, std::min(3, atoi(spe)));
-  else if (hasShadowRays) {
-    auto it = ctx->shadow_modes.find(shadowKey);
-    shadowMode = it == ctx->shadow_modes.end() ? -1 : it->second;
-  }
-  if (shadowMode < 0 && (d->flags & LT_RENDER_FLAG_NO_WALK_TIMING))   // the caller wants no timing launches in this call
-    shadowMode = ctx->shadow_mode[d->program] >= 0 ? ctx->shadow_mode[d->program] : 1;
-  if (shadowMode == 3 && d->program != LT_PROGRAM_ACCUMULATOR) shadowMode = 0;   // (queued shadow rays are accumulator's)
+  if (const int rc = plan_fusion(ctx, k, d, p, frames, stats, fp.giMaxDepth, fu)) return rc;
+  const bool fused = fu.chunk > 1, meanInLaunch = d->frame_count && d->accumulate && !fused;
+  const uint32_t firstFrames = fused ? std::min(fu.chunk, frames) : 1u;   // frames of the first (and largest) launch
+  // (keyed on the image geometry too: how coherent a wavefront's 64 shadow rays are depends on how large its 8x8 pixels are in the
+  // scene; and on the frames per launch in three classes: a launch pays a fixed price for its slowest squares, which the walks share
+  // out differently.  shadow_mode[program] keeps the most recent verdict for callers without a geometry of their own: the GI pipeline)
+  const std::vector<uint32_t> shadowKey = {(uint32_t)d->program, d->width, d->height, p.tileW, p.tileH, p.tileFirst, p.tileStride,
+                                           firstFrames == 1u ? 1u : firstFrames < 8u ? 2u : 8u};
+  const bool queueOk = d->program == LT_PROGRAM_ACCUMULATOR && k.persistent && !stats && ctx->d_rank8 != nullptr && !meanInLaunch &&
+                       nblocks * firstFrames * kBlock < 0xffffffffull;
+  int shadowMode = choose_shadow_walk(ctx, k, d, shadowKey, queueOk || nblocks == 0);
   sc.shadowPackets = shadowMode > 0 ? (uint32_t)shadowMode : 0u;
+  const bool calibrate = k.persistent && !stats && ctx->bvh_height <= kLdsStack && !meanInLaunch;
+
+  // LDS stack rows: a lane never holds more entries than a node has interior ancestors (= bvh_height, validate_scene).  The counting
+  // kernels (and the LDS-resident small scenes of the GI bounce stage: launch_gi_sample) keep one stack entry per lane and level of
+  // the caller's tree in LDS; the others the kOwnRows rows of the per-lane walks over the own tree (the packet walks park their
+  // stack register in the first of them).  LT_DEBUG_LDS_ROWS (occupancy experiments, tests): more rows than the launch needs, for
+  // every kernel; FEWER only for the counting kernels, whose deep-tree form keeps what does not fit in private memory (the others
+  // index their rows with compile-time bounds).  The kernel is told what it got (FrameParams::ldsRows) and the form is chosen from that.
+  const uint32_t rowBytes = (uint32_t)(kBlock * sizeof(int));
+  const uint32_t ldsRefBytes = (uint32_t)std::max(kPacketRows, std::min(ctx->bvh_height, kLdsStack)) * rowBytes;
+  uint32_t lds = stats ? ldsRefBytes : (uint32_t)std::max(kPacketRows, kOwnRows) * rowBytes;
+  if (k.debug_lds_rows) lds = stats ? k.debug_lds_rows * rowBytes : std::max(lds, k.debug_lds_rows * rowBytes);
+  fp.ldsRows = lds / rowBytes;
+  // (the non-counting kernels have no deep-tree form: they keep no per-lane stack of the caller's tree in LDS)
+  RenderCall call{d, k, s, stats && (uint32_t)ctx->bvh_height > fp.ldsRows, stats, devlibm, lds, ldsRefBytes, nblocks, 0u};
+  const bool paddedTiles = d->width % p.tileW != 0 || d->height % p.tileH != 0;
+  const uint32_t resident = (uint32_t)ctx->cu_count * 32u;   // every wave slot of the chip, once
   ctx->mean_pairs = 0;
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
-  uint32_t launches = 0;
-  if (nblocks > 0) {
-    uint32_t launchIndex = 0;
-    for (uint32_t f = 0; f < frames; launchIndex++) {
-      const uint32_t nf = fused ? std::min(chunk, frames - f) : 1u;   // frames of this launch
-      fp.frameCount = d->frame_count ? d->frame_first + f : camFrame;
-      fp.accumulateN = (d->frame_count && d->accumulate && !fused) ? (int32_t)(d->accumulate_base + f) : -1;
-      fp.fusedFrames = nf;
-      fp.frameStride = fused ? p.floats : 0;
-      float* const out_launch = fused ? ctx->d_samples : out_device;
-      const uint32_t firstFrame = f;
-      f += nf;
-      const uint32_t resident = (uint32_t)ctx->cu_count * 32u;   // every wave slot of the chip, once
-      const dim3 grid(persistent ? (uint32_t)std::min<uint64_t>(nblocks * nf, resident) : (uint32_t)nblocks);
-      uint32_t* queues = persistent ? ctx->d_queues + (size_t)launchIndex * 8 * kQueueStride : nullptr;
-      // LDS stack rows: a lane never holds more entries than a node has interior ancestors (= bvh_height, validate_scene)
-      // The counting kernels (and the LDS-resident small scenes of the GI bounce stage: launch_gi_sample) keep one stack entry
-      // per lane and level of the caller's tree in LDS; the others the kOwnRows rows of the per-lane walks over the own tree (the
-      // packet walks park their stack register in the first of them).
-      ctx->lds_ref_bytes = (uint32_t)std::max(kPacketRows, std::min(ctx->bvh_height, kLdsStack)) * kBlock * sizeof(int);
-      uint32_t lds = stats ? ctx->lds_ref_bytes : (uint32_t)std::max(kPacketRows, kOwnRows) * kBlock * sizeof(int);
-      // LT_DEBUG_LDS_ROWS (occupancy experiments, tests): more rows than the launch needs, for every kernel; FEWER only for the
-      // counting kernels, whose deep-tree form keeps what does not fit in private memory (the others index their rows with
-      // compile-time bounds).  The kernel is told what it got (FrameParams::ldsRows) and the form is chosen from that.
-      if (const char* e = getenv("LT_DEBUG_LDS_ROWS")) {
-        const uint32_t want = (uint32_t)std::max(1, std::min(160, atoi(e))) * (uint32_t)(kBlock * sizeof(int));
-        lds = stats ? want : std::max(lds, want);
-      }
-      fp.ldsRows = lds / (uint32_t)(kBlock * sizeof(int));
-      LaunchConfig lcl = lc;
-      lcl.deep = stats && (uint32_t)ctx->bvh_height > fp.ldsRows;   // (the non-counting kernels have no deep-tree form: they keep no per-lane stack of the caller's tree in LDS)
-      if (giWavefront) {
-        SceneDev scGi = sc;
-        scGi.shadowPackets = spe ? sc.shadowPackets : 0u;   // the pipeline's bounce stages cast incoherent shadow rays: per lane
-        const int grc = launch_gi_sets(ctx, s, scGi, fp, lcl, lds, giPixels, gi25Sets ? samplesPerSet : 0u, p.floats, out_launch, out_device, launches);
-        if (grc) return grc;
-        launches--;   // (counted again below)
-      } else if (userProgram) {
-        const lt_hip_context::UserProgram& up = ctx->user_programs[d->program - LT_PROGRAM_USER_BASE];
-        unsigned long long* statsPtr = ctx->d_stats;
-        float* outPtr = out_launch;
-        void* args[] = {(void*)&sc, (void*)&fp, (void*)&outPtr, (void*)&statsPtr, (void*)&queues};
-        const hipFunction_t fn = devlibm == 2 ? up.lds : devlibm == 1 ? up.ldsStrict : up.ldsPortable;
-        LT_HIP_CHECK(ctx, hipModuleLaunchKernel(fn, grid.x, 1, 1, kBlock, 1, 1, lds, s, args, nullptr));
-      } else {
-        // One frame-set of the call with a given shadow-ray walk: the render launch and, when the shadow rays are queued (mode 3:
-        // accumulator, a tree of the backend's own, a launch that overwrites what it writes), lt_trace_kernel over the queue and
-        // the kernel that blacks out the occluded samples.
-        auto launch_render = [&](const FrameParams& fpl, dim3 g) {
-          switch (d->program) {
-            case LT_PROGRAM_BASIC: launch_program<kBasic>(lcl, g, lds, s, sc, fpl, out_launch, ctx->d_stats, queues); break;
-            case LT_PROGRAM_BASIC_LIGHTING: launch_program<kBasicLighting>(lcl, g, lds, s, sc, fpl, out_launch, ctx->d_stats, queues); break;
-            case LT_PROGRAM_ACCUMULATOR:
-              if (sc.shadowPackets == 3u) launch_program<kAccumulatorQueue>(lcl, g, lds, s, sc, fpl, out_launch, ctx->d_stats, queues);
-              else launch_program<kAccumulator>(lcl, g, lds, s, sc, fpl, out_launch, ctx->d_stats, queues);
-              break;
-            case LT_PROGRAM_GLOBAL_ILLUMINATION: launch_program<kGI>(lcl, g, lds, s, sc, fpl, out_launch, ctx->d_stats, queues); break;
-            case LT_PROGRAM_GLOBAL_ILLUMINATION_25: launch_program<kGI25>(lcl, g, lds, s, sc, fpl, out_launch, ctx->d_stats, queues); break;
-            default: launch_program<kCustom>(lcl, g, lds, s, sc, fpl, out_launch, ctx->d_stats, queues); break;
-          }
-        };
-        const bool queueOk = d->program == LT_PROGRAM_ACCUMULATOR && persistent && !stats && ctx->d_rank8 != nullptr && fp.accumulateN < 0 &&
-                             nblocks * nf * kBlock < 0xffffffffull;
-        auto launch_walk = [&](uint32_t mode, const FrameParams& fpl, dim3 g) -> int {
-          sc.shadowPackets = mode;
-          if (mode != 3u) { launch_render(fpl, g); return LT_OK; }
-          const uint64_t slots = nblocks * fpl.fusedFrames * kBlock;
-          if (ctx->shadowq_slots < slots) {
-            if (ctx->d_shadowq) LT_HIP_CHECK(ctx, hipFree(ctx->d_shadowq));
-            ctx->d_shadowq = nullptr;
-            ctx->shadowq_slots = 0;
-            LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_shadowq, slots * 52));   // (origin + tmax, direction, pixel / primitive / frame: 48 bytes; its fate: 4)
-            ctx->shadowq_slots = slots;
-          }
-          if (!ctx->d_shadowCtl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_shadowCtl, 9 * kQueueStride * sizeof(uint32_t)));
-          LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_shadowCtl, 0, 8 * kQueueStride * sizeof(uint32_t), s));
-          LT_HIP_CHECK(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->d_shadowCtl + 8 * kQueueStride), (int)(uint32_t)slots, 1, s));
-          sc.shadowQueue = (float4*)ctx->d_shadowq;
-          sc.shadowCap = (uint32_t)ctx->shadowq_slots;
-          launch_render(fpl, g);
-          TraceParams tp{};
-          tp.o = sc.shadowQueue; tp.d = sc.shadowQueue + sc.shadowCap; tp.m = (const uint4*)(sc.shadowQueue + 2 * (size_t)sc.shadowCap);
-          tp.occluded = (uint32_t*)(sc.shadowQueue + 3 * (size_t)sc.shadowCap);
-          tp.count = ctx->d_shadowCtl + 8 * kQueueStride;
-          tp.next = ctx->d_shadowCtl;
-          const char* re = getenv("LT_TRACE_REFILL");
-          tp.refill = re ? (uint32_t)std::max(1, std::min(64, atoi(re))) : 24u;
-          tp.dead = 1u;
-          hipLaunchKernelGGL((lt_trace_kernel<kGI, true>), dim3(resident), dim3(kBlock), (uint32_t)((kTraceRows + kTraceStage) * kBlock * sizeof(int)), s, sc, tp);
-          hipLaunchKernelGGL(lt_shadow_resolve_kernel, dim3((uint32_t)ctx->cu_count * 8u), dim3(256), 0, s, tp.m, (const uint32_t*)tp.occluded, (uint32_t)slots, out_launch,
-                             fpl.frameStride, fpl.depth);
-          LT_HIP_CHECK(ctx, hipGetLastError());
-          launches += 2;
-          return LT_OK;
-        };
-        if (shadowMode == 3 && !queueOk) shadowMode = spe ? 0 : -1;   // (a forced or remembered mode 3 where it cannot run)
-        // Time the shadow-ray walks (any-hit packets, per lane, chosen per wavefront, queued for lt_trace_kernel) once per (scene,
-        // program, image geometry, frames per launch), ahead of a launch whose output they may scribble on (it overwrites what it
-        // writes, as every fused launch does): the launch as it is -- a verdict on fewer frames is another launch's verdict: a
-        // launch pays a fixed price for its slowest squares, which the walks share out differently -- once per walk after one
-        // untimed run.  The fastest wins, unless the walk an earlier verdict on this scene picked is within 3 % of it: two walks
-        // that close must not take turns from call to call.
-        const bool calibrate = shadowMode < 0 && persistent && !stats && ctx->bvh_height <= kLdsStack && fp.accumulateN < 0;
-        if (calibrate) {
-          for (hipEvent_t& e : ctx->cal_ev) if (!e) LT_HIP_CHECK(ctx, hipEventCreate(&e));
-          const uint32_t kOrder[4] = {1u, 0u, 2u, 3u};
-          const int candidates = queueOk ? 4 : 3;
-          for (int pass = -1; pass < candidates; pass++) {
-            if (pass >= 0) LT_HIP_CHECK(ctx, hipEventRecord(ctx->cal_ev[2 * pass], s));
-            const int wrc = launch_walk(kOrder[pass < 0 ? 0 : pass], fp, grid);
-            if (wrc) return wrc;
-            if (pass >= 0) LT_HIP_CHECK(ctx, hipEventRecord(ctx->cal_ev[2 * pass + 1], s));
-            LT_HIP_CHECK(ctx, hipMemsetAsync(queues, 0, 8 * kQueueStride * sizeof(uint32_t), s));
-          }
-          float t[4] = {0, 0, 0, 0};
-          LT_HIP_CHECK(ctx, hipEventSynchronize(ctx->cal_ev[2 * candidates - 1]));
-          for (int k = 0; k < candidates; k++) LT_HIP_CHECK(ctx, hipEventElapsedTime(&t[k], ctx->cal_ev[2 * k], ctx->cal_ev[2 * k + 1]));
-          if (getenv("LT_DEBUG_CALIBRATION"))
-            fprintf(stderr, "shadow-walk timing (ms, %u frames): packets %.3f, per lane %.3f, per wavefront %.3f, queued %.3f\n", fp.fusedFrames, t[0], t[1], t[2], t[3]);
-          int best = 0;
-          for (int k = 1; k < candidates; k++) if (t[k] < t[best]) best = k;
-          shadowMode = (int)kOrder[best];
-          const int earlier = ctx->shadow_mode[d->program];
-          for (int k = 0; k < candidates; k++)
-            if ((int)kOrder[k] == earlier && t[k] <= 1.03f * t[best]) shadowMode = earlier;
-          ctx->shadow_modes[shadowKey] = shadowMode;
-          ctx->shadow_mode[d->program] = shadowMode;
-          launches += (uint32_t)candidates + 1u;
-        }
-        const int wrc = launch_walk((uint32_t)std::max(0, shadowMode), fp, grid);
-        if (wrc) return wrc;
-      }
-      LT_HIP_CHECK(ctx, hipGetLastError());
-      launches++;
-      if (fused) {
-        const int mrc = launch_running_mean(ctx, s, fp, p.floats, nf, (int32_t)(d->accumulate_base + firstFrame), paddedTiles, out_device, f >= frames);
-        if (mrc) return mrc;
-      }
+  for (uint32_t f = 0, launchIndex = 0; f < frames && nblocks > 0; launchIndex++) {
+    const uint32_t nf = fused ? std::min(fu.chunk, frames - f) : 1u;   // frames of this launch
+    fp.frameCount = d->frame_count ? d->frame_first + f : camFrame;
+    fp.accumulateN = meanInLaunch ? (int32_t)(d->accumulate_base + f) : -1;
+    fp.fusedFrames = nf;
+    fp.frameStride = fused ? p.floats : 0;
+    float* const out = fused ? ctx->d_samples : out_device;
+    const dim3 grid(k.persistent ? (uint32_t)std::min<uint64_t>(nblocks * nf, resident) : (uint32_t)nblocks);
+    uint32_t* queues = k.persistent ? ctx->d_queues + (size_t)launchIndex * 8 * kQueueStride : nullptr;
+    if (fu.giWavefront) {
+      SceneDev scGi = sc;
+      scGi.shadowPackets = k.shadow_packets >= 0 ? sc.shadowPackets : 0u;   // the pipeline's bounce stages cast incoherent shadow rays: per lane
+      if (const int rc = launch_gi_sets(ctx, call, scGi, fp, fu.giPixels, fu.samplesPerSet, p.floats, out, out_device)) return rc;
+      call.launches--;   // (counted again below)
+    } else if (d->program >= LT_PROGRAM_USER_BASE) {
+      const lt_hip_context::UserProgram& up = ctx->user_programs[d->program - LT_PROGRAM_USER_BASE];
+      unsigned long long* statsPtr = ctx->d_stats;
+      float* outPtr = out;
+      void* args[] = {(void*)&sc, (void*)&fp, (void*)&outPtr, (void*)&statsPtr, (void*)&queues};
+      const hipFunction_t fn = devlibm == 2 ? up.lds : devlibm == 1 ? up.ldsStrict : up.ldsPortable;
+      LT_HIP_CHECK(ctx, hipModuleLaunchKernel(fn, grid.x, 1, 1, kBlock, 1, 1, lds, s, args, nullptr));
+    } else {
+      if (shadowMode < 0 && calibrate)
+        if (const int rc = calibrate_shadow_walk(ctx, call, sc, fp, grid, out, queues, queueOk, shadowKey, shadowMode)) return rc;
+      if (const int rc = launch_walk(ctx, call, sc, (uint32_t)std::max(0, shadowMode), fp, grid, out, queues)) return rc;
     }
+    LT_HIP_CHECK(ctx, hipGetLastError());
+    call.launches++;
+    if (fused)
+      if (const int rc = launch_running_mean(ctx, s, fp, p.floats, nf, (int32_t)(d->accumulate_base + f), paddedTiles, out_device, f + nf >= frames ? rb : nullptr))
+        return rc;
+    f += nf;
   }
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
   ctx->last = lt_hip_stats{};
   ctx->last.frames = frames;
-  ctx->last.kernel_launches = launches;
+  ctx->last.kernel_launches = call.launches;
   ctx->last.shadow_packets = shadowMode;
   // pixels actually inside the image for this call's tiles
   uint64_t px = 0;
-  for (uint32_t k = 0; k < p.tilesInCall; k++) {
-    const uint32_t tile = p.tileFirst + k * p.tileStride, tx = tile % p.tilesX, ty = tile / p.tilesX;
+  for (uint32_t t = 0; t < p.tilesInCall; t++) {
+    const uint32_t tile = p.tileFirst + t * p.tileStride, tx = tile % p.tilesX, ty = tile / p.tilesX;
     const uint32_t w = std::min(p.tileW, d->width - tx * p.tileW), h = std::min(p.tileH, d->height - ty * p.tileH);
     px += (uint64_t)w * h;
   }
   ctx->last.pixels = px;
-  ctx->last_stream = s;
   ctx->pending = true;
   ctx->pending_stats = stats;
   return LT_OK;
@@ -1722,59 +1732,54 @@ static int finish_pending(lt_hip_context* ctx) {
 
 extern "C" int lt_hip_render_device(lt_hip_context* ctx, const lt_hip_render_desc* desc, float* out_device, uint64_t out_bytes,
                                     void* hip_stream) {
-  return render_on_stream(ctx, desc, out_device, out_bytes, (hipStream_t)hip_stream);
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_render before lt_hip_set_scene");
+  TilePlan p;
+  std::string msg;
+  if (const int rc = plan_tiles(desc, p, msg)) return fail(ctx, rc, msg);
+  return render_on_stream(ctx, desc, p, out_device, out_bytes, (hipStream_t)hip_stream, RenderKnobs(), nullptr);
 }
 
 // The read-back of lt_hip_render: device -> the context's pinned buffer in eight pieces (enqueued behind the kernels), each piece
 // copied on to the caller's buffer by a few host threads as soon as it has arrived, so that the link and the host's copy overlap.
 // LT_PINNED_READBACK=0: one hipMemcpyAsync into the caller's (pageable) buffer, as round 2 did it.
-static int enqueue_readback(lt_hip_context* ctx, uint64_t need, float* out_host, bool& staged) {
-  const char* pe = getenv("LT_PINNED_READBACK");
-  staged = !(pe && atoi(pe) == 0) && need >= (1u << 20);
-  if (staged && ctx->h_out_bytes < need) {
+static int enqueue_readback(lt_hip_context* ctx, float* out_host, ReadBack& rb) {
+  if (rb.piece && ctx->h_out_bytes < rb.need) {
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
-    ctx->h_out = nullptr;
     ctx->h_out_bytes = 0;
-    if (hipHostMalloc(&ctx->h_out, need, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->h_out = nullptr;
-      staged = false;
-    } else {
-      ctx->h_out_bytes = need;
-    }
+    if (hipHostMalloc(&ctx->h_out, rb.need, hipHostMallocDefault) == hipSuccess) ctx->h_out_bytes = rb.need;
+    else { (void)hipGetLastError(); ctx->h_out = nullptr; rb.piece = 0; }
   }
-  if (!staged) {
-    LT_HIP_CHECK(ctx, hipMemcpyAsync(out_host, ctx->d_out, need, hipMemcpyDeviceToHost, ctx->stream));
+  if (!rb.piece) {
+    LT_HIP_CHECK(ctx, hipMemcpyAsync(out_host, ctx->d_out, rb.need, hipMemcpyDeviceToHost, ctx->stream));
     return LT_OK;
   }
   for (hipEvent_t& e : ctx->out_ev) if (!e) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  const uint64_t piece = ((need + 7) / 8 + 4095) / 4096 * 4096;
   hipStream_t cs = ctx->stream;
-  if (ctx->fold_pieced && ctx->fold_piece_bytes == piece) {   // (the frame's last fold came in these pieces: each travels behind its own)
+  if (rb.foldPieced) {   // (the frame's last fold came in these pieces: each travels behind its own)
     if (!ctx->copy_stream) LT_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     cs = ctx->copy_stream;
   }
   for (int k = 0; k < 8; k++) {
-    const uint64_t off = std::min(need, (uint64_t)k * piece), n = std::min(piece, need - off);
+    const uint64_t off = std::min(rb.need, (uint64_t)k * rb.piece), n = std::min(rb.piece, rb.need - off);
     if (cs != ctx->stream) LT_HIP_CHECK(ctx, hipStreamWaitEvent(cs, ctx->fold_ev[k], 0));
     if (n) LT_HIP_CHECK(ctx, hipMemcpyAsync((char*)ctx->h_out + off, (const char*)ctx->d_out + off, n, hipMemcpyDeviceToHost, cs));
     LT_HIP_CHECK(ctx, hipEventRecord(ctx->out_ev[k], cs));
   }
   return LT_OK;
 }
-static int finish_readback(lt_hip_context* ctx, uint64_t need, float* out_host, bool staged) {
-  if (!staged) {
+static int finish_readback(lt_hip_context* ctx, float* out_host, const ReadBack& rb) {
+  if (!rb.piece) {
     LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return LT_OK;
   }
-  const uint64_t piece = ((need + 7) / 8 + 4095) / 4096 * 4096;
   const int threads = std::max(1, std::min(8, host_threads()));
   std::atomic<int> failed{0};
   auto work = [&](int t, int of) {
     (void)hipSetDevice(ctx->device);
     for (int k = 0; k < 8; k++) {
       if (hipEventSynchronize(ctx->out_ev[k]) != hipSuccess) { failed = 1; return; }
-      const uint64_t off = std::min(need, (uint64_t)k * piece), n = std::min(piece, need - off);
+      const uint64_t off = std::min(rb.need, (uint64_t)k * rb.piece), n = std::min(rb.piece, rb.need - off);
       const uint64_t lo = off + n * (uint64_t)t / (uint64_t)of, hi = off + n * (uint64_t)(t + 1) / (uint64_t)of;
       memcpy((char*)out_host + lo, (const char*)ctx->h_out + lo, (size_t)(hi - lo));
     }
@@ -1794,51 +1799,43 @@ static int finish_readback(lt_hip_context* ctx, uint64_t need, float* out_host, 
   return LT_OK;
 }
 
-static int render_to_host(lt_hip_context* ctx, const lt_hip_render_desc* desc, float* out_host, uint64_t out_bytes, uint64_t& need, bool& staged) {
+// lt_hip_render up to the enqueued read-back: the image is rendered into ctx->d_out and travels to out_host (finish_readback).
+static int render_to_host(lt_hip_context* ctx, const lt_hip_render_desc* desc, float* out_host, uint64_t out_bytes, const RenderKnobs& k, ReadBack& rb) {
   if (!out_host) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "output pointer is NULL");
   TilePlan p;
   std::string msg;
-  int rc = plan_tiles(desc, p, msg);
-  if (rc) return fail(ctx, rc, msg);
-  need = p.floats * sizeof(float);
-  if (out_bytes < need) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "outputBufferSize smaller than W*H*depth floats");
+  if (const int rc = plan_tiles(desc, p, msg)) return fail(ctx, rc, msg);
+  rb = ReadBack{};
+  rb.need = p.floats * sizeof(float);
+  if (out_bytes < rb.need) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "outputBufferSize smaller than W*H*depth floats");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_render before lt_hip_set_scene");
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->d_out_bytes < need) {
-    if (ctx->d_out) LT_HIP_CHECK(ctx, hipFree(ctx->d_out));
-    ctx->d_out = nullptr;
-    ctx->d_out_bytes = 0;
-    LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_out, need ? need : 4));
-    ctx->d_out_bytes = need;
-  }
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_out, ctx->d_out_bytes, rb.need, rb.need ? rb.need : 4));
   // a running mean continues from the caller's buffer when accumulate_base > 0
   if (desc->frame_count && desc->accumulate && desc->accumulate_base > 0)
-    LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_out, out_host, need, hipMemcpyHostToDevice, ctx->stream));
+    LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_out, out_host, rb.need, hipMemcpyHostToDevice, ctx->stream));
   else
-    LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_out, 0, need, ctx->stream));
-  {   // (the pieces of the read-back, for the call's last fold: enqueue_readback's arithmetic; LT_PINNED_READBACK=0: one piece, one fold)
-    const char* pe = getenv("LT_PINNED_READBACK");
-    ctx->fold_piece_bytes = (!(pe && atoi(pe) == 0) && need >= (1u << 20)) ? ((need + 7) / 8 + 4095) / 4096 * 4096 : 0;
-  }
-  ctx->fold_pieced = false;
-  rc = render_on_stream(ctx, desc, ctx->d_out, need, ctx->stream);
-  if (rc == LT_OK) rc = enqueue_readback(ctx, need, out_host, staged);
-  ctx->fold_piece_bytes = 0;
+    LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_out, 0, rb.need, ctx->stream));
+  rb.piece = readback_piece(k, rb.need);
+  const int rc = render_on_stream(ctx, desc, p, ctx->d_out, rb.need, ctx->stream, k, &rb);
+  return rc == LT_OK ? enqueue_readback(ctx, out_host, rb) : rc;
+}
+
+// lt_hip_render, its host time counted from t0 (lt_hip_stats::total_ms)
+static int render_host(lt_hip_context* ctx, const lt_hip_render_desc* desc, float* out_host, uint64_t out_bytes, const RenderKnobs& k,
+                       std::chrono::steady_clock::time_point t0) {
+  ReadBack rb;
+  int rc = render_to_host(ctx, desc, out_host, out_bytes, k, rb);
+  if (rc == LT_OK) rc = finish_readback(ctx, out_host, rb);
+  if (rc == LT_OK) rc = finish_pending(ctx);
+  if (rc == LT_OK) ctx->last.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
 
 extern "C" int lt_hip_render(lt_hip_context* ctx, const lt_hip_render_desc* desc, float* out_host, uint64_t out_bytes) {
   if (!ctx) return LT_ERR_INVALID_ARGUMENT;
   const auto t0 = std::chrono::steady_clock::now();
-  uint64_t need = 0;
-  bool staged = false;
-  int rc = render_to_host(ctx, desc, out_host, out_bytes, need, staged);
-  if (rc) return rc;
-  rc = finish_readback(ctx, need, out_host, staged);
-  if (rc) return rc;
-  rc = finish_pending(ctx);
-  if (rc) return rc;
-  ctx->last.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return LT_OK;
+  return render_host(ctx, desc, out_host, out_bytes, RenderKnobs(), t0);
 }
 
 // lt_hip_set_scene + lt_hip_render in one call, as the plugin's render() needs them (the reference hands over its scene on every
@@ -1853,6 +1850,8 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
   if (!nodes || !prims || !materials || !lights) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "NULL scene buffer");
   try {
     const auto t0 = std::chrono::steady_clock::now();
+    const SceneKnobs sk;
+    const RenderKnobs rk;
     const uint64_t sizes[4] = {node_bytes, prim_bytes, material_bytes, light_bytes};
     const void* const bufs[4] = {nodes, prims, materials, lights};
     const bool continues = desc && desc->frame_count && desc->accumulate && desc->accumulate_base > 0;   // (reads the caller's buffer: no second try)
@@ -1860,36 +1859,30 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
     // a still scene, every call but the first.  A caller whose scene changed last time (an animation) gets the hash first: a
     // millisecond in front of the frame instead of a whole frame rendered for nothing.
     const bool speculate = ctx->has_scene && ctx->speculate_next && memcmp(sizes, ctx->scene_sizes, sizeof(sizes)) == 0 &&
-                           !getenv("LT_SCENE_ALWAYS_UPLOAD") && !continues;
-    uint64_t need = 0;
-    bool staged = false;
+                           !sk.always_upload && !continues;
     int rc;
     if (speculate) {
-      rc = render_to_host(ctx, desc, out_host, out_bytes, need, staged);
+      ReadBack rb;
+      rc = render_to_host(ctx, desc, out_host, out_bytes, rk, rb);
       if (rc) return rc;
       const SceneHash hash = hash_scene(bufs, sizes);   // (while the GPU renders)
-      rc = finish_readback(ctx, need, out_host, staged);
-      if (rc) return rc;
-      if (hash == ctx->scene_hash) {
-        ctx->scene_reused++;
-        rc = finish_pending(ctx);
-        if (rc) return rc;
+      if ((rc = finish_readback(ctx, out_host, rb))) return rc;
+      const bool stands = hash == ctx->scene_hash;
+      if (stands) ctx->scene_reused++;
+      if ((rc = finish_pending(ctx))) return rc;
+      if (stands) {
         ctx->last.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return LT_OK;
       }
-      rc = finish_pending(ctx);
-      if (rc) return rc;
       ctx->speculate_next = false;
-      rc = set_scene_impl(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, &hash);
+      rc = set_scene_impl(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, sk, &hash);
     } else {
       const uint32_t reused = ctx->scene_reused;
-      rc = set_scene_impl(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, nullptr);
+      rc = set_scene_impl(ctx, nodes, node_bytes, prims, prim_bytes, materials, material_bytes, lights, light_bytes, sk, nullptr);
       ctx->speculate_next = rc == LT_OK && ctx->scene_reused != reused;   // (the resident scene again: the next frame may start at once)
     }
     if (rc) return rc;
-    rc = lt_hip_render(ctx, desc, out_host, out_bytes);
-    if (rc == LT_OK) ctx->last.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    return render_host(ctx, desc, out_host, out_bytes, rk, t0);
   } catch (const std::exception& e) {
     return fail(ctx, LT_ERR_HIP, std::string("lt_hip_render_scene: ") + e.what());
   }

@@ -216,3 +216,70 @@ def test_sah_built_scenes_match_the_oracle_bit_for_bit(renderer, monkeypatch, na
         got = np.empty((40, 64, 3), dtype=np.float32)
         renderer.render(RenderPropertiesHIP(PATHS["global_illumination"], (64, 40, 3), got, s, pCamera=cam))
         assert np.array_equal(got, want), "LT_GI_MEGAKERNEL=%s" % mega
+
+
+def test_render_desc_errors_keep_their_codes_and_order():
+    """Every argument error of a render call (lt_capi.hip: check_render_desc) with its code, through lt_hip_render_device; a desc
+    with two faults reports the one that has always been reported first."""
+    import ctypes
+    import torch
+    from lens_trace_amd.renderer import make_desc
+    from tests.conftest import GOLDEN
+    r = RendererHIP(0)
+    try:
+        L, ctx = r._L, r._ctx
+        W, H = 16, 8
+        buf = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
+        stream = torch.cuda.current_stream().cuda_stream
+        cam = sc.camera_bytes(0.0, 2.5, -50.0, 0.0, 0.0, 0.0, 1)
+
+        def desc(program=C.PROGRAM_BASIC, depth=3, **kw):
+            return make_desc(program, W, H, depth, cam, **kw)
+
+        def call(d, ptr=None, nbytes=None):
+            rc = L.lt_hip_render_device(ctx, ctypes.byref(d), ctypes.c_void_p(buf.data_ptr() if ptr is None else ptr),
+                                        buf.numel() * 4 if nbytes is None else nbytes, ctypes.c_void_p(stream))
+            torch.cuda.synchronize()
+            return rc, L.lt_hip_last_error(ctx).decode()
+
+        bad_size = desc()
+        bad_size.width = 0
+        assert call(bad_size)[0] == C.LT_ERR_NO_SCENE                        # (no scene yet: that comes first, before the desc)
+        r.set_scene(sc.load_ltsb(os.path.join(GOLDEN, "cornell_box_O0.ltsb")).validate())
+        assert call(desc())[0] == C.LT_OK
+        user = r.resolve_program(os.path.join(os.path.dirname(os.path.abspath(__file__)), "user_kernels", "barycentric.hip"))
+
+        def with_(d, **fields):
+            for k, v in fields.items():
+                setattr(d, k, v)
+            return d
+        both_math = C.RENDER_FLAG_PORTABLE_MATH | C.RENDER_FLAG_STRICT_MATH
+        cases = [  # (desc, output pointer, bytes) -> code, message
+            ((with_(desc(), program=C.PROGRAM_CUSTOM_OPENCL + 1),), C.LT_ERR_UNKNOWN_PROGRAM, "unknown program"),
+            ((with_(desc(), program=-1),), C.LT_ERR_UNKNOWN_PROGRAM, "unknown program"),
+            ((with_(desc(), program=user + 1),), C.LT_ERR_UNKNOWN_PROGRAM, "unknown program"),
+            ((desc(user, stats=True),), C.LT_ERR_INVALID_ARGUMENT, "user programs are compiled without the counting variants"),
+            ((desc(user, depth=4, pixel_counters=True),), C.LT_ERR_INVALID_ARGUMENT, "user programs are compiled without the counting variants"),
+            ((desc(kernel_mode=2),), C.LT_ERR_INVALID_ARGUMENT, "unknown kernel mode"),
+            ((desc(), 0), C.LT_ERR_INVALID_ARGUMENT, "output pointer is NULL"),
+            ((desc(), None, W * H * 3 * 4 - 4), C.LT_ERR_BUFFER_TOO_SMALL, "output buffer smaller than the image/tile stack"),
+            ((desc(gi_max_depth=65),), C.LT_ERR_INVALID_ARGUMENT, "gi_max_depth out of range"),
+            ((desc(gi_max_depth=-1),), C.LT_ERR_INVALID_ARGUMENT, "gi_max_depth out of range"),
+            ((with_(desc(), flags=both_math),), C.LT_ERR_INVALID_ARGUMENT, "exclude each other"),
+            ((desc(pixel_counters=True),), C.LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PIXEL_COUNTERS needs depth >= 4"),
+            # two faults: the first of the list above wins
+            ((with_(desc(kernel_mode=2), program=-1),), C.LT_ERR_UNKNOWN_PROGRAM, "unknown program"),
+            ((desc(user, stats=True, kernel_mode=2), 0), C.LT_ERR_INVALID_ARGUMENT, "user programs are compiled without the counting variants"),
+            ((desc(kernel_mode=2), 0), C.LT_ERR_INVALID_ARGUMENT, "unknown kernel mode"),
+            ((desc(), 0, 0), C.LT_ERR_INVALID_ARGUMENT, "output pointer is NULL"),
+            ((desc(gi_max_depth=65), None, 4), C.LT_ERR_BUFFER_TOO_SMALL, "output buffer smaller than the image/tile stack"),
+            ((with_(desc(gi_max_depth=65), flags=both_math),), C.LT_ERR_INVALID_ARGUMENT, "gi_max_depth out of range"),
+            ((with_(desc(gi_max_depth=65), flags=C.RENDER_FLAG_PIXEL_COUNTERS),), C.LT_ERR_INVALID_ARGUMENT, "gi_max_depth out of range"),
+            ((with_(desc(), flags=both_math | C.RENDER_FLAG_PIXEL_COUNTERS),), C.LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PIXEL_COUNTERS needs depth >= 4"),
+        ]
+        for args, code, text in cases:
+            got, msg = call(*args)
+            assert got == code and text in msg, (args[1:], got, msg, code, text)
+        assert call(desc())[0] == C.LT_OK                                    # (the context is none the worse)
+    finally:
+        r.close()

@@ -267,6 +267,36 @@ def test_random_scheduling_configurations(renderer, cornell, monkeypatch, seed):
         assert np.array_equal(got_tiled, want), (prog_name, W, H, count, first, base, depth, tile, env)
 
 
+# ---- switches no other test sets: the pixels of the default, and where lt_hip_stats can show it, the switch at work ----
+@pytest.mark.parametrize("env,path,base_env", [
+    ({"LT_SQUARE_MAJOR": "0"}, ACC, {}),
+    ({"LT_TRACE_REFILL": "8"}, ACC, {"LT_SHADOW_PACKETS": "3"}),                                  # (accumulator's queued shadow rays)
+    ({"LT_TRACE_REFILL": "8"}, GI, {"LT_GI_MEGAKERNEL": "0", "LT_GI_LDS_SCENE": "0"}),           # (the bounce stages' trace launches)
+    ({"LT_GI_LDS_SCENE": "0"}, GI, {"LT_GI_MEGAKERNEL": "0"}),
+    ({"LT_NATURAL_ORDER": "0"}, ACC, {}),                                                        # (presence only: "0" too skips the order)
+    ({"LT_SCENE_ALWAYS_UPLOAD": "1"}, ACC, {}),
+])
+def test_switches_leave_the_pixels_alone(renderer, cornell, monkeypatch, env, path, base_env):
+    W, H, count, depth = 64, 48, 3, 4
+
+    def render(extra):
+        with monkeypatch.context() as m:
+            for k, v in {**base_env, **extra}.items():
+                m.setenv(k, v)
+            frames(renderer, cornell, path, W, H, 0, count, giMaxDepth=depth)   # (the scene resident)
+            uploads = renderer.stats()["scene_uploads"]
+            out, st = frames(renderer, cornell, path, W, H, 0, count, giMaxDepth=depth)
+            return out, st, st["scene_uploads"] - uploads
+
+    want, st0, uploads0 = render({})
+    got, st1, uploads1 = render(env)
+    assert np.array_equal(got, want), env
+    if "LT_SCENE_ALWAYS_UPLOAD" in env:
+        assert (uploads0, uploads1) == (0, 1)
+    if "LT_GI_LDS_SCENE" in env and st1["own_tree_height"] > 0:   # (the bounce stages walk the own tree: five launches each instead of one)
+        assert st1["kernel_launches"] > st0["kernel_launches"]
+
+
 @pytest.mark.parametrize("path", [ACC, GI])
 def test_fused_launch_with_depth_4_leaves_the_fourth_channel_alone(renderer, cornell, monkeypatch, path):
     """imageDimensions[2] > 3: only channels 0..2 of a pixel are written (accumulator.cl:316-318 writes three floats at
