@@ -258,7 +258,7 @@ struct lt_hip_context {
   hipStream_t copy_stream = nullptr; //     the pieces travel on a stream of their own, each behind its fold
   unsigned long long* d_stats = nullptr;
   uint32_t* d_prep_flag = nullptr;   // scene preparation's flag word: the slot behind d_stats, which no render launch writes
-  uint32_t* d_queues = nullptr;      // persistent mode: 8 per-XCD work counters per launch of a call
+  uint32_t* d_queues = nullptr;      // persistent mode: 8 per-XCD work counters per launch of a call, and 8 for its camera-hit pass
   uint64_t queue_frames = 0;
   int shadow_mode[6] = {-1, -1, -1, -1, -1, -1};   // per built-in program: shadow rays as any-hit packets (1) or per lane (0); -1 = not timed yet
   hipEvent_t cal_ev[12] = {};
@@ -267,6 +267,8 @@ struct lt_hip_context {
   uint64_t shadowq_slots = 0;
   uint32_t* d_shadowCtl = nullptr;   // ... the trace launch's eight work counters (kQueueStride apart) and, behind them, the queue's length
   float* d_samples = nullptr;        // un-accumulated sample images of a fused multi-sample launch
+  uint4* d_camhits = nullptr;        // the camera-hit pass's hits (FrameParams::cameraHits): 16 bytes per lane of every square of a call
+  uint64_t camhits_slots = 0;
   uint64_t d_samples_bytes = 0;
   uint32_t* d_order = nullptr;       // persistent mode: hand-out order of the squares (slow-path squares first), cached
   uint64_t order_capacity = 0;
@@ -382,6 +384,7 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_stats) (void)hipFree(ctx->d_stats);
   if (ctx->d_queues) (void)hipFree(ctx->d_queues);
   if (ctx->d_samples) (void)hipFree(ctx->d_samples);
+  if (ctx->d_camhits) (void)hipFree(ctx->d_camhits);
   if (ctx->d_shadowq) (void)hipFree(ctx->d_shadowq);
   if (ctx->d_shadowCtl) (void)hipFree(ctx->d_shadowCtl);
   if (ctx->d_order) (void)hipFree(ctx->d_order);
@@ -1018,7 +1021,9 @@ struct RenderKnobs {
   uint64_t fused_bytes = 16ull << 30;   // LT_FUSED_BYTES: the scratch memory of fused launches
   uint32_t debug_lds_rows = 0;          // LT_DEBUG_LDS_ROWS=1..160: LDS rows of every render launch (render_on_stream); 0: what it needs
   bool debug_calibration = getenv("LT_DEBUG_CALIBRATION") != nullptr;   // calibrate_shadow_walk prints its timings to stderr
+  bool debug_camera_hits = getenv("LT_DEBUG_CAMERA_HITS") != nullptr;   // launch_camera_hits prints the squares of its pass to stderr
   bool pinned_readback = !env_off("LT_PINNED_READBACK");   // off: lt_hip_render reads back in one copy (readback_piece)
+  bool camera_hits = !env_off("LT_CAMERA_HITS");   // off: every launch walks its camera rays (launch_camera_hits)
   RenderKnobs() {
     if (const char* e = getenv("LT_SHADOW_PACKETS")) shadow_packets = std::max(0, std::min(3, atoi(e)));
     if (const char* e = getenv("LT_SHADOW_SPREAD")) shadow_spread = (float)atof(e);
@@ -1597,6 +1602,32 @@ static int calibrate_shadow_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& s
   return LT_OK;
 }
 
+// The camera-hit pass (lt_camera_hits_kernel, FrameParams::cameraHits): a camera ray is the same in every frame of a call, and so is
+// its walk -- 1 002 530-triangle wall, 4K, 16 frames: 6.4 of the 17 ms of accumulator's launch were its 16 walks of each camera
+// ray (`basic`, nothing but those walks).  So a call of accumulator that renders two or more frames walks each camera ray once,
+// before its render launches, which read the hits and shade from them; its head squares (ensure_square_order: 1.9 ms for one on the
+// wall, a floor under the pass's length) stay out and are walked by the render launches, where they start first and overlap.  A
+// one-frame call keeps the walk in its launch (the pass would add a launch and its drain).  Nothing is kept from one call to the
+// next.  Not the counting kernels: their walks are what their ray, node and triangle counts count.  Run after ev0 (render_ms holds it),
+// not counted in kernel_launches.  LT_CAMERA_HITS=0: every launch walks its camera rays.
+static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const SceneDev& sc, FrameParams& fp, uint32_t* queues, uint32_t resident) {
+  uint64_t squares = 0;   // those of the pass: every square but the head squares (the kernel's own count, lt_kernel.hpp)
+  for (uint32_t xcd = 0; xcd < 8; xcd++) squares += camera_hit_squares(fp, xcd);
+  if (c.k.debug_camera_hits) fprintf(stderr, "camera-hit pass: %llu of %llu squares\n", (unsigned long long)squares, (unsigned long long)c.nblocks);
+  if (squares == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_camhits, ctx->camhits_slots, c.nblocks * kBlock, c.nblocks * kBlock * sizeof(uint4)));
+  fp.cameraHits = ctx->d_camhits;
+  FrameParams fh = fp;
+  fh.fusedFrames = 1;
+  with_math(c.devlibm, [&](auto m) {
+    hipLaunchKernelGGL((lt_camera_hits_kernel<Config<false, false, decltype(m)::value>>), dim3((uint32_t)std::min<uint64_t>(squares, resident)), dim3(kBlock),
+                       c.lds, c.s, sc, fh, queues);
+    return 0;
+  });
+  LT_HIP_CHECK(ctx, hipGetLastError());
+  return LT_OK;
+}
+
 // `rb`: lt_hip_render's read-back of out_device (= ctx->d_out, on ctx->stream), whose pieces the call's last fold follows; null
 // for lt_hip_render_device.
 static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, const TilePlan& p, float* out_device, uint64_t out_bytes,
@@ -1614,8 +1645,8 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
 
   if (stats) LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_stats, 0, 8 * sizeof(unsigned long long), s));
   if (k.persistent) {   // (persistent wavefronts by default; LT_PERSISTENT=0 selects one-square-per-workgroup dispatch: A/B measurements)
-    const uint64_t queueBytes = (uint64_t)frames * 8 * kQueueStride * sizeof(uint32_t);
-    LT_HIP_CHECK(ctx, grow_scratch(ctx->d_queues, ctx->queue_frames, frames, queueBytes));
+    const uint64_t queueBytes = ((uint64_t)frames + 1) * 8 * kQueueStride * sizeof(uint32_t);   // (the last eight: the camera-hit pass's)
+    LT_HIP_CHECK(ctx, grow_scratch(ctx->d_queues, ctx->queue_frames, (uint64_t)frames + 1, queueBytes));
     LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_queues, 0, queueBytes, s));
     if (k.square_order)
       if (const int rc = ensure_square_order(ctx, d, p, fp.sinYaw == 0.0f, s, &fp.order, fp.orderHead)) return rc;
@@ -1652,6 +1683,8 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   const uint32_t resident = (uint32_t)ctx->cu_count * 32u;   // every wave slot of the chip, once
   ctx->mean_pairs = 0;
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  if (k.camera_hits && k.persistent && !stats && frames > 1 && nblocks > 0 && d->program == LT_PROGRAM_ACCUMULATOR)
+    if (const int rc = launch_camera_hits(ctx, call, sc, fp, ctx->d_queues + (size_t)frames * 8 * kQueueStride, resident)) return rc;
   for (uint32_t f = 0, launchIndex = 0; f < frames && nblocks > 0; launchIndex++) {
     const uint32_t nf = fused ? std::min(fu.chunk, frames - f) : 1u;   // frames of this launch
     fp.frameCount = d->frame_count ? d->frame_first + f : camFrame;

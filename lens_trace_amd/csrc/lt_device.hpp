@@ -1151,15 +1151,28 @@ __device__ inline V3 shade_custom(const SceneDev& sc, const Ray& ray, Stack<CFG:
   return V3{0.0f, 0.0f, 0.0f};
 }
 
-// acc.cl:219-282 / basic_lighting.cl:220-277
+// The hit of a camera ray (acc.cl:229-231): walked, or -- hitRow != null, a non-counting kernel -- read from the call's
+// camera-hit pass (FrameParams::cameraHits; hitRow: the square's 64 slots, wave-uniform).  Same bits either way: the pass walks
+// the same ray with the same walk over the same lanes of the square.  (t is not stored: no shading code reads it.)
+template <int PROGRAM, class CFG>
+__device__ __forceinline__ Hit camera_hit(const SceneDev& sc, const Ray& cameraRay, const uint4* hitRow, Stack<CFG::kDeep>& st, Counters& c) {
+  Hit pl{0, 0, kFltMax, 0.0f, 0.0f};
+  if (!CFG::kStats && hitRow != nullptr) {
+    const uint4 h = hitRow[__lane_id()];
+    pl.prim = (int)h.x; pl.hitType = (int)h.y; pl.u = __uint_as_float(h.z); pl.v = __uint_as_float(h.w);
+  } else {
+    traverse_camera<PROGRAM, CFG::kDeep, CFG::kStats>(sc, cameraRay, pl, st, c);
+  }
+  return pl;
+}
+
+// acc.cl:219-282 / basic_lighting.cl:220-277 from the camera ray's hit on (camera_hit)
 // (qslot / qpixel / qframe: where a queued shadow ray goes and which stored colour it decides -- SceneDev::shadowPackets == 3;
 // queued: it went)
 template <int PROGRAM, class CFG>
-__device__ inline V3 shade_lighting(const SceneDev& sc, const Ray& cameraRay, float fx, float fy, uint32_t s,
+__device__ inline V3 shade_lighting(const SceneDev& sc, const Hit& pl, float fx, float fy, uint32_t s,
                                     Stack<CFG::kDeep>& st, Counters& c, uint32_t qslot, uint32_t qpixel, uint32_t qframe, bool& queued) {
   V3 out{0.0f, 0.0f, 0.0f};
-  Hit pl{0, 0, kFltMax, 0.0f, 0.0f};
-  traverse_camera<PROGRAM, CFG::kDeep, CFG::kStats>(sc, cameraRay, pl, st, c);
   if (PROGRAM == kAccumulator || PROGRAM == kAccumulatorQueue) {
     if (is_light(sc.lights, pl.prim)) return V3{1.0f, 1.0f, 1.0f};
   }
@@ -1300,6 +1313,11 @@ struct FrameParams {
   // head squares of ALL its frames before anything else, so that its longest wavefronts start first.
   const uint32_t* order;
   uint32_t orderHead[8];
+  // The camera ray of a pixel is the same in every frame (camera_ray takes no frame), and so is its walk.  A call of accumulator
+  // that renders two or more frames walks every camera ray once, ahead of its render launches (lt_camera_hits_kernel): the hit
+  // of lane l of the square at hand-out position p at cameraHits[p * 64 + l], (primitive, hitType, u, v) -- every square but the
+  // head squares of the XCDs' shares, which the render launches walk themselves.  Null: every launch walks its camera rays.
+  uint4* cameraHits;
 };
 
 // Camera ray of pixel (x,y): acc.cl:304-312.
@@ -1331,9 +1349,10 @@ __device__ V3 user_shade(const SceneDev& sc, const Ray& cameraRay, float filmX, 
 
 // The body of linearKernel / tileKernel for one pixel, all five programs
 // (acc.cl:314-318, basic.cl:338-342, basic_lighting.cl:309-321, resources gi :408-420).
+// hitRow: the square's stored camera hits (camera_hit), or null.
 template <int PROGRAM, class CFG>
 __device__ inline V3 shade_pixel(const SceneDev& sc, const FrameParams& fp, uint32_t frameCount, int x, int y, Stack<CFG::kDeep>& st,
-                                 Counters& c, uint32_t qslot, uint32_t qpixel, uint32_t qframe, bool& queued) {
+                                 Counters& c, uint32_t qslot, uint32_t qpixel, uint32_t qframe, bool& queued, const uint4* hitRow) {
   float fx, fy;
   const Ray ray = camera_ray<CFG::kDevLibm>(fp, x, y, fx, fy);
   V3 color;
@@ -1346,14 +1365,20 @@ __device__ inline V3 shade_pixel(const SceneDev& sc, const FrameParams& fp, uint
     color = user_shade<CFG>(sc, ray, fx, fy, frameCount, st, c);
 #endif
   } else if (PROGRAM == kAccumulator || PROGRAM == kAccumulatorQueue) {
-    color = shade_lighting<PROGRAM, CFG>(sc, ray, fx, fy, frameCount, st, c, qslot, qpixel, qframe, queued);
+    const Hit pl = camera_hit<PROGRAM, CFG>(sc, ray, hitRow, st, c);
+    color = shade_lighting<PROGRAM, CFG>(sc, pl, fx, fy, frameCount, st, c, qslot, qpixel, qframe, queued);
   } else if (PROGRAM == kGI) {
     color = shade_gi<CFG>(sc, ray, fx, fy, frameCount, fp.giMaxDepth, st, c);
   } else {
     const uint32_t base = frameCount * 32u;
+    // basic_lighting's 25 samples shade one camera ray: walked once here (the counting kernel walks it 25 times, as the
+    // reference does: its ray, node and triangle counts are the reference's)
+    Hit pl{0, 0, kFltMax, 0.0f, 0.0f};
+    if (PROGRAM == kBasicLighting && !CFG::kStats) pl = camera_hit<kBasicLighting, CFG>(sc, ray, nullptr, st, c);
     for (int k = 0; k < 25; k++) {
+      if (PROGRAM == kBasicLighting && CFG::kStats) pl = camera_hit<kBasicLighting, CFG>(sc, ray, nullptr, st, c);
       const V3 cn = (PROGRAM == kBasicLighting)
-                        ? shade_lighting<kBasicLighting, CFG>(sc, ray, fx, fy, base + (uint32_t)k, st, c, 0u, 0u, 0u, queued)
+                        ? shade_lighting<kBasicLighting, CFG>(sc, pl, fx, fy, base + (uint32_t)k, st, c, 0u, 0u, 0u, queued)
                         : shade_gi<CFG>(sc, ray, fx, fy, base + (uint32_t)k, fp.giMaxDepth, st, c);
       if (k == 0) {
         color = cn;

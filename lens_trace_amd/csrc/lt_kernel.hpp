@@ -16,11 +16,38 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t n) {
   return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + b / 8u;
 }
 
+// A persistent launch's n squares in eight contiguous shares, one per XCD: XCD x hands out [xcd_share_start, + xcd_share_size).
+__host__ __device__ inline uint32_t xcd_share_size(uint32_t n, uint32_t xcd) { return n / 8u + (xcd < n % 8u ? 1u : 0u); }
+__host__ __device__ inline uint32_t xcd_share_start(uint32_t n, uint32_t xcd) {
+  const uint32_t q = n / 8u, r = n % 8u;
+  return xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q;
+}
+// The squares of XCD x's share that the camera-hit pass walks (lt_camera_hits_kernel): all but its head squares, which the render
+// launches walk themselves.  (ensure_square_order puts at most the share at its head.)
+__host__ __device__ inline uint32_t camera_hit_squares(const FrameParams& fp, uint32_t xcd) {
+  return xcd_share_size(fp.totalSquares, xcd) - (fp.order ? fp.orderHead[xcd] : 0u);
+}
+
+// Pixel of this lane in square b: false outside the image or the call's tiles.
+__device__ __forceinline__ bool square_pixel(const FrameParams& fp, uint32_t b, uint32_t& x, uint32_t& y, uint32_t& pix) {
+  const uint32_t k = b / fp.blocksPerTile, sb = b % fp.blocksPerTile;
+  const uint32_t sbx = sb % fp.blocksPerTileX, sby = sb / fp.blocksPerTileX;
+  const uint32_t tile = fp.tileFirst + k * fp.tileStride;
+  const uint32_t tx = tile % fp.tilesX, ty = tile / fp.tilesX;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t lx = sbx * 8u + (lane & 7u), ly = sby * 8u + (lane >> 3);
+  x = tx * fp.tileW + lx;
+  y = ty * fp.tileH + ly;
+  pix = (k * fp.tileH + ly) * fp.tileW + lx;
+  return k < fp.tilesInCall && lx < fp.tileW && ly < fp.tileH && x < fp.width && y < fp.height;
+}
+
 // One 8x8 pixel square (logical index b, already XCD-ordered) by one wavefront.
-// (pos: the square's position in the hand-out order -- what a queued shadow ray's slot is made of, SceneDev::shadowPackets == 3)
+// (pos: the square's position in the hand-out order -- what a queued shadow ray's slot is made of, SceneDev::shadowPackets == 3;
+// hitRow: the square's stored camera hits, FrameParams::cameraHits, or null)
 template <int PROGRAM, class CFG>
 __device__ __forceinline__ void render_square(const SceneDev& sc, const FrameParams& fp, float* __restrict__ out, uint32_t b,
-                                              uint32_t frame, Stack<CFG::kDeep>& st, Counters& c, uint32_t pos) {
+                                              uint32_t frame, Stack<CFG::kDeep>& st, Counters& c, uint32_t pos, const uint4* hitRow) {
   constexpr bool STATS = CFG::kStats;
   const uint32_t k = b / fp.blocksPerTile, sb = b % fp.blocksPerTile;
   const uint32_t sbx = sb % fp.blocksPerTileX, sby = sb / fp.blocksPerTileX;
@@ -37,7 +64,7 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
   if (valid) {
     Counters pc{};   // this pixel's own counters (diagnostic output), folded into the lane's totals below
     const uint32_t pixel = (k * fp.tileH + ly) * fp.tileW + lx;
-    const V3 color = shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, STATS ? pc : c, qslot, pixel, frame, queued);
+    const V3 color = shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, STATS ? pc : c, qslot, pixel, frame, queued, hitRow);
     float* o = out + (size_t)frame * fp.frameStride + (((size_t)k * fp.tileH + ly) * fp.tileW + lx) * fp.depth;
     if (STATS && fp.pixelCounters) {
       o[0] = (float)pc.rays; o[1] = (float)pc.shadow; o[2] = (float)pc.nodes; o[3] = (float)pc.tris;
@@ -61,6 +88,20 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
   if (queueing && !queued) ((uint4*)sc.shadowQueue)[2 * (size_t)sc.shadowCap + qslot] = make_uint4(kDeadSlot, 0u, 0u, 0u);
 }
 
+// The camera-hit pass's work on one square: the walk of render_square's camera rays (same lanes, same walk: kAccumulator's and
+// kAccumulatorQueue's are one), the hits stored for every frame's render_square.  All 64 slots are written: four whole lines.
+template <class CFG>
+__device__ __forceinline__ void camera_hit_square(const SceneDev& sc, const FrameParams& fp, uint32_t b, uint32_t pos, Stack<CFG::kDeep>& st, Counters& c) {
+  uint32_t x, y, pix;
+  Hit pl{0, 0, kFltMax, 0.0f, 0.0f};
+  if (square_pixel(fp, b, x, y, pix)) {
+    float fx, fy;
+    const Ray ray = camera_ray<CFG::kDevLibm>(fp, (int)x, (int)y, fx, fy);
+    pl = camera_hit<kAccumulator, CFG>(sc, ray, nullptr, st, c);
+  }
+  fp.cameraHits[(size_t)pos * kBlock + threadIdx.x] = make_uint4((uint32_t)pl.prim, (uint32_t)pl.hitType, __float_as_uint(pl.u), __float_as_uint(pl.v));
+}
+
 // Registers: the traversal wants every wave slot (8 per SIMD = 64 VGPRs); the single-bounce programs fit that with a few
 // spilled values in their shading code; the 16-bounce / 25-sample programs as ONE kernel would spill 85-140 values at 8 and
 // run best at 5 waves per SIMD (Cornell GI 1080p, 16 bounces, 16 frames per launch: 31.5 / 30.2 / 32.8 / 45.7 ms at
@@ -78,7 +119,9 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
 #endif
 constexpr int waves_per_simd(int program) { return (program == kGI || program == kGI25) ? LT_GI_WAVES : LT_ACC_WAVES; }
 
-template <int PROGRAM, class CFG>
+// HITS: the camera-hit pass (lt_camera_hits_kernel): every square of the XCDs' shares but their head squares, once, through
+// camera_hit_square, in the order and on the XCD that the render launches give them.
+template <int PROGRAM, class CFG, bool HITS = false>
 __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const FrameParams& fp, float* __restrict__ out,
                                                    unsigned long long* __restrict__ stats, uint32_t* __restrict__ queues) {
   extern __shared__ int lds_stack[];   // [BVH height (<= kLdsStack)][kBlock], sized by the launch
@@ -94,29 +137,32 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
   //    XCD it runs on (its contiguous share of the logical square list, so each XCD's L2 keeps serving one image region)
   //    and, when that is drained, from the other XCDs' queues.  Every wave reaches the exit: each queue hands out at most
   //    its share, and the loop ends after one empty sweep over all eight.
-  const uint32_t n = fp.totalSquares, q = n / 8u, r = n % 8u;
   const uint32_t home = fp.persistent ? (__builtin_amdgcn_s_getreg((3u << 11) | 20u) & 7u) : 0u;   // HW_REG_XCC_ID
   uint32_t sweep = 0;
   bool done = false;
   while (!done) {
     uint32_t b, frame = 0, pos = 0;
+    bool stored = false;   // the item's camera hits are in fp.cameraHits
     if (!fp.persistent) {
       b = xcd_remap(blockIdx.x, gridDim.x);
       pos = b;
       done = true;
     } else {
       const uint32_t xcd = (home + sweep) & 7u;
-      const uint32_t share = q + (xcd < r ? 1u : 0u), start = xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q;
+      const uint32_t share = xcd_share_size(fp.totalSquares, xcd), start = xcd_share_start(fp.totalSquares, xcd);
       uint32_t t = 0;
       if (threadIdx.x == 0) t = atomicAdd(&queues[xcd * kQueueStride], 1u);
       t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-      if (t >= share * fp.fusedFrames) {   // (share * fusedFrames < 2^32: checked by the host)
+      const uint32_t head = fp.order ? fp.orderHead[xcd] : 0u;
+      if (t >= (HITS ? camera_hit_squares(fp, xcd) : share * fp.fusedFrames)) {   // (share * fusedFrames < 2^32: checked by the host)
         done = ++sweep >= 8u;
         continue;
       }
+      stored = fp.cameraHits != nullptr && t >= head * fp.fusedFrames;
       // frame-major inside the XCD's share (every frame of a square stays on its XCD), the head squares of all frames first
-      const uint32_t head = fp.order ? fp.orderHead[xcd] : 0u;
-      if (t < head * fp.fusedFrames) {
+      if (HITS) {
+        t += head;
+      } else if (t < head * fp.fusedFrames) {
         frame = t / head;
         t -= frame * head;
       } else if (fp.fusedFrames > 1u) {
@@ -133,7 +179,8 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
       pos = b;
       if (fp.order) b = (uint32_t)__builtin_amdgcn_readfirstlane((int)fp.order[b]);
     }
-    render_square<PROGRAM, CFG>(sc, fp, out, b, frame, st, c, pos);
+    if (HITS) camera_hit_square<CFG>(sc, fp, b, pos, st, c);
+    else render_square<PROGRAM, CFG>(sc, fp, out, b, frame, st, c, pos, stored ? fp.cameraHits + (size_t)pos * kBlock : nullptr);
   }
   if (STATS) {
     atomicAdd(&stats[0], (unsigned long long)c.rays);
@@ -152,6 +199,13 @@ template <int PROGRAM, class CFG>
 __global__ __launch_bounds__(kBlock, waves_per_simd(PROGRAM)) void lt_render_kernel(SceneDev sc, FrameParams fp, float* __restrict__ out,
                                                           unsigned long long* __restrict__ stats, uint32_t* __restrict__ queues) {
   render_kernel_body<PROGRAM, CFG>(sc, fp, out, stats, queues);
+}
+
+// The camera-hit pass of a call (FrameParams::cameraHits; lt_capi.hip: render_on_stream).  Same scheduling as the render launches
+// it serves, so that a square's hits are written through the L2 of the XCD that renders its frames.
+template <class CFG>
+__global__ __launch_bounds__(kBlock, LT_ACC_WAVES) void lt_camera_hits_kernel(SceneDev sc, FrameParams fp, uint32_t* __restrict__ queues) {
+  render_kernel_body<kAccumulator, CFG, true>(sc, fp, nullptr, nullptr, queues);
 }
 
 // =====================================================================================================================
@@ -205,19 +259,6 @@ struct GiParams {
   float4* so; float4* sd; uint4* sm; float4* sn;
   const uint32_t* occluded;   // [i of the list] != 0: the shadow ray met something
 };
-
-__device__ __forceinline__ bool square_pixel(const FrameParams& fp, uint32_t b, uint32_t& x, uint32_t& y, uint32_t& pix) {
-  const uint32_t k = b / fp.blocksPerTile, sb = b % fp.blocksPerTile;
-  const uint32_t sbx = sb % fp.blocksPerTileX, sby = sb / fp.blocksPerTileX;
-  const uint32_t tile = fp.tileFirst + k * fp.tileStride;
-  const uint32_t tx = tile % fp.tilesX, ty = tile / fp.tilesX;
-  const uint32_t lane = threadIdx.x;
-  const uint32_t lx = sbx * 8u + (lane & 7u), ly = sby * 8u + (lane >> 3);
-  x = tx * fp.tileW + lx;
-  y = ty * fp.tileH + ly;
-  pix = (k * fp.tileH + ly) * fp.tileW + lx;
-  return k < fp.tilesInCall && lx < fp.tileW && ly < fp.tileH && x < fp.width && y < fp.height;
-}
 
 // one atomic per wave: slot of this lane among the lanes with `keep`
 __device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool keep) {
