@@ -262,7 +262,9 @@ struct lt_hip_context {
   uint64_t queue_frames = 0;
   int shadow_mode[6] = {-1, -1, -1, -1, -1, -1};   // per built-in program: shadow rays as any-hit packets (1) or per lane (0); -1 = not timed yet
   hipEvent_t cal_ev[12] = {};
-  std::map<std::vector<uint32_t>, int> shadow_modes;   // (program, W, H, tile geometry) -> the walk timed faster for it on the resident scene
+  std::map<std::vector<uint32_t>, int> shadow_modes;
+  std::map<std::vector<uint32_t>, uint32_t> shadow_groups;   // ... and the frames per work item it was timed with (launch_walk)
+  unsigned long long* d_groupWalks = nullptr;   // LT_DEBUG_SHADOW_FRAMES: waves whose two frames walked together / apart (launch_walk)   // (program, W, H, tile geometry) -> the walk timed faster for it on the resident scene
   void* d_shadowq = nullptr;         // accumulator's queued shadow rays (shadow mode 3): origin+tmax, direction, (pixel, primitive, frame), occluded: 52 bytes per slot
   uint64_t shadowq_slots = 0;
   uint32_t* d_shadowCtl = nullptr;   // ... the trace launch's eight work counters (kQueueStride apart) and, behind them, the queue's length
@@ -385,6 +387,7 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_queues) (void)hipFree(ctx->d_queues);
   if (ctx->d_samples) (void)hipFree(ctx->d_samples);
   if (ctx->d_camhits) (void)hipFree(ctx->d_camhits);
+  if (ctx->d_groupWalks) (void)hipFree(ctx->d_groupWalks);
   if (ctx->d_shadowq) (void)hipFree(ctx->d_shadowq);
   if (ctx->d_shadowCtl) (void)hipFree(ctx->d_shadowCtl);
   if (ctx->d_order) (void)hipFree(ctx->d_order);
@@ -807,6 +810,7 @@ static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const Scen
   if (ctx->verdict_sizes_valid && memcmp(sizes, ctx->verdict_sizes, sizeof(ctx->verdict_sizes)) == 0 && !k.retime) return;
   for (int& m : ctx->shadow_mode) m = -1;
   ctx->shadow_modes.clear();
+  ctx->shadow_groups.clear();
   memcpy(ctx->verdict_sizes, sizes, sizeof(ctx->verdict_sizes));
   ctx->verdict_sizes_valid = true;
 }
@@ -1024,6 +1028,9 @@ struct RenderKnobs {
   bool debug_camera_hits = getenv("LT_DEBUG_CAMERA_HITS") != nullptr;   // launch_camera_hits prints the squares of its pass to stderr
   bool pinned_readback = !env_off("LT_PINNED_READBACK");   // off: lt_hip_render reads back in one copy (readback_piece)
   bool camera_hits = !env_off("LT_CAMERA_HITS");   // off: every launch walks its camera rays (launch_camera_hits)
+  uint32_t shadow_frames = 2;           // LT_SHADOW_FRAMES=1..2: frames per work item whose shadow rays walk together (launch_walk)
+  bool debug_shadow_frames = getenv("LT_DEBUG_SHADOW_FRAMES") != nullptr;   // launch_walk prints the frame groups of every render launch
+                                                                            // and, where there are groups, how many waves walked them together
   RenderKnobs() {
     if (const char* e = getenv("LT_SHADOW_PACKETS")) shadow_packets = std::max(0, std::min(3, atoi(e)));
     if (const char* e = getenv("LT_SHADOW_SPREAD")) shadow_spread = (float)atof(e);
@@ -1031,6 +1038,7 @@ struct RenderKnobs {
     if (const char* e = getenv("LT_TRACE_REFILL")) trace_refill = (uint32_t)std::max(1, std::min(64, atoi(e)));
     if (const char* e = getenv("LT_FUSED_BYTES")) fused_bytes = strtoull(e, nullptr, 10);
     if (const char* e = getenv("LT_DEBUG_LDS_ROWS")) debug_lds_rows = (uint32_t)std::max(1, std::min(160, atoi(e)));
+    if (const char* e = getenv("LT_SHADOW_FRAMES")) shadow_frames = (uint32_t)std::max(1, std::min(2, atoi(e)));
   }
 };
 
@@ -1138,6 +1146,7 @@ static FrameParams frame_params(const lt_hip_render_desc* d, const TilePlan& p, 
   fp.blocksPerTileX = p.bptx; fp.blocksPerTile = p.bptx * p.bpty;
   fp.pixelCounters = (d->flags & LT_RENDER_FLAG_PIXEL_COUNTERS) != 0;
   fp.persistent = k.persistent;
+  fp.shadowFrames = 1;
   return fp;
 }
 
@@ -1168,7 +1177,10 @@ static void launch_program(const RenderCall& c, const SceneDev& sc, const FrameP
     if constexpr (PROGRAM == kAccumulatorQueue) launch(Config<false, false, M>{});
     else if (c.stats && c.deep) launch(Config<true, true, M>{});
     else if (c.stats) launch(Config<false, true, M>{});
-    else launch(Config<false, false, M>{});
+    else if constexpr (PROGRAM == kAccumulator) {
+      if (fp.shadowFrames > 1u) launch(Config<false, false, M, false, true>{});   // (frame groups: a kernel of their own)
+      else launch(Config<false, false, M>{});
+    } else launch(Config<false, false, M>{});
   });
 }
 
@@ -1539,13 +1551,33 @@ static void launch_builtin(const RenderCall& c, const SceneDev& sc, const FrameP
 
 // One frame-set of the call with a given shadow-ray walk: the render launch and, when the shadow rays are queued (mode 3:
 // accumulator, a tree of the backend's own, a launch that overwrites what it writes), lt_trace_kernel over the queue and the
-// kernel that blacks out the occluded samples.
-static int launch_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& sc, uint32_t mode, const FrameParams& fp, dim3 grid, float* out, uint32_t* queues) {
+// kernel that blacks out the occluded samples.  With the packet walks (1, 2) accumulator's squares whose camera hits are stored
+// are rendered `group` frames at a time (at most LT_SHADOW_FRAMES), their shadow rays walking together (FrameParams::shadowFrames).
+static int launch_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& sc, uint32_t mode, uint32_t group, const FrameParams& fp0, dim3 grid, float* out,
+                       uint32_t* queues) {
   sc.shadowPackets = mode;
+  FrameParams fp = fp0;
+  fp.shadowFrames = (mode == 1u || mode == 2u) && c.d->program == LT_PROGRAM_ACCUMULATOR && !c.stats && fp.cameraHits != nullptr
+                        ? std::min(std::min(group, c.k.shadow_frames), fp.fusedFrames) : 1u;
   if (mode != 3u) {
+    if (c.k.debug_shadow_frames && fp.shadowFrames > 1u) {   // (a debugging aid: counts the waves of each kind, and waits for them)
+      if (!ctx->d_groupWalks) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_groupWalks, 2 * sizeof(unsigned long long)));
+      LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_groupWalks, 0, 2 * sizeof(unsigned long long), c.s));
+      SceneDev sd = sc;
+      sd.groupWalks = ctx->d_groupWalks;
+      launch_builtin(c, sd, fp, grid, out, ctx->d_stats, queues);
+      unsigned long long h[2];
+      LT_HIP_CHECK(ctx, hipMemcpyAsync(h, ctx->d_groupWalks, sizeof(h), hipMemcpyDeviceToHost, c.s));
+      LT_HIP_CHECK(ctx, hipStreamSynchronize(c.s));
+      fprintf(stderr, "shadow-ray frame groups: %u (walk %u, %u frames): %llu waves walked both frames together, %llu apart\n", fp.shadowFrames,
+              mode, fp.fusedFrames, h[0], h[1]);
+      return LT_OK;
+    }
+    if (c.k.debug_shadow_frames) fprintf(stderr, "shadow-ray frame groups: %u (walk %u, %u frames)\n", fp.shadowFrames, mode, fp.fusedFrames);
     launch_builtin(c, sc, fp, grid, out, ctx->d_stats, queues);
     return LT_OK;
   }
+  if (c.k.debug_shadow_frames) fprintf(stderr, "shadow-ray frame groups: %u (walk %u, %u frames)\n", fp.shadowFrames, mode, fp.fusedFrames);
   const uint64_t slots = c.nblocks * fp.fusedFrames * kBlock;
   LT_HIP_CHECK(ctx, grow_scratch(ctx->d_shadowq, ctx->shadowq_slots, slots, slots * 52));   // (origin + tmax, direction, pixel / primitive / frame: 48 bytes; its fate: 4)
   if (!ctx->d_shadowCtl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_shadowCtl, 9 * kQueueStride * sizeof(uint32_t)));
@@ -1573,15 +1605,18 @@ static int launch_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& sc, uint32_
 // writes, as every fused launch does): the launch as it is -- a verdict on fewer frames is another launch's verdict: a
 // launch pays a fixed price for its slowest squares, which the walks share out differently -- once per walk after one
 // untimed run.  The fastest wins, unless the walk an earlier verdict on this scene picked is within 3 % of it: two walks
-// that close must not take turns from call to call.
+// that close must not take turns from call to call.  Frame groups (launch_walk) are a matter of speed too, and they do not win
+// everywhere (colonnade: 16.0 ms with one frame per work item, 16.6 with two): walk 1 is timed with groups, walk 2 without, so
+// that a scene where groups lose keeps the packets of single frames (walk 2 takes them where its rays are coherent); `group` is
+// the frames per work item of the winner, remembered with it.
 static int calibrate_shadow_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& sc, const FrameParams& fp, dim3 grid, float* out, uint32_t* queues,
-                                 bool queueOk, const std::vector<uint32_t>& key, int& mode) {
+                                 bool queueOk, const std::vector<uint32_t>& key, int& mode, uint32_t& group) {
   for (hipEvent_t& e : ctx->cal_ev) if (!e) LT_HIP_CHECK(ctx, hipEventCreate(&e));
-  const uint32_t kOrder[4] = {1u, 0u, 2u, 3u};
+  const uint32_t kOrder[4] = {1u, 0u, 2u, 3u}, kGroup[4] = {c.k.shadow_frames, 1u, 1u, 1u};
   const int candidates = queueOk ? 4 : 3;
   for (int pass = -1; pass < candidates; pass++) {
     if (pass >= 0) LT_HIP_CHECK(ctx, hipEventRecord(ctx->cal_ev[2 * pass], c.s));
-    if (const int rc = launch_walk(ctx, c, sc, kOrder[pass < 0 ? 0 : pass], fp, grid, out, queues)) return rc;
+    if (const int rc = launch_walk(ctx, c, sc, kOrder[pass < 0 ? 0 : pass], kGroup[pass < 0 ? 0 : pass], fp, grid, out, queues)) return rc;
     if (pass >= 0) LT_HIP_CHECK(ctx, hipEventRecord(ctx->cal_ev[2 * pass + 1], c.s));
     LT_HIP_CHECK(ctx, hipMemsetAsync(queues, 0, 8 * kQueueStride * sizeof(uint32_t), c.s));
   }
@@ -1592,11 +1627,14 @@ static int calibrate_shadow_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& s
     fprintf(stderr, "shadow-walk timing (ms, %u frames): packets %.3f, per lane %.3f, per wavefront %.3f, queued %.3f\n", fp.fusedFrames, t[0], t[1], t[2], t[3]);
   int best = 0;
   for (int k = 1; k < candidates; k++) if (t[k] < t[best]) best = k;
-  mode = (int)kOrder[best];
+  int kept = best;
   const int earlier = ctx->shadow_mode[c.d->program];
   for (int k = 0; k < candidates; k++)
-    if ((int)kOrder[k] == earlier && t[k] <= 1.03f * t[best]) mode = earlier;
+    if ((int)kOrder[k] == earlier && t[k] <= 1.03f * t[best]) kept = k;
+  mode = (int)kOrder[kept];
+  group = kGroup[kept];
   ctx->shadow_modes[key] = mode;
+  ctx->shadow_groups[key] = group;
   ctx->shadow_mode[c.d->program] = mode;
   c.launches += (uint32_t)candidates + 1u;
   return LT_OK;
@@ -1663,6 +1701,9 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   const bool queueOk = d->program == LT_PROGRAM_ACCUMULATOR && k.persistent && !stats && ctx->d_rank8 != nullptr && !meanInLaunch &&
                        nblocks * firstFrames * kBlock < 0xffffffffull;
   int shadowMode = choose_shadow_walk(ctx, k, d, shadowKey, queueOk || nblocks == 0);
+  // frames per work item of walks 1 and 2 (launch_walk): LT_SHADOW_FRAMES where the walk is forced, else what it was timed with
+  uint32_t shadowGroup = k.shadow_frames;
+  if (k.shadow_packets < 0 && ctx->shadow_groups.count(shadowKey)) shadowGroup = ctx->shadow_groups[shadowKey];
   sc.shadowPackets = shadowMode > 0 ? (uint32_t)shadowMode : 0u;
   const bool calibrate = k.persistent && !stats && ctx->bvh_height <= kLdsStack && !meanInLaunch;
 
@@ -1708,8 +1749,8 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
       LT_HIP_CHECK(ctx, hipModuleLaunchKernel(fn, grid.x, 1, 1, kBlock, 1, 1, lds, s, args, nullptr));
     } else {
       if (shadowMode < 0 && calibrate)
-        if (const int rc = calibrate_shadow_walk(ctx, call, sc, fp, grid, out, queues, queueOk, shadowKey, shadowMode)) return rc;
-      if (const int rc = launch_walk(ctx, call, sc, (uint32_t)std::max(0, shadowMode), fp, grid, out, queues)) return rc;
+        if (const int rc = calibrate_shadow_walk(ctx, call, sc, fp, grid, out, queues, queueOk, shadowKey, shadowMode, shadowGroup)) return rc;
+      if (const int rc = launch_walk(ctx, call, sc, (uint32_t)std::max(0, shadowMode), shadowGroup, fp, grid, out, queues)) return rc;
     }
     LT_HIP_CHECK(ctx, hipGetLastError());
     call.launches++;

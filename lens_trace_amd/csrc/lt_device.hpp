@@ -112,6 +112,7 @@ struct SceneDev {
   uint32_t fastRcp;         // != 0: intersectTriangle's 1 / det as the reference's as-shipped build computes it (Math<2>::rcp), in every walk
   float shadowSpread;       // shadowPackets == 2: a wave's shadow rays walk as a packet iff every origin lies within sqrt(shadowSpread) x its
                             // own ray's length of the first lane's origin (one surface patch looking at one light), else per lane
+  unsigned long long* groupWalks;   // LT_DEBUG_SHADOW_FRAMES, else null: [0] waves whose two frames' shadow rays walked together, [1] apart
 };
 
 typedef float F4v __attribute__((ext_vector_type(4)));
@@ -713,12 +714,15 @@ __device__ inline void traverse_own_lane(const SceneDev& sc, const Ray& ray, flo
 }
 
 // Compile-time configuration of one kernel instantiation.
-template <bool DEEP_, bool STATS_, int DEVLIBM_, bool LDSSCENE_ = false>
+template <bool DEEP_, bool STATS_, int DEVLIBM_, bool LDSSCENE_ = false, bool GROUPS_ = false>
 struct Config {
   static constexpr bool kDeep = DEEP_;       // BVH deeper than the LDS stack: spill entries >= kLdsStack to scratch
   static constexpr bool kStats = STATS_;     // count rays / node visits / triangle tests
   static constexpr int kDevLibm = DEVLIBM_;  // math flavour: 0 portable, 1 device-library leaf math, 2 as shipped (Math<>)
   static constexpr bool kLdsScene = LDSSCENE_; // the per-lane walks read nodes and triangles from the workgroup's LDS copy (SceneDev::ldsNodes)
+  // accumulator's launches with frame groups (FrameParams::shadowFrames > 1) only: the two-frame shading and walk live in a kernel of
+  // their own, so that the one-frame kernel keeps its registers and code (with them it spilled more, and colonnade lost 4 %)
+  static constexpr bool kGroups = GROUPS_;
 };
 
 template <int PROGRAM, bool DEEP, bool STATS, bool SHADOW, bool LDSSCENE = false>
@@ -893,6 +897,74 @@ __device__ __forceinline__ bool packet_ray_ok(const Ray& ray, float ix, float iy
          __builtin_fabsf(ray.o.x) < 0x1p+40f && __builtin_fabsf(ray.o.y) < 0x1p+40f && __builtin_fabsf(ray.o.z) < 0x1p+40f;
 }
 
+// ---- two frames' shadow rays of one camera hit in one any-hit packet walk (lt_walk_asm.hpp: LT_ASM_WALK2 makes the argument):
+// ray[0] and ray[1] share their origin, both frames' rays of the wave lie in the octant NEG.  On return pl[j].hitType is 1 where
+// frame j's ray met an occluder.  The plain-C++ form first (-DLT_NO_ASM_WALKS): packet_walk_cpp's any-hit walk with a `live` mask
+// per frame and a child pushed when some lane of either frame enters it.
+template <int PROGRAM, int NEG>
+__device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave) {
+  using u64 = unsigned long long;
+  const __attribute__((address_space(4))) char* const pairs = (const __attribute__((address_space(4))) char*)(unsigned long long)sc.ownPairs;
+  const int lane = (int)__lane_id();
+  PacketRayC pr[2];
+  u64 live[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    pr[j].px = ray[j].o.x * inv[j][0]; pr[j].py = ray[j].o.y * inv[j][1]; pr[j].pz = ray[j].o.z * inv[j][2];
+    pr[j].mg = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(pr[j].px), __builtin_fabsf(pr[j].py)), __builtin_fabsf(pr[j].pz)) * 0x1p-19f + 0x1p-140f;
+    live[j] = __builtin_amdgcn_ballot_w64(true);
+  }
+  const bool fast = sc.fastRcp != 0u;
+  uint32_t cur = 0u;
+  int sp = 0;
+  for (;;) {
+    const F16v r = *(ConstF16)(pairs + (cur << 6));
+    if ((int)cur >= 0) {
+      u64 hmL = 0ull, hmR = 0ull;
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        hmL |= box_mask_cheap<NEG>(r.s0, r.s1, r.s2, r.s3, r.s4, r.s5, inv[j][0], inv[j][1], inv[j][2], pr[j]) & live[j];
+        hmR |= box_mask_cheap<NEG>(r.s8, r.s9, r.sa, r.sb, r.sc, r.sd, inv[j][0], inv[j][1], inv[j][2], pr[j]) & live[j];
+      }
+      if (hmL != 0ull) ldsWave[sp++] = __float_as_int(r.s6);
+      if (hmR != 0ull) ldsWave[sp++] = __float_as_int(r.se);
+    } else {
+      const int prim = __float_as_int(r.sf);
+      const float4 t0 = make_float4(r.s0, r.s1, r.s2, r.s3), t1 = make_float4(r.s4, r.s5, r.s6, r.s7), t2 = make_float4(r.s8, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        const u64 m = box_mask<NEG>(r.s9, r.sa, r.sb, r.sc, r.sd, r.se, ray[j], inv[j][0], inv[j][1], inv[j][2]) & live[j];
+        if (m != 0ull) {
+          const bool active = ((m >> lane) & 1ull) != 0ull && prim != ign;
+          live[j] &= ~__builtin_amdgcn_ballot_w64(intersect_triangle_anyhit<PROGRAM>(t0, t1, t2, ray[j], pl[j].t, active, fast));
+        }
+      }
+      if ((live[0] | live[1]) == 0ull) break;
+    }
+    if (sp == 0) break;
+    cur = (uint32_t)__builtin_amdgcn_readfirstlane(ldsWave[--sp]);
+  }
+#pragma unroll
+  for (int j = 0; j < 2; j++) pl[j].hitType = ((live[j] >> lane) & 1ull) != 0ull ? pl[j].hitType : 1;
+}
+
+template <int PROGRAM, int NEG>
+__device__ __forceinline__ void packet_walk2(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave) {
+#ifndef LT_NO_ASM_WALKS
+  const float eps = (PROGRAM == kBasic || PROGRAM == kCustom) ? 0.0000001f
+                    : (PROGRAM == kBasicLighting) ? __uint_as_float(0x33d6bf95u) : __uint_as_float(0x38d1b718u);
+  const uint32_t ldsrow = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) int*)ldsWave);
+  unsigned long long open0 = __builtin_amdgcn_ballot_w64(true), open1 = open0;
+  packet_anyhit_walk2<NEG>((const void*)sc.ownPairs, ray[0].o.x, ray[0].o.y, ray[0].o.z, inv[0][0], inv[0][1], inv[0][2], ray[0].d.x, ray[0].d.y,
+                           ray[0].d.z, ray[0].d.w, pl[0].t, inv[1][0], inv[1][1], inv[1][2], ray[1].d.x, ray[1].d.y, ray[1].d.z, ray[1].d.w,
+                           pl[1].t, ign, eps, sc.fastRcp, open0, open1, ldsrow);
+  pl[0].hitType = ((open0 >> __lane_id()) & 1ull) != 0ull ? pl[0].hitType : 1;
+  pl[1].hitType = ((open1 >> __lane_id()) & 1ull) != 0ull ? pl[1].hitType : 1;
+#else
+  packet_walk2_cpp<PROGRAM, NEG>(sc, ray, inv, ign, pl, ldsWave);
+#endif
+}
+
 // Camera rays: packet traversal when the wave qualifies, the per-lane traversal otherwise.
 template <int PROGRAM, bool DEEP, bool STATS>
 __device__ inline void traverse_camera(const SceneDev& sc, const Ray& ray, Hit& pl, Stack<DEEP>& st, Counters& c) {
@@ -991,6 +1063,55 @@ __device__ inline void traverse(const SceneDev& sc, const Ray& ray, bool useIgno
     ScratchStack ss;
     traverse_nodes_impl<PROGRAM, ScratchStack, false, false, ANYHIT, false>(sc, ray, ix, iy, iz, useIgnore, ignore, pl, ss, c);
   }
+}
+
+// Two frames' shadow rays of one camera hit (shade_lighting2: one origin, the primitive `ignore` under it; pl[j].t = frame j's
+// tmax).  One walk for both (packet_walk2) when each frame's rays would walk as a packet in traverse -- finite, of ordinary
+// magnitudes, walk 1 or walk 2 with the spread test passed for that frame's tmax -- and all 128 rays share one direction-sign
+// octant: true.  Otherwise false, and nothing is walked: the caller renders each frame as it does alone (render_square), so that
+// the kernel holds one copy of traverse and its walks, not two.
+template <int PROGRAM, class CFG>
+__device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2], int ignore, Hit (&pl)[2], Stack<CFG::kDeep>& st, Counters& c) {
+  bool ok = false;
+  if constexpr (!CFG::kStats && !CFG::kDeep && !CFG::kLdsScene) {
+    float inv[2][3];
+    ok = sc.shadowPackets == 1u || sc.shadowPackets == 2u;
+    unsigned long long sign[2][3];
+    const unsigned long long all = __builtin_amdgcn_ballot_w64(true);
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      inv[j][0] = 1.0f / ray[j].d.x; inv[j][1] = 1.0f / ray[j].d.y; inv[j][2] = 1.0f / ray[j].d.z;
+      const bool finite = __builtin_fabsf(inv[j][0]) < __builtin_inff() && __builtin_fabsf(inv[j][1]) < __builtin_inff() &&
+                          __builtin_fabsf(inv[j][2]) < __builtin_inff() && __builtin_fabsf(ray[j].o.x) < __builtin_inff() &&
+                          __builtin_fabsf(ray[j].o.y) < __builtin_inff() && __builtin_fabsf(ray[j].o.z) < __builtin_inff();
+      ok = ok && __all(finite) && sc.rank8 != nullptr && __all(packet_ray_ok(ray[j], inv[j][0], inv[j][1], inv[j][2]));
+      if (ok && sc.shadowPackets == 2u) {   // traverse's per-wavefront test, with this frame's ray length
+        auto first = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+        const float rx = first(ray[j].o.x), ry = first(ray[j].o.y), rz = first(ray[j].o.z);
+        const float ex = ray[j].o.x - rx, ey = ray[j].o.y - ry, ez = ray[j].o.z - rz;
+        ok = __builtin_amdgcn_ballot_w64(ex * ex + ey * ey + ez * ez > sc.shadowSpread * (pl[j].t * pl[j].t)) == 0ull;
+      }
+#pragma unroll
+      for (int a = 0; a < 3; a++) sign[j][a] = __builtin_amdgcn_ballot_w64(inv[j][a] < 0.0f);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) ok = ok && (sign[0][a] == 0ull || sign[0][a] == all) && sign[1][a] == sign[0][a];
+    if (sc.groupWalks != nullptr && (int)__lane_id() == __ffsll((long long)all) - 1) atomicAdd(&sc.groupWalks[ok ? 0 : 1], 1ull);
+    if (ok) {
+      int* const row = st.lds - __lane_id();
+      switch ((sign[0][0] != 0ull ? 1 : 0) | (sign[0][1] != 0ull ? 2 : 0) | (sign[0][2] != 0ull ? 4 : 0)) {
+        case 0: packet_walk2<PROGRAM, 0>(sc, ray, inv, ignore, pl, row); break;
+        case 1: packet_walk2<PROGRAM, 1>(sc, ray, inv, ignore, pl, row); break;
+        case 2: packet_walk2<PROGRAM, 2>(sc, ray, inv, ignore, pl, row); break;
+        case 3: packet_walk2<PROGRAM, 3>(sc, ray, inv, ignore, pl, row); break;
+        case 4: packet_walk2<PROGRAM, 4>(sc, ray, inv, ignore, pl, row); break;
+        case 5: packet_walk2<PROGRAM, 5>(sc, ray, inv, ignore, pl, row); break;
+        case 6: packet_walk2<PROGRAM, 6>(sc, ray, inv, ignore, pl, row); break;
+        default: packet_walk2<PROGRAM, 7>(sc, ray, inv, ignore, pl, row); break;
+      }
+    }
+  }
+  return ok;
 }
 
 // ---------------------------------------------------------------- shading helpers
@@ -1202,6 +1323,62 @@ __device__ inline V3 shade_lighting(const SceneDev& sc, const Hit& pl, float fx,
   return out;
 }
 
+// accumulator's shade_lighting for frames s and s + 1 of one camera hit, every value the one-frame code's: random() once per seed
+// (frame s draws seeds s, s + 1, s + 2, frame s + 1 seeds s + 1, s + 2, s + 3: four evaluations instead of six), the hit's position
+// and normal once, the two shadow rays -- one origin -- through traverse_shadow2.  Same order of evaluation as light_sample /
+// direct_light, and their fences.  False where the two rays could not walk together: `out` is then not the colours.
+template <class CFG>
+__device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float fx, float fy, uint32_t s, Stack<CFG::kDeep>& st, Counters& c,
+                                       V3 (&out)[2]) {
+  out[0] = out[1] = V3{0.0f, 0.0f, 0.0f};
+  if (is_light(sc.lights, pl.prim)) {
+    out[0] = out[1] = V3{1.0f, 1.0f, 1.0f};
+    return true;
+  }
+  if (pl.hitType != 1) return true;
+  const float* pr = prim_ptr(sc, pl.prim);
+  float rnd[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) rnd[i] = random_<CFG::kDevLibm>(fx, fy, (float)(s + (uint32_t)i));
+  V4 lightPosition[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const float* lp = light_prim(sc, rnd[j]);
+    float uvx = rnd[j + 1], uvy = rnd[j + 2];
+    if (uvx + uvy > 1.0f) {
+      uvx = 1.0f - uvx;
+      uvy = 1.0f - uvy;
+    }
+    const V3 l3 = bary3<CFG::kDevLibm>(lp + 0, lp + 3, lp + 6, barycentrics(uvx, uvy));
+    lightPosition[j] = mk4(l3.x, l3.y, l3.z, 1.0f);
+  }
+  asm volatile("" ::: "memory");
+
+  const V3 b = barycentrics(pl.u, pl.v);
+  const V3 p3 = bary3<CFG::kDevLibm>(pr + 0, pr + 3, pr + 6, b);
+  const V4 position = mk4(p3.x, p3.y, p3.z, 1.0f);
+  const V3 n3 = bary3<CFG::kDevLibm>(pr + 9, pr + 12, pr + 15, b);
+  const V4 normal = mk4(n3.x, n3.y, n3.z, 0.0f);
+  Ray ray[2];
+  Hit spl[2];
+  float ndotl[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const V4 toLight = normalize4<CFG::kDevLibm>(sub4(lightPosition[j], position));
+    spl[j] = Hit{0, 0, (float)((double)distance4<CFG::kDevLibm>(position, lightPosition[j]) - 0.01), 0.0f, 0.0f};
+    ndotl[j] = dot4(toLight, normal);
+    ray[j] = Ray{position, toLight};
+  }
+  asm volatile("" : "+v"(ndotl[0]), "+v"(ndotl[1]));
+  if (!traverse_shadow2<kAccumulator, CFG>(sc, ray, pl.prim, spl, st, c)) return false;
+  asm volatile("" ::: "memory");
+  const Material* m = sc.mats + prim_material(pr);
+#pragma unroll
+  for (int j = 0; j < 2; j++)
+    if (spl[j].hitType == 0) out[j] = V3{m->diffuse[0] * ndotl[j], m->diffuse[1] * ndotl[j], m->diffuse[2] * ndotl[j]};
+  return true;
+}
+
 // gi.cl:68-74
 template <int DEVLIBM>
 __device__ inline V4 uniform_sample_hemisphere(float uvx, float uvy) {
@@ -1318,6 +1495,10 @@ struct FrameParams {
   // of lane l of the square at hand-out position p at cameraHits[p * 64 + l], (primitive, hitType, u, v) -- every square but the
   // head squares of the XCDs' shares, which the render launches walk themselves.  Null: every launch walks its camera rays.
   uint4* cameraHits;
+  // ... and then a work item of accumulator over stored hits covers shadowFrames consecutive frames of its square (1 or 2; the last
+  // item of a square covers what is left): the frames' shadow rays leave the same points, and two of them walk together
+  // (shade_pixel2).  The host sets it for shadow walks 1 and 2 (LT_SHADOW_FRAMES); 1 everywhere else.
+  uint32_t shadowFrames;
 };
 
 // Camera ray of pixel (x,y): acc.cl:304-312.
@@ -1335,6 +1516,22 @@ __device__ __forceinline__ Ray camera_ray(const FrameParams& fp, int x, int y, f
   fx = film.x;
   fy = film.y;
   return ray;
+}
+
+// shade_pixel of accumulator for frames frameCount and frameCount + 1 of a pixel whose camera hit is stored (hitRow): both colours,
+// or false where the frames' shadow rays could not walk together (shade_lighting2)
+template <class CFG>
+__device__ inline bool shade_pixel2(const SceneDev& sc, const FrameParams& fp, uint32_t frameCount, int x, int y, Stack<CFG::kDeep>& st,
+                                    Counters& c, const uint4* hitRow, V3 (&color)[2]) {
+  float fx, fy;
+  const Ray ray = camera_ray<CFG::kDevLibm>(fp, x, y, fx, fy);
+  const Hit pl = camera_hit<kAccumulator, CFG>(sc, ray, hitRow, st, c);
+  if (!shade_lighting2<CFG>(sc, pl, fx, fy, frameCount, st, c, color)) return false;
+  if (fp.clampOutput)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+      color[j] = V3{Math<CFG::kDevLibm>::clamp01(color[j].x), Math<CFG::kDevLibm>::clamp01(color[j].y), Math<CFG::kDevLibm>::clamp01(color[j].z)};
+  return true;
 }
 
 #ifdef LT_USER_PROGRAM

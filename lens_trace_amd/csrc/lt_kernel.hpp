@@ -44,10 +44,12 @@ __device__ __forceinline__ bool square_pixel(const FrameParams& fp, uint32_t b, 
 
 // One 8x8 pixel square (logical index b, already XCD-ordered) by one wavefront.
 // (pos: the square's position in the hand-out order -- what a queued shadow ray's slot is made of, SceneDev::shadowPackets == 3;
-// hitRow: the square's stored camera hits, FrameParams::cameraHits, or null)
+// hitRow: the square's stored camera hits, FrameParams::cameraHits, or null; frames: 2 for a work item of two frames, frame and
+// frame + 1, of accumulator over stored hits -- FrameParams::shadowFrames -- else 1)
 template <int PROGRAM, class CFG>
 __device__ __forceinline__ void render_square(const SceneDev& sc, const FrameParams& fp, float* __restrict__ out, uint32_t b,
-                                              uint32_t frame, Stack<CFG::kDeep>& st, Counters& c, uint32_t pos, const uint4* hitRow) {
+                                              uint32_t frame, uint32_t frames, Stack<CFG::kDeep>& st, Counters& c, uint32_t pos,
+                                              const uint4* hitRow) {
   constexpr bool STATS = CFG::kStats;
   const uint32_t k = b / fp.blocksPerTile, sb = b % fp.blocksPerTile;
   const uint32_t sbx = sb % fp.blocksPerTileX, sby = sb / fp.blocksPerTileX;
@@ -64,17 +66,41 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
   if (valid) {
     Counters pc{};   // this pixel's own counters (diagnostic output), folded into the lane's totals below
     const uint32_t pixel = (k * fp.tileH + ly) * fp.tileW + lx;
-    const V3 color = shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, STATS ? pc : c, qslot, pixel, frame, queued, hitRow);
     float* o = out + (size_t)frame * fp.frameStride + (((size_t)k * fp.tileH + ly) * fp.tileW + lx) * fp.depth;
-    if (STATS && fp.pixelCounters) {
-      o[0] = (float)pc.rays; o[1] = (float)pc.shadow; o[2] = (float)pc.nodes; o[3] = (float)pc.tris;
-    } else if (fp.accumulateN <= 0) {   // overwrite, or first frame of a running mean (`if (frameCount > 0)` guard)
-      o[0] = color.x; o[1] = color.y; o[2] = color.z;
-    } else {                     // accumulator.frag:12-18: (c + acc*n) / (n+1)
-      const float n = (float)fp.accumulateN, n1 = (float)(fp.accumulateN + 1);
-      o[0] = (color.x + (o[0] * n)) / n1;
-      o[1] = (color.y + (o[1] * n)) / n1;
-      o[2] = (color.z + (o[2] * n)) / n1;
+    auto store = [&](float* d, const V3& color) {
+      if (fp.accumulateN <= 0) {   // overwrite, or first frame of a running mean (`if (frameCount > 0)` guard)
+        d[0] = color.x; d[1] = color.y; d[2] = color.z;
+      } else {                     // accumulator.frag:12-18: (c + acc*n) / (n+1)
+        const float n = (float)fp.accumulateN, n1 = (float)(fp.accumulateN + 1);
+        d[0] = (color.x + (d[0] * n)) / n1;
+        d[1] = (color.y + (d[1] * n)) / n1;
+        d[2] = (color.z + (d[2] * n)) / n1;
+      }
+    };
+    bool grouped = false;
+    if constexpr (PROGRAM == kAccumulator && CFG::kGroups && !STATS) {
+      if (frames > 1u) {
+        V3 color[2];
+        grouped = shade_pixel2<CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, c, hitRow, color);
+        if (grouped) {
+          store(o, color[0]);
+          store(o + fp.frameStride, color[1]);
+        }
+      }
+    }
+    if constexpr (PROGRAM == kAccumulator && CFG::kGroups && !STATS) {
+      // one frame at a time: every item of one frame, and the lanes of a group whose shadow rays could not walk together (a loop the
+      // compiler keeps: one inlined copy of shade_pixel and its walks)
+#pragma unroll 1
+      for (uint32_t f = frame; !grouped && f < frame + frames; f++)
+        store(o + (size_t)(f - frame) * fp.frameStride, shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + f, (int)x, (int)y, st, c, qslot, pixel, f, queued, hitRow));
+    } else {
+      const V3 color = shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, STATS ? pc : c, qslot, pixel, frame, queued, hitRow);
+      if (STATS && fp.pixelCounters) {
+        o[0] = (float)pc.rays; o[1] = (float)pc.shadow; o[2] = (float)pc.nodes; o[3] = (float)pc.tris;
+      } else {
+        store(o, color);
+      }
     }
     if (STATS) {
       c.rays += pc.rays; c.shadow += pc.shadow; c.nodes += pc.nodes; c.tris += pc.tris;
@@ -141,7 +167,7 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
   uint32_t sweep = 0;
   bool done = false;
   while (!done) {
-    uint32_t b, frame = 0, pos = 0;
+    uint32_t b, frame = 0, frames = 1, pos = 0;
     bool stored = false;   // the item's camera hits are in fp.cameraHits
     if (!fp.persistent) {
       b = xcd_remap(blockIdx.x, gridDim.x);
@@ -154,7 +180,12 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
       if (threadIdx.x == 0) t = atomicAdd(&queues[xcd * kQueueStride], 1u);
       t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
       const uint32_t head = fp.order ? fp.orderHead[xcd] : 0u;
-      if (t >= (HITS ? camera_hit_squares(fp, xcd) : share * fp.fusedFrames)) {   // (share * fusedFrames < 2^32: checked by the host)
+      // accumulator's squares with stored hits come in work items of `group` consecutive frames (FrameParams::shadowFrames), the last
+      // of a square shorter when the launch's frames are not a multiple of it: `groups` items per square
+      const uint32_t group = PROGRAM == kAccumulator && CFG::kGroups && !STATS && !HITS && fp.cameraHits != nullptr && fp.shadowFrames >= 2u ? 2u : 1u;
+      const uint32_t groups = (fp.fusedFrames + group - 1u) / group;
+      // (head * fusedFrames + (share - head) * groups <= share * fusedFrames < 2^32: checked by the host)
+      if (t >= (HITS ? camera_hit_squares(fp, xcd) : head * fp.fusedFrames + (share - head) * groups)) {
         done = ++sweep >= 8u;
         continue;
       }
@@ -167,20 +198,23 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
         t -= frame * head;
       } else if (fp.fusedFrames > 1u) {
         t -= head * fp.fusedFrames;
+        uint32_t item;   // the item's frame group
         if (fp.squareMajor) {   // the frames of a square side by side: their rays meet the same nodes while those are in the L2
-          frame = t % fp.fusedFrames;
-          t = head + t / fp.fusedFrames;
+          item = t % groups;
+          t = head + t / groups;
         } else {
-          frame = t / (share - head);
-          t = head + (t - frame * (share - head));
+          item = t / (share - head);
+          t = head + (t - item * (share - head));
         }
+        frame = item * group;
+        frames = fp.fusedFrames - frame < group ? fp.fusedFrames - frame : group;
       }
       b = start + t;
       pos = b;
       if (fp.order) b = (uint32_t)__builtin_amdgcn_readfirstlane((int)fp.order[b]);
     }
     if (HITS) camera_hit_square<CFG>(sc, fp, b, pos, st, c);
-    else render_square<PROGRAM, CFG>(sc, fp, out, b, frame, st, c, pos, stored ? fp.cameraHits + (size_t)pos * kBlock : nullptr);
+    else render_square<PROGRAM, CFG>(sc, fp, out, b, frame, frames, st, c, pos, stored ? fp.cameraHits + (size_t)pos * kBlock : nullptr);
   }
   if (STATS) {
     atomicAdd(&stats[0], (unsigned long long)c.rays);

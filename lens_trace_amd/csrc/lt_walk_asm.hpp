@@ -92,16 +92,16 @@ typedef unsigned long long lt_u64;
   "vcc", "scc", "memory"
 
 // conservative slab test of one child of an interior record (see the head of the file): 11 instructions
-#define LT_ASM_BOXC(NX, NY, NZ, FX, FY, FZ, OUT)       \
-  "v_fma_f32 %[t0], " NX ", %[ix], -%[px]\n"          \
-  "v_fma_f32 %[t1], " NY ", %[iy], -%[py]\n"          \
-  "v_fma_f32 %[t2], " NZ ", %[iz], -%[pz]\n"          \
+#define LT_ASM_BOXC(NX, NY, NZ, FX, FY, FZ, OUT, S)       \
+  "v_fma_f32 %[t0], " NX ", %[ix" S "], -%[px" S "]\n"          \
+  "v_fma_f32 %[t1], " NY ", %[iy" S "], -%[py" S "]\n"          \
+  "v_fma_f32 %[t2], " NZ ", %[iz" S "], -%[pz" S "]\n"          \
   "v_max3_f32 %[t0], %[t0], %[t1], %[t2]\n"           \
-  "v_fma_f32 %[t1], " FX ", %[ix], -%[px]\n"          \
-  "v_fma_f32 %[t2], " FY ", %[iy], -%[py]\n"          \
-  "v_fma_f32 %[t3], " FZ ", %[iz], -%[pz]\n"          \
+  "v_fma_f32 %[t1], " FX ", %[ix" S "], -%[px" S "]\n"          \
+  "v_fma_f32 %[t2], " FY ", %[iy" S "], -%[py" S "]\n"          \
+  "v_fma_f32 %[t3], " FZ ", %[iz" S "], -%[pz" S "]\n"          \
   "v_min3_f32 %[t1], %[t1], %[t2], %[t3]\n"           \
-  "v_add_f32_e32 %[t1], %[t1], %[mg]\n"               \
+  "v_add_f32_e32 %[t1], %[t1], %[mg" S "]\n"               \
   "v_max_f32_e32 %[t0], 1, %[t0]\n"                   \
   "v_cmp_ge_f32_e64 " OUT ", %[t1], %[t0]\n"
 
@@ -127,40 +127,40 @@ typedef unsigned long long lt_u64;
 // ... the same test AFTER the triangle test (LT_ASM_WALK: a leaf's box is what the parent's conservative test has just let some
 // lane through, so it hardly ever stops the whole wavefront, while most triangles are missed by every lane: the box test then
 // only has to run for the lanes that hit the triangle, i.e. seldom).  t0 .. t3 hold invDet, u, v, t by then.
-#define LT_ASM_BOXX_LATE(NX, NY, NZ, FX, FY, FZ)       \
+#define LT_ASM_BOXX_LATE(NX, NY, NZ, FX, FY, FZ, S)       \
   "v_sub_f32_e32 %[t4], " NX ", %[ox]\n"              \
   "v_sub_f32_e32 %[t5], " NY ", %[oy]\n"              \
   "v_sub_f32_e32 %[t6], " NZ ", %[oz]\n"              \
-  "v_mul_f32_e32 %[t4], %[t4], %[ix]\n"               \
-  "v_mul_f32_e32 %[t5], %[t5], %[iy]\n"               \
-  "v_mul_f32_e32 %[t6], %[t6], %[iz]\n"               \
+  "v_mul_f32_e32 %[t4], %[t4], %[ix" S "]\n"               \
+  "v_mul_f32_e32 %[t5], %[t5], %[iy" S "]\n"               \
+  "v_mul_f32_e32 %[t6], %[t6], %[iz" S "]\n"               \
   "v_max3_f32 %[t4], %[t4], %[t5], %[t6]\n"           \
   "v_sub_f32_e32 %[t5], " FX ", %[ox]\n"              \
   "v_sub_f32_e32 %[t6], " FY ", %[oy]\n"              \
   "v_sub_f32_e32 %[t7], " FZ ", %[oz]\n"              \
-  "v_mul_f32_e32 %[t5], %[t5], %[ix]\n"               \
-  "v_mul_f32_e32 %[t6], %[t6], %[iy]\n"               \
-  "v_mul_f32_e32 %[t7], %[t7], %[iz]\n"               \
+  "v_mul_f32_e32 %[t5], %[t5], %[ix" S "]\n"               \
+  "v_mul_f32_e32 %[t6], %[t6], %[iy" S "]\n"               \
+  "v_mul_f32_e32 %[t7], %[t7], %[iz" S "]\n"               \
   "v_min3_f32 %[t5], %[t5], %[t6], %[t7]\n"           \
   "v_max_f32_e32 %[t4], 1, %[t4]\n"                   \
   "v_cmpx_ge_f32_e64 " LT_R_HML ", %[t5], %[t4]\n"
-#define LT_ASM_BOXX_G_LATE(LX, LY, LZ, HX, HY, HZ)     \
+#define LT_ASM_BOXX_G_LATE(LX, LY, LZ, HX, HY, HZ, S)     \
   "v_sub_f32_e32 %[t4], " LX ", %[ox]\n"              \
   "v_sub_f32_e32 %[t5], " HX ", %[ox]\n"              \
-  "v_mul_f32_e32 %[t4], %[t4], %[ix]\n"               \
-  "v_mul_f32_e32 %[t5], %[t5], %[ix]\n"               \
+  "v_mul_f32_e32 %[t4], %[t4], %[ix" S "]\n"               \
+  "v_mul_f32_e32 %[t5], %[t5], %[ix" S "]\n"               \
   "v_min_f32_e32 %[t6], %[t4], %[t5]\n"               \
   "v_max_f32_e32 %[t7], %[t4], %[t5]\n"               \
   "v_sub_f32_e32 %[t4], " LY ", %[oy]\n"              \
   "v_sub_f32_e32 %[t5], " HY ", %[oy]\n"              \
-  "v_mul_f32_e32 %[t4], %[t4], %[iy]\n"               \
-  "v_mul_f32_e32 %[t5], %[t5], %[iy]\n"               \
+  "v_mul_f32_e32 %[t4], %[t4], %[iy" S "]\n"               \
+  "v_mul_f32_e32 %[t5], %[t5], %[iy" S "]\n"               \
   "v_min_f32_e32 %[t8], %[t4], %[t5]\n"               \
   "v_max_f32_e32 %[t9], %[t4], %[t5]\n"               \
   "v_sub_f32_e32 %[t4], " LZ ", %[oz]\n"              \
   "v_sub_f32_e32 %[t5], " HZ ", %[oz]\n"              \
-  "v_mul_f32_e32 %[t4], %[t4], %[iz]\n"               \
-  "v_mul_f32_e32 %[t5], %[t5], %[iz]\n"               \
+  "v_mul_f32_e32 %[t4], %[t4], %[iz" S "]\n"               \
+  "v_mul_f32_e32 %[t5], %[t5], %[iz" S "]\n"               \
   "v_min_f32_e32 %[t10], %[t4], %[t5]\n"              \
   "v_max_f32_e32 %[t0], %[t4], %[t5]\n"               \
   "v_max3_f32 %[t6], %[t6], %[t8], %[t10]\n"          \
@@ -178,13 +178,13 @@ typedef unsigned long long lt_u64;
 // ... and for a wave whose rays do not share an octant (shadow rays around a light overhead): the same two tests with each
 // axis' near / far plane picked per lane, min / max of the two products (fma and (bound - o) * inv are monotonic in the bound and
 // lo <= hi, so the smaller product is the near plane's): 17 and 22 instructions
-#define LT_ASM_BOXC_G(LX, LY, LZ, HX, HY, HZ, OUT)     \
-  "v_fma_f32 %[t0], " LX ", %[ix], -%[px]\n"          \
-  "v_fma_f32 %[t1], " HX ", %[ix], -%[px]\n"          \
-  "v_fma_f32 %[t2], " LY ", %[iy], -%[py]\n"          \
-  "v_fma_f32 %[t3], " HY ", %[iy], -%[py]\n"          \
-  "v_fma_f32 %[t4], " LZ ", %[iz], -%[pz]\n"          \
-  "v_fma_f32 %[t5], " HZ ", %[iz], -%[pz]\n"          \
+#define LT_ASM_BOXC_G(LX, LY, LZ, HX, HY, HZ, OUT, S)     \
+  "v_fma_f32 %[t0], " LX ", %[ix" S "], -%[px" S "]\n"          \
+  "v_fma_f32 %[t1], " HX ", %[ix" S "], -%[px" S "]\n"          \
+  "v_fma_f32 %[t2], " LY ", %[iy" S "], -%[py" S "]\n"          \
+  "v_fma_f32 %[t3], " HY ", %[iy" S "], -%[py" S "]\n"          \
+  "v_fma_f32 %[t4], " LZ ", %[iz" S "], -%[pz" S "]\n"          \
+  "v_fma_f32 %[t5], " HZ ", %[iz" S "], -%[pz" S "]\n"          \
   "v_min_f32_e32 %[t6], %[t0], %[t1]\n"               \
   "v_min_f32_e32 %[t7], %[t2], %[t3]\n"               \
   "v_min_f32_e32 %[t8], %[t4], %[t5]\n"               \
@@ -193,7 +193,7 @@ typedef unsigned long long lt_u64;
   "v_max_f32_e32 %[t4], %[t4], %[t5]\n"               \
   "v_max3_f32 %[t6], %[t6], %[t7], %[t8]\n"           \
   "v_min3_f32 %[t0], %[t0], %[t2], %[t4]\n"           \
-  "v_add_f32_e32 %[t0], %[t0], %[mg]\n"               \
+  "v_add_f32_e32 %[t0], %[t0], %[mg" S "]\n"               \
   "v_max_f32_e32 %[t6], 1, %[t6]\n"                   \
   "v_cmp_ge_f32_e64 " OUT ", %[t0], %[t6]\n"
 #define LT_ASM_BOXX_G(LX, LY, LZ, HX, HY, HZ)          \
@@ -221,36 +221,36 @@ typedef unsigned long long lt_u64;
   "v_cmpx_ge_f32_e64 " LT_R_HML ", %[t0], %[t6]\n"
 // What LT_ASM_WALK takes as its first argument, LT_NF_<octant> or LT_NF_G, names a pair of tests: for the octant NEG the near
 // plane of axis a is the box's max when direction component a is negative (bit a of NEG).
-#define LT_BC_LT_NF_0(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC(LX, LY, LZ, HX, HY, HZ, OUT)
+#define LT_BC_LT_NF_0(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC(LX, LY, LZ, HX, HY, HZ, OUT, S)
 #define LT_BX_LT_NF_0(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX(LX, LY, LZ, HX, HY, HZ)
-#define LT_BXL_LT_NF_0(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_LATE(LX, LY, LZ, HX, HY, HZ)
-#define LT_BC_LT_NF_1(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC(HX, LY, LZ, LX, HY, HZ, OUT)
+#define LT_BXL_LT_NF_0(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_LATE(LX, LY, LZ, HX, HY, HZ, S)
+#define LT_BC_LT_NF_1(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC(HX, LY, LZ, LX, HY, HZ, OUT, S)
 #define LT_BX_LT_NF_1(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX(HX, LY, LZ, LX, HY, HZ)
-#define LT_BXL_LT_NF_1(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_LATE(HX, LY, LZ, LX, HY, HZ)
-#define LT_BC_LT_NF_2(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC(LX, HY, LZ, HX, LY, HZ, OUT)
+#define LT_BXL_LT_NF_1(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_LATE(HX, LY, LZ, LX, HY, HZ, S)
+#define LT_BC_LT_NF_2(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC(LX, HY, LZ, HX, LY, HZ, OUT, S)
 #define LT_BX_LT_NF_2(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX(LX, HY, LZ, HX, LY, HZ)
-#define LT_BXL_LT_NF_2(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_LATE(LX, HY, LZ, HX, LY, HZ)
-#define LT_BC_LT_NF_3(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC(HX, HY, LZ, LX, LY, HZ, OUT)
+#define LT_BXL_LT_NF_2(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_LATE(LX, HY, LZ, HX, LY, HZ, S)
+#define LT_BC_LT_NF_3(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC(HX, HY, LZ, LX, LY, HZ, OUT, S)
 #define LT_BX_LT_NF_3(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX(HX, HY, LZ, LX, LY, HZ)
-#define LT_BXL_LT_NF_3(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_LATE(HX, HY, LZ, LX, LY, HZ)
-#define LT_BC_LT_NF_4(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC(LX, LY, HZ, HX, HY, LZ, OUT)
+#define LT_BXL_LT_NF_3(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_LATE(HX, HY, LZ, LX, LY, HZ, S)
+#define LT_BC_LT_NF_4(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC(LX, LY, HZ, HX, HY, LZ, OUT, S)
 #define LT_BX_LT_NF_4(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX(LX, LY, HZ, HX, HY, LZ)
-#define LT_BXL_LT_NF_4(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_LATE(LX, LY, HZ, HX, HY, LZ)
-#define LT_BC_LT_NF_5(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC(HX, LY, HZ, LX, HY, LZ, OUT)
+#define LT_BXL_LT_NF_4(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_LATE(LX, LY, HZ, HX, HY, LZ, S)
+#define LT_BC_LT_NF_5(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC(HX, LY, HZ, LX, HY, LZ, OUT, S)
 #define LT_BX_LT_NF_5(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX(HX, LY, HZ, LX, HY, LZ)
-#define LT_BXL_LT_NF_5(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_LATE(HX, LY, HZ, LX, HY, LZ)
-#define LT_BC_LT_NF_6(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC(LX, HY, HZ, HX, LY, LZ, OUT)
+#define LT_BXL_LT_NF_5(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_LATE(HX, LY, HZ, LX, HY, LZ, S)
+#define LT_BC_LT_NF_6(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC(LX, HY, HZ, HX, LY, LZ, OUT, S)
 #define LT_BX_LT_NF_6(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX(LX, HY, HZ, HX, LY, LZ)
-#define LT_BXL_LT_NF_6(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_LATE(LX, HY, HZ, HX, LY, LZ)
-#define LT_BC_LT_NF_7(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC(HX, HY, HZ, LX, LY, LZ, OUT)
+#define LT_BXL_LT_NF_6(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_LATE(LX, HY, HZ, HX, LY, LZ, S)
+#define LT_BC_LT_NF_7(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC(HX, HY, HZ, LX, LY, LZ, OUT, S)
 #define LT_BX_LT_NF_7(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX(HX, HY, HZ, LX, LY, LZ)
-#define LT_BXL_LT_NF_7(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_LATE(HX, HY, HZ, LX, LY, LZ)
-#define LT_BC_LT_NF_G(LX, LY, LZ, HX, HY, HZ, OUT) LT_ASM_BOXC_G(LX, LY, LZ, HX, HY, HZ, OUT)
+#define LT_BXL_LT_NF_7(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_LATE(HX, HY, HZ, LX, LY, LZ, S)
+#define LT_BC_LT_NF_G(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_G(LX, LY, LZ, HX, HY, HZ, OUT, S)
 #define LT_BX_LT_NF_G(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_G(LX, LY, LZ, HX, HY, HZ)
-#define LT_BXL_LT_NF_G(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_G_LATE(LX, LY, LZ, HX, HY, HZ)
-#define LT_BC(NF, LOHI, OUT) LT_BC_##NF(LOHI, OUT)
+#define LT_BXL_LT_NF_G(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_G_LATE(LX, LY, LZ, HX, HY, HZ, S)
+#define LT_BC(NF, LOHI, OUT, S) LT_BC_##NF(LOHI, OUT, S)
 #define LT_BX(NF, LOHI) LT_BX_##NF(LOHI)
-#define LT_BXL(NF, LOHI) LT_BXL_##NF(LOHI)
+#define LT_BXL(NF, LOHI, S) LT_BXL_##NF(LOHI, S)
 
 // branch-free push of a child reference: written at the top, kept iff some lane hit the child
 #define LT_ASM_PUSH(REF, HM)                        \
@@ -259,19 +259,19 @@ typedef unsigned long long lt_u64;
   "s_addc_u32 m0, m0, 0\n"
 
 // det, 1 / det, u (EXEC narrowed by the det and u tests); leaves: t0 = invDet, t1 = u, t7 t8 t9 = tvec
-#define LT_ASM_TRI_PART1                                                                                                        \
-  "v_mul_f32_e64 %[t4], %[dz], -" LT_R_E2Y "\n"     /* pvec = cross(d, e2) */                                                   \
-  "v_mul_f32_e64 %[t5], %[dx], -" LT_R_E2Z "\n"                                                                                 \
-  "v_fmac_f32_e32 %[t4], " LT_R_E2Z ", %[dy]\n"                                                                                 \
-  "v_fmac_f32_e32 %[t5], " LT_R_E2X ", %[dz]\n"                                                                                 \
-  "v_mul_f32_e64 %[t6], %[dy], -" LT_R_E2X "\n"                                                                                 \
+#define LT_ASM_TRI_PART1(S)                                                                                                       \
+  "v_mul_f32_e64 %[t4], %[dz" S "], -" LT_R_E2Y "\n"     /* pvec = cross(d, e2) */                                                   \
+  "v_mul_f32_e64 %[t5], %[dx" S "], -" LT_R_E2Z "\n"                                                                                 \
+  "v_fmac_f32_e32 %[t4], " LT_R_E2Z ", %[dy" S "]\n"                                                                                 \
+  "v_fmac_f32_e32 %[t5], " LT_R_E2X ", %[dz" S "]\n"                                                                                 \
+  "v_mul_f32_e64 %[t6], %[dy" S "], -" LT_R_E2X "\n"                                                                                 \
   "v_mul_f32_e32 %[t0], " LT_R_E1X ", %[t4]\n"                                                                                  \
-  "v_fmac_f32_e32 %[t6], " LT_R_E2Y ", %[dx]\n"                                                                                 \
+  "v_fmac_f32_e32 %[t6], " LT_R_E2Y ", %[dx" S "]\n"                                                                                 \
   "v_fmac_f32_e32 %[t0], " LT_R_E1Y ", %[t5]\n"                                                                                 \
   "v_fmac_f32_e32 %[t0], " LT_R_E1Z ", %[t6]\n"                                                                                 \
   "v_add_f32_e32 %[t0], 0, %[t0]\n"                 /* det */                                                                   \
   "s_cmp_lg_u32 %[fast], 0\n"                                                                                                   \
-  "s_cbranch_scc1 .LfastRcp%=\n"                                                                                                \
+  "s_cbranch_scc1 .LfastRcp" S "%=\n"                                                                                                \
   "v_div_scale_f32 %[t1], " LT_R_HML ", %[t0], %[t0], 1.0\n"                                                                    \
   "v_rcp_f32_e32 %[t2], %[t1]\n"                                                                                                \
   "v_cmpx_nlt_f32_e64 " LT_R_HML ", |%[t0]|, %[eps]\n" /* !(fabs(det) < epsilon) */                                             \
@@ -286,8 +286,8 @@ typedef unsigned long long lt_u64;
   "v_fma_f32 %[t1], -%[t1], %[t9], %[t3]\n"                                                                                     \
   "v_div_fmas_f32 %[t1], %[t1], %[t2], %[t9]\n"                                                                                 \
   "v_div_fixup_f32 %[t0], %[t1], %[t0], 1.0\n"      /* invDet = 1 / det, correctly rounded */                                   \
-  "s_branch .LrcpDone%=\n"                                                                                                      \
-  ".LfastRcp%=:\n"                                  /* the as-shipped build's 1 / det: ldexp(rcp(frexp_mant), -frexp_exp) */    \
+  "s_branch .LrcpDone" S "%=\n"                                                                                                      \
+  ".LfastRcp" S "%=:\n"                                  /* the as-shipped build's 1 / det: ldexp(rcp(frexp_mant), -frexp_exp) */    \
   "v_frexp_mant_f32_e32 %[t1], %[t0]\n"                                                                                         \
   "v_rcp_f32_e32 %[t1], %[t1]\n"                                                                                                \
   "v_cmpx_nlt_f32_e64 " LT_R_HML ", |%[t0]|, %[eps]\n"                                                                          \
@@ -296,7 +296,7 @@ typedef unsigned long long lt_u64;
   "v_frexp_exp_i32_f32_e32 %[t2], %[t0]\n"                                                                                      \
   "v_sub_u32_e32 %[t2], 0, %[t2]\n"                                                                                             \
   "v_ldexp_f32 %[t0], %[t1], %[t2]\n"                                                                                           \
-  ".LrcpDone%=:\n"                                                                                                              \
+  ".LrcpDone" S "%=:\n"                                                                                                              \
   "v_subrev_f32_e32 %[t9], " LT_R_AZ ", %[oz]\n"                                                                                \
   "v_mul_f32_e32 %[t1], %[t7], %[t4]\n"                                                                                         \
   "v_fmac_f32_e32 %[t1], %[t8], %[t5]\n"                                                                                        \
@@ -305,20 +305,20 @@ typedef unsigned long long lt_u64;
   "v_mul_f32_e32 %[t1], %[t1], %[t0]\n"             /* u */                                                                     \
   "v_cmpx_ngt_f32_e64 " LT_R_HML ", 0, %[t1]\n"     /* !(u < 0) */                                                              \
   "v_cmpx_nlt_f32_e64 " LT_R_HML ", 1.0, %[t1]\n"   /* !(u > 1) */                                                              \
-  "s_cbranch_execz .LleafEnd%=\n"
+  "s_cbranch_execz .LleafEnd" S "%=\n"
 
 // v, u + v, t (EXEC narrowed by the v and u + v tests); leaves: t1 = u, t2 = v, t3 = t
-#define LT_ASM_TRI_PART2                                                                                                        \
+#define LT_ASM_TRI_PART2(S)                                                                                                       \
   "v_mul_f32_e64 %[t4], %[t9], -" LT_R_E1Y "\n"     /* qvec = cross(tvec, e1) */                                                \
   "v_fmac_f32_e32 %[t4], " LT_R_E1Z ", %[t8]\n"                                                                                 \
   "v_mul_f32_e64 %[t5], %[t7], -" LT_R_E1Z "\n"                                                                                 \
   "v_mul_f32_e64 %[t6], %[t8], -" LT_R_E1X "\n"                                                                                 \
   "v_fmac_f32_e32 %[t5], " LT_R_E1X ", %[t9]\n"                                                                                 \
   "v_fmac_f32_e32 %[t6], " LT_R_E1Y ", %[t7]\n"                                                                                 \
-  "v_mul_f32_e32 %[t2], %[dx], %[t4]\n"                                                                                         \
-  "v_fmac_f32_e32 %[t2], %[dy], %[t5]\n"                                                                                        \
-  "v_fmac_f32_e32 %[t2], %[dz], %[t6]\n"                                                                                        \
-  "v_fmac_f32_e32 %[t2], 0, %[dw]\n"                                                                                            \
+  "v_mul_f32_e32 %[t2], %[dx" S "], %[t4]\n"                                                                                         \
+  "v_fmac_f32_e32 %[t2], %[dy" S "], %[t5]\n"                                                                                        \
+  "v_fmac_f32_e32 %[t2], %[dz" S "], %[t6]\n"                                                                                        \
+  "v_fmac_f32_e32 %[t2], 0, %[dw" S "]\n"                                                                                            \
   "v_mul_f32_e32 %[t2], %[t2], %[t0]\n"             /* v */                                                                     \
   "v_add_f32_e32 %[t10], %[t1], %[t2]\n"            /* u + v */                                                                 \
   "v_mul_f32_e32 %[t3], " LT_R_E2X ", %[t4]\n"                                                                                  \
@@ -402,12 +402,12 @@ typedef unsigned long long lt_u64;
   "s_load_dwordx16 " LT_R_REC1 ", %[pairs], " LT_R_TMPHI "\n"                                                                   \
   "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
   "s_mov_b64 exec, " LIVE "\n"                                                                                                  \
-  LT_BC(NF, LT_LOHI_0, LT_R_HML)                                                                                               \
-  LT_BC(NF, LT_LOHI_1, LT_R_HMR)                                                                                               \
+  LT_BC(NF, LT_LOHI_0, LT_R_HML, "")                                                                                           \
+  LT_BC(NF, LT_LOHI_1, LT_R_HMR, "")                                                                                           \
   LT_ASM_PUSH(LT_R_REF0L, LT_R_HML)                                                                                             \
   LT_ASM_PUSH(LT_R_REF0R, LT_R_HMR)                                                                                             \
-  LT_BC(NF, LT_LOHI_2, LT_R_HML)                                                                                               \
-  LT_BC(NF, LT_LOHI_3, LT_R_HMR)                                                                                               \
+  LT_BC(NF, LT_LOHI_2, LT_R_HML, "")                                                                                           \
+  LT_BC(NF, LT_LOHI_3, LT_R_HMR, "")                                                                                           \
   LT_ASM_PUSH(LT_R_REF1L, LT_R_HML)                                                                                             \
   LT_ASM_PUSH(LT_R_REF1R, LT_R_HMR)                                                                                             \
   "s_branch .Lpop%=\n"                                                                                                          \
@@ -416,8 +416,8 @@ typedef unsigned long long lt_u64;
   ".Lone%=:\n"                                                                                                                  \
   "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
   "s_mov_b64 exec, " LIVE "\n"                                                                                                  \
-  LT_BC(NF, LT_LOHI_0, LT_R_HML)                                                                                               \
-  LT_BC(NF, LT_LOHI_1, LT_R_HMR)                                                                                               \
+  LT_BC(NF, LT_LOHI_0, LT_R_HML, "")                                                                                           \
+  LT_BC(NF, LT_LOHI_1, LT_R_HMR, "")                                                                                           \
   LT_ASM_PUSH(LT_R_REF0L, LT_R_HML)                                                                                             \
   LT_ASM_PUSH(LT_R_REF0R, LT_R_HMR)                                                                                             \
   "s_branch .Lpop%=\n"                                                                                                          \
@@ -427,10 +427,10 @@ typedef unsigned long long lt_u64;
   "s_mov_b64 exec, " LIVE "\n"                                                                                                  \
   "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
   IGNORE                                                                                                                        \
-  LT_ASM_TRI_PART1                                                                                                              \
-  LT_ASM_TRI_PART2                                                                                                              \
+  LT_ASM_TRI_PART1("")                                                                                                          \
+  LT_ASM_TRI_PART2("")                                                                                                          \
   "s_cbranch_execz .LleafEnd%=\n"                                                                                               \
-  LT_BXL(NF, LT_LOHI_LEAF)                          /* the reference's own test of the leaf's own box, for the lanes that hit the triangle */ \
+  LT_BXL(NF, LT_LOHI_LEAF, "")                        /* the reference's own test of the leaf's own box, for the lanes that hit the triangle */ \
   ACCEPT                                                                                                                        \
   ".LleafEnd%=:\n"                                                                                                              \
   "s_branch .Lpop%=\n"                                                                                                          \
@@ -446,6 +446,108 @@ typedef unsigned long long lt_u64;
   "s_mov_b64 exec, " LT_R_EXEC "\n"
 
 #define LT_ASM_IGNORE_ANYHIT "v_cmpx_ne_u32_e64 " LT_R_HML ", " LT_R_PRIM ", %[ign]\n"
+
+// ---- the any-hit walk of TWO frames' shadow rays at once (packet_anyhit_walk2).  Every lane carries two rays with one origin --
+// the shadow rays of one camera hit towards two samples of the light, frames s and s + 1 of a fused launch -- and the wave walks
+// the tree once for both: one stack, one chain of record fetches; each frame keeps its own `open` mask (operand suffix S: "" for
+// the first frame, "_1" for the second).  Why the pixels are those of two separate walks is the argument for lanes above, once
+// more: a child is pushed iff some lane still open in SOME frame passes its conservative test, so every node a frame's own walk
+// would reach is reached (the pushes of its own lanes are among these); a frame's rays also meet nodes that only the other
+// frame's rays entered, and there a lane either passes the leaf's exact tests or fails them, as it would have had its own walk
+// reached that leaf -- a finite ray reaches a leaf of the reference's traversal iff it passes the slab test of the leaf's own box
+// (lt_retree.hpp).  An any-hit caller reads "accepted or not" only, so the order in which a frame meets its leaves is free.
+// Interior record: each frame's conservative test with EXEC = its `open`, the two hit masks OR-ed (TMPM is free once the record
+// fetches have been issued).  Leaf: each frame's complete test in turn (the triangle's tvec / qvec and the box's (bound - o)
+// depend on the origin only, but qvec is only computed for the lanes past the u test, mostly none; recomputing them keeps every
+// value what the one-frame walk computes and costs no register); the walk ends when both masks are empty.
+#define LT_ASM_TESTS2(NF, L, R)                                                                                                 \
+  "s_mov_b64 exec, %[open]\n"                                                                                                   \
+  LT_BC(NF, LT_LOHI_##L, LT_R_HML, "")                                                                                           \
+  LT_BC(NF, LT_LOHI_##R, LT_R_HMR, "")                                                                                           \
+  "s_mov_b64 exec, %[open_1]\n"                                                                                                 \
+  LT_BC(NF, LT_LOHI_##L, LT_R_TMPM, "_1")                                                                                        \
+  "s_or_b64 " LT_R_HML ", " LT_R_HML ", " LT_R_TMPM "\n"                                                                        \
+  LT_BC(NF, LT_LOHI_##R, LT_R_TMPM, "_1")                                                                                        \
+  "s_or_b64 " LT_R_HMR ", " LT_R_HMR ", " LT_R_TMPM "\n"
+
+#define LT_ASM_LEAF2(NF, S)                                                                                                     \
+  "s_mov_b64 exec, %[open" S "]\n"                                                                                              \
+  "s_cbranch_execz .LleafEnd" S "%=\n"                                                                                          \
+  LT_ASM_IGNORE_ANYHIT                                                                                                          \
+  LT_ASM_TRI_PART1(S)                                                                                                           \
+  LT_ASM_TRI_PART2(S)                                                                                                           \
+  "s_cbranch_execz .LleafEnd" S "%=\n"                                                                                          \
+  LT_BXL(NF, LT_LOHI_LEAF, S)                                                                                                   \
+  "v_cmpx_lt_f32_e64 " LT_R_HML ", %[t3], %[tmax" S "]\n" /* t < payload.t: accepted */                                         \
+  "s_andn2_b64 %[open" S "], %[open" S "], exec\n"                                                                              \
+  ".LleafEnd" S "%=:\n"
+
+#define LT_ASM_WALK2(NF)                                                                                                        \
+  "s_mov_b64 " LT_R_EXEC ", exec\n"                                                                                             \
+  "s_mov_b32 " LT_R_M0 ", m0\n"                                                                                                 \
+  "s_cmp_eq_u64 exec, -1\n"                         /* (the stack register's lanes parked as in LT_ASM_WALK) */                 \
+  "s_cbranch_scc1 .Lsaved%=\n"                                                                                                  \
+  "s_mov_b32 m0, %[ldsrow]\n"                                                                                                   \
+  "s_mov_b64 exec, -1\n"                                                                                                        \
+  "ds_write_addtid_b32 %[stk]\n"                                                                                                \
+  "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
+  "s_mov_b64 exec, " LT_R_EXEC "\n"                                                                                             \
+  ".Lsaved%=:\n"                                                                                                                \
+  "s_mov_b32 m0, 0\n"                                                                                                           \
+  "s_mov_b32 " LT_R_CUR ", 0\n"                                                                                                 \
+  "s_branch .Lnode%=\n"                                                                                                         \
+  ".Lpop%=:\n"                                                                                                                  \
+  "s_cmp_eq_u32 m0, 0\n"                                                                                                        \
+  "s_cbranch_scc1 .Ldone%=\n"                                                                                                   \
+  "s_sub_u32 m0, m0, 1\n"                                                                                                       \
+  "v_readlane_b32 " LT_R_CUR ", %[stk], m0\n"                                                                                   \
+  "s_cmp_lt_i32 " LT_R_CUR ", 0\n"                                                                                              \
+  "s_cbranch_scc1 .Lleaf%=\n"                                                                                                   \
+  ".Lnode%=:\n"                                                                                                                 \
+  "s_lshl_b32 " LT_R_TMPLO ", " LT_R_CUR ", 6\n"                                                                                \
+  "s_load_dwordx16 " LT_R_REC0 ", %[pairs], " LT_R_TMPLO "\n"                                                                   \
+  "s_cmp_eq_u32 m0, 0\n"                                                                                                        \
+  "s_cbranch_scc1 .Lone%=\n"                                                                                                    \
+  "s_sub_u32 m0, m0, 1\n"                                                                                                       \
+  "v_readlane_b32 " LT_R_CUR2 ", %[stk], m0\n"                                                                                  \
+  "s_cmp_lt_i32 " LT_R_CUR2 ", 0\n"                                                                                             \
+  "s_cbranch_scc1 .LoneBack%=\n"                                                                                                \
+  "s_lshl_b32 " LT_R_TMPHI ", " LT_R_CUR2 ", 6\n"                                                                               \
+  "s_load_dwordx16 " LT_R_REC1 ", %[pairs], " LT_R_TMPHI "\n"                                                                   \
+  "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
+  LT_ASM_TESTS2(NF, 0, 1)                                                                                                       \
+  LT_ASM_PUSH(LT_R_REF0L, LT_R_HML)                                                                                             \
+  LT_ASM_PUSH(LT_R_REF0R, LT_R_HMR)                                                                                             \
+  LT_ASM_TESTS2(NF, 2, 3)                                                                                                       \
+  LT_ASM_PUSH(LT_R_REF1L, LT_R_HML)                                                                                             \
+  LT_ASM_PUSH(LT_R_REF1R, LT_R_HMR)                                                                                             \
+  "s_branch .Lpop%=\n"                                                                                                          \
+  ".LoneBack%=:\n"                                                                                                              \
+  "s_add_u32 m0, m0, 1\n"                                                                                                       \
+  ".Lone%=:\n"                                                                                                                  \
+  "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
+  LT_ASM_TESTS2(NF, 0, 1)                                                                                                       \
+  LT_ASM_PUSH(LT_R_REF0L, LT_R_HML)                                                                                             \
+  LT_ASM_PUSH(LT_R_REF0R, LT_R_HMR)                                                                                             \
+  "s_branch .Lpop%=\n"                                                                                                          \
+  ".Lleaf%=:\n"                                                                                                                 \
+  "s_lshl_b32 " LT_R_TMPLO ", " LT_R_CUR ", 6\n"                                                                                \
+  "s_load_dwordx16 " LT_R_REC0 ", %[pairs], " LT_R_TMPLO "\n"                                                                   \
+  "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
+  LT_ASM_LEAF2(NF, "")                                                                                                          \
+  LT_ASM_LEAF2(NF, "_1")                                                                                                        \
+  "s_or_b64 " LT_R_TMPM ", %[open], %[open_1]\n"    /* SCC = some lane of some frame still looking */                           \
+  "s_cbranch_scc1 .Lpop%=\n"                                                                                                    \
+  ".Ldone%=:\n"                                                                                                                 \
+  "s_cmp_eq_u64 " LT_R_EXEC ", -1\n"                                                                                            \
+  "s_cbranch_scc1 .Lrestored%=\n"                                                                                               \
+  "s_mov_b32 m0, %[ldsrow]\n"                                                                                                   \
+  "s_mov_b64 exec, -1\n"                                                                                                        \
+  "ds_read_addtid_b32 %[stk]\n"                                                                                                 \
+  "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
+  ".Lrestored%=:\n"                                                                                                             \
+  "s_mov_b32 m0, " LT_R_M0 "\n"                                                                                                 \
+  "s_mov_b64 exec, " LT_R_EXEC "\n"
 
 // Per-ray constants of the conservative test.
 struct PacketRay {
@@ -488,6 +590,39 @@ __device__ __forceinline__ lt_u64 packet_anyhit_walk(const void* pairs, float ox
   else LT_ANYHIT_INSTANCE(LT_NF_G);   // NEG < 0: the rays' direction signs differ
 #undef LT_ANYHIT_INSTANCE
   return open;
+}
+
+// The any-hit walk of two frames' rays from one origin (LT_ASM_WALK2), one octant NEG >= 0 for both: on return open0 / open1 hold
+// the lanes whose ray of that frame found no occluder.  The second frame's ray: inverse direction i?1, direction d?1, tmax1.
+template <int NEG>
+__device__ __forceinline__ void packet_anyhit_walk2(const void* pairs, float ox, float oy, float oz, float ix, float iy, float iz, float dx,
+                                                    float dy, float dz, float dw, float tmax, float ix1, float iy1, float iz1, float dx1,
+                                                    float dy1, float dz1, float dw1, float tmax1, int ign, float eps, uint32_t fast,
+                                                    lt_u64& open0, lt_u64& open1, uint32_t ldsrow) {
+  const PacketRay pr = packet_ray(ox, oy, oz, ix, iy, iz), pr1 = packet_ray(ox, oy, oz, ix1, iy1, iz1);
+  int stk = 0;
+  float t0, t1, t2, t3, t4, t5, t6, t7, t8, t9, t10;
+#define LT_ANYHIT2_INSTANCE(NF)                                                                                                          \
+  asm volatile(LT_ASM_WALK2(NF)                                                                                                          \
+               : [open] "+s"(open0), [open_1] "+s"(open1), [stk] "+v"(stk), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),             \
+                 [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6), [t7] "=&v"(t7), [t8] "=&v"(t8), [t9] "=&v"(t9),         \
+                 [t10] "=&v"(t10)                                                                                                        \
+               : [pairs] "s"(pairs), [ox] "v"(ox), [oy] "v"(oy), [oz] "v"(oz), [ign] "v"(ign), [eps] "s"(eps), [fast] "s"(fast),          \
+                 [ldsrow] "s"(ldsrow),                                                                                                   \
+                 [ix] "v"(ix), [iy] "v"(iy), [iz] "v"(iz), [px] "v"(pr.px), [py] "v"(pr.py), [pz] "v"(pr.pz), [mg] "v"(pr.mg),             \
+                 [dx] "v"(dx), [dy] "v"(dy), [dz] "v"(dz), [dw] "v"(dw), [tmax] "v"(tmax),                                                \
+                 [ix_1] "v"(ix1), [iy_1] "v"(iy1), [iz_1] "v"(iz1), [px_1] "v"(pr1.px), [py_1] "v"(pr1.py), [pz_1] "v"(pr1.pz),           \
+                 [mg_1] "v"(pr1.mg), [dx_1] "v"(dx1), [dy_1] "v"(dy1), [dz_1] "v"(dz1), [dw_1] "v"(dw1), [tmax_1] "v"(tmax1)              \
+               : LT_ASM_CLOBBERS)
+  if constexpr (NEG == 0) LT_ANYHIT2_INSTANCE(LT_NF_0);
+  else if constexpr (NEG == 1) LT_ANYHIT2_INSTANCE(LT_NF_1);
+  else if constexpr (NEG == 2) LT_ANYHIT2_INSTANCE(LT_NF_2);
+  else if constexpr (NEG == 3) LT_ANYHIT2_INSTANCE(LT_NF_3);
+  else if constexpr (NEG == 4) LT_ANYHIT2_INSTANCE(LT_NF_4);
+  else if constexpr (NEG == 5) LT_ANYHIT2_INSTANCE(LT_NF_5);
+  else if constexpr (NEG == 6) LT_ANYHIT2_INSTANCE(LT_NF_6);
+  else LT_ANYHIT2_INSTANCE(LT_NF_7);
+#undef LT_ANYHIT2_INSTANCE
 }
 
 // The closest-hit walk (camera rays).
