@@ -257,7 +257,42 @@ int lt_hip_own_wide(const void* own_nodes, uint64_t node_bytes, uint32_t n_prims
  * structure (it then walks the caller's tree). */
 int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* out, uint64_t capacity, uint64_t* out_bytes);
 
-/* Statistics of the most recent render call on ctx (waits for it to finish). */
+/* Ray queries over the resident scene (the scene of the last lt_hip_set_scene).  Each ray is traced as the reference traces
+ * one of its own -- `intersect`, or `intersectIgnorePrimitiveIndex` when ignore >= 0 (accumulator.cl:132-217) -- from the
+ * payload {t = tmax, primitiveIndex = hitType = 0}, over the caller's LinearBVHNode tree in the reference's order, with the
+ * intersectTriangle epsilon of the kernel file `program` names (basic.cl:77-117 and custom_opencl: 1e-7f compared in float;
+ * basic_lighting.cl:4: 1e-7 in double; the three others: 1e-4 in double).  Kept as the reference has them: no t > 0 test, no
+ * tmin, `t < tmax` with tmax as given (0, negative, inf and NaN included).  The kernel sets origin.w = 1, direction.w = +0.
+ * The walk may follow the backend's own hierarchy: results are the same bit for bit (equal t from two triangles: the
+ * reference's first leaf wins).  lens_trace_amd/csrc/lt_query.hip. */
+typedef struct lt_hip_ray { float origin[3]; float tmax; float direction[3]; int32_t ignore; } lt_hip_ray;   /* 32 B, ignore -1 = none */
+typedef struct lt_hip_hit { float t; int32_t prim; float u, v; } lt_hip_hit;   /* 16 B; a miss: prim = -1, t = tmax, u = v = 0 */
+
+/* LT_TRACE_CLOSEST writes one lt_hip_hit per ray; LT_TRACE_ANY one uint32 per ray: 1 when the closest-hit query of the same
+ * ray would report prim >= 0, else 0 (the walk may stop at the first accepted triangle). */
+enum { LT_TRACE_CLOSEST = 0, LT_TRACE_ANY = 1 };
+/* flags: LT_RENDER_FLAG_STRICT_MATH or LT_RENDER_FLAG_PORTABLE_MATH (the render path's meaning; default: as shipped), and */
+#define LT_TRACE_FLAG_COHERENT 0x100u   /* caller promises: runs of 64 consecutive rays are coherent (walked as packets) */
+
+typedef struct lt_hip_trace_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_trace_desc) */
+  int32_t program;              /* a built-in LT_PROGRAM_* (selects the epsilon) */
+  int32_t kind;                 /* LT_TRACE_CLOSEST / LT_TRACE_ANY */
+  uint32_t flags;
+} lt_hip_trace_desc;
+
+/* Host memory, synchronous.  LT_ERR_INVALID_ARGUMENT: null ctx / desc, a null pointer with n > 0, an unknown kind, n >= 2^32, a
+ * user program, STRICT with PORTABLE, any other flag, struct_size too small (and, device entry point, pointers that are not
+ * 16-byte aligned); LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when out_bytes < n records.  A failed call writes nothing to out;
+ * n == 0 launches nothing.  lt_hip_get_stats then reports rays = n (closest) or shadow_rays = n (any), kernel_launches and
+ * kernel_ms. */
+int lt_hip_trace_rays(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                      void* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_trace_rays_device(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                             void* out, uint64_t out_bytes, void* hip_stream);
+
+/* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
 
 #ifdef __cplusplus

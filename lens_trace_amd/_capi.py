@@ -20,12 +20,15 @@ RENDER_FLAG_DEVICE_LIBM = 4      # ignored (ABI 2 name of RENDER_FLAG_STRICT_MAT
 RENDER_FLAG_PORTABLE_MATH = 8
 RENDER_FLAG_STRICT_MATH = 16
 RENDER_FLAG_NO_WALK_TIMING = 32
+TRACE_CLOSEST, TRACE_ANY = 0, 1      # lt_hip_trace_desc::kind
+TRACE_FLAG_COHERENT = 0x100          # runs of 64 consecutive rays are coherent: walked as packets
 
 # every symbol include/lenstrace_hip.h declares
 EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last_error", "lt_hip_program_from_path",
            "lt_hip_resolve_program",
            "lt_hip_set_scene", "lt_hip_output_floats", "lt_hip_render", "lt_hip_render_scene", "lt_hip_render_device", "lt_hip_untile",
-           "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure"]
+           "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure",
+           "lt_hip_trace_rays", "lt_hip_trace_rays_device"]
 
 
 class RenderDesc(ctypes.Structure):
@@ -49,6 +52,28 @@ class Stats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TraceRay(ctypes.Structure):   # lt_hip_ray
+    _fields_ = [("origin", ctypes.c_float * 3), ("tmax", ctypes.c_float), ("direction", ctypes.c_float * 3), ("ignore", ctypes.c_int32)]
+
+
+class TraceHit(ctypes.Structure):   # lt_hip_hit
+    _fields_ = [("t", ctypes.c_float), ("prim", ctypes.c_int32), ("u", ctypes.c_float), ("v", ctypes.c_float)]
+
+
+class TraceDesc(ctypes.Structure):   # lt_hip_trace_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("program", ctypes.c_int32), ("kind", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+def _np_dtypes():
+    import numpy as np
+    ray = np.dtype([("origin", "<f4", (3,)), ("tmax", "<f4"), ("direction", "<f4", (3,)), ("ignore", "<i4")])
+    hit = np.dtype([("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4")])
+    return ray, hit
+
+
+RAY_DTYPE, HIT_DTYPE = _np_dtypes()   # numpy views of lt_hip_ray (32 bytes) and lt_hip_hit (16 bytes)
 
 
 class LensTraceError(RuntimeError):
@@ -95,6 +120,9 @@ def load():
     L.lt_hip_untile.argtypes = [vp, vp, u64, u32, u32, u32, u32, u32, u32, vp, vp]
     L.lt_hip_synchronize.argtypes = [vp, vp]
     L.lt_hip_get_stats.argtypes = [vp, ctypes.POINTER(Stats)]
+    if hasattr(L, "lt_hip_trace_rays"):
+        L.lt_hip_trace_rays.argtypes = [vp, ctypes.POINTER(TraceDesc), vp, u64, vp, u64]
+        L.lt_hip_trace_rays_device.argtypes = [vp, ctypes.POINTER(TraceDesc), vp, u64, vp, u64, vp]
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

@@ -4,6 +4,7 @@
 #include "lt_retree.hpp"
 #include "lt_own16.hpp"
 #include "lt_prep.hpp"
+#include "lt_query.hpp"
 
 #include "../../include/lenstrace_hip.h"
 
@@ -281,7 +282,17 @@ struct lt_hip_context {
   std::vector<hipEvent_t> mean_events;   // pairs around the running-mean kernels of the last call
   uint32_t mean_pairs = 0;
   bool pending = false, pending_stats = false;
+  bool pending_query = false;        // ... and it is a ray query (lt_hip_trace_rays*): no render_ms
   lt_hip_stats last{};
+  // ray queries (lt_query.hip): lt_query_kernel's eight work counters (kQueueStride apart), the host entry point's device copies
+  // of the rays and the results, and an event behind the last query's launch (the next one waits for it before it zeroes the
+  // counters: a query enqueued on another stream may still be running)
+  uint32_t* d_query_ctl = nullptr;
+  void* d_query_rays = nullptr;
+  uint64_t query_rays_bytes = 0;
+  void* d_query_out = nullptr;
+  uint64_t query_out_bytes = 0;
+  hipEvent_t query_ev = nullptr;
   // wavefront GI pipeline: path queues, per-pixel direct / indirect / blend, control block (queue lengths, work counters)
   void* d_gi[17] = {nullptr};
   uint64_t gi_pixels = 0;
@@ -390,6 +401,10 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_groupWalks) (void)hipFree(ctx->d_groupWalks);
   if (ctx->d_shadowq) (void)hipFree(ctx->d_shadowq);
   if (ctx->d_shadowCtl) (void)hipFree(ctx->d_shadowCtl);
+  if (ctx->d_query_ctl) (void)hipFree(ctx->d_query_ctl);
+  if (ctx->d_query_rays) (void)hipFree(ctx->d_query_rays);
+  if (ctx->d_query_out) (void)hipFree(ctx->d_query_out);
+  if (ctx->query_ev) (void)hipEventDestroy(ctx->query_ev);
   if (ctx->d_order) (void)hipFree(ctx->d_order);
   for (auto& up : ctx->user_programs) (void)hipModuleUnload(up.module);
   for (void*& b : ctx->d_gi) if (b) (void)hipFree(b);
@@ -1774,6 +1789,7 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   ctx->last.pixels = px;
   ctx->pending = true;
   ctx->pending_stats = stats;
+  ctx->pending_query = false;
   return LT_OK;
 }
 
@@ -1790,7 +1806,7 @@ static int finish_pending(lt_hip_context* ctx) {
     LT_HIP_CHECK(ctx, hipEventElapsedTime(&m, ctx->mean_events[2 * i], ctx->mean_events[2 * i + 1]));
     meanMs += m;
   }
-  ctx->last.render_ms = ms - meanMs;
+  ctx->last.render_ms = ctx->pending_query ? 0.0f : ms - meanMs;
   if (ctx->pending_stats) {
     unsigned long long h[8];
     LT_HIP_CHECK(ctx, hipMemcpy(h, ctx->d_stats, sizeof(h), hipMemcpyDeviceToHost));
@@ -1960,6 +1976,99 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
   } catch (const std::exception& e) {
     return fail(ctx, LT_ERR_HIP, std::string("lt_hip_render_scene: ") + e.what());
   }
+}
+
+// ---------------------------------------------------------------------------------- ray queries
+// lt_hip_trace_rays / lt_hip_trace_rays_device: caller-supplied rays against the resident scene (lt_query.hip).  Every argument
+// error is found before anything is enqueued, so that a failed call writes nothing to `out`.
+struct TraceCall {
+  lt_query::Epsilon eps;
+  bool anyHit, coherent;
+  int devlibm;
+  uint64_t outBytes;   // what n results take
+};
+static_assert(sizeof(lt_hip_ray) == 32 && sizeof(lt_hip_hit) == 16 && sizeof(lt_hip_trace_desc) == 16, "ray query records (include/lenstrace_hip.h)");
+
+static int check_trace(lt_hip_context* ctx, const lt_hip_trace_desc* d, const lt_hip_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
+                       bool device, TraceCall& tc) {
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_trace_rays: desc is NULL");
+  if (d->struct_size < sizeof(lt_hip_trace_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_trace_desc (struct_size)");
+  if (d->kind != LT_TRACE_CLOSEST && d->kind != LT_TRACE_ANY) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown trace kind");
+  if (d->program >= LT_PROGRAM_USER_BASE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take a built-in program (it selects the triangle epsilon)");
+  if (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL) return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
+  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only");
+  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 rays per query");
+  if (n > 0 && (!rays || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "rays or out is NULL");
+  if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "ray query before lt_hip_set_scene");
+  tc.anyHit = d->kind == LT_TRACE_ANY;
+  tc.outBytes = n * (tc.anyHit ? sizeof(uint32_t) : sizeof(lt_hip_hit));
+  if (out_bytes < tc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
+  tc.eps = (d->program == LT_PROGRAM_BASIC || d->program == LT_PROGRAM_CUSTOM_OPENCL) ? lt_query::kEpsFloat7
+           : d->program == LT_PROGRAM_BASIC_LIGHTING ? lt_query::kEpsDouble7 : lt_query::kEpsDouble4;
+  tc.coherent = (d->flags & LT_TRACE_FLAG_COHERENT) != 0;
+  tc.devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
+  return LT_OK;
+}
+
+// Enqueues the query on `s` between the context's timing events; lt_hip_get_stats reports it (finish_pending).
+static int enqueue_trace(lt_hip_context* ctx, const TraceCall& tc, const void* rays, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  if (!ctx->d_query_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_query_ctl, 8 * kQueueStride * sizeof(uint32_t)));
+  if (!ctx->query_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->query_ev, hipEventDisableTiming));
+  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->query_ev, 0));   // (the counters are the previous query's until it is done)
+  lt_query::Params qp{};
+  qp.rays = (const float4*)rays;
+  qp.hits = tc.anyHit ? nullptr : (uint4*)out;
+  qp.occluded = tc.anyHit ? (uint32_t*)out : nullptr;
+  qp.n = (uint32_t)n;
+  qp.next = ctx->d_query_ctl;
+  qp.refill = k.trace_refill;
+  const SceneDev sc = scene_dev(ctx, k, tc.devlibm);
+  ctx->mean_pairs = 0;
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  LT_HIP_CHECK(ctx, lt_query::launch(sc, qp, tc.eps, tc.anyHit, tc.coherent, (uint32_t)ctx->cu_count, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->query_ev, s));
+  ctx->last = lt_hip_stats{};
+  ctx->last.kernel_launches = 1;
+  if (tc.anyHit) ctx->last.shadow_rays = n;
+  else ctx->last.rays = n;
+  ctx->pending = true;
+  ctx->pending_stats = false;
+  ctx->pending_query = true;
+  return LT_OK;
+}
+
+extern "C" int lt_hip_trace_rays(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, void* out,
+                                 uint64_t out_bytes) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  TraceCall tc{};
+  if (const int rc = check_trace(ctx, desc, rays, n, out, out_bytes, false, tc)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint64_t rayBytes = n * sizeof(lt_hip_ray);
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, tc.outBytes, tc.outBytes));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = enqueue_trace(ctx, tc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
+  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (const int rc = finish_pending(ctx)) return rc;
+  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, tc.outBytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+extern "C" int lt_hip_trace_rays_device(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, void* out,
+                                        uint64_t out_bytes, void* hip_stream) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  TraceCall tc{};
+  if (const int rc = check_trace(ctx, desc, rays, n, out, out_bytes, true, tc)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return enqueue_trace(ctx, tc, rays, n, out, (hipStream_t)hip_stream);
 }
 
 extern "C" int lt_hip_untile(lt_hip_context* ctx, const float* gathered, uint64_t floats_per_rank, uint32_t n_ranks, uint32_t width,

@@ -1,0 +1,222 @@
+// lt_query.hip -- ray queries over the resident scene: the kernels behind lt_hip_trace_rays / lt_hip_trace_rays_device.
+//
+// A query traces caller-supplied rays as the reference traces one of its own (acc.cl:132-217: `intersect`, and
+// `intersectIgnorePrimitiveIndex` for a ray with ignore >= 0) from a payload {t = tmax, primitiveIndex = hitType = 0}, with
+// the triangle epsilon of one of the reference's kernel files (basic.cl:77-117 compares 1e-7f in float, basic_lighting.cl:4
+// 1e-7 in double, accumulator.cl:84 and the others 1e-4 in double: three instantiations).  What the reference does not do, the
+// query does not do either: no t > 0 test, no tmin, `t < tmax` as given (0, negative, inf and NaN included).  Ray w components
+// are the kernel's: origin.w = 1, direction.w = +0 (dot4 reads them).
+//
+// Which hierarchy a ray walks does not change its result (lt_retree.hpp): the walks over the backend's own tree, with the
+// reference's leaf order settling equal-t ties (SceneDev::rank8), for rays the own tree takes (finite, of packet_ray_ok's
+// magnitudes, a scene that has one); the caller's tree in the reference's order for the others.  Two kernels:
+//   lt_query_kernel         the default: lt_trace_kernel's per-lane walk with lane refill (lt_kernel.hpp says why), reading the
+//                           caller's records and keeping t;
+//   lt_query_packet_kernel  LT_TRACE_FLAG_COHERENT: one wave per 64 consecutive rays, walked as one packet (packet_walk) when
+//                           the 64 qualify, per lane otherwise.
+#include "lt_query.hpp"
+
+using namespace lt;
+
+namespace {
+
+constexpr int kQueryClaim = 512;   // rays a wave of lt_query_kernel claims per atomic (lt_trace_kernel's kTraceClaim)
+
+// The result of one ray: one 16-byte store (closest hit) or one word (any hit).
+template <bool ANYHIT>
+__device__ __forceinline__ void put_result(const lt_query::Params& qp, uint32_t idx, const Hit& pl) {
+  if (ANYHIT) qp.occluded[idx] = pl.hitType != 0 ? 1u : 0u;
+  else qp.hits[idx] = make_uint4(__float_as_uint(pl.t), pl.hitType != 0 ? (uint32_t)pl.prim : 0xffffffffu, __float_as_uint(pl.u), __float_as_uint(pl.v));
+}
+
+__device__ __forceinline__ bool finite_ray(const Ray& ray, float ix, float iy, float iz) {
+  return __builtin_fabsf(ix) < __builtin_inff() && __builtin_fabsf(iy) < __builtin_inff() && __builtin_fabsf(iz) < __builtin_inff() &&
+         __builtin_fabsf(ray.o.x) < __builtin_inff() && __builtin_fabsf(ray.o.y) < __builtin_inff() && __builtin_fabsf(ray.o.z) < __builtin_inff();
+}
+
+// A ray the own tree does not take, or any ray of a scene without one: the reference's order over the caller's tree.
+template <int PROGRAM, bool ANYHIT>
+__device__ __forceinline__ void walk_reference(const SceneDev& sc, const Ray& ray, float ix, float iy, float iz, int ign, Hit& pl) {
+  ScratchStack ss;
+  Counters c{};
+  traverse_nodes_impl<PROGRAM, ScratchStack, false, false, ANYHIT, false>(sc, ray, ix, iy, iz, true, ign, pl, ss, c);
+}
+
+// The packet walk of a chunk whose 64 rays the own tree takes: false (nothing walked) for closest-hit rays of mixed octants.
+template <int PROGRAM, bool ANYHIT>
+__device__ __forceinline__ bool packet_query(const SceneDev& sc, const Ray& ray, float ix, float iy, float iz, int ign, Hit& pl, int* row) {
+  const unsigned long long all = __builtin_amdgcn_ballot_w64(true), bx = __builtin_amdgcn_ballot_w64(ix < 0.0f),
+                           by = __builtin_amdgcn_ballot_w64(iy < 0.0f), bz = __builtin_amdgcn_ballot_w64(iz < 0.0f);
+  if ((bx == 0ull || bx == all) && (by == 0ull || by == all) && (bz == 0ull || bz == all)) {
+    switch ((bx != 0ull ? 1 : 0) | (by != 0ull ? 2 : 0) | (bz != 0ull ? 4 : 0)) {   // one specialisation per sign octant
+      case 0: packet_walk<PROGRAM, 0, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, row); return true;
+      case 1: packet_walk<PROGRAM, 1, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, row); return true;
+      case 2: packet_walk<PROGRAM, 2, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, row); return true;
+      case 3: packet_walk<PROGRAM, 3, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, row); return true;
+      case 4: packet_walk<PROGRAM, 4, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, row); return true;
+      case 5: packet_walk<PROGRAM, 5, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, row); return true;
+      case 6: packet_walk<PROGRAM, 6, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, row); return true;
+      default: packet_walk<PROGRAM, 7, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, row); return true;
+    }
+  }
+  if constexpr (ANYHIT) {
+    packet_walk<PROGRAM, -1, true>(sc, ray, ix, iy, iz, ign, pl, row);   // (the sign-generic form of the walk)
+    return true;
+  }
+  return false;
+}
+
+}  // namespace
+
+// lt_trace_kernel (lt_kernel.hpp) over the caller's records: waves claim rays from the eighth of the batch of the XCD they run on
+// (then from the others'), 64 at a time into an LDS stage, and a lane whose ray is done takes the next staged one whenever
+// `refill` lanes (or all) are idle.  Rays the own tree does not take are walked at once by the lane that drew them.
+template <int PROGRAM, bool ANYHIT>
+__global__ __launch_bounds__(kBlock, 8) void lt_query_kernel(SceneDev sc, lt_query::Params qp) {
+  using u64 = unsigned long long;
+  extern __shared__ int lds_stack[];   // [kTraceRows stack rows][kTraceStage rows of staged rays], 64 lanes each
+  int* const col = lds_stack + threadIdx.x;
+  int* const stage = lds_stack + kTraceRows * kBlock;
+  const uint32_t total = qp.n;
+  const uint32_t lane = threadIdx.x;
+  const u64 below = (1ull << lane) - 1ull;
+  const bool ownTree = sc.rank8 != nullptr;
+  const uint32_t share = total / (gridDim.x * 4u) / (uint32_t)kBlock * (uint32_t)kBlock;
+  const uint32_t claim = share < (uint32_t)kBlock ? (uint32_t)kBlock : (share > (uint32_t)kQueryClaim ? (uint32_t)kQueryClaim : share);
+  bool active = false;
+  uint32_t stageCount = 0u, stageTaken = 0u, claimNext = 0u, claimEnd = 0u, sweep = 0u;
+  const uint32_t home = __builtin_amdgcn_s_getreg((3u << 11) | 20u) & 7u;   // HW_REG_XCC_ID
+  bool drained = false;
+  Ray ray{};
+  float ix = 0.0f, iy = 0.0f, iz = 0.0f;
+  OwnRay w{};
+  Hit pl{0, 0, 0.0f, 0.0f, 0.0f};
+  uint32_t idx = 0u, e = 0u;
+  int sp = 0;
+  int deep[kOwnRows + kOwnDeep - kTraceRows];
+  for (;;) {
+    const u64 idle = __builtin_amdgcn_ballot_w64(!active);
+    const uint32_t nIdle = (uint32_t)__popcll(idle);
+    if ((nIdle >= qp.refill || nIdle == (uint32_t)kBlock) && (stageTaken < stageCount || !drained)) {
+      if (stageTaken == stageCount) {
+        while (claimNext == claimEnd && sweep < 8u) {
+          const uint32_t part = (home + sweep) & 7u;
+          const uint32_t lo = (uint32_t)((uint64_t)total * part / 8u / kBlock * kBlock), hi = part == 7u ? total : (uint32_t)((uint64_t)total * (part + 1u) / 8u / kBlock * kBlock);
+          uint32_t got = 0u;
+          if (lane == 0u) got = atomicAdd(&qp.next[part * kQueueStride], claim);
+          got = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
+          if (got >= hi - lo) { sweep++; continue; }
+          claimNext = lo + got;
+          claimEnd = hi - claimNext < claim ? hi : claimNext + claim;
+        }
+        const uint32_t base = claimNext;
+        const uint32_t batch = claimEnd - base < (uint32_t)kBlock ? claimEnd - base : (uint32_t)kBlock;
+        claimNext = base + batch;
+        drained = claimNext == claimEnd && sweep >= 8u;
+        stageTaken = 0u;
+        stageCount = batch;
+        if (lane < batch) {   // the caller's record: two coalesced 16-byte loads
+          const float4 a = qp.rays[2 * (size_t)(base + lane)], b = qp.rays[2 * (size_t)(base + lane) + 1];
+          stage[0 * kBlock + lane] = __float_as_int(a.x); stage[1 * kBlock + lane] = __float_as_int(a.y); stage[2 * kBlock + lane] = __float_as_int(a.z);
+          stage[3 * kBlock + lane] = __float_as_int(b.x); stage[4 * kBlock + lane] = __float_as_int(b.y); stage[5 * kBlock + lane] = __float_as_int(b.z);
+          stage[6 * kBlock + lane] = __float_as_int(b.w);   // ignore
+          stage[7 * kBlock + lane] = __float_as_int(a.w);   // tmax
+          stage[8 * kBlock + lane] = (int)(base + lane);
+        }
+        // (one wavefront per workgroup: its own LDS writes are visible to it once they have completed -- the reads below wait for them)
+      }
+      const uint32_t take = nIdle < stageCount - stageTaken ? nIdle : stageCount - stageTaken;
+      const uint32_t mine = (uint32_t)__popcll(idle & below);
+      if (!active && mine < take) {
+        const uint32_t s = stageTaken + mine;
+        idx = (uint32_t)stage[8 * kBlock + s];
+        ray = Ray{mk4(__int_as_float(stage[0 * kBlock + s]), __int_as_float(stage[1 * kBlock + s]), __int_as_float(stage[2 * kBlock + s]), 1.0f),
+                  mk4(__int_as_float(stage[3 * kBlock + s]), __int_as_float(stage[4 * kBlock + s]), __int_as_float(stage[5 * kBlock + s]), 0.0f)};
+        const int ignRaw = stage[6 * kBlock + s];
+        const int ign = ignRaw >= 0 ? ignRaw : -1;
+        ix = 1.0f / ray.d.x; iy = 1.0f / ray.d.y; iz = 1.0f / ray.d.z;
+        pl = Hit{0, 0, __int_as_float(stage[7 * kBlock + s]), 0.0f, 0.0f};
+        if (ownTree && finite_ray(ray, ix, iy, iz) && packet_ray_ok(ray, ix, iy, iz)) {
+          w = own_ray(sc, ray, ix, iy, iz, ign);
+          e = 0u;
+          sp = 0;
+          active = true;
+        } else {
+          walk_reference<PROGRAM, ANYHIT>(sc, ray, ix, iy, iz, ign, pl);
+          put_result<ANYHIT>(qp, idx, pl);
+        }
+      }
+      stageTaken += take;
+    }
+    if (__builtin_amdgcn_ballot_w64(active) == 0ull) {
+      if (drained && stageTaken == stageCount) break;
+      continue;
+    }
+    if (active) {
+      if (own_walk_step<PROGRAM, ANYHIT, kTraceRows>(sc, ray, ix, iy, iz, w, pl, col, deep, e, sp)) {
+        put_result<ANYHIT>(qp, idx, pl);
+        active = false;
+      }
+    }
+  }
+}
+
+// LT_TRACE_FLAG_COHERENT: workgroup b takes rays [64 b, 64 b + 64).  They walk as ONE packet when every one of them is finite and
+// passes packet_ray_ok on a scene with an own tree, and -- closest hit -- they share a direction-sign octant (the leaf order that
+// settles ties is the octant's) and none ignores a primitive (the closest-hit packet walk applies no `ignore`); any-hit rays of
+// mixed octants take the sign-generic packet walk.  Otherwise each lane walks its own ray.  Lanes past the end of the batch walk a
+// copy of the chunk's first ray and store nothing, so that every walk runs with the whole wave.
+template <int PROGRAM, bool ANYHIT>
+__global__ __launch_bounds__(kBlock, 8) void lt_query_packet_kernel(SceneDev sc, lt_query::Params qp) {
+  extern __shared__ int lds_stack[];   // kOwnRows rows: the per-lane walks' stacks; the packet walks use the first two
+  const uint32_t base = blockIdx.x * (uint32_t)kBlock;
+  const uint32_t idx = base + threadIdx.x;
+  const bool valid = idx < qp.n;
+  const size_t src = valid ? idx : base;
+  const float4 a = qp.rays[2 * src], b = qp.rays[2 * src + 1];
+  const Ray ray{mk4(a.x, a.y, a.z, 1.0f), mk4(b.x, b.y, b.z, 0.0f)};
+  const int ignRaw = __float_as_int(b.w);
+  const int ign = ignRaw >= 0 ? ignRaw : -1;
+  const float ix = 1.0f / ray.d.x, iy = 1.0f / ray.d.y, iz = 1.0f / ray.d.z;
+  Hit pl{0, 0, a.w, 0.0f, 0.0f};
+  const bool ownOk = sc.rank8 != nullptr && finite_ray(ray, ix, iy, iz) && packet_ray_ok(ray, ix, iy, iz);
+  if (!(__all(ownOk) && (ANYHIT || __all(ign < 0)) && packet_query<PROGRAM, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, lds_stack))) {
+    if (ownOk) traverse_own_lane<PROGRAM, ANYHIT>(sc, ray, ix, iy, iz, ign, pl, lds_stack + threadIdx.x);
+    else walk_reference<PROGRAM, ANYHIT>(sc, ray, ix, iy, iz, ign, pl);
+  }
+  if (valid) put_result<ANYHIT>(qp, idx, pl);
+}
+
+namespace lt_query {
+
+template <int PROGRAM, bool ANYHIT>
+static void launch_one(const SceneDev& sc, const Params& p, bool coherent, uint32_t cuCount, hipStream_t s) {
+  const uint32_t chunks = (uint32_t)(((uint64_t)p.n + kBlock - 1) / kBlock);
+  if (coherent) {
+    hipLaunchKernelGGL((lt_query_packet_kernel<PROGRAM, ANYHIT>), dim3(chunks), dim3(kBlock), (uint32_t)(kOwnRows * kBlock * sizeof(int)), s, sc, p);
+  } else {
+    const uint32_t resident = cuCount * 32u;   // every wave slot of the chip, once
+    hipLaunchKernelGGL((lt_query_kernel<PROGRAM, ANYHIT>), dim3(chunks < resident ? chunks : resident), dim3(kBlock),
+                       (uint32_t)((kTraceRows + kTraceStage) * kBlock * sizeof(int)), s, sc, p);
+  }
+}
+
+hipError_t launch(const SceneDev& sc, const Params& p, Epsilon eps, bool anyHit, bool coherent, uint32_t cuCount, hipStream_t s) {
+  if (p.n == 0) return hipSuccess;
+  if (!coherent) {
+    const hipError_t e = hipMemsetAsync(p.next, 0, 8 * kQueueStride * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+  }
+  switch (eps) {
+    case kEpsFloat7: anyHit ? launch_one<kBasic, true>(sc, p, coherent, cuCount, s) : launch_one<kBasic, false>(sc, p, coherent, cuCount, s); break;
+    case kEpsDouble7:
+      anyHit ? launch_one<kBasicLighting, true>(sc, p, coherent, cuCount, s) : launch_one<kBasicLighting, false>(sc, p, coherent, cuCount, s);
+      break;
+    default:
+      anyHit ? launch_one<kAccumulator, true>(sc, p, coherent, cuCount, s) : launch_one<kAccumulator, false>(sc, p, coherent, cuCount, s);
+      break;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace lt_query

@@ -1,0 +1,26 @@
+// lt_query.hpp -- ray queries over the resident scene (lt_query.hip): caller-supplied rays, each traced as the reference's
+// `intersect` / `intersectIgnorePrimitiveIndex` would trace it (accumulator.cl:132-217) with the triangle epsilon of one of its
+// kernel files (basic.cl:77-117, basic_lighting.cl:4, accumulator.cl:84), closest hit or any hit.  lt_capi.hip checks the call
+// (lt_hip_trace_rays, lt_hip_trace_rays_device) and keeps the statistics; this is the launch.
+#pragma once
+#include "lt_device.hpp"
+
+namespace lt_query {
+
+// The caller's records, as the kernels read them: two 16-byte halves per ray, (origin.xyz, tmax) and (direction.xyz, ignore as
+// int32 bits) -- lt_hip_ray.  Results: 16 bytes per ray (t, primitive or -1, u, v) -- lt_hip_hit -- or one occluded word.
+struct Params {
+  const float4* rays;
+  uint4* hits;          // closest hit
+  uint32_t* occluded;   // any hit
+  uint32_t n;           // rays
+  uint32_t* next;       // lt_query_kernel's work counters: eight, kQueueStride dwords apart, zeroed by launch() on the call's stream
+  uint32_t refill;      // idle lanes that make a wave of lt_query_kernel take new rays
+};
+
+enum Epsilon { kEpsFloat7 = 0, kEpsDouble7 = 1, kEpsDouble4 = 2 };   // basic / custom_opencl, basic_lighting, the three others
+
+// Enqueues the query on `s`: lt_query_packet_kernel when `coherent`, else lt_query_kernel.  Returns the first HIP error.
+hipError_t launch(const lt::SceneDev& sc, const Params& p, Epsilon eps, bool anyHit, bool coherent, uint32_t cuCount, hipStream_t s);
+
+}  // namespace lt_query

@@ -73,11 +73,38 @@ def make_desc(program, W, H, depth, camera28, kernel_mode=KERNEL_MODE_LINEAR, fr
     return d
 
 
+FLT_MAX = float(np.finfo(np.float32).max)   # the reference's payload start (acc.cl: RayPayload.t = FLT_MAX)
+RAY_DTYPE, HIT_DTYPE = C.RAY_DTYPE, C.HIT_DTYPE
+
+
+def make_rays(origins, directions, tmax=FLT_MAX, ignore=-1):
+    """Packs rays for RendererHIP.trace_rays: (n, 3) origins and directions, tmax and ignore (the primitive a ray starts on,
+    -1 = none) as scalars or (n,) arrays, into an (n, 8) float32 array of lt_hip_ray records (ignore's int32 bits in column 7)."""
+    o = np.asarray(origins, dtype=np.float32)
+    d = np.asarray(directions, dtype=np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("origins and directions must both have shape (n, 3)")
+    n = o.shape[0]
+    t = np.asarray(tmax, dtype=np.float32)
+    ig = np.asarray(ignore)
+    if t.shape not in ((), (n,)) or ig.shape not in ((), (n,)):
+        raise ValueError("tmax and ignore must be scalars or have shape (n,)")
+    if ig.size and (not np.issubdtype(ig.dtype, np.integer) or ig.min() < -2 ** 31 or ig.max() >= 2 ** 31):
+        raise ValueError("ignore must hold int32 primitive indices")
+    out = np.empty((n, 8), dtype=np.float32)
+    out[:, 0:3] = o
+    out[:, 3] = t
+    out[:, 4:7] = d
+    out[:, 7] = np.broadcast_to(ig.astype(np.int32), (n,)).view(np.float32)
+    return out
+
+
 class RendererHIP:
     """One context per GPU.  `device` is the HIP ordinal."""
 
     def __init__(self, device=0):
         self._L = C.load()
+        self.device = device
         self._ctx = ctypes.c_void_p()
         rc = self._L.lt_hip_create(device, ctypes.byref(self._ctx))
         if rc:
@@ -185,6 +212,52 @@ class RendererHIP:
         if what == 3:
             return tuple(int(x) for x in buf.view(np.int32))
         return buf
+
+    # -- ray queries ------------------------------------------------------------------------------------
+    def trace_rays(self, rays, any_hit=False, program="accumulator", coherent=False, portable_math=False, strict_math=False, stream=None):
+        """Traces caller-supplied rays against the scene of the last set_scene / render (lt_hip_trace_rays): as the reference's
+        intersect / intersectIgnorePrimitiveIndex would, with the triangle epsilon of `program` (an LT_PROGRAM_* id or a kernel path).
+        rays: an (n, 8) float32 array of lt_hip_ray records (make_rays) or a RAY_DTYPE array -- then the host entry point runs and
+        numpy comes back: a HIT_DTYPE array (t, prim -- -1 on a miss --, u, v) or, any_hit, uint32 occluded words; or a contiguous
+        (n, 8) float32 torch tensor on this context's GPU -- then the query is enqueued on `stream` (default: the current torch
+        stream) and torch comes back: an (n, 4) float32 tensor of lt_hip_hit records (column 1 holds int32 bits: .view(torch.int32))
+        or an (n,) int32 tensor of occluded words.  coherent: runs of 64 consecutive rays are coherent (LT_TRACE_FLAG_COHERENT)."""
+        if not isinstance(program, int):
+            program = C.program_from_path(str(program))
+        d = C.TraceDesc()
+        d.struct_size = ctypes.sizeof(C.TraceDesc)
+        d.program = program
+        d.kind = C.TRACE_ANY if any_hit else C.TRACE_CLOSEST
+        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
+                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
+        if isinstance(rays, np.ndarray):
+            if rays.dtype == RAY_DTYPE and rays.ndim == 1:
+                rays = rays.view(np.float32).reshape(-1, 8)
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an (n, 8) float32 array (make_rays) or a RAY_DTYPE array")
+            rays = np.ascontiguousarray(rays)
+            n = rays.shape[0]
+            out = np.zeros(n, dtype=np.uint32 if any_hit else HIT_DTYPE)
+            self._check(self._L.lt_hip_trace_rays(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
+                                                  out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+            return out
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError("rays must be a numpy array or a torch tensor")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
+        dev = torch.device("cuda", self.device)
+        if rays.device != dev:
+            raise ValueError("rays must be on %s, the context's device" % dev)
+        n = rays.shape[0]
+        out = torch.empty((n,) if any_hit else (n, 4), dtype=torch.int32 if any_hit else torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        self._check(self._L.lt_hip_trace_rays_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
+                                                     ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                                                     ctypes.c_void_p(handle)))
+        return out
 
     def stats(self):
         s = C.Stats()
