@@ -619,7 +619,9 @@ __device__ inline void traverse_nodes_impl(const SceneDev& sc, const Ray& ray, f
 // makes such a ray accept every box within 2^-19 E |inv| of its path: a handful of rays per million that walk half the tree and
 // hold their wavefronts' launch back (measured: the 1 M-triangle wall's bounce stages twice as long).  All magnitudes stay below
 // 2^102 (|o|, |O|, E < 2^41, |inv| < 2^60: packet_ray_ok, checked per wave; the scene's bounds below 2^40:
-// lt_retree::collect_leaves), gradual underflow adds at most 2^-148 per operation: the 2^-140.
+// lt_retree::collect_leaves).  Gradual underflow adds at most 2^-149 per operation, but sI = fl(S inv) is multiplied by q < 2^16
+// after its rounding: a subnormal sI (a small step S and a large direction) is off by up to 2^-150, q sI by up to 2^-134 -- the
+// 2^-132.  (It was 2^-140 until tests/test_gpu_query_edges.py's scene at scale 2^-40 met rays of |d| ~ 2^83 that missed.)
 // tests/test_own_hierarchy_cpu.py tries the inequality on random and grazing rays against quantised boxes made by the build's
 // own arithmetic.
 struct Own16Ray { float sx, sy, sz, nx, ny, nz, fx, fy, fz; };   // sI; cN; cF
@@ -629,9 +631,9 @@ __device__ __forceinline__ Own16Ray own16_ray(const SceneDev& sc, const Ray& ray
   const float px = ray.o.x * ix, py = ray.o.y * iy, pz = ray.o.z * iz;
   r.sx = fr.s4 * ix; r.sy = fr.s5 * iy; r.sz = fr.s6 * iz;
   const float cx = __builtin_fmaf(fr.s0, ix, -px), cy = __builtin_fmaf(fr.s1, iy, -py), cz = __builtin_fmaf(fr.s2, iz, -pz);
-  const float mx = (__builtin_fabsf(65535.0f * fr.s4 * ix) + __builtin_fabsf(fr.s0 * ix) + __builtin_fabsf(px)) * 0x1p-21f + 0x1p-140f;
-  const float my = (__builtin_fabsf(65535.0f * fr.s5 * iy) + __builtin_fabsf(fr.s1 * iy) + __builtin_fabsf(py)) * 0x1p-21f + 0x1p-140f;
-  const float mz = (__builtin_fabsf(65535.0f * fr.s6 * iz) + __builtin_fabsf(fr.s2 * iz) + __builtin_fabsf(pz)) * 0x1p-21f + 0x1p-140f;
+  const float mx = (__builtin_fabsf(65535.0f * fr.s4 * ix) + __builtin_fabsf(fr.s0 * ix) + __builtin_fabsf(px)) * 0x1p-21f + 0x1p-132f;
+  const float my = (__builtin_fabsf(65535.0f * fr.s5 * iy) + __builtin_fabsf(fr.s1 * iy) + __builtin_fabsf(py)) * 0x1p-21f + 0x1p-132f;
+  const float mz = (__builtin_fabsf(65535.0f * fr.s6 * iz) + __builtin_fabsf(fr.s2 * iz) + __builtin_fabsf(pz)) * 0x1p-21f + 0x1p-132f;
   r.nx = cx - mx; r.ny = cy - my; r.nz = cz - mz;
   r.fx = cx + mx; r.fy = cy + my; r.fz = cz + mz;
   return r;

@@ -1,0 +1,515 @@
+"""Seeded ray batches and scenes for the tests of the ray-query kernels at their edges (tests/test_gpu_query_edges.py; what each
+fixture claims: tests/test_query_edges_cpu.py).
+
+lt_query_packet_kernel (lens_trace_amd/csrc/lt_query.hip) hands rays [64 b, 64 b + 64) to wave b.  The wave walks them as ONE
+packet when all 64 are finite and pass packet_ray_ok (|origin| < 2^40, |1 / direction| < 2^60) and, for closest hit, share one
+direction-sign octant and ignore nothing; any-hit rays of mixed octants take the sign-generic walk.  Otherwise every lane walks
+alone.  A partial last chunk's missing lanes walk a copy of its first ray.  `verdict` restates that rule: None (per lane), an
+octant 0..7 (that octant's packet walk) or -1 (the sign-generic any-hit walk).  An octant has bit a set where 1 / d_a < 0 (so a
+direction component of -inf, whose inverse is -0, counts as positive).
+
+* Batch: rays (make_rays records) and, per chunk of 64, the verdict the construction means for closest and for any hit.
+* families(scene, seed): every batch family -- coherent chunks per octant, mixed tmax, ignoring lanes, bit-equal triangle
+  pairs, one intruder lane, partial last chunks, rays at the magnitude limits, epsilon bands.
+* scaled_scene(scene, s, t): the scene under x -> s x + t (s a power of two); the EXTREME cases, two of them just outside the
+  own tree's limits; scale_rays maps a batch onto a scaled scene.
+* brute_force(scene, rays): float64 Moeller-Trumbore over every triangle, no hierarchy, and which of its answers are robust."""
+import numpy as np
+
+from lens_trace_amd import scene as sc
+from lens_trace_amd.renderer import FLT_MAX, make_rays
+from tests import octant_scenes as oc
+
+LANES = 64
+O_LIMIT = 2.0 ** 40            # packet_ray_ok: |origin| < 2^40
+INV_LIMIT = 2.0 ** 60          # ... and |1 / direction| < 2^60
+F32 = np.float32
+EPS_BASIC = F32(1e-7)          # basic.cl: const float EPSILON = 0.0000001, a float compare
+EPS_DOUBLE7 = 1e-7             # basic_lighting.cl: the same constant compared in double
+EPS_DOUBLE4 = 1e-4             # accumulator.cl and the others
+EPS4_FLOAT = np.uint32(0x38d1b718).view(F32)   # the smallest float >= 1e-4: (double)|det| < 1e-4 <=> |det| < this
+PACKET_SLOTS = (0, 1, 31, 32, 62, 63)
+INTRUDERS = ("sign", "zero", "inf_o", "nan_o", "nan_d", "inf_d", "far_o", "tiny_d", "ignore")
+
+
+# ------------------------------------------------------------------------------------------------------- the kernel's rule
+def inverse(d):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        return (F32(1.0) / np.asarray(d, dtype=F32)).astype(F32)
+
+
+def own_ok(rays):
+    """Per ray: finite origin and inverse, packet_ray_ok's magnitudes (lt_query.hip: finite_ray && packet_ray_ok)."""
+    o, inv = rays[:, 0:3].astype(F32), inverse(rays[:, 4:7])
+    with np.errstate(invalid="ignore"):
+        return (np.isfinite(o) & np.isfinite(inv) & (np.abs(o) < O_LIMIT) & (np.abs(inv) < INV_LIMIT)).all(axis=1)
+
+
+def octant(rays):
+    inv = inverse(rays[:, 4:7])
+    return (inv[:, 0] < 0) * 1 + (inv[:, 1] < 0) * 2 + (inv[:, 2] < 0) * 4
+
+
+def ignores(rays):
+    return rays[:, 7].view(np.int32) >= 0
+
+
+def verdict(chunk, any_hit):
+    """How lt_query_packet_kernel walks one chunk (its real lanes: the copies of lane 0 change nothing)."""
+    if not own_ok(chunk).all():
+        return None
+    q = np.unique(octant(chunk))
+    if any_hit:
+        return int(q[0]) if len(q) == 1 else -1
+    if ignores(chunk).any() or len(q) != 1:
+        return None
+    return int(q[0])
+
+
+def chunk_verdicts(rays, any_hit):
+    return [verdict(rays[i:i + LANES], any_hit) for i in range(0, len(rays), LANES)]
+
+
+class Batch:
+    def __init__(self, name):
+        self.name, self.chunks, self.claims = name, [], []
+
+    def add(self, rays, closest, any_hit):
+        """One chunk (64 rays, or fewer as the batch's last) and the verdicts it is built to have."""
+        assert len(rays) == LANES or (0 < len(rays) < LANES), len(rays)
+        assert not self.chunks or len(self.chunks[-1]) == LANES
+        self.chunks.append(rays.astype(F32))
+        self.claims.append((closest, any_hit))
+        return self
+
+    @property
+    def rays(self):
+        return np.concatenate(self.chunks)
+
+
+# ------------------------------------------------------------------------------------------------------- scene and targets
+def base_scene(seed=0):
+    """octant_scene's geometry (random triangles in [-4, 4]^3 with slivers, a zero-area triangle and 40 bit-equal pairs) and a
+    light patch in [13, 15]^3."""
+    return oc.octant_scene(0, seed)
+
+
+def corners(scene):
+    pv = scene.prim_view
+    return np.stack([pv["positionA"], pv["positionB"], pv["positionC"]], axis=1).astype(np.float64)   # [N, 3, 3]
+
+
+def geometry_prims(scene):
+    """The triangles inside the geometry box, with a real area (targets for rays meant to hit)."""
+    P = corners(scene)
+    area = np.linalg.norm(np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]), axis=1)
+    return np.flatnonzero((np.abs(P) <= oc.BOX).all(axis=(1, 2)) & (area > 1e-3))
+
+
+def bit_equal_pairs(scene):
+    """Primitives whose three corners have the bits of another primitive's."""
+    key = np.ascontiguousarray(corners(scene).astype(F32)).view(np.uint8).reshape(scene.n_prims, -1)
+    _, inv, cnt = np.unique(key, axis=0, return_inverse=True, return_counts=True)
+    return np.flatnonzero(cnt[inv.reshape(-1)] > 1)
+
+
+def points_on(scene, prims, rng, where="mixed"):
+    """A point of each triangle (float64): its interior, an edge (one barycentric 0) or a vertex; "mixed" draws all three."""
+    P = corners(scene)[prims]
+    n = len(prims)
+    b = rng.dirichlet([1, 1, 1], n)
+    kind = {"interior": np.zeros(n, int), "edge": np.ones(n, int), "vertex": np.full(n, 2)}.get(where)
+    if kind is None:
+        kind = rng.integers(0, 3, n)
+    e = kind == 1
+    b[e, rng.integers(0, 3, e.sum())] = 0.0
+    b[e] /= b[e].sum(axis=1, keepdims=True)
+    v = kind == 2
+    b[v] = np.eye(3)[rng.integers(0, 3, v.sum())]
+    return np.einsum("nk,nkc->nc", b, P)
+
+
+def coherent_chunk(scene, k, rng, jitter=False, prims=None, where="mixed"):
+    """64 rays of octant k: from one origin (or 64 nearby ones) beyond the geometry box on the side opposite the octant, to points
+    of triangles inside it.  Every component of every direction has the octant's sign, whatever the draws (|target| <= 4 < 11)."""
+    s = oc.octant_signs(k)
+    o = -12.0 * s + (rng.uniform(-1, 1, (LANES, 3)) if jitter else rng.uniform(-1, 1, 3))
+    o = np.broadcast_to(o, (LANES, 3)).astype(F32).astype(np.float64)
+    pool = geometry_prims(scene) if prims is None else prims
+    target = points_on(scene, rng.choice(pool, LANES), rng, where)
+    return make_rays(o, target - o)
+
+
+TMAX_KINDS = np.array([FLT_MAX, np.inf, 0.0, -0.0, -1.0, np.nan, 0.5, 1.0, 1.5], dtype=F32)
+
+
+# ------------------------------------------------------------------------------------------------------- the families
+def fam_coherent(scene, rng):
+    b = Batch("coherent")
+    for k in range(8):
+        for jitter in (False, True):
+            b.add(coherent_chunk(scene, k, rng, jitter), k, k)
+    return b
+
+
+def fam_tmax(scene, rng):
+    """Per-lane tmax inside qualifying packets: FLT_MAX, inf, 0, -0, negative, NaN and values around the hit (t ~ 1)."""
+    b = Batch("tmax")
+    for k in range(8):
+        r = coherent_chunk(scene, k, rng)
+        r[:, 3] = TMAX_KINDS[rng.integers(0, len(TMAX_KINDS), LANES)]
+        rnd = rng.integers(0, 3, LANES) == 0
+        r[rnd, 3] = rng.uniform(0.0, 2.0, rnd.sum())
+        b.add(r, k, k)
+    return b
+
+
+def fam_ignore(scene, rng):
+    """Rays that start on a triangle and ignore it, mixed with rays that ignore nothing: one octant (any hit: that octant's
+    walk) and mixed octants (any hit: the sign-generic walk); closest hit walks these per lane."""
+    b = Batch("ignore")
+    pool = geometry_prims(scene)
+    for k in range(8):
+        r = coherent_chunk(scene, k, rng)
+        lanes = rng.permutation(LANES)[: LANES // 2]
+        p = rng.choice(pool, len(lanes))
+        o = points_on(scene, p, rng, "interior")
+        d = oc.octant_signs(k) * rng.uniform(0.2, 1.0, (len(lanes), 3))
+        r[lanes] = make_rays(o, d, FLT_MAX, p)
+        b.add(r, None, k)
+    for _ in range(4):
+        p = rng.choice(pool, LANES)
+        d = rng.normal(0, 1, (LANES, 3))
+        d[:8] = np.abs(d[:8])        # (both signs on every axis)
+        d[8:16] = -np.abs(d[8:16])
+        ign = np.where(rng.integers(0, 2, LANES) == 0, p, -1)
+        b.add(make_rays(points_on(scene, p, rng, "interior"), d, FLT_MAX, ign), None, -1)
+    r = coherent_chunk(scene, 2, rng)           # mixed octants, nothing ignored
+    r[::2, 4:7] *= -1.0
+    b.add(r, None, -1)
+    return b
+
+
+def fam_ties(scene, rng):
+    """Rays at the bit-equal pairs: their hits tie in t, and the reference's leaf order decides."""
+    b = Batch("ties")
+    pairs = bit_equal_pairs(scene)
+    for k in range(8):
+        b.add(coherent_chunk(scene, k, rng, prims=pairs, where="interior"), k, k)
+    return b
+
+
+def spoil(r, lane, kind, k, rng, n_prims):
+    """Lane `lane` of a qualifying chunk of octant k made one kind of intruder; returns the verdicts it is built to have."""
+    a = int(rng.integers(0, 3))
+    s = oc.octant_signs(k)
+    if kind == "sign":
+        r[lane, 4 + a] = -r[lane, 4 + a]
+        return None, -1
+    if kind == "zero":
+        r[lane, 4 + a] = F32(0.0) * F32(rng.choice([-1.0, 1.0]))
+        return None, None
+    if kind in ("inf_o", "nan_o"):
+        r[lane, a] = np.nan if kind == "nan_o" else rng.choice([-np.inf, np.inf])
+        return None, None
+    if kind == "nan_d":
+        r[lane, 4 + a] = np.nan
+        return None, None
+    if kind == "inf_d":       # an infinite component of the octant's sign: inverse +-0, finite -- the lane stays in the packet
+        r[lane, 4 + a] = np.inf * s[a]                                    # unless -inf, whose inverse -0 is not < 0
+        return (k, k) if s[a] > 0 else (None, -1)
+    if kind == "far_o":
+        r[lane, a] = O_LIMIT * rng.choice([-1.0, 1.0])
+        return None, None
+    if kind == "tiny_d":
+        r[lane, 4 + a] = s[a] * 2.0 ** -60
+        return None, None
+    assert kind == "ignore"
+    r[lane, 7] = np.int32(rng.integers(0, n_prims)).view(F32)
+    return None, k
+
+
+def fam_intruders(scene, rng):
+    """Qualifying chunks with exactly one bad lane, at either end of the wave and of its halves."""
+    b = Batch("intruders")
+    i = 0
+    for kind in INTRUDERS:
+        for lane in PACKET_SLOTS:
+            k = i % 8
+            i += 1
+            r = coherent_chunk(scene, k, rng)
+            b.add(r, *spoil(r, lane, kind, k, rng, scene.n_prims))
+    return b
+
+
+def fam_partial(scene, rng, rest):
+    """Two whole chunks, then a last chunk of `rest` rays (1, 33 or 63) that qualifies."""
+    b = Batch("partial%d" % rest)
+    for k in (3, 4):
+        b.add(coherent_chunk(scene, k, rng), k, k)
+    k = rest % 8
+    return b.add(coherent_chunk(scene, k, rng)[:rest], k, k)
+
+
+def fam_limits(scene, rng):
+    """Rays at packet_ray_ok's limits, aimed at interior, edge and vertex points of triangles (vertices and edges lie on the faces
+    of the leaf boxes: the rays graze the conservative tests where they are tightest):
+      * an origin component of +-nextafter(2^40, 0) (the packet walks) and of +-2^40 (not);
+      * a direction component of +-nextafter(2^-60, inf) (the packet walks) and of +-2^-60 (not): rays in the plane of a vertex;
+      * directions of magnitude 2^100 .. 2^126 and FLT_MAX (subnormal inverses) and +inf (a zero inverse): the packet walks."""
+    b = Batch("limits")
+    pool = geometry_prims(scene)
+    below = float(np.nextafter(F32(O_LIMIT), F32(0)))
+    above = float(np.nextafter(F32(2.0 ** -60), F32(np.inf)))
+    for a in range(3):
+        for sign in (1.0, -1.0):
+            for v, ok in ((below, True), (O_LIMIT, False)):
+                o = np.zeros(3)
+                others = [c for c in range(3) if c != a]
+                so = rng.choice([-1.0, 1.0], 2)
+                o[others] = -10.0 * so
+                o[a] = sign * v
+                t = points_on(scene, rng.choice(pool, LANES), rng)
+                r = make_rays(np.tile(o, (LANES, 1)), t - o)
+                k = int(octant(r)[0])
+                b.add(r, k if ok else None, k if ok else None)
+            for w, ok in ((above, True), (2.0 ** -60, False)):
+                s = np.where(rng.integers(0, 2, 3) == 1, 1.0, -1.0)
+                s[a] = sign
+                d = s * rng.uniform(0.5, 1.0, (LANES, 3))
+                d[:, a] = sign * w
+                t = points_on(scene, rng.choice(pool, LANES), rng)
+                r = make_rays(t - 8.0 * d, d)
+                k = int(octant(r)[0])
+                b.add(r, k if ok else None, k if ok else None)
+    for e in (100, 120, 126, 128):
+        for k in (0, 5):
+            r = coherent_chunk(scene, k, rng)
+            d = r[:, 4:7].astype(np.float64)
+            if e == 128:                                     # one component FLT_MAX, the others large
+                d = d / np.abs(d).max(axis=1, keepdims=True) * 2.0 ** 120
+                a = int(rng.integers(0, 3))
+                d[:, a] = np.sign(d[:, a]) * FLT_MAX
+            else:                                            # a power of two: the same geometric ray
+                d = d * 2.0 ** (e - 5)
+            r[:, 4:7] = d.astype(F32)
+            b.add(r, k, k)
+    r = coherent_chunk(scene, 0, rng)
+    r[:, 4] = np.inf                                         # a zero inverse on x
+    b.add(r, 0, 0)
+    return b
+
+
+def eps_band_rays(scene, rng, n):
+    """Rays nearly parallel to a triangle, aimed at its interior, whose det = v0v1 . (d x v0v2) (the reference's, in float32)
+    falls below 1e-7f, at 1e-7f and one float below, between 1e-7 and 1e-4, at 0x38d1b718 (the smallest float >= 1e-4) and one
+    float below, and above 1e-4.  Returns the rays and the det the construction aims at."""
+    P = corners(scene)
+    pool = geometry_prims(scene)
+    targets = [3e-8, float(EPS_BASIC), float(np.nextafter(EPS_BASIC, F32(0))), 1e-6, 1e-5, 5e-5, float(EPS4_FLOAT),
+               float(np.nextafter(EPS4_FLOAT, F32(0))), 1e-3]
+    p = rng.choice(pool, n)
+    want = np.array(targets)[np.arange(n) % len(targets)] * rng.choice([-1.0, 1.0], n)
+    A, B, C = P[p, 0], P[p, 1], P[p, 2]
+    e1, e2 = B - A, C - A
+    nrm = np.cross(e1, e2)
+    inplane = e1 / np.linalg.norm(e1, axis=1, keepdims=True)
+    # det = -d . n for d = (an in-plane part) - want n / |n|^2: det = want, up to rounding.  The four rays of nine aimed at a
+    # threshold float or its neighbour have no in-plane part (the ray crosses the plane steeply, det rounds finely) and are then
+    # stepped by relative 2^-25 until det is that float exactly; the rest are nearly parallel to the triangle.
+    exact = np.isin(np.arange(n) % len(targets), (1, 2, 6, 7))
+    d = np.where(exact[:, None], 0.0, 2.0 ** -8 * inplane) - (want / np.einsum("ij,ij->i", nrm, nrm))[:, None] * nrm
+    d32 = d.astype(F32)
+    goal = np.abs(want).astype(F32)
+    done = ~exact
+    for k in sorted(range(-600, 601), key=abs):
+        cand = (d * (1.0 + k * 2.0 ** -25)).astype(F32)
+        rays = make_rays(np.zeros((n, 3)), cand)
+        hit = ~done & (np.abs(det_of(scene, rays, p)) == goal)
+        d32[hit] = cand[hit]
+        done |= hit
+    d = d32.astype(np.float64)
+    bary = rng.dirichlet([4, 4, 4], n)
+    target = np.einsum("nk,nkc->nc", bary, P[p])
+    return make_rays(target - 0.5 * d, d32), p
+
+
+def fam_eps(scene, rng):
+    """Chunks of epsilon-band rays (rays[:, det] ~ the bands of eps_band_rays): they change their answer with the program."""
+    b = Batch("eps")
+    r, _ = eps_band_rays(scene, rng, 8 * LANES)
+    for i in range(8):
+        c = r[i * LANES:(i + 1) * LANES]
+        b.add(c, verdict(c, False), verdict(c, True))
+    return b
+
+
+def families(scene, seed=0):
+    rng = np.random.default_rng(seed)
+    out = [fam_coherent(scene, rng), fam_tmax(scene, rng), fam_ignore(scene, rng), fam_ties(scene, rng), fam_intruders(scene, rng)]
+    out += [fam_partial(scene, rng, rest) for rest in (1, 33, 63)]
+    return out + [fam_limits(scene, rng), fam_eps(scene, rng)]
+
+
+def det_of(scene, rays, prims):
+    """The reference's det (acc.cl:72-111: dot(v0v1, cross(d, v0v2)), float32 with its fma chains) of each ray and primitive."""
+    P = corners(scene).astype(F32)[prims]
+    v1, v2 = (P[:, 1] - P[:, 0]).astype(F32), (P[:, 2] - P[:, 0]).astype(F32)
+    d = rays[:, 4:7].astype(F32)
+
+    def fma(a, b, c):
+        return (a.astype(np.float64) * b + c).astype(F32)      # exact product of two floats in double, one rounding
+
+    px = fma(d[:, 1], v2[:, 2], -(d[:, 2] * v2[:, 1]).astype(F32))
+    py = fma(d[:, 2], v2[:, 0], -(d[:, 0] * v2[:, 2]).astype(F32))
+    pz = fma(d[:, 0], v2[:, 1], -(d[:, 1] * v2[:, 0]).astype(F32))
+    return fma(v1[:, 2], pz, fma(v1[:, 1], py, (v1[:, 0] * px).astype(F32)))
+
+
+# ------------------------------------------------------------------------------------------------------- extreme magnitudes
+def scaled_scene(scene, s, t):
+    """Every vertex and node bound under x -> fl32(s x + t) per axis (s a power of two): monotone, so boxes still nest and every
+    triangle stays inside its leaf.  Normals, materials and lights as they were; the camera's position goes along."""
+    t = np.broadcast_to(np.asarray(t, dtype=np.float64), (3,))
+    nodes, prims = scene.nodes.copy(), scene.prims.copy()
+    nv, pv = nodes.view(sc.NODE_DTYPE), prims.view(sc.PRIM_DTYPE)
+    for v, keys in ((nv, ("boundsMin", "boundsMax")), (pv, ("positionA", "positionB", "positionC"))):
+        for k in keys:
+            v[k] = (v[k].astype(np.float64) * s + t).astype(F32)
+    import struct
+    cam = list(struct.unpack("<6fI", bytes(scene.camera)))
+    cam[:3] = [float(F32(c * s + t[i])) for i, c in enumerate(cam[:3])]
+    return sc.Scene(nodes=nodes, prims=prims, materials=scene.materials.copy(), lights=scene.lights.copy(),
+                    camera=sc.camera_bytes(*cam[:6], cam[6])).validate()
+
+
+def direction_scale(s):
+    """The factor k of a scaled scene's directions: det is trilinear in (v0v1, d, v0v2), so d' = k d keeps it at s^2 k times the
+    base scene's -- k = s^-2 for s < 1 keeps it where it was; k = 1 above (det grows as s^2, and 1 / d stays below 2^60)."""
+    return s ** -2.0 if s < 1 else 1.0
+
+
+def scale_rays(rays, s, t):
+    """The base scene's rays on scaled_scene(s, t): origins mapped as the vertices are, directions times direction_scale(s) (a
+    power of two: exact, the same lines), tmax times s / direction_scale(s) (the hit's t scales by that)."""
+    t = np.broadcast_to(np.asarray(t, dtype=np.float64), (3,))
+    k = direction_scale(s)
+    r = rays.copy()
+    with np.errstate(over="ignore", invalid="ignore"):
+        r[:, 0:3] = (rays[:, 0:3].astype(np.float64) * s + t).astype(F32)
+        r[:, 4:7] = (rays[:, 4:7].astype(np.float64) * k).astype(F32)
+        r[:, 3] = (rays[:, 3].astype(np.float64) * (s / k)).astype(F32)
+    return r
+
+
+NEAR = 2.0 ** 40 - 2.0 ** 33        # a translation just inside the limit: the scaled geometry box stays below 2^40
+# name: (s, t, camera z or None (camera_for), own tree expected)
+EXTREME = {
+    "tiny": (2.0 ** -40, (0.0, 0.0, 0.0), None, True),
+    "small": (2.0 ** -20, (3e-6, -2e-6, 1e-6), None, True),
+    "large": (2.0 ** 35, (0.0, 0.0, 0.0), None, True),
+    "far+": (2.0 ** 28, (NEAR, NEAR, NEAR), None, True),
+    "far-": (2.0 ** 28, (-NEAR, -NEAR, -NEAR), None, True),
+    "far+-+": (2.0 ** 28, (NEAR, -NEAR, NEAR), None, True),
+    "cam_inside": (2.0 ** 33, None, float(np.nextafter(F32(-O_LIMIT), F32(0))), True),
+    "cam_at": (2.0 ** 33, None, -O_LIMIT, True),
+    "bound_at_limit": (2.0 ** 28, (NEAR, NEAR, NEAR), None, False),
+    "bound_at_-limit": (2.0 ** 28, (-NEAR, -NEAR, -NEAR), None, False),
+    "nan_bound": (2.0 ** 28, (NEAR, -NEAR, NEAR), None, False),
+}
+
+
+def extreme_scene(base, name):
+    """(scene, camera bytes, s, t) of EXTREME[name].  cam_*: the camera on the -z side at the given z, yaw 0, the scene in front
+    of it at camera_for's distance; bound_at_*: the root box widened to exactly +-2^40 on one axis; nan_bound: a NaN bound in an
+    interior node below the root."""
+    s, t, camz, _ = EXTREME[name]
+    lo, hi = oc.box_of(base)
+    if t is None:
+        ext = (hi - lo) * s
+        R = float(ext.max()) / 2.0 / oc.FILM_HALF
+        t = np.array([-s * (lo[0] + hi[0]) / 2, -s * (lo[1] + hi[1]) / 2, camz + R - s * (lo[2] + hi[2]) / 2])
+    out = scaled_scene(base, s, t)
+    nv = out.node_view
+    if name == "bound_at_limit":
+        nv["boundsMax"][0, 0] = F32(O_LIMIT)
+    elif name == "bound_at_-limit":
+        nv["boundsMin"][0, 1] = F32(-O_LIMIT)
+    elif name == "nan_bound":
+        inner = np.flatnonzero(nv["primitiveCount"] == 0)
+        nv["boundsMin"][inner[len(inner) // 2], 2] = np.nan
+    if camz is not None:
+        cam = sc.camera_bytes(0.0, 0.0, camz, 0.0, 0.0, 0.0, 3)
+    else:
+        sl, sh = (lo * s + t), (hi * s + t)
+        cam = oc.camera_for(0.0, (sl, sh), frame=3)
+    return out, cam, s, np.asarray(t, dtype=np.float64)
+
+
+def nests(scene):
+    """lt_retree::collect_leaves' verdict: root bounds finite and inside (-2^40, 2^40), every child box inside its parent's."""
+    nv = scene.node_view
+    lo, hi = nv["boundsMin"].astype(np.float64), nv["boundsMax"].astype(np.float64)
+    if not ((lo[0] > -O_LIMIT) & (hi[0] < O_LIMIT) & (lo[0] <= hi[0])).all():
+        return False
+    for i in np.flatnonzero(nv["primitiveCount"] == 0):
+        for c in (i + 1, int(nv["offset"][i])):
+            if not ((lo[c] >= lo[i]) & (hi[c] <= hi[i]) & (lo[c] <= hi[c])).all():
+                return False
+    return True
+
+
+def inside_leaves(scene):
+    """Every primitive of a leaf inside that leaf's box."""
+    nv = scene.node_view
+    leaf = np.flatnonzero(nv["primitiveCount"] != 0)
+    P = corners(scene)[nv["offset"][leaf]]
+    return bool(((P >= nv["boundsMin"][leaf][:, None, :]) & (P <= nv["boundsMax"][leaf][:, None, :])).all())
+
+
+# ------------------------------------------------------------------------------------------------------- float64 brute force
+def brute_force(scene, rays, eps=1e-4):
+    """Float64 Moeller-Trumbore over every triangle, no hierarchy; ignore and tmax as the reference reads them, t > 0 not asked
+    (the reference does not ask it either).  Returns (prim, t, robust): the nearest hit's primitive (-1: none) and t, and whether
+    the answer is robust -- the ray's barycentrics on the hit triangle clear of its edges, |det| clear of the epsilon, no other
+    triangle met on or near its boundary short of the hit, tmax and the origin well away, no product of the float32 test
+    near overflow or underflow -- by margins far above float32's
+    error at the ray's magnitudes."""
+    P = corners(scene)
+    A, e1, e2 = P[:, 0], P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]
+    n = len(rays)
+    o, d = rays[:, 0:3].astype(np.float64), rays[:, 4:7].astype(np.float64)
+    tmax = rays[:, 3].astype(np.float64)
+    ign = rays[:, 7].view(np.int32)
+    prim, tbest, robust = np.full(n, -1), np.full(n, np.inf), np.zeros(n, bool)
+    scale = np.abs(P).max() + np.abs(e1).max()
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            if not (np.isfinite(o[i]).all() and np.isfinite(d[i]).all() and np.abs(d[i]).max() > 0):
+                continue
+            pv = np.cross(d[i], e2)
+            det = np.einsum("ij,ij->i", e1, pv)
+            tv = o[i] - A
+            u = np.einsum("ij,ij->i", tv, pv) / det
+            qv = np.cross(tv, e1)
+            v = (qv @ d[i]) / det
+            t = np.einsum("ij,ij->i", e2, qv) / det
+            ok = (np.abs(det) >= eps) & (u >= 0) & (v >= 0) & (u + v <= 1) & (np.arange(len(P)) != ign[i])
+            ok &= t < tmax[i] if not np.isnan(tmax[i]) else False
+            if not ok.any():
+                continue
+            j = np.flatnonzero(ok)[np.argmin(t[ok])]
+            prim[i], tbest[i] = j, t[j]
+            # robustness: float32 errors at this ray's magnitudes, in t and in the barycentrics
+            mag = (np.abs(o[i]).max() + scale) * 2.0 ** -20
+            dn = np.linalg.norm(d[i])
+            mb = np.minimum(np.minimum(u, v), 1 - u - v)
+            # a competitor: another triangle the ray meets on or near its boundary, not clearly behind the hit
+            rival = (np.abs(det) > 0) & (mb >= -1e-3) & (t < t[j] + 1e3 * mag / dn) & (np.arange(len(P)) != ign[i])
+            rival[j] = False
+            tgap = abs(tmax[i] - t[j]) * dn > 1e3 * mag if np.isfinite(tmax[i]) else True
+            steep = abs(det[j]) / (np.linalg.norm(e1[j]) * np.linalg.norm(e2[j]) * dn)
+            prod = dn * (np.abs(o[i]).max() + scale) ** 2       # the largest products of the float32 test: no overflow, no underflow
+            robust[i] = (2.0 ** -100 < prod < 2.0 ** 100 and mb[j] > 1e-3 and abs(det[j]) > 1e3 * eps and steep > 0.05 and not rival.any() and tgap and
+                         t[j] * dn > 1e3 * mag)
+    return prim, tbest, robust

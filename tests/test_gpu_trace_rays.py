@@ -51,7 +51,9 @@ def on_triangle(s, prims, rng):
 
 
 def random_rays(s, rng, n):
-    """n rays of every kind the contract names, then 4 chunks of 64 coherent rays (so that the packet kernel walks packets)."""
+    """n rays of every kind the contract names, rounded up to whole chunks of 64, then 4 chunks of 64 coherent rays that start on
+    a multiple of 64 (so that the packet kernel walks them as packets)."""
+    n = -(-n // 64) * 64
     lo, hi = root_box(s)
     ext = np.maximum(hi - lo, 1e-3)
     o = rng.uniform(lo - 0.5 * ext, hi + 0.5 * ext, (n, 3))

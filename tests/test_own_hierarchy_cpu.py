@@ -318,7 +318,7 @@ def own16_test(O, S, q, o, inv):
     c = fma32(Ob, inv, -p)
     k = (np.abs(((f32(65535.0) * S[None, :]).astype(f32) * inv).astype(f32)) + np.abs((Ob * inv).astype(f32))).astype(f32)
     k = (k + np.abs(p)).astype(f32)
-    m = ((k * f32(2.0 ** -21)).astype(f32) + f32(2.0 ** -140)).astype(f32)
+    m = ((k * f32(2.0 ** -21)).astype(f32) + f32(2.0 ** -132)).astype(f32)
     cN, cF = (c - m).astype(f32), (c + m).astype(f32)
     neg = inv < 0
     ql, qh = q[:, :3].astype(f32), q[:, 3:].astype(f32)
