@@ -9,14 +9,22 @@
 #       clBuildProgram would produce on the MI355X.  "strict" = -ffp-contract=off
 #       -cl-fp32-correctly-rounded-divide-sqrt (the floating-point model oracle/lt_oracle.c
 #       restates); "default" = what NULL build options give (renderer_opencl.cpp:50).
-# No-op (exit 0) when /root/reference is absent (the GPU box uses the prebuilt files).
+#   math_probe.strict.co / math_probe.default.co : oracle/math_probe.cl, the project's own probe of the OpenCL builtins and
+#       operators, compiled the same two ways.  Needs no reference tree: built (when its source is newer) before anything else.
+# The reference-derived part is a no-op (exit 0) when /root/reference is absent (the GPU box uses the prebuilt files).
 set -e
 REF=${LT_REFERENCE_DIR:-/root/reference}
 HERE=$(cd "$(dirname "$0")" && pwd)
 OUT=$HERE/_ref
-if [ ! -d "$REF/src" ]; then echo "build_ref: $REF not present, keeping prebuilt oracle/_ref"; exit 0; fi
 mkdir -p "$OUT"
-CLANG=/opt/rocm/lib/llvm/bin/clang
+CLANG=${LT_OPENCL_CLANG:-/opt/rocm/lib/llvm/bin/clang}
+CLFLAGS="-x cl -cl-std=CL2.0 -target amdgcn-amd-amdhsa -mcpu=gfx950 -Xclang -finclude-default-header -O3 -w"
+STRICT="-ffp-contract=off -cl-fp32-correctly-rounded-divide-sqrt"
+if [ "$OUT/math_probe.default.co" -ot "$HERE/math_probe.cl" ] || [ "$OUT/math_probe.strict.co" -ot "$HERE/math_probe.cl" ]; then
+  $CLANG $CLFLAGS $STRICT "$HERE/math_probe.cl" -o "$OUT/math_probe.strict.co"
+  $CLANG $CLFLAGS "$HERE/math_probe.cl" -o "$OUT/math_probe.default.co"
+fi
+if [ ! -d "$REF/src" ]; then echo "build_ref: $REF not present, keeping prebuilt oracle/_ref"; exit 0; fi
 for opt in O0; do
   g++ -std=c++17 -$opt -w -I"$REF/include" "$HERE/ref_host_dump.cpp" \
       "$REF/src/model.cpp" "$REF/src/acceleration_structure_explicit.cpp" "$REF/src/camera.cpp" "$REF/src/resource.cpp" \
@@ -32,9 +40,7 @@ declare -A K=(
 )
 for name in "${!K[@]}"; do
   src="$REF/${K[$name]}"
-  $CLANG -x cl -cl-std=CL2.0 -target amdgcn-amd-amdhsa -mcpu=gfx950 -Xclang -finclude-default-header -O3 -w \
-      -ffp-contract=off -cl-fp32-correctly-rounded-divide-sqrt "$src" -o "$OUT/$name.strict.co"
-  $CLANG -x cl -cl-std=CL2.0 -target amdgcn-amd-amdhsa -mcpu=gfx950 -Xclang -finclude-default-header -O3 -w \
-      "$src" -o "$OUT/$name.default.co"
+  $CLANG $CLFLAGS $STRICT "$src" -o "$OUT/$name.strict.co"
+  $CLANG $CLFLAGS "$src" -o "$OUT/$name.default.co"
 done
 ls -la "$OUT"

@@ -695,3 +695,48 @@ int lt_oracle_trace(int program, const void* nodes, const void* prims, const flo
   tuv[0] = pl.t; tuv[1] = pl.u; tuv[2] = pl.v;
   return pl.hitType;
 }
+
+/* The leaf functions above over arrays of bit patterns (tests/test_math_edges_cpu.py holds them against a float64 reference;
+ * tests/test_gpu_math_edges.py holds the HIP path's portable flavour against them).  Record i is n_in words of `in` and n_out
+ * words of `out`, laid out as oracle/math_probe.cl's kernels of the same names; the operators are C's own, unfused.
+ * Returns 0, or -1 for an unknown op. */
+enum { LT_LEAF_NORMALIZE = 1, LT_LEAF_DISTANCE, LT_LEAF_DOT4, LT_LEAF_DOT2, LT_LEAF_CROSS, LT_LEAF_CLAMP01, LT_LEAF_SIN, LT_LEAF_COS,
+       LT_LEAF_FDIV, LT_LEAF_RCP, LT_LEAF_DIV25, LT_LEAF_SQRT, LT_LEAF_MAD1, LT_LEAF_MAD2, LT_LEAF_MAD3, LT_LEAF_MAD1D, LT_LEAF_RSQRT };
+static inline float leaf_f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+static inline uint32_t leaf_u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+static inline f4 leaf_f4(const uint32_t* a) { return mk4(leaf_f(a[0]), leaf_f(a[1]), leaf_f(a[2]), leaf_f(a[3])); }
+static inline void leaf_put4(uint32_t* r, f4 v) { r[0] = leaf_u(v.x); r[1] = leaf_u(v.y); r[2] = leaf_u(v.z); r[3] = leaf_u(v.w); }
+int lt_oracle_leaf(int op, const uint32_t* in, uint32_t* out, uint64_t n) {
+  static const int n_in[] = {0, 4, 8, 8, 4, 8, 1, 1, 1, 2, 1, 1, 1, 3, 4, 6, 6, 1}, n_out[] = {0, 4, 1, 1, 1, 4, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 1};
+  if (op < LT_LEAF_NORMALIZE || op > LT_LEAF_RSQRT) return -1;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t* a = in + i * (uint64_t)n_in[op];
+    uint32_t* r = out + i * (uint64_t)n_out[op];
+    switch (op) {
+      case LT_LEAF_NORMALIZE: leaf_put4(r, normalize4(leaf_f4(a))); break;
+      case LT_LEAF_DISTANCE: r[0] = leaf_u(distance4(leaf_f4(a), leaf_f4(a + 4))); break;
+      case LT_LEAF_DOT4: r[0] = leaf_u(dot4(leaf_f4(a), leaf_f4(a + 4))); break;
+      case LT_LEAF_DOT2: r[0] = leaf_u(dot2(leaf_f(a[0]), leaf_f(a[1]), leaf_f(a[2]), leaf_f(a[3]))); break;
+      case LT_LEAF_CROSS: leaf_put4(r, cross4(leaf_f4(a), leaf_f4(a + 4))); break;
+      case LT_LEAF_CLAMP01: r[0] = leaf_u(clamp01(leaf_f(a[0]))); break;
+      case LT_LEAF_SIN: r[0] = leaf_u(sinf_portable(leaf_f(a[0]))); break;
+      case LT_LEAF_COS: r[0] = leaf_u(cosf_portable(leaf_f(a[0]))); break;
+      case LT_LEAF_FDIV: r[0] = leaf_u(leaf_f(a[0]) / leaf_f(a[1])); break;
+      case LT_LEAF_RCP: r[0] = leaf_u(1.0f / leaf_f(a[0])); break;
+      case LT_LEAF_DIV25: r[0] = leaf_u(leaf_f(a[0]) / 25.0f); break;
+      case LT_LEAF_SQRT: r[0] = leaf_u(sqrtf(leaf_f(a[0]))); break;
+      case LT_LEAF_MAD1: r[0] = leaf_u(leaf_f(a[0]) * leaf_f(a[1]) + leaf_f(a[2])); break;
+      case LT_LEAF_MAD2: r[0] = leaf_u(leaf_f(a[0]) * leaf_f(a[1]) + leaf_f(a[2]) * leaf_f(a[3])); break;
+      case LT_LEAF_MAD3: r[0] = leaf_u((leaf_f(a[0]) * leaf_f(a[1]) + leaf_f(a[2]) * leaf_f(a[3])) + leaf_f(a[4]) * leaf_f(a[5])); break;
+      case LT_LEAF_MAD1D: {
+        double d[3], v;
+        memcpy(d, a, 24);
+        v = d[0] * d[1] + d[2];
+        memcpy(r, &v, 8);
+        break;
+      }
+      case LT_LEAF_RSQRT: r[0] = leaf_u(rsqrt_portable(leaf_f(a[0]))); break;
+    }
+  }
+  return 0;
+}

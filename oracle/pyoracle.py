@@ -52,6 +52,8 @@ def lib():
         L.lt_oracle_random.restype = ctypes.c_float
         L.lt_oracle_trace.argtypes = [i32, vp, vp, vp, vp, ctypes.c_float, i32, i32, ctypes.POINTER(i32), vp]
         L.lt_oracle_trace.restype = i32
+        L.lt_oracle_leaf.argtypes = [i32, vp, vp, ctypes.c_uint64]
+        L.lt_oracle_leaf.restype = i32
         _lib = L
     return _lib
 
@@ -148,3 +150,21 @@ def trace(scene, origin, direction, program=ACCUMULATOR, tmax=np.finfo(np.float3
     hit = L.lt_oracle_trace(program, _p(n), _p(p), _p(o), _p(d), tmax, 0 if ignore is None else 1,
                             0 if ignore is None else ignore, ctypes.byref(prim), _p(tuv))
     return hit, prim.value, tuv
+
+
+# lt_oracle_leaf: op -> (id, input words, output words) per record; the names and layouts of oracle/math_probe.cl's kernels
+LEAF_OPS = {"normalize": (1, 4, 4), "distance": (2, 8, 1), "dot4": (3, 8, 1), "dot2": (4, 4, 1), "cross": (5, 8, 4),
+            "clamp01": (6, 1, 1), "sin": (7, 1, 1), "cos": (8, 1, 1), "fdiv": (9, 2, 1), "rcp": (10, 1, 1), "div25": (11, 1, 1),
+            "sqrt": (12, 1, 1), "mad1": (13, 3, 1), "mad2": (14, 4, 1), "mad3": (15, 6, 1), "mad1d": (16, 6, 2), "rsqrt": (17, 1, 1)}
+
+
+def leaf(op, words_in):
+    """The oracle's leaf function `op` over an (n, k) uint32 array of input bit patterns; returns (n, m) uint32 result words."""
+    opid, k, m = LEAF_OPS[op]
+    a = np.ascontiguousarray(words_in, dtype=np.uint32)
+    if a.ndim != 2 or a.shape[1] != k:
+        raise ValueError("%s takes records of %d words" % (op, k))
+    out = np.zeros((a.shape[0], m), dtype=np.uint32)
+    if lib().lt_oracle_leaf(opid, _p(a), _p(out), a.shape[0]):
+        raise ValueError("unknown leaf op %r" % op)
+    return out

@@ -10,7 +10,10 @@ RendererOpenCL::render does (src/opencl/renderer_opencl.cpp:128-145) when the wo
 
   strict  : -ffp-contract=off -cl-fp32-correctly-rounded-divide-sqrt (the floating-point model the oracle restates;
             the device library's builtins still use v_rsq_f32 / v_sqrt_f32 / its own sinf, cosf -- see DESIGN.md)
-  default : NULL build options, as the reference passes (renderer_opencl.cpp:50)."""
+  default : NULL build options, as the reference passes (renderer_opencl.cpp:50).
+
+probe() runs an entry point of oracle/math_probe.cl -- the project's own probe of the OpenCL builtins and operators, built the
+same two ways into oracle/_ref/math_probe.{strict,default}.co -- over 1-D arrays of bit patterns."""
 import ctypes
 import os
 
@@ -96,3 +99,24 @@ def render(scene, camera28, W, H, kernel="basic", flavor="strict", mode=0, depth
     _check(L.hipModuleLaunchKernel(fn, W // lx, H // ly, 1, lx, ly, 1, 0, None, argv, None), "hipModuleLaunchKernel")
     torch.cuda.synchronize()
     return out.cpu().numpy()
+
+
+def probe(entry, flavor, words_in, n_out):
+    """Runs `entry` of math_probe.<flavor>.co: words_in is an (n, k) uint32 array, one record of k input words per work-item;
+    returns the (n, n_out) uint32 array of result words."""
+    import torch
+    L = _lib()
+    dev = torch.device("cuda", 0)
+    words_in = np.ascontiguousarray(words_in, dtype=np.uint32)
+    n = words_in.shape[0]
+    fn = _function("math_probe", flavor, entry)
+    # (int32 views: torch has no uint32 arithmetic, and none is needed)
+    src = torch.from_numpy(words_in.view(np.int32).copy()).to(dev)
+    out = torch.zeros((n, n_out), dtype=torch.int32, device=dev)
+    args = [ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.c_uint(n)]
+    argv = (ctypes.c_void_p * len(args))(*[ctypes.cast(ctypes.pointer(a), ctypes.c_void_p) for a in args])
+    torch.cuda.synchronize()
+    if n:
+        _check(L.hipModuleLaunchKernel(fn, (n + 63) // 64, 1, 1, 64, 1, 1, 0, None, argv, None), "hipModuleLaunchKernel")
+    torch.cuda.synchronize()
+    return out.cpu().numpy().view(np.uint32)
