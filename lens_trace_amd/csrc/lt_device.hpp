@@ -902,7 +902,7 @@ __device__ __forceinline__ bool packet_ray_ok(const Ray& ray, float ix, float iy
 // ---- two frames' shadow rays of one camera hit in one any-hit packet walk (lt_walk_asm.hpp: LT_ASM_WALK2 makes the argument):
 // ray[0] and ray[1] share their origin, both frames' rays of the wave lie in the octant NEG.  On return pl[j].hitType is 1 where
 // frame j's ray met an occluder.  The plain-C++ form first (-DLT_NO_ASM_WALKS): packet_walk_cpp's any-hit walk with a `live` mask
-// per frame and a child pushed when some lane of either frame enters it.
+// per frame and a child pushed when some lane of either frame enters it (frame 1 is asked only where frame 0 does not).
 template <int PROGRAM, int NEG>
 __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave) {
   using u64 = unsigned long long;
@@ -922,12 +922,11 @@ __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2],
   for (;;) {
     const F16v r = *(ConstF16)(pairs + (cur << 6));
     if ((int)cur >= 0) {
-      u64 hmL = 0ull, hmR = 0ull;
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        hmL |= box_mask_cheap<NEG>(r.s0, r.s1, r.s2, r.s3, r.s4, r.s5, inv[j][0], inv[j][1], inv[j][2], pr[j]) & live[j];
-        hmR |= box_mask_cheap<NEG>(r.s8, r.s9, r.sa, r.sb, r.sc, r.sd, inv[j][0], inv[j][1], inv[j][2], pr[j]) & live[j];
-      }
+      // (a child that frame 0 enters is pushed whatever frame 1 finds: frame 1 tests only the children frame 0 missed)
+      u64 hmL = box_mask_cheap<NEG>(r.s0, r.s1, r.s2, r.s3, r.s4, r.s5, inv[0][0], inv[0][1], inv[0][2], pr[0]) & live[0];
+      u64 hmR = box_mask_cheap<NEG>(r.s8, r.s9, r.sa, r.sb, r.sc, r.sd, inv[0][0], inv[0][1], inv[0][2], pr[0]) & live[0];
+      if (hmL == 0ull) hmL = box_mask_cheap<NEG>(r.s0, r.s1, r.s2, r.s3, r.s4, r.s5, inv[1][0], inv[1][1], inv[1][2], pr[1]) & live[1];
+      if (hmR == 0ull) hmR = box_mask_cheap<NEG>(r.s8, r.s9, r.sa, r.sb, r.sc, r.sd, inv[1][0], inv[1][1], inv[1][2], pr[1]) & live[1];
       if (hmL != 0ull) ldsWave[sp++] = __float_as_int(r.s6);
       if (hmR != 0ull) ldsWave[sp++] = __float_as_int(r.se);
     } else {

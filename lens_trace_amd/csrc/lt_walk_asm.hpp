@@ -456,19 +456,36 @@ typedef unsigned long long lt_u64;
 // frame's rays entered, and there a lane either passes the leaf's exact tests or fails them, as it would have had its own walk
 // reached that leaf -- a finite ray reaches a leaf of the reference's traversal iff it passes the slab test of the leaf's own box
 // (lt_retree.hpp).  An any-hit caller reads "accepted or not" only, so the order in which a frame meets its leaves is free.
-// Interior record: each frame's conservative test with EXEC = its `open`, the two hit masks OR-ed (TMPM is free once the record
-// fetches have been issued).  Leaf: each frame's complete test in turn (the triangle's tvec / qvec and the box's (bound - o)
-// depend on the origin only, but qvec is only computed for the lanes past the u test, mostly none; recomputing them keeps every
-// value what the one-frame walk computes and costs no register); the walk ends when both masks are empty.
-#define LT_ASM_TESTS2(NF, L, R)                                                                                                 \
+// Interior record: a child is pushed iff its hit mask is non-zero and a stack entry carries no lane mask, so once frame 0's test
+// (EXEC = `open`) has let a lane into a child, frame 1's test of that child has no reader: it runs (EXEC = `open_1`, writing the mask
+// itself: nothing to OR) only for the children frame 0 missed -- the set of pushed children is that of testing both frames always.
+// A frame with no lane left looking has its tests branched over (frame 0's masks are then zeroed out of line: LT_ASM_TESTS2_ZERO).
+// Leaf: each frame's complete test in turn (the triangle's tvec / qvec and the box's (bound - o) depend on the origin only, but qvec
+// is only computed for the lanes past the u test, mostly none; recomputing them keeps every value what the one-frame walk computes
+// and costs no register); the walk ends when both masks are empty.
+// LT_ASM_TESTS2's S: a suffix for its labels, distinct in every expansion inside one asm block (%= is unique per block only);
+// LT_ASM_TESTS2_ZERO(S), placed where control cannot fall into it, is the expansion's out-of-line part.
+#define LT_ASM_TESTS2(NF, L, R, S)                                                                                              \
   "s_mov_b64 exec, %[open]\n"                                                                                                   \
+  "s_cbranch_execz .Lt2zero" S "%=\n"               /* frame 0 is done: no lane to test */                                      \
   LT_BC(NF, LT_LOHI_##L, LT_R_HML, "")                                                                                           \
   LT_BC(NF, LT_LOHI_##R, LT_R_HMR, "")                                                                                           \
+  ".Lt2second" S "%=:\n"                                                                                                        \
   "s_mov_b64 exec, %[open_1]\n"                                                                                                 \
-  LT_BC(NF, LT_LOHI_##L, LT_R_TMPM, "_1")                                                                                        \
-  "s_or_b64 " LT_R_HML ", " LT_R_HML ", " LT_R_TMPM "\n"                                                                        \
-  LT_BC(NF, LT_LOHI_##R, LT_R_TMPM, "_1")                                                                                        \
-  "s_or_b64 " LT_R_HMR ", " LT_R_HMR ", " LT_R_TMPM "\n"
+  "s_cbranch_execz .Lt2end" S "%=\n"                /* frame 1 is done */                                                       \
+  "s_cmp_lg_u64 " LT_R_HML ", 0\n"                                                                                              \
+  "s_cbranch_scc1 .Lt2right" S "%=\n"               /* frame 0 entered the left child: it is pushed whatever frame 1 finds */   \
+  LT_BC(NF, LT_LOHI_##L, LT_R_HML, "_1")                                                                                         \
+  ".Lt2right" S "%=:\n"                                                                                                         \
+  "s_cmp_lg_u64 " LT_R_HMR ", 0\n"                                                                                              \
+  "s_cbranch_scc1 .Lt2end" S "%=\n"                                                                                             \
+  LT_BC(NF, LT_LOHI_##R, LT_R_HMR, "_1")                                                                                         \
+  ".Lt2end" S "%=:\n"
+#define LT_ASM_TESTS2_ZERO(S)                                                                                                   \
+  ".Lt2zero" S "%=:\n"                                                                                                          \
+  "s_mov_b64 " LT_R_HML ", 0\n"                                                                                                 \
+  "s_mov_b64 " LT_R_HMR ", 0\n"                                                                                                 \
+  "s_branch .Lt2second" S "%=\n"
 
 #define LT_ASM_LEAF2(NF, S)                                                                                                     \
   "s_mov_b64 exec, %[open" S "]\n"                                                                                              \
@@ -515,10 +532,10 @@ typedef unsigned long long lt_u64;
   "s_lshl_b32 " LT_R_TMPHI ", " LT_R_CUR2 ", 6\n"                                                                               \
   "s_load_dwordx16 " LT_R_REC1 ", %[pairs], " LT_R_TMPHI "\n"                                                                   \
   "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
-  LT_ASM_TESTS2(NF, 0, 1)                                                                                                       \
+  LT_ASM_TESTS2(NF, 0, 1, "a")                                                                                                  \
   LT_ASM_PUSH(LT_R_REF0L, LT_R_HML)                                                                                             \
   LT_ASM_PUSH(LT_R_REF0R, LT_R_HMR)                                                                                             \
-  LT_ASM_TESTS2(NF, 2, 3)                                                                                                       \
+  LT_ASM_TESTS2(NF, 2, 3, "b")                                                                                                  \
   LT_ASM_PUSH(LT_R_REF1L, LT_R_HML)                                                                                             \
   LT_ASM_PUSH(LT_R_REF1R, LT_R_HMR)                                                                                             \
   "s_branch .Lpop%=\n"                                                                                                          \
@@ -526,10 +543,13 @@ typedef unsigned long long lt_u64;
   "s_add_u32 m0, m0, 1\n"                                                                                                       \
   ".Lone%=:\n"                                                                                                                  \
   "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
-  LT_ASM_TESTS2(NF, 0, 1)                                                                                                       \
+  LT_ASM_TESTS2(NF, 0, 1, "c")                                                                                                  \
   LT_ASM_PUSH(LT_R_REF0L, LT_R_HML)                                                                                             \
   LT_ASM_PUSH(LT_R_REF0R, LT_R_HMR)                                                                                             \
   "s_branch .Lpop%=\n"                                                                                                          \
+  LT_ASM_TESTS2_ZERO("a")                                                                                                       \
+  LT_ASM_TESTS2_ZERO("b")                                                                                                       \
+  LT_ASM_TESTS2_ZERO("c")                                                                                                       \
   ".Lleaf%=:\n"                                                                                                                 \
   "s_lshl_b32 " LT_R_TMPLO ", " LT_R_CUR ", 6\n"                                                                                \
   "s_load_dwordx16 " LT_R_REC0 ", %[pairs], " LT_R_TMPLO "\n"                                                                   \
