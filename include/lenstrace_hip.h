@@ -292,6 +292,50 @@ int lt_hip_trace_rays(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const 
 int lt_hip_trace_rays_device(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n,
                              void* out, uint64_t out_bytes, void* hip_stream);
 
+/* Multi-hit ray queries: what lies BEHIND the first surface, in one walk -- transparency, lens stacks, thickness and
+ * penetration counts, inside / outside by crossing parity.  (A second lt_hip_trace_rays from the hit point would need an offset
+ * the reference's rules do not have, and `ignore` names one primitive only.)
+ *
+ * The HIT SEQUENCE of a ray {origin, tmax, direction, ignore} under an epsilon program is defined by peeling.  Hit 0 is what the
+ * reference's `intersect` (`intersectIgnorePrimitiveIndex` when ignore >= 0) returns from the payload {t = tmax, primitiveIndex =
+ * hitType = 0}: what lt_hip_trace_rays / LT_TRACE_CLOSEST reports.  Hit j is what the same call returns on the same scene after
+ * the primitives of hits 0 .. j-1 have been made degenerate (B = C = A: intersectTriangle rejects such a primitive for every ray,
+ * and the node boxes stay as they are).  The sequence ends at the first miss.  Equivalently: it holds, once each, every primitive
+ * whose leaf the reference's box tests reach and which intersectTriangle accepts with t < tmax, in ascending t by the float `<`;
+ * primitives of bit-equal t (-0 == +0) in the reference's traversal order for that ray.  Everything else is lt_hip_trace_rays':
+ * no t > 0 test, no tmin, tmax as given (0, negative, inf, NaN), origin.w = 1, direction.w = +0, the `ignore` leaf is never
+ * entered, a leaf with primitiveCount > 1 tests its one primitive once.  (The reference's builder never makes two leaves that name
+ * one primitive.  A scene that has such leaves gets no own hierarchy, and there a primitive may appear once per leaf.)
+ *
+ * LT_TRACE_FIRST_K writes the first max_hits entries of the sequence as max_hits consecutive lt_hip_hit records per ray, ray-major
+ * (record i * max_hits + j is hit j of ray i); unused slots hold the miss record {t = tmax, prim = -1, u = v = 0}.
+ * LT_TRACE_COUNT writes one uint32 per ray: the length of the whole sequence.
+ * flags: LT_RENDER_FLAG_STRICT_MATH or LT_RENDER_FLAG_PORTABLE_MATH, with the render path's meaning.  LT_TRACE_FLAG_COHERENT is
+ * accepted and has no effect on these kinds: there is no multi-hit packet walk, every ray walks per lane (lens_trace_amd/csrc/
+ * lt_query.hip, lt_query_hits_kernel). */
+#define LT_TRACE_MAX_HITS 8
+enum { LT_TRACE_FIRST_K = 0, LT_TRACE_COUNT = 1 };   /* kinds of lt_hip_trace_hits only (not lt_hip_trace_desc::kind) */
+
+typedef struct lt_hip_multihit_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_multihit_desc) */
+  int32_t program;              /* a built-in LT_PROGRAM_* (selects the epsilon) */
+  int32_t kind;                 /* LT_TRACE_FIRST_K / LT_TRACE_COUNT */
+  uint32_t flags;
+  uint32_t max_hits;            /* FIRST_K: 1 .. LT_TRACE_MAX_HITS; COUNT: 0 */
+  uint32_t reserved;            /* 0 */
+} lt_hip_multihit_desc;         /* 24 B */
+
+/* Host memory, synchronous.  Errors as lt_hip_trace_rays (null ctx / desc, a null pointer with n > 0, an unknown kind, n >= 2^32,
+ * a user program, STRICT with PORTABLE, any other flag, struct_size too small; device entry point: pointers that are not 16-byte
+ * aligned), and LT_ERR_INVALID_ARGUMENT for max_hits outside 1 .. LT_TRACE_MAX_HITS (FIRST_K), max_hits != 0 (COUNT) or
+ * reserved != 0; LT_ERR_UNKNOWN_PROGRAM for a program id that is neither; LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when out_bytes < n * max_hits * 16 (FIRST_K) or n * 4 (COUNT).  A failed
+ * call writes nothing to out; n == 0 launches nothing.  lt_hip_get_stats then reports rays = n, kernel_launches and kernel_ms. */
+int lt_hip_trace_hits(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                      void* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_trace_hits_device(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                             void* out, uint64_t out_bytes, void* hip_stream);
+
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
 

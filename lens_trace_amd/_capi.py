@@ -22,13 +22,15 @@ RENDER_FLAG_STRICT_MATH = 16
 RENDER_FLAG_NO_WALK_TIMING = 32
 TRACE_CLOSEST, TRACE_ANY = 0, 1      # lt_hip_trace_desc::kind
 TRACE_FLAG_COHERENT = 0x100          # runs of 64 consecutive rays are coherent: walked as packets
+TRACE_FIRST_K, TRACE_COUNT = 0, 1    # lt_hip_multihit_desc::kind (lt_hip_trace_hits only)
+TRACE_MAX_HITS = 8                   # LT_TRACE_MAX_HITS
 
 # every symbol include/lenstrace_hip.h declares
 EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last_error", "lt_hip_program_from_path",
            "lt_hip_resolve_program",
            "lt_hip_set_scene", "lt_hip_output_floats", "lt_hip_render", "lt_hip_render_scene", "lt_hip_render_device", "lt_hip_untile",
            "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure",
-           "lt_hip_trace_rays", "lt_hip_trace_rays_device"]
+           "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device"]
 
 
 class RenderDesc(ctypes.Structure):
@@ -64,6 +66,11 @@ class TraceHit(ctypes.Structure):   # lt_hip_hit
 
 class TraceDesc(ctypes.Structure):   # lt_hip_trace_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("program", ctypes.c_int32), ("kind", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class MultiHitDesc(ctypes.Structure):   # lt_hip_multihit_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("program", ctypes.c_int32), ("kind", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("max_hits", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 def _np_dtypes():
@@ -123,6 +130,9 @@ def load():
     if hasattr(L, "lt_hip_trace_rays"):
         L.lt_hip_trace_rays.argtypes = [vp, ctypes.POINTER(TraceDesc), vp, u64, vp, u64]
         L.lt_hip_trace_rays_device.argtypes = [vp, ctypes.POINTER(TraceDesc), vp, u64, vp, u64, vp]
+    if hasattr(L, "lt_hip_trace_hits"):
+        L.lt_hip_trace_hits.argtypes = [vp, ctypes.POINTER(MultiHitDesc), vp, u64, vp, u64]
+        L.lt_hip_trace_hits_device.argtypes = [vp, ctypes.POINTER(MultiHitDesc), vp, u64, vp, u64, vp]
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

@@ -2071,6 +2071,100 @@ extern "C" int lt_hip_trace_rays_device(lt_hip_context* ctx, const lt_hip_trace_
   return enqueue_trace(ctx, tc, rays, n, out, (hipStream_t)hip_stream);
 }
 
+// lt_hip_trace_hits / lt_hip_trace_hits_device: the first K hits of each ray, or their number (lt_query.hip,
+// lt_query_hits_kernel).  check_trace's rules with the descriptor's two further fields; the same staging and read-back.
+struct HitsCall {
+  lt_query::Epsilon eps;
+  uint32_t maxHits;    // 0: count
+  int devlibm;
+  uint64_t outBytes;
+};
+static_assert(sizeof(lt_hip_multihit_desc) == 24 && LT_TRACE_MAX_HITS == lt_query::kMaxHits, "multi-hit records (include/lenstrace_hip.h)");
+
+static int check_hits(lt_hip_context* ctx, const lt_hip_multihit_desc* d, const lt_hip_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
+                      bool device, HitsCall& hc) {
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_trace_hits: desc is NULL");
+  if (d->struct_size < sizeof(lt_hip_multihit_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_multihit_desc (struct_size)");
+  if (d->kind != LT_TRACE_FIRST_K && d->kind != LT_TRACE_COUNT) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown multi-hit kind");
+  if (d->program >= LT_PROGRAM_USER_BASE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take a built-in program (it selects the triangle epsilon)");
+  if (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL) return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
+  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only");
+  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (d->kind == LT_TRACE_FIRST_K && (d->max_hits < 1 || d->max_hits > LT_TRACE_MAX_HITS))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_TRACE_FIRST_K takes max_hits in 1 .. LT_TRACE_MAX_HITS");
+  if (d->kind == LT_TRACE_COUNT && d->max_hits != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_TRACE_COUNT takes max_hits = 0");
+  if (d->reserved != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_multihit_desc::reserved must be 0");
+  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 rays per query");
+  if (n > 0 && (!rays || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "rays or out is NULL");
+  if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "ray query before lt_hip_set_scene");
+  hc.maxHits = d->max_hits;
+  hc.outBytes = d->kind == LT_TRACE_COUNT ? n * sizeof(uint32_t) : n * d->max_hits * sizeof(lt_hip_hit);
+  if (out_bytes < hc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
+  hc.eps = (d->program == LT_PROGRAM_BASIC || d->program == LT_PROGRAM_CUSTOM_OPENCL) ? lt_query::kEpsFloat7
+           : d->program == LT_PROGRAM_BASIC_LIGHTING ? lt_query::kEpsDouble7 : lt_query::kEpsDouble4;
+  hc.devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
+  return LT_OK;
+}
+
+static int enqueue_hits(lt_hip_context* ctx, const HitsCall& hc, const void* rays, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  if (!ctx->d_query_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_query_ctl, 8 * kQueueStride * sizeof(uint32_t)));
+  if (!ctx->query_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->query_ev, hipEventDisableTiming));
+  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->query_ev, 0));   // (the counters are the previous query's until it is done)
+  lt_query::HitsParams qp{};
+  qp.rays = (const float4*)rays;
+  qp.hits = hc.maxHits ? (uint4*)out : nullptr;
+  qp.counts = hc.maxHits ? nullptr : (uint32_t*)out;
+  qp.n = (uint32_t)n;
+  qp.maxHits = hc.maxHits;
+  qp.next = ctx->d_query_ctl;
+  qp.refill = k.trace_refill;
+  const SceneDev sc = scene_dev(ctx, k, hc.devlibm);
+  ctx->mean_pairs = 0;
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  LT_HIP_CHECK(ctx, lt_query::launch_hits(sc, qp, hc.eps, (uint32_t)ctx->cu_count, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->query_ev, s));
+  ctx->last = lt_hip_stats{};
+  ctx->last.kernel_launches = 1;
+  ctx->last.rays = n;
+  ctx->pending = true;
+  ctx->pending_stats = false;
+  ctx->pending_query = true;
+  return LT_OK;
+}
+
+extern "C" int lt_hip_trace_hits(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, const lt_hip_ray* rays, uint64_t n, void* out,
+                                 uint64_t out_bytes) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  HitsCall hc{};
+  if (const int rc = check_hits(ctx, desc, rays, n, out, out_bytes, false, hc)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint64_t rayBytes = n * sizeof(lt_hip_ray);
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, hc.outBytes, hc.outBytes));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = enqueue_hits(ctx, hc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
+  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (const int rc = finish_pending(ctx)) return rc;
+  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, hc.outBytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+extern "C" int lt_hip_trace_hits_device(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, const lt_hip_ray* rays, uint64_t n, void* out,
+                                        uint64_t out_bytes, void* hip_stream) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  HitsCall hc{};
+  if (const int rc = check_hits(ctx, desc, rays, n, out, out_bytes, true, hc)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return enqueue_hits(ctx, hc, rays, n, out, (hipStream_t)hip_stream);
+}
+
 extern "C" int lt_hip_untile(lt_hip_context* ctx, const float* gathered, uint64_t floats_per_rank, uint32_t n_ranks, uint32_t width,
                              uint32_t height, uint32_t depth, uint32_t tile_w, uint32_t tile_h, float* image_out, void* hip_stream) {
   if (!ctx) return LT_ERR_INVALID_ARGUMENT;

@@ -715,6 +715,40 @@ __device__ inline void traverse_own_lane(const SceneDev& sc, const Ray& ray, flo
   while (!own_walk_step<PROGRAM, ANYHIT>(sc, ray, ix, iy, iz, w, pl, col, deep, e, sp)) {}
 }
 
+// own_walk_step for the queries that want EVERY hit of a ray (lt_query.hip, lt_query_hits_kernel): the same records, the same
+// group step and the same stack, another leaf action.  The walk never prunes by t, so it meets every leaf the reference's box
+// tests reach; here each leaf's triangle is tested from a payload of constant t = tmax -- accepted iff intersectTriangle accepts
+// it with t < tmax, whatever was found before -- and an accepted one that also passes the reference's test of the leaf's own
+// box goes to sink(t, primitive).  Returns true when the stack is empty.
+template <int PROGRAM, int ROWS, class SINK>
+__device__ __forceinline__ bool own_walk_step_all(const SceneDev& sc, const Ray& ray, float ix, float iy, float iz, const OwnRay& w, float tmax,
+                                                  SINK& sink, int* col, int* deep, uint32_t& e, int& sp) {
+  const uint4* rec = (const uint4*)((const char*)sc.wide + ((size_t)(e & 0x7fffffffu) << 6));
+  const uint4 s0 = rec[0], s1 = rec[1], s2 = rec[2], s3 = rec[3];
+  if ((int)e < 0) {
+    const float4 t0 = make_float4(__uint_as_float(s0.x), __uint_as_float(s0.y), __uint_as_float(s0.z), __uint_as_float(s0.w));
+    const float4 t1 = make_float4(__uint_as_float(s1.x), __uint_as_float(s1.y), __uint_as_float(s1.z), __uint_as_float(s1.w));
+    Hit trial{0, 0, tmax, 0.0f, 0.0f};
+    if (intersect_triangle_data<PROGRAM>(t0, t1, make_float4(__uint_as_float(s2.x), 0.0f, 0.0f, 0.0f), ray, trial, sc.fastRcp != 0u) &&
+        box_test_finite(__uint_as_float(s2.y), __uint_as_float(s2.z), __uint_as_float(s2.w), __uint_as_float(s3.x), __uint_as_float(s3.y),
+                        __uint_as_float(s3.z), ray, ix, iy, iz))
+      sink(trial.t, (int)s3.w);
+  } else {
+    const uint4 slot[4] = {s0, s1, s2, s3};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (own16_box_test(slot[k], w.qr, w.negx, w.negy, w.negz) && slot[k].w != w.ignLink) {
+        if (sp < ROWS) col[sp * kBlock] = (int)slot[k].w; else deep[sp - ROWS] = (int)slot[k].w;
+        sp++;
+      }
+    }
+  }
+  if (sp == 0) return true;
+  sp--;
+  e = (uint32_t)(sp < ROWS ? col[sp * kBlock] : deep[sp - ROWS]);
+  return false;
+}
+
 // Compile-time configuration of one kernel instantiation.
 template <bool DEEP_, bool STATS_, int DEVLIBM_, bool LDSSCENE_ = false, bool GROUPS_ = false>
 struct Config {

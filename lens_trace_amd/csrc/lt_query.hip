@@ -14,6 +14,8 @@
 //                           caller's records and keeping t;
 //   lt_query_packet_kernel  LT_TRACE_FLAG_COHERENT: one wave per 64 consecutive rays, walked as one packet (packet_walk) when
 //                           the 64 qualify, per lane otherwise.
+// And the multi-hit queries (lt_hip_trace_hits): lt_query_hits_kernel, lt_query_kernel's loop with another leaf action -- every
+// accepted primitive goes into a per-lane list sorted by t (the first K hits), or is counted.
 #include "lt_query.hpp"
 
 using namespace lt;
@@ -64,6 +66,81 @@ __device__ __forceinline__ bool packet_query(const SceneDev& sc, const Ray& ray,
     return true;
   }
   return false;
+}
+
+// ---------------------------------------------------------------------------------------------------- multi-hit queries
+// The hits of one ray, nearest first: K entries {t, primitive} in the lane's column of 2 K LDS rows behind the stage (entry j:
+// rows 2 j and 2 j + 1).  Only what the order needs is kept while the ray walks -- u and v are computed again for the K
+// survivors when it is done (finish) -- so a wave of the K = 8 kernel takes 36 rows, not 52.  An empty entry is the miss record's
+// {tmax, -1}: every accepted hit has t < tmax and sorts in front of it.  Order: t by the float `<`; equal t (-0 == +0) by the
+// reference's leaf order for the ray's octant (rank8), or, for a walk that follows the reference's own order (rank8 null), behind
+// what is there (insert's rank8 / octant).  An entry pushed past the end is dropped.
+struct HitList {
+  int* col;
+  uint32_t k;
+  __device__ __forceinline__ void reset(float tmax) {
+    for (uint32_t j = 0; j < k; j++) { col[2 * j * kBlock] = __float_as_int(tmax); col[(2 * j + 1) * kBlock] = -1; }
+  }
+  __device__ __forceinline__ void insert(float tt, int prim, const uint32_t* rank8, uint32_t octant) {
+    uint32_t j = k;
+    while (j > 0u) {
+      const float ti = __int_as_float(col[(2 * j - 2) * kBlock]);
+      const int pi = col[(2 * j - 1) * kBlock];
+      bool before = tt < ti;
+      if (tt == ti && rank8 != nullptr && pi >= 0) before = rank8[8 * (size_t)prim + octant] < rank8[8 * (size_t)pi + octant];
+      if (!before) break;
+      if (j < k) { col[2 * j * kBlock] = __float_as_int(ti); col[(2 * j + 1) * kBlock] = pi; }
+      j--;
+    }
+    if (j < k) { col[2 * j * kBlock] = __float_as_int(tt); col[(2 * j + 1) * kBlock] = prim; }
+  }
+  // The ray's K records: t and the primitive from the list, u and v from the triangle test run once more on the same triangle
+  // from the same payload {t = tmax} -- the same function on the same operands, hence the bits the walk saw.
+  template <int PROGRAM>
+  __device__ __forceinline__ void finish(const SceneDev& sc, const Ray& ray, float tmax, uint4* out) const {
+    for (uint32_t j = 0; j < k; j++) {
+      const int tb = col[2 * j * kBlock], prim = col[(2 * j + 1) * kBlock];
+      Hit trial{0, 0, tmax, 0.0f, 0.0f};
+      if (prim >= 0) intersect_triangle<PROGRAM>(sc.tris, prim, ray, trial, sc.fastRcp != 0u);
+      out[j] = make_uint4((uint32_t)tb, (uint32_t)prim, __float_as_uint(trial.u), __float_as_uint(trial.v));
+    }
+  }
+};
+
+struct HitCount {
+  uint32_t n;
+  __device__ __forceinline__ void operator()(float, int) { n++; }
+};
+
+// walk_reference for these queries: the caller's tree in the reference's order (acc.cl:132-217: near child first by
+// dirIsNeg[axis], its box test compare for compare, a leaf's one primitive tested once, the ignored leaf never entered), every
+// accepted triangle handed to `sink` in that order.
+template <int PROGRAM, class SINK>
+__device__ __forceinline__ void walk_reference_all(const SceneDev& sc, const Ray& ray, float ix, float iy, float iz, int ign, float tmax, SINK& sink) {
+  const bool nx = ix < 0.0f, ny = iy < 0.0f, nz = iz < 0.0f;
+  const uint32_t negBits = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
+  int todo[kMaxStack];   // (set_scene refuses trees deeper than the reference's nodesToVisit[64])
+  int sp = 0, cur = 0;
+  for (;;) {
+    const float4* n = (const float4*)((const char*)sc.nodes + ((uint32_t)cur << 5));
+    const float4 a = n[0], b = n[1];
+    const uint32_t meta = __float_as_uint(b.w);
+    const int off = __float_as_int(b.z);
+    if (box_test_reference(a.x, a.y, a.z, a.w, b.x, b.y, ray, ix, iy, iz, nx, ny, nz)) {
+      if ((meta & 0xffffu) == 0u) {
+        const bool neg = (negBits >> ((meta >> 16) & 0xffu)) & 1u;
+        todo[sp++] = neg ? cur + 1 : off;
+        cur = neg ? off : cur + 1;
+        continue;
+      }
+      if (off != ign) {
+        Hit trial{0, 0, tmax, 0.0f, 0.0f};
+        if (intersect_triangle<PROGRAM>(sc.tris, off, ray, trial, sc.fastRcp != 0u)) sink(trial.t, off);
+      }
+    }
+    if (sp == 0) break;
+    cur = todo[--sp];
+  }
 }
 
 }  // namespace
@@ -187,6 +264,110 @@ __global__ __launch_bounds__(kBlock, 8) void lt_query_packet_kernel(SceneDev sc,
   if (valid) put_result<ANYHIT>(qp, idx, pl);
 }
 
+// lt_query_kernel's claim, stage and refill loop with the multi-hit leaf action (own_walk_step_all): COUNT counts a ray's accepted
+// primitives in a register; otherwise they go into the lane's HitList of qp.maxHits entries, 2 maxHits LDS rows behind the stage,
+// which the lane resets when it takes a new ray -- its neighbours' lists stay as they are -- and writes out when its walk is done.
+template <int PROGRAM, bool COUNT>
+__global__ __launch_bounds__(kBlock, 8) void lt_query_hits_kernel(SceneDev sc, lt_query::HitsParams qp) {
+  using u64 = unsigned long long;
+  extern __shared__ int lds_stack[];   // [kTraceRows stack rows][kTraceStage rows of staged rays][2 maxHits list rows], 64 lanes each
+  int* const col = lds_stack + threadIdx.x;
+  int* const stage = lds_stack + kTraceRows * kBlock;
+  const uint32_t total = qp.n;
+  const uint32_t lane = threadIdx.x;
+  const u64 below = (1ull << lane) - 1ull;
+  const bool ownTree = sc.rank8 != nullptr;
+  const uint32_t share = total / (gridDim.x * 4u) / (uint32_t)kBlock * (uint32_t)kBlock;
+  const uint32_t claim = share < (uint32_t)kBlock ? (uint32_t)kBlock : (share > (uint32_t)kQueryClaim ? (uint32_t)kQueryClaim : share);
+  bool active = false;
+  uint32_t stageCount = 0u, stageTaken = 0u, claimNext = 0u, claimEnd = 0u, sweep = 0u;
+  const uint32_t home = __builtin_amdgcn_s_getreg((3u << 11) | 20u) & 7u;   // HW_REG_XCC_ID
+  bool drained = false;
+  Ray ray{};
+  float ix = 0.0f, iy = 0.0f, iz = 0.0f, tmax = 0.0f;
+  OwnRay w{};
+  HitList list{lds_stack + (kTraceRows + kTraceStage) * kBlock + threadIdx.x, COUNT ? 0u : qp.maxHits};
+  HitCount count{0u};
+  auto ranked = [&](float t, int prim) { list.insert(t, prim, sc.rank8, w.octant); };   // the own tree's order is not the reference's
+  auto inOrder = [&](float t, int prim) { list.insert(t, prim, nullptr, 0u); };
+  uint32_t idx = 0u, e = 0u;
+  int sp = 0;
+  int deep[kOwnRows + kOwnDeep - kTraceRows];
+  for (;;) {
+    const u64 idle = __builtin_amdgcn_ballot_w64(!active);
+    const uint32_t nIdle = (uint32_t)__popcll(idle);
+    if ((nIdle >= qp.refill || nIdle == (uint32_t)kBlock) && (stageTaken < stageCount || !drained)) {
+      if (stageTaken == stageCount) {
+        while (claimNext == claimEnd && sweep < 8u) {
+          const uint32_t part = (home + sweep) & 7u;
+          const uint32_t lo = (uint32_t)((uint64_t)total * part / 8u / kBlock * kBlock), hi = part == 7u ? total : (uint32_t)((uint64_t)total * (part + 1u) / 8u / kBlock * kBlock);
+          uint32_t got = 0u;
+          if (lane == 0u) got = atomicAdd(&qp.next[part * kQueueStride], claim);
+          got = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
+          if (got >= hi - lo) { sweep++; continue; }
+          claimNext = lo + got;
+          claimEnd = hi - claimNext < claim ? hi : claimNext + claim;
+        }
+        const uint32_t base = claimNext;
+        const uint32_t batch = claimEnd - base < (uint32_t)kBlock ? claimEnd - base : (uint32_t)kBlock;
+        claimNext = base + batch;
+        drained = claimNext == claimEnd && sweep >= 8u;
+        stageTaken = 0u;
+        stageCount = batch;
+        if (lane < batch) {
+          const float4 a = qp.rays[2 * (size_t)(base + lane)], b = qp.rays[2 * (size_t)(base + lane) + 1];
+          stage[0 * kBlock + lane] = __float_as_int(a.x); stage[1 * kBlock + lane] = __float_as_int(a.y); stage[2 * kBlock + lane] = __float_as_int(a.z);
+          stage[3 * kBlock + lane] = __float_as_int(b.x); stage[4 * kBlock + lane] = __float_as_int(b.y); stage[5 * kBlock + lane] = __float_as_int(b.z);
+          stage[6 * kBlock + lane] = __float_as_int(b.w);   // ignore
+          stage[7 * kBlock + lane] = __float_as_int(a.w);   // tmax
+          stage[8 * kBlock + lane] = (int)(base + lane);
+        }
+      }
+      const uint32_t take = nIdle < stageCount - stageTaken ? nIdle : stageCount - stageTaken;
+      const uint32_t mine = (uint32_t)__popcll(idle & below);
+      if (!active && mine < take) {
+        const uint32_t s = stageTaken + mine;
+        idx = (uint32_t)stage[8 * kBlock + s];
+        ray = Ray{mk4(__int_as_float(stage[0 * kBlock + s]), __int_as_float(stage[1 * kBlock + s]), __int_as_float(stage[2 * kBlock + s]), 1.0f),
+                  mk4(__int_as_float(stage[3 * kBlock + s]), __int_as_float(stage[4 * kBlock + s]), __int_as_float(stage[5 * kBlock + s]), 0.0f)};
+        const int ignRaw = stage[6 * kBlock + s];
+        const int ign = ignRaw >= 0 ? ignRaw : -1;
+        ix = 1.0f / ray.d.x; iy = 1.0f / ray.d.y; iz = 1.0f / ray.d.z;
+        tmax = __int_as_float(stage[7 * kBlock + s]);
+        if (COUNT) count.n = 0u; else list.reset(tmax);
+        if (ownTree && finite_ray(ray, ix, iy, iz) && packet_ray_ok(ray, ix, iy, iz)) {
+          w = own_ray(sc, ray, ix, iy, iz, ign);
+          e = 0u;
+          sp = 0;
+          active = true;
+        } else {
+          if (COUNT) {
+            walk_reference_all<PROGRAM>(sc, ray, ix, iy, iz, ign, tmax, count);
+            qp.counts[idx] = count.n;
+          } else {
+            walk_reference_all<PROGRAM>(sc, ray, ix, iy, iz, ign, tmax, inOrder);
+            list.template finish<PROGRAM>(sc, ray, tmax, qp.hits + (size_t)idx * qp.maxHits);
+          }
+        }
+      }
+      stageTaken += take;
+    }
+    if (__builtin_amdgcn_ballot_w64(active) == 0ull) {
+      if (drained && stageTaken == stageCount) break;
+      continue;
+    }
+    if (active) {
+      const bool done = COUNT ? own_walk_step_all<PROGRAM, kTraceRows>(sc, ray, ix, iy, iz, w, tmax, count, col, deep, e, sp)
+                              : own_walk_step_all<PROGRAM, kTraceRows>(sc, ray, ix, iy, iz, w, tmax, ranked, col, deep, e, sp);
+      if (done) {
+        if (COUNT) qp.counts[idx] = count.n;
+        else list.template finish<PROGRAM>(sc, ray, tmax, qp.hits + (size_t)idx * qp.maxHits);
+        active = false;
+      }
+    }
+  }
+}
+
 namespace lt_query {
 
 template <int PROGRAM, bool ANYHIT>
@@ -215,6 +396,31 @@ hipError_t launch(const SceneDev& sc, const Params& p, Epsilon eps, bool anyHit,
     default:
       anyHit ? launch_one<kAccumulator, true>(sc, p, coherent, cuCount, s) : launch_one<kAccumulator, false>(sc, p, coherent, cuCount, s);
       break;
+  }
+  return hipGetLastError();
+}
+
+template <int PROGRAM>
+static void launch_hits_one(const SceneDev& sc, const HitsParams& p, uint32_t cuCount, hipStream_t s) {
+  const uint32_t chunks = (uint32_t)(((uint64_t)p.n + kBlock - 1) / kBlock);
+  const uint32_t rows = (uint32_t)(kTraceRows + kTraceStage) + 2u * p.maxHits;
+  // every wave slot the list rows leave: 160 KB of LDS per CU, at most 32 waves
+  const uint32_t fit = 160u * 1024u / (rows * kBlock * (uint32_t)sizeof(int)), perCu = fit < 32u ? fit : 32u;
+  const uint32_t resident = cuCount * perCu;
+  const dim3 grid(chunks < resident ? chunks : resident);
+  if (p.maxHits == 0u) hipLaunchKernelGGL((lt_query_hits_kernel<PROGRAM, true>), grid, dim3(kBlock), rows * kBlock * (uint32_t)sizeof(int), s, sc, p);
+  else hipLaunchKernelGGL((lt_query_hits_kernel<PROGRAM, false>), grid, dim3(kBlock), rows * kBlock * (uint32_t)sizeof(int), s, sc, p);
+}
+
+hipError_t launch_hits(const SceneDev& sc, const HitsParams& p, Epsilon eps, uint32_t cuCount, hipStream_t s) {
+  if (p.n == 0) return hipSuccess;
+  if (p.maxHits > kMaxHits) return hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(p.next, 0, 8 * kQueueStride * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  switch (eps) {
+    case kEpsFloat7: launch_hits_one<kBasic>(sc, p, cuCount, s); break;
+    case kEpsDouble7: launch_hits_one<kBasicLighting>(sc, p, cuCount, s); break;
+    default: launch_hits_one<kAccumulator>(sc, p, cuCount, s); break;
   }
   return hipGetLastError();
 }

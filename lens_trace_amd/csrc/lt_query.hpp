@@ -23,4 +23,21 @@ enum Epsilon { kEpsFloat7 = 0, kEpsDouble7 = 1, kEpsDouble4 = 2 };   // basic / 
 // Enqueues the query on `s`: lt_query_packet_kernel when `coherent`, else lt_query_kernel.  Returns the first HIP error.
 hipError_t launch(const lt::SceneDev& sc, const Params& p, Epsilon eps, bool anyHit, bool coherent, uint32_t cuCount, hipStream_t s);
 
+// Multi-hit queries (lt_hip_trace_hits, lt_hip_trace_hits_device): every primitive the reference's traversal would accept with
+// t < tmax, in ascending t (bit-equal t: the reference's traversal order).  Results: the first maxHits of them as maxHits
+// lt_hip_hit records per ray, ray-major, unused slots {tmax, -1, 0, 0}; or, maxHits == 0, their number as one word per ray.
+constexpr uint32_t kMaxHits = 8;   // LT_TRACE_MAX_HITS
+struct HitsParams {
+  const float4* rays;
+  uint4* hits;          // first K: record i * maxHits + j
+  uint32_t* counts;     // count
+  uint32_t n;
+  uint32_t maxHits;     // 1..kMaxHits; 0 = count
+  uint32_t* next;       // as Params::next
+  uint32_t refill;      // as Params::refill
+};
+
+// Enqueues lt_query_hits_kernel on `s`.  Returns the first HIP error.
+hipError_t launch_hits(const lt::SceneDev& sc, const HitsParams& p, Epsilon eps, uint32_t cuCount, hipStream_t s);
+
 }  // namespace lt_query

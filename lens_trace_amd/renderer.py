@@ -259,6 +259,56 @@ class RendererHIP:
                                                      ctypes.c_void_p(handle)))
         return out
 
+    def trace_hits(self, rays, max_hits=4, count=False, program="accumulator", portable_math=False, strict_math=False, coherent=False,
+                   stream=None):
+        """The first `max_hits` (1..C.TRACE_MAX_HITS) hits of each ray, nearest first, or with count=True how many there are
+        (lt_hip_trace_hits; include/lenstrace_hip.h defines the hit sequence: every primitive the reference's traversal accepts
+        with t < tmax, by t, bit-equal t in the reference's traversal order).  Rays as trace_rays takes them.  A numpy array goes
+        to the host entry point and numpy comes back: an (n, max_hits) HIT_DTYPE array whose unused slots are miss records
+        (t = tmax, prim -1), or (n,) uint32 counts; a torch tensor on this context's GPU is enqueued on `stream` (default: the
+        current torch stream) and torch comes back: (n, max_hits, 4) float32 (column 1: int32 bits) or (n,) int32 counts.
+        coherent is accepted and changes nothing: these queries have no packet walk."""
+        if not isinstance(program, int):
+            program = C.program_from_path(str(program))
+        d = C.MultiHitDesc()
+        d.struct_size = ctypes.sizeof(C.MultiHitDesc)
+        d.program = program
+        d.kind = C.TRACE_COUNT if count else C.TRACE_FIRST_K
+        d.max_hits = 0 if count else max_hits
+        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
+                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
+        if not count and not 1 <= max_hits <= C.TRACE_MAX_HITS:
+            raise ValueError("max_hits must be in 1..%d" % C.TRACE_MAX_HITS)
+        k = 0 if count else int(max_hits)
+        if isinstance(rays, np.ndarray):
+            if rays.dtype == RAY_DTYPE and rays.ndim == 1:
+                rays = rays.view(np.float32).reshape(-1, 8)
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an (n, 8) float32 array (make_rays) or a RAY_DTYPE array")
+            rays = np.ascontiguousarray(rays)
+            n = rays.shape[0]
+            out = np.zeros(n, dtype=np.uint32) if count else np.zeros((n, k), dtype=HIT_DTYPE)
+            self._check(self._L.lt_hip_trace_hits(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
+                                                  out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+            return out
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError("rays must be a numpy array or a torch tensor")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
+        dev = torch.device("cuda", self.device)
+        if rays.device != dev:
+            raise ValueError("rays must be on %s, the context's device" % dev)
+        n = rays.shape[0]
+        out = torch.empty((n,) if count else (n, k, 4), dtype=torch.int32 if count else torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        self._check(self._L.lt_hip_trace_hits_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
+                                                     ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                                                     ctypes.c_void_p(handle)))
+        return out
+
     def stats(self):
         s = C.Stats()
         self._check(self._L.lt_hip_get_stats(self._ctx, ctypes.byref(s)))
