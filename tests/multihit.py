@@ -57,18 +57,24 @@ class Peeler:
         return (self.tuv[0].copy(), self.prim.value, self.tuv[1].copy(), self.tuv[2].copy()) if hit else None
 
     def peel(self, ray, program, limit=None):
+        """Every peel takes one primitive out of the scene, so a sequence has at most n_prims entries and peel n_prims + 1 is a
+        miss: the loop stops there at the latest, and a peel that would go on is an assertion, not a hang."""
         seq, saved = [], []
-        while limit is None or len(seq) < limit:
-            h = self.trace(ray, program)
-            if h is None:
-                break
-            seq.append(h)
-            p = h[1]
-            saved.append((p, self.pv["positionB"][p].copy(), self.pv["positionC"][p].copy()))
-            self.pv["positionB"][p] = self.pv["positionA"][p]
-            self.pv["positionC"][p] = self.pv["positionA"][p]
-        for p, b, c in saved:
-            self.pv["positionB"][p], self.pv["positionC"][p] = b, c
+        stop = self.pv.size + 1
+        try:
+            while limit is None or len(seq) < limit:
+                h = self.trace(ray, program)
+                if h is None:
+                    break
+                assert len(seq) + 1 < stop, ("peel %d of a scene of %d primitives is a hit: the peel does not end" % (stop, stop - 1), h, ray)
+                seq.append(h)
+                p = h[1]
+                saved.append((p, self.pv["positionB"][p].copy(), self.pv["positionC"][p].copy()))
+                self.pv["positionB"][p] = self.pv["positionA"][p]
+                self.pv["positionC"][p] = self.pv["positionA"][p]
+        finally:
+            for p, b, c in reversed(saved):
+                self.pv["positionB"][p], self.pv["positionC"][p] = b, c
         return seq
 
 
