@@ -336,6 +336,44 @@ int lt_hip_trace_hits(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, con
 int lt_hip_trace_hits_device(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, const lt_hip_ray* rays, uint64_t n,
                              void* out, uint64_t out_bytes, void* hip_stream);
 
+/* Shading of caller-supplied rays: a picture through any camera model (pitched, orthographic, fisheye, a calibrated lens, a light
+ * probe, a tensor of rays).  For each ray the result is the colour the named program's `shade` returns for it -- what linearKernel /
+ * tileKernel would have stored had this ray been a pixel's camera ray at film position (film_x, film_y) and frame frameCount:
+ * random() is keyed by the film position and the frame, so two rays with one film position draw the same light samples.
+ *   rgb   frames frameCount = frame_first + f, f = 0 .. frame_count - 1, each with linearKernel's [0, 1] clamp of the lighting
+ *         programs when kernel_mode == LT_KERNEL_MODE_LINEAR, folded in frame order by accumulator.frag's running mean from n = 0:
+ *         what lt_hip_render with accumulate = 1, accumulate_base = 0 leaves in a pixel.  frame_count = 1: the frame itself.
+ *   prim  the primitive the ray itself hit, before any lens, or -1 on a miss.
+ * The ray's w components are the reference camera's: origin.w = 2 (cameraPosition.w + film.w), direction.w = +0 (aperture.w -
+ * film.w).  The camera payload starts at t = FLT_MAX and ignores nothing.
+ * Programs: LT_PROGRAM_BASIC (with the lens chain), LT_PROGRAM_BASIC_LIGHTING (25 blended samples per frame), LT_PROGRAM_ACCUMULATOR
+ * and LT_PROGRAM_CUSTOM_OPENCL.  The two global-illumination programs and user programs are refused with LT_ERR_INVALID_ARGUMENT:
+ * the GI wavefront pipeline is indexed by pixel -- a follow-up.
+ * flags: LT_RENDER_FLAG_STRICT_MATH or LT_RENDER_FLAG_PORTABLE_MATH, with the render path's meaning.  LT_TRACE_FLAG_COHERENT is
+ * accepted and has no effect: there is no packet path, every ray walks per lane (lens_trace_amd/csrc/lt_shade.hip). */
+typedef struct lt_hip_shade_ray { float origin[3]; float film_x; float direction[3]; float film_y; } lt_hip_shade_ray;   /* 32 B */
+typedef struct lt_hip_shade { float rgb[3]; int32_t prim; } lt_hip_shade;                                                /* 16 B */
+
+typedef struct lt_hip_shade_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_shade_desc) */
+  int32_t program;              /* LT_PROGRAM_BASIC, _BASIC_LIGHTING, _ACCUMULATOR or _CUSTOM_OPENCL */
+  int32_t kernel_mode;          /* LT_KERNEL_MODE_LINEAR / LT_KERNEL_MODE_TILE */
+  uint32_t flags;
+  uint32_t frame_first;
+  uint32_t frame_count;         /* >= 1 */
+} lt_hip_shade_desc;            /* 24 B */
+
+/* Host memory, synchronous.  LT_ERR_INVALID_ARGUMENT: null ctx / desc, a null pointer with n > 0, n >= 2^32, struct_size too small,
+ * STRICT with PORTABLE, any other flag, an unknown kernel_mode, frame_count == 0, a global-illumination or user program (and,
+ * device entry point, pointers that are not 16-byte aligned); LT_ERR_UNKNOWN_PROGRAM for an id that is no program;
+ * LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when out_bytes < 16 n.  A failed call writes nothing to out; n == 0 launches nothing.
+ * lt_hip_get_stats then reports rays = n, kernel_launches and kernel_ms. */
+int lt_hip_shade_rays(lt_hip_context* ctx, const lt_hip_shade_desc* desc, const lt_hip_shade_ray* rays, uint64_t n,
+                      lt_hip_shade* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_shade_rays_device(lt_hip_context* ctx, const lt_hip_shade_desc* desc, const lt_hip_shade_ray* rays, uint64_t n,
+                             lt_hip_shade* out, uint64_t out_bytes, void* hip_stream);
+
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
 

@@ -30,7 +30,8 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_resolve_program",
            "lt_hip_set_scene", "lt_hip_output_floats", "lt_hip_render", "lt_hip_render_scene", "lt_hip_render_device", "lt_hip_untile",
            "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure",
-           "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device"]
+           "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device",
+           "lt_hip_shade_rays", "lt_hip_shade_rays_device"]
 
 
 class RenderDesc(ctypes.Structure):
@@ -73,6 +74,19 @@ class MultiHitDesc(ctypes.Structure):   # lt_hip_multihit_desc
                 ("max_hits", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class ShadeRay(ctypes.Structure):   # lt_hip_shade_ray
+    _fields_ = [("origin", ctypes.c_float * 3), ("film_x", ctypes.c_float), ("direction", ctypes.c_float * 3), ("film_y", ctypes.c_float)]
+
+
+class ShadeResult(ctypes.Structure):   # lt_hip_shade
+    _fields_ = [("rgb", ctypes.c_float * 3), ("prim", ctypes.c_int32)]
+
+
+class ShadeDesc(ctypes.Structure):   # lt_hip_shade_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("program", ctypes.c_int32), ("kernel_mode", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("frame_first", ctypes.c_uint32), ("frame_count", ctypes.c_uint32)]
+
+
 def _np_dtypes():
     import numpy as np
     ray = np.dtype([("origin", "<f4", (3,)), ("tmax", "<f4"), ("direction", "<f4", (3,)), ("ignore", "<i4")])
@@ -81,6 +95,16 @@ def _np_dtypes():
 
 
 RAY_DTYPE, HIT_DTYPE = _np_dtypes()   # numpy views of lt_hip_ray (32 bytes) and lt_hip_hit (16 bytes)
+
+
+def _np_shade_dtypes():
+    import numpy as np
+    ray = np.dtype([("origin", "<f4", (3,)), ("film_x", "<f4"), ("direction", "<f4", (3,)), ("film_y", "<f4")])
+    out = np.dtype([("rgb", "<f4", (3,)), ("prim", "<i4")])
+    return ray, out
+
+
+SHADE_RAY_DTYPE, SHADE_DTYPE = _np_shade_dtypes()   # numpy views of lt_hip_shade_ray (32 bytes) and lt_hip_shade (16 bytes)
 
 
 class LensTraceError(RuntimeError):
@@ -133,6 +157,9 @@ def load():
     if hasattr(L, "lt_hip_trace_hits"):
         L.lt_hip_trace_hits.argtypes = [vp, ctypes.POINTER(MultiHitDesc), vp, u64, vp, u64]
         L.lt_hip_trace_hits_device.argtypes = [vp, ctypes.POINTER(MultiHitDesc), vp, u64, vp, u64, vp]
+    if hasattr(L, "lt_hip_shade_rays"):
+        L.lt_hip_shade_rays.argtypes = [vp, ctypes.POINTER(ShadeDesc), vp, u64, vp, u64]
+        L.lt_hip_shade_rays_device.argtypes = [vp, ctypes.POINTER(ShadeDesc), vp, u64, vp, u64, vp]
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

@@ -5,6 +5,7 @@
 #include "lt_own16.hpp"
 #include "lt_prep.hpp"
 #include "lt_query.hpp"
+#include "lt_shade.hpp"
 
 #include "../../include/lenstrace_hip.h"
 
@@ -293,6 +294,9 @@ struct lt_hip_context {
   void* d_query_out = nullptr;
   uint64_t query_out_bytes = 0;
   hipEvent_t query_ev = nullptr;
+  // shaded rays (lt_shade.hip): lt_shade_rays_kernel's own eight work counters and the event behind its last launch, as above
+  uint32_t* d_shade_ctl = nullptr;
+  hipEvent_t shade_ev = nullptr;
   // wavefront GI pipeline: path queues, per-pixel direct / indirect / blend, control block (queue lengths, work counters)
   void* d_gi[17] = {nullptr};
   uint64_t gi_pixels = 0;
@@ -405,6 +409,8 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_query_rays) (void)hipFree(ctx->d_query_rays);
   if (ctx->d_query_out) (void)hipFree(ctx->d_query_out);
   if (ctx->query_ev) (void)hipEventDestroy(ctx->query_ev);
+  if (ctx->d_shade_ctl) (void)hipFree(ctx->d_shade_ctl);
+  if (ctx->shade_ev) (void)hipEventDestroy(ctx->shade_ev);
   if (ctx->d_order) (void)hipFree(ctx->d_order);
   for (auto& up : ctx->user_programs) (void)hipModuleUnload(up.module);
   for (void*& b : ctx->d_gi) if (b) (void)hipFree(b);
@@ -2163,6 +2169,104 @@ extern "C" int lt_hip_trace_hits_device(lt_hip_context* ctx, const lt_hip_multih
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   return enqueue_hits(ctx, hc, rays, n, out, (hipStream_t)hip_stream);
+}
+
+// lt_hip_shade_rays / lt_hip_shade_rays_device: the colour a program's `shade` returns for caller-supplied rays (lt_shade.hip).
+// check_trace's rules: every argument error is found before anything is enqueued.
+struct ShadeCall {
+  int program;         // lt::Program
+  int devlibm;
+  uint64_t outBytes;
+};
+static_assert(sizeof(lt_hip_shade_ray) == 32 && sizeof(lt_hip_shade) == 16 && sizeof(lt_hip_shade_desc) == 24, "shaded-ray records (include/lenstrace_hip.h)");
+
+static int check_shade(lt_hip_context* ctx, const lt_hip_shade_desc* d, const lt_hip_shade_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
+                       bool device, ShadeCall& sc) {
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_rays: desc is NULL");
+  if (d->struct_size < sizeof(lt_hip_shade_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_shade_desc (struct_size)");
+  const bool userProgram = d->program >= LT_PROGRAM_USER_BASE;
+  if (userProgram ? (size_t)(d->program - LT_PROGRAM_USER_BASE) >= ctx->user_programs.size()
+                  : (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL))
+    return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
+  if (userProgram) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_rays does not take user programs");
+  if (d->program == LT_PROGRAM_GLOBAL_ILLUMINATION || d->program == LT_PROGRAM_GLOBAL_ILLUMINATION_25)
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_rays does not take the global-illumination programs (their pipeline is indexed by pixel)");
+  if (d->kernel_mode != LT_KERNEL_MODE_LINEAR && d->kernel_mode != LT_KERNEL_MODE_TILE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown kernel mode");
+  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "shaded rays take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only");
+  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (d->frame_count == 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_desc::frame_count must be at least 1");
+  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 rays per call");
+  if (n > 0 && (!rays || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "rays or out is NULL");
+  if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_shade_rays before lt_hip_set_scene");
+  sc.outBytes = n * sizeof(lt_hip_shade);
+  if (out_bytes < sc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
+  sc.program = d->program == LT_PROGRAM_BASIC ? kBasic : d->program == LT_PROGRAM_BASIC_LIGHTING ? kBasicLighting
+               : d->program == LT_PROGRAM_ACCUMULATOR ? kAccumulator : kCustom;
+  sc.devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
+  return LT_OK;
+}
+
+// Enqueues the kernel on `s` between the context's timing events; lt_hip_get_stats reports it (finish_pending).
+static int enqueue_shade(lt_hip_context* ctx, const ShadeCall& call, const lt_hip_shade_desc* d, const void* rays, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  if (!ctx->d_shade_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_shade_ctl, 8 * kQueueStride * sizeof(uint32_t)));
+  if (!ctx->shade_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->shade_ev, hipEventDisableTiming));
+  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->shade_ev, 0));   // (the counters are the previous call's until it is done)
+  lt_shade::Params sp{};
+  sp.rays = (const float4*)rays;
+  sp.out = (uint4*)out;
+  sp.n = (uint32_t)n;
+  sp.next = ctx->d_shade_ctl;
+  sp.refill = k.trace_refill;
+  sp.shadeBatch = 16;   // LT_SHADE_BATCH=1..64 (A/B measurements; no result depends on it)
+  if (const char* e = getenv("LT_SHADE_BATCH")) sp.shadeBatch = (uint32_t)std::max(1, std::min(64, atoi(e)));
+  sp.frameFirst = d->frame_first;
+  sp.frameCount = d->frame_count;
+  sp.clampOutput = d->kernel_mode == LT_KERNEL_MODE_LINEAR;
+  const SceneDev sc = scene_dev(ctx, k, call.devlibm);
+  ctx->mean_pairs = 0;
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  LT_HIP_CHECK(ctx, lt_shade::launch(sc, sp, call.program, call.devlibm, (uint32_t)ctx->cu_count, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->shade_ev, s));
+  ctx->last = lt_hip_stats{};
+  ctx->last.kernel_launches = 1;
+  ctx->last.rays = n;
+  ctx->pending = true;
+  ctx->pending_stats = false;
+  ctx->pending_query = true;
+  return LT_OK;
+}
+
+extern "C" int lt_hip_shade_rays(lt_hip_context* ctx, const lt_hip_shade_desc* desc, const lt_hip_shade_ray* rays, uint64_t n, lt_hip_shade* out,
+                                 uint64_t out_bytes) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  ShadeCall call{};
+  if (const int rc = check_shade(ctx, desc, rays, n, out, out_bytes, false, call)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint64_t rayBytes = n * sizeof(lt_hip_shade_ray);
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, call.outBytes, call.outBytes));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = enqueue_shade(ctx, call, desc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
+  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (const int rc = finish_pending(ctx)) return rc;
+  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, call.outBytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+extern "C" int lt_hip_shade_rays_device(lt_hip_context* ctx, const lt_hip_shade_desc* desc, const lt_hip_shade_ray* rays, uint64_t n, lt_hip_shade* out,
+                                        uint64_t out_bytes, void* hip_stream) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  ShadeCall call{};
+  if (const int rc = check_shade(ctx, desc, rays, n, out, out_bytes, true, call)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return enqueue_shade(ctx, call, desc, rays, n, out, (hipStream_t)hip_stream);
 }
 
 extern "C" int lt_hip_untile(lt_hip_context* ctx, const float* gathered, uint64_t floats_per_rank, uint32_t n_ranks, uint32_t width,

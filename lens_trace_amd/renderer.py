@@ -99,6 +99,57 @@ def make_rays(origins, directions, tmax=FLT_MAX, ignore=-1):
     return out
 
 
+SHADE_RAY_DTYPE, SHADE_DTYPE = C.SHADE_RAY_DTYPE, C.SHADE_DTYPE
+
+
+def make_shade_rays(origins, directions, film_x, film_y):
+    """Packs rays for RendererHIP.shade_rays: (n, 3) origins and directions, film_x and film_y (the film position that keys the
+    program's random(): scalars or (n,) arrays), into an (n, 8) float32 array of lt_hip_shade_ray records -- origin, film_x,
+    direction, film_y."""
+    o = np.asarray(origins, dtype=np.float32)
+    d = np.asarray(directions, dtype=np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("origins and directions must both have shape (n, 3)")
+    n = o.shape[0]
+    fx = np.asarray(film_x, dtype=np.float32)
+    fy = np.asarray(film_y, dtype=np.float32)
+    if fx.shape not in ((), (n,)) or fy.shape not in ((), (n,)):
+        raise ValueError("film_x and film_y must be scalars or have shape (n,)")
+    out = np.empty((n, 8), dtype=np.float32)
+    out[:, 0:3] = o
+    out[:, 3] = fx
+    out[:, 4:7] = d
+    out[:, 7] = fy
+    return out
+
+
+def reference_camera_rays(camera28, W, H):
+    """The reference camera's rays (accumulator.cl:304-312: a pinhole at cameraPosition + film aiming at the aperture (0, 0, 5),
+    turned by yaw alone) in portable arithmetic, pixel-major (pixel y * W + x): (origins (n, 3), directions (n, 3), film_x (n,),
+    film_y (n,)), all float32 -- the starting point for a caller's own camera.  In the portable flavour these are the render
+    kernel's rays bit for bit; in the default and strict flavours only for yaw 0 and power-of-two W, H (they use a fused
+    multiply-add in the rotation and the device's divide)."""
+    cam = np.frombuffer(bytes(camera28), dtype=np.float32, count=7)
+    f32 = np.float32
+    x = np.tile(np.arange(W, dtype=np.float32), H)
+    y = np.repeat(np.arange(H, dtype=np.float32), W)
+    fx = (x / f32(W) - f32(0.5)).astype(np.float32)
+    fy = (y / f32(H) - f32(0.5)).astype(np.float32)
+    o = np.empty((W * H, 3), dtype=np.float32)
+    o[:, 0] = cam[0] + fx
+    o[:, 1] = cam[1] + fy
+    o[:, 2] = cam[2] + f32(0.0)
+    dx = f32(0.0) - fx
+    dy = f32(0.0) - fy
+    dz = np.full(W * H, f32(5.0) - f32(0.0), dtype=np.float32)
+    cy, sy = f32(np.cos(np.float64(cam[3]))), f32(np.sin(np.float64(cam[3])))
+    d = np.empty((W * H, 3), dtype=np.float32)
+    d[:, 0] = (cy * dx).astype(np.float32) + (sy * dz).astype(np.float32)
+    d[:, 1] = dy
+    d[:, 2] = (-sy * dx).astype(np.float32) + (cy * dz).astype(np.float32)
+    return o, d, fx, fy
+
+
 class RendererHIP:
     """One context per GPU.  `device` is the HIP ordinal."""
 
@@ -305,6 +356,56 @@ class RendererHIP:
             stream = torch.cuda.current_stream(dev)
         handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
         self._check(self._L.lt_hip_trace_hits_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
+                                                     ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                                                     ctypes.c_void_p(handle)))
+        return out
+
+    # -- shaded rays ------------------------------------------------------------------------------------
+    def shade_rays(self, rays, program="accumulator", frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR, portable_math=False,
+                   strict_math=False, coherent=False, stream=None):
+        """Shades caller-supplied rays (lt_hip_shade_rays): for each ray the colour `program`'s shade returns for it -- what the
+        render kernels would have stored had it been a pixel's camera ray at that film position -- for frames frame_first ..
+        frame_first + frame_count - 1, folded by the running mean, and the primitive the ray itself hit (-1: none).  Programs:
+        basic, basic_lighting, accumulator, custom_opencl (an LT_PROGRAM_* id or a kernel path).
+        rays: an (n, 8) float32 array of lt_hip_shade_ray records (make_shade_rays) or a SHADE_RAY_DTYPE array -- then the host
+        entry point runs and a SHADE_DTYPE array (rgb, prim) comes back; or a contiguous (n, 8) float32 torch tensor on this
+        context's GPU -- then the call is enqueued on `stream` (default: the current torch stream) and an (n, 4) float32 tensor
+        comes back (column 3 holds int32 bits: .view(torch.int32)).  coherent is accepted and changes nothing: there is no
+        packet path."""
+        if not isinstance(program, int):
+            program = C.program_from_path(str(program))
+        d = C.ShadeDesc()
+        d.struct_size = ctypes.sizeof(C.ShadeDesc)
+        d.program = program
+        d.kernel_mode = kernel_mode
+        d.frame_first, d.frame_count = frame_first, frame_count
+        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
+                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
+        if isinstance(rays, np.ndarray):
+            if rays.dtype == SHADE_RAY_DTYPE and rays.ndim == 1:
+                rays = rays.view(np.float32).reshape(-1, 8)
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an (n, 8) float32 array (make_shade_rays) or a SHADE_RAY_DTYPE array")
+            rays = np.ascontiguousarray(rays)
+            n = rays.shape[0]
+            out = np.zeros(n, dtype=SHADE_DTYPE)
+            self._check(self._L.lt_hip_shade_rays(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
+                                                  out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+            return out
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError("rays must be a numpy array or a torch tensor")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
+        dev = torch.device("cuda", self.device)
+        if rays.device != dev:
+            raise ValueError("rays must be on %s, the context's device" % dev)
+        n = rays.shape[0]
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        self._check(self._L.lt_hip_shade_rays_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
                                                      ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
                                                      ctypes.c_void_p(handle)))
         return out
