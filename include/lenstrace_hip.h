@@ -348,7 +348,7 @@ int lt_hip_trace_hits_device(lt_hip_context* ctx, const lt_hip_multihit_desc* de
  * film.w).  The camera payload starts at t = FLT_MAX and ignores nothing.
  * Programs: LT_PROGRAM_BASIC (with the lens chain), LT_PROGRAM_BASIC_LIGHTING (25 blended samples per frame), LT_PROGRAM_ACCUMULATOR
  * and LT_PROGRAM_CUSTOM_OPENCL.  The two global-illumination programs and user programs are refused with LT_ERR_INVALID_ARGUMENT:
- * the GI wavefront pipeline is indexed by pixel -- a follow-up.
+ * the global-illumination programs have an entry point of their own, lt_hip_shade_paths (below).
  * flags: LT_RENDER_FLAG_STRICT_MATH or LT_RENDER_FLAG_PORTABLE_MATH, with the render path's meaning.  LT_TRACE_FLAG_COHERENT is
  * accepted and has no effect: there is no packet path, every ray walks per lane (lens_trace_amd/csrc/lt_shade.hip). */
 typedef struct lt_hip_shade_ray { float origin[3]; float film_x; float direction[3]; float film_y; } lt_hip_shade_ray;   /* 32 B */
@@ -373,6 +373,49 @@ int lt_hip_shade_rays(lt_hip_context* ctx, const lt_hip_shade_desc* desc, const 
 /* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
 int lt_hip_shade_rays_device(lt_hip_context* ctx, const lt_hip_shade_desc* desc, const lt_hip_shade_ray* rays, uint64_t n,
                              lt_hip_shade* out, uint64_t out_bytes, void* hip_stream);
+
+/* The global-illumination programs over caller-supplied rays: an environment probe, a 360-degree panorama, a lens model in front
+ * of the path tracer.  Records are lt_hip_shade_rays' own: lt_hip_shade_ray in, lt_hip_shade out.
+ *   rgb   what lt_hip_render of the same program leaves in a pixel whose camera ray this is, at film position (film_x, film_y),
+ *         with frame_count frames from frame_first, accumulate = 1, accumulate_base = 0 and the same gi_max_depth:
+ *         LT_PROGRAM_GLOBAL_ILLUMINATION: frame f is shade(ray, film, sampleIndex = frame_first + f), clamped to [0, 1] when
+ *         kernel_mode == LT_KERNEL_MODE_LINEAR; LT_PROGRAM_GLOBAL_ILLUMINATION_25: frame f is the 25 samples sampleIndex =
+ *         (frame_first + f) * 32 + k blended in order, c = (1 - a) c + a c_k with a = (25 - k) / 25 (sample 0 replaces), the blend
+ *         clamped when linear.  The frames are folded in frame order by accumulator.frag's running mean from n = 0.
+ *   prim  the primitive the ray itself hit, or -1 on a miss.
+ * The ray's w components are the reference camera's (origin.w = 2, direction.w = +0); the camera payload starts at t = FLT_MAX
+ * and ignores nothing.  Each ray's camera walk runs once per call, whatever the frames and samples.
+ * flags: LT_RENDER_FLAG_STRICT_MATH or LT_RENDER_FLAG_PORTABLE_MATH, with the render path's meaning.  LT_TRACE_FLAG_COHERENT is
+ * accepted and has no effect: every ray walks per lane.
+ * Scratch memory: 272 bytes per path slot (ray x frame, x 25 for the 25-sample program) of the wavefront pipeline the programs'
+ * renders use, in sets of bounded size -- no result depends on how a call is cut into sets (LT_PATHS_SLOTS forces the bound, for
+ * tests and measurements; LT_FUSED_BYTES bounds it as it bounds a render's sets).
+ * Streams: the scratch and its control block are the context's, shared with the programs' renders.  Calls of this entry point are
+ * ordered among themselves on any streams (each waits for the one enqueued before it).  A call and a global-illumination
+ * lt_hip_render_device on two different streams are NOT ordered by the library, exactly as two such renders on two streams are
+ * not: order them (one stream, an event, lt_hip_synchronize) or use two contexts.  (lens_trace_amd/csrc/lt_paths.hip) */
+typedef struct lt_hip_paths_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_paths_desc) */
+  int32_t program;              /* LT_PROGRAM_GLOBAL_ILLUMINATION or LT_PROGRAM_GLOBAL_ILLUMINATION_25 */
+  int32_t kernel_mode;          /* LT_KERNEL_MODE_LINEAR / LT_KERNEL_MODE_TILE */
+  uint32_t flags;
+  uint32_t frame_first;
+  uint32_t frame_count;         /* >= 1 */
+  int32_t gi_max_depth;         /* 0 = the reference's 16; 1 .. 64 */
+  uint32_t reserved;            /* 0 */
+} lt_hip_paths_desc;            /* 32 B */
+
+/* Host memory, synchronous.  Errors in lt_hip_shade_rays' order.  LT_ERR_INVALID_ARGUMENT: null ctx / desc, a null pointer with
+ * n > 0, n >= 2^32, struct_size too small, STRICT with PORTABLE, any other flag, an unknown kernel_mode, frame_count == 0,
+ * gi_max_depth outside 0 .. 64, reserved != 0, one of the four other built-in programs or a user program (the text names
+ * lt_hip_shade_rays) (and, device entry point, pointers that are not 16-byte aligned); LT_ERR_UNKNOWN_PROGRAM for an id that is no
+ * program; LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when out_bytes < 16 n.  A failed call writes nothing to out; n == 0 launches
+ * nothing.  lt_hip_get_stats then reports rays = n, kernel_launches and kernel_ms. */
+int lt_hip_shade_paths(lt_hip_context* ctx, const lt_hip_paths_desc* desc, const lt_hip_shade_ray* rays, uint64_t n,
+                       lt_hip_shade* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_shade_paths_device(lt_hip_context* ctx, const lt_hip_paths_desc* desc, const lt_hip_shade_ray* rays, uint64_t n,
+                              lt_hip_shade* out, uint64_t out_bytes, void* hip_stream);
 
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);

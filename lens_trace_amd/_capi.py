@@ -31,7 +31,7 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_set_scene", "lt_hip_output_floats", "lt_hip_render", "lt_hip_render_scene", "lt_hip_render_device", "lt_hip_untile",
            "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure",
            "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device",
-           "lt_hip_shade_rays", "lt_hip_shade_rays_device"]
+           "lt_hip_shade_rays", "lt_hip_shade_rays_device", "lt_hip_shade_paths", "lt_hip_shade_paths_device"]
 
 
 class RenderDesc(ctypes.Structure):
@@ -85,6 +85,12 @@ class ShadeResult(ctypes.Structure):   # lt_hip_shade
 class ShadeDesc(ctypes.Structure):   # lt_hip_shade_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("program", ctypes.c_int32), ("kernel_mode", ctypes.c_int32), ("flags", ctypes.c_uint32),
                 ("frame_first", ctypes.c_uint32), ("frame_count", ctypes.c_uint32)]
+
+
+class PathsDesc(ctypes.Structure):   # lt_hip_paths_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("program", ctypes.c_int32), ("kernel_mode", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("frame_first", ctypes.c_uint32), ("frame_count", ctypes.c_uint32), ("gi_max_depth", ctypes.c_int32),
+                ("reserved", ctypes.c_uint32)]
 
 
 def _np_dtypes():
@@ -160,6 +166,9 @@ def load():
     if hasattr(L, "lt_hip_shade_rays"):
         L.lt_hip_shade_rays.argtypes = [vp, ctypes.POINTER(ShadeDesc), vp, u64, vp, u64]
         L.lt_hip_shade_rays_device.argtypes = [vp, ctypes.POINTER(ShadeDesc), vp, u64, vp, u64, vp]
+    if hasattr(L, "lt_hip_shade_paths"):
+        L.lt_hip_shade_paths.argtypes = [vp, ctypes.POINTER(PathsDesc), vp, u64, vp, u64]
+        L.lt_hip_shade_paths_device.argtypes = [vp, ctypes.POINTER(PathsDesc), vp, u64, vp, u64, vp]
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

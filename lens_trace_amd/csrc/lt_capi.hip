@@ -6,6 +6,7 @@
 #include "lt_prep.hpp"
 #include "lt_query.hpp"
 #include "lt_shade.hpp"
+#include "lt_paths.hpp"
 
 #include "../../include/lenstrace_hip.h"
 
@@ -301,6 +302,11 @@ struct lt_hip_context {
   void* d_gi[17] = {nullptr};
   uint64_t gi_pixels = 0;
   uint32_t* d_giCtl = nullptr;
+  // the GI programs over caller-supplied rays (lt_paths.hip): the camera hits of a range of rays, and the event behind the last
+  // call's last launch (the next call waits for it before it touches the control block or the scratch above)
+  uint4* d_paths_hits = nullptr;
+  uint64_t paths_hits_rays = 0;
+  hipEvent_t paths_ev = nullptr;
   // user programs (hipRTC), cached by path like the reference's programMap
   struct UserProgram { hipModule_t module; hipFunction_t lds, ldsStrict, ldsPortable; };   // one kernel per math flavour
   std::vector<UserProgram> user_programs;
@@ -415,6 +421,8 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   for (auto& up : ctx->user_programs) (void)hipModuleUnload(up.module);
   for (void*& b : ctx->d_gi) if (b) (void)hipFree(b);
   if (ctx->d_giCtl) (void)hipFree(ctx->d_giCtl);
+  if (ctx->d_paths_hits) (void)hipFree(ctx->d_paths_hits);
+  if (ctx->paths_ev) (void)hipEventDestroy(ctx->paths_ev);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   for (hipEvent_t e : ctx->mean_events) (void)hipEventDestroy(e);
@@ -2267,6 +2275,231 @@ extern "C" int lt_hip_shade_rays_device(lt_hip_context* ctx, const lt_hip_shade_
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   return enqueue_shade(ctx, call, desc, rays, n, out, (hipStream_t)hip_stream);
+}
+
+// lt_hip_shade_paths / lt_hip_shade_paths_device: the global-illumination programs over caller-supplied rays (lt_paths.hip).
+// check_shade's rules and order: every argument error is found before anything is enqueued.
+struct PathsCall {
+  bool gi25;
+  int devlibm;
+  uint64_t outBytes;
+};
+static_assert(sizeof(lt_hip_paths_desc) == 32, "path-shading descriptor (include/lenstrace_hip.h)");
+
+static int check_paths(lt_hip_context* ctx, const lt_hip_paths_desc* d, const lt_hip_shade_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
+                       bool device, PathsCall& pc) {
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_paths: desc is NULL");
+  if (d->struct_size < sizeof(lt_hip_paths_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_paths_desc (struct_size)");
+  const bool userProgram = d->program >= LT_PROGRAM_USER_BASE;
+  if (userProgram ? (size_t)(d->program - LT_PROGRAM_USER_BASE) >= ctx->user_programs.size()
+                  : (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL))
+    return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
+  if (userProgram) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_paths does not take user programs (nor does lt_hip_shade_rays)");
+  if (d->program != LT_PROGRAM_GLOBAL_ILLUMINATION && d->program != LT_PROGRAM_GLOBAL_ILLUMINATION_25)
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_paths takes the global-illumination programs only: this program's entry point is lt_hip_shade_rays");
+  if (d->kernel_mode != LT_KERNEL_MODE_LINEAR && d->kernel_mode != LT_KERNEL_MODE_TILE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown kernel mode");
+  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "shaded paths take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only");
+  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (d->frame_count == 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_paths_desc::frame_count must be at least 1");
+  if (d->gi_max_depth < 0 || d->gi_max_depth > 64) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "gi_max_depth out of range");
+  if (d->reserved != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_paths_desc::reserved must be 0");
+  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 rays per call");
+  if (n > 0 && (!rays || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "rays or out is NULL");
+  if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_shade_paths before lt_hip_set_scene");
+  pc.outBytes = n * sizeof(lt_hip_shade);
+  if (out_bytes < pc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
+  pc.gi25 = d->program == LT_PROGRAM_GLOBAL_ILLUMINATION_25;
+  pc.devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
+  return LT_OK;
+}
+
+// Path slots of one set when neither LT_PATHS_SLOTS nor LT_FUSED_BYTES says otherwise (DESIGN.md 5.11 has the timings of the
+// candidates): 272 bytes of scratch each.
+constexpr uint64_t kPathsSlots = 64ull << 20;
+
+// One set of a call (lt_paths::Params) through the pipeline: lt_paths_primary_kernel, the bounce stages -- launch_gi_sample's
+// launches in its three forms, over path slots instead of pixels -- and lt_paths_resolve_kernel.
+template <class CFG>
+static int launch_paths_set(lt_hip_context* ctx, const RenderKnobs& k, const SceneDev& sc, lt_paths::Params pp, hipStream_t s, uint32_t& launches) {
+  GiParams gp{};
+  for (int q = 0; q < 2; q++) {
+    gp.q[q].o = (float4*)ctx->d_gi[4 * q + 0]; gp.q[q].d = (float4*)ctx->d_gi[4 * q + 1];
+    gp.q[q].n = (float4*)ctx->d_gi[4 * q + 2]; gp.q[q].m = (uint4*)ctx->d_gi[4 * q + 3];
+  }
+  gp.direct = (float4*)ctx->d_gi[8]; gp.indirect = (float4*)ctx->d_gi[9]; gp.blend = (float4*)ctx->d_gi[10];
+  auto ctl = [&](uint32_t run) { return ctx->d_giCtl + (8 + run * (kMaxStack + 2)) * kQueueStride; };
+  gp.counts = ctl(0); gp.work = ctl(1); gp.hitCount = ctl(2);
+  uint32_t* const traceWork = ctl(3);
+  uint32_t* const shadowWork = ctl(11);
+  gp.sample = pp.sample;
+  gp.pixels = pp.nRays * pp.frames * pp.perFrame;   // (the slots of the set; every path's m.w is its sample's offset from gp.sample)
+  FrameParams fp{};
+  fp.giMaxDepth = pp.giMaxDepth;
+  fp.clampOutput = pp.clampOutput;
+  fp.fusedFrames = 1;
+  LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_giCtl, 0, kGiCtlWords * sizeof(uint32_t), s));
+  const uint32_t resident = (uint32_t)ctx->cu_count * 4u * LT_GI_STAGE_WAVES;
+  // the LDS of the stage launches, as render_on_stream computes it for its non-counting launches
+  const uint32_t rowBytes = (uint32_t)(kBlock * sizeof(int));
+  const uint32_t ldsRefBytes = (uint32_t)std::max(kPacketRows, std::min(ctx->bvh_height, kLdsStack)) * rowBytes;
+  uint32_t lds = (uint32_t)std::max(kPacketRows, kOwnRows) * rowBytes;
+  if (k.debug_lds_rows) lds = std::max(lds, k.debug_lds_rows * rowBytes);
+  const bool ldsScene = gi_lds_scene(ctx, k);
+  const bool pretrace = !ldsScene && ctx->d_rank8 != nullptr && k.gi_trace;
+  gp.directQueue = pretrace ? 1u : 0u;
+  pp.qo = gp.q[0].o; pp.qd = gp.q[0].d; pp.qn = gp.q[0].n; pp.qm = gp.q[0].m;
+  pp.direct = gp.direct; pp.indirect = gp.indirect;
+  pp.count0 = gp.counts;
+  pp.directQueue = gp.directQueue;
+  LT_HIP_CHECK(ctx, lt_paths::launch_primary(sc, pp, CFG::kDevLibm, s));
+  launches++;
+  gp.ldsRows = ldsRefBytes / rowBytes;
+  gp.hitList = (uint32_t*)ctx->d_gi[12];
+  gp.so = (float4*)ctx->d_gi[13]; gp.sd = (float4*)ctx->d_gi[14]; gp.sm = (uint4*)ctx->d_gi[15]; gp.sn = (float4*)ctx->d_gi[16];
+  const uint32_t traceLds = (uint32_t)((kTraceRows + kTraceStage) * kBlock * sizeof(int));
+  const dim3 streamGrid((uint32_t)ctx->cu_count * 8u), streamBlock(256);
+  for (int d = 0; d < fp.giMaxDepth; d++) {
+    gp.hits = nullptr;
+    if (pretrace) {
+      TraceParams tp{};
+      const GiQueue& q = gp.q[d & 1];
+      tp.o = q.o; tp.d = q.d; tp.m = q.m;
+      tp.hit = (uint4*)ctx->d_gi[11];
+      tp.count = gp.counts + (size_t)d * kQueueStride;
+      tp.next = traceWork + (size_t)d * 8 * kQueueStride;
+      tp.refill = k.trace_refill;
+      tp.dead = d == 0 ? 1u : 0u;
+      gp.hits = tp.hit;
+      hipLaunchKernelGGL((lt_trace_kernel<kGI, false>), dim3(resident), dim3(kBlock), traceLds, s, sc, tp);
+      hipLaunchKernelGGL((lt_gi_classify_kernel<CFG>), streamGrid, streamBlock, 0, s, sc, fp, gp, (uint32_t)d);
+      hipLaunchKernelGGL((lt_gi_shadow_kernel<CFG>), streamGrid, streamBlock, 0, s, sc, fp, gp, (uint32_t)d);
+      tp.o = gp.so; tp.d = gp.sd; tp.m = gp.sm;
+      tp.occluded = (uint32_t*)ctx->d_gi[11];
+      gp.occluded = tp.occluded;
+      tp.count = gp.hitCount + (size_t)d * kQueueStride;
+      tp.next = shadowWork + (size_t)d * 8 * kQueueStride;
+      tp.dead = 0u;
+      hipLaunchKernelGGL((lt_trace_kernel<kGI, true>), dim3(resident), dim3(kBlock), traceLds, s, sc, tp);
+      hipLaunchKernelGGL((lt_gi_finish_kernel<CFG>), streamGrid, streamBlock, 0, s, sc, fp, gp, (uint32_t)d);
+      LT_HIP_CHECK(ctx, hipGetLastError());
+      launches += 5;
+      continue;
+    }
+    if (ldsScene) {
+      using CFGL = Config<false, false, CFG::kDevLibm, true>;
+      hipLaunchKernelGGL((lt_gi_bounce_kernel<CFGL>), dim3((resident + kLdsSceneWaves - 1) / kLdsSceneWaves), dim3(kBlock * kLdsSceneWaves),
+                         (uint32_t)scene_lds_bytes(ctx) + kLdsSceneWaves * ldsRefBytes, s, sc, fp, gp, (uint32_t)d);
+    } else {
+      hipLaunchKernelGGL((lt_gi_bounce_kernel<CFG>), dim3(resident), dim3(kBlock), lds, s, sc, fp, gp, (uint32_t)d);
+    }
+    LT_HIP_CHECK(ctx, hipGetLastError());
+    launches++;
+  }
+  LT_HIP_CHECK(ctx, lt_paths::launch_resolve(pp, CFG::kDevLibm, s));
+  launches++;
+  return LT_OK;
+}
+
+// Enqueues the call on `s` between the context's timing events; lt_hip_get_stats reports it (finish_pending).  The call is cut
+// into SETS of at most `cap` path slots: ranges of rays with all their frames, or -- one ray's frames alone exceed the cap --
+// ranges of frames as well; a frame's 25 samples stay together.  A range of rays walks its camera rays once, ahead of its sets;
+// between the sets of a range the running mean waits in the caller's record (lt_paths::Params::folded).
+static int enqueue_paths(lt_hip_context* ctx, const PathsCall& call, const lt_hip_paths_desc* d, const void* rays, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  const uint32_t perFrame = call.gi25 ? 25u : 1u, frames = d->frame_count;
+  uint64_t cap = std::min<uint64_t>(kPathsSlots, k.fused_bytes / (17 * 16));
+  if (const char* e = getenv("LT_PATHS_SLOTS")) cap = strtoull(e, nullptr, 10);   // (tests, A/B measurements; no result depends on it)
+  cap = std::min<uint64_t>(std::max<uint64_t>(cap, perFrame), 0xffffffffull);
+  const uint64_t perRay = (uint64_t)frames * perFrame;
+  const uint32_t framesPerSet = perRay <= cap ? frames : (uint32_t)(cap / perFrame);
+  const uint64_t raysAtMost = std::min<uint64_t>(n, std::max<uint64_t>(1, cap / ((uint64_t)framesPerSet * perFrame)));
+  const uint64_t ranges = (n + raysAtMost - 1) / raysAtMost;
+  const uint32_t raysPerSet = (uint32_t)((n + ranges - 1) / ranges);   // (ranges of equal size: a short last one costs its launches all the same)
+  if (const int rc = ensure_gi_buffers(ctx, (uint64_t)raysPerSet * framesPerSet * perFrame)) return rc;
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_paths_hits, ctx->paths_hits_rays, (uint64_t)raysPerSet, (uint64_t)raysPerSet * sizeof(uint4)));
+  if (!ctx->paths_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->paths_ev, hipEventDisableTiming));
+  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->paths_ev, 0));   // (the control block and the scratch are the previous call's until it is done)
+  SceneDev sc = scene_dev(ctx, k, call.devlibm);
+  sc.shadowPackets = 0u;   // (every shadow ray of these launches walks per lane)
+  lt_paths::Params pp{};
+  pp.rays = (const float4*)rays;
+  pp.out = (uint4*)out;
+  pp.hits = ctx->d_paths_hits;
+  pp.perFrame = perFrame;
+  pp.giMaxDepth = d->gi_max_depth ? d->gi_max_depth : 16;
+  pp.clampOutput = d->kernel_mode == LT_KERNEL_MODE_LINEAR;
+  uint32_t launches = 0;
+  ctx->mean_pairs = 0;
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  for (uint64_t r0 = 0; r0 < n; r0 += raysPerSet) {
+    pp.ray0 = (uint32_t)r0;
+    pp.nRays = (uint32_t)std::min<uint64_t>(raysPerSet, n - r0);
+    if (ctx->d_rank8 != nullptr) {   // lt_trace_kernel over the staged rays; its counters: the control block's first eight, its length: a spare one
+      uint32_t* const count = ctx->d_giCtl + (8 + kMaxStack + 1) * kQueueStride;
+      LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_giCtl, 0, kGiCtlWords * sizeof(uint32_t), s));
+      LT_HIP_CHECK(ctx, lt_paths::launch_stage(pp, (float4*)ctx->d_gi[0], (float4*)ctx->d_gi[1], (uint4*)ctx->d_gi[3], count, s));
+      TraceParams tp{};
+      tp.o = (const float4*)ctx->d_gi[0]; tp.d = (const float4*)ctx->d_gi[1]; tp.m = (const uint4*)ctx->d_gi[3];
+      tp.hit = ctx->d_paths_hits;
+      tp.count = count;
+      tp.next = ctx->d_giCtl;
+      tp.refill = k.trace_refill;
+      hipLaunchKernelGGL((lt_trace_kernel<kGI, false>), dim3((uint32_t)ctx->cu_count * 4u * LT_GI_STAGE_WAVES), dim3(kBlock),
+                         (uint32_t)((kTraceRows + kTraceStage) * kBlock * sizeof(int)), s, sc, tp);
+      LT_HIP_CHECK(ctx, hipGetLastError());
+      launches += 2;
+    } else {
+      LT_HIP_CHECK(ctx, lt_paths::launch_camera(sc, pp, s));
+      launches++;
+    }
+    for (uint32_t f0 = 0; f0 < frames; f0 += framesPerSet) {
+      pp.frames = std::min(framesPerSet, frames - f0);
+      pp.folded = f0;
+      pp.sample = call.gi25 ? (d->frame_first + f0) * 32u : d->frame_first + f0;
+      const int rc = with_math(call.devlibm, [&](auto m) { return launch_paths_set<Config<false, false, decltype(m)::value>>(ctx, k, sc, pp, s, launches); });
+      if (rc) return rc;
+    }
+  }
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->paths_ev, s));
+  ctx->last = lt_hip_stats{};
+  ctx->last.kernel_launches = launches;
+  ctx->last.rays = n;
+  ctx->pending = true;
+  ctx->pending_stats = false;
+  ctx->pending_query = true;
+  return LT_OK;
+}
+
+extern "C" int lt_hip_shade_paths(lt_hip_context* ctx, const lt_hip_paths_desc* desc, const lt_hip_shade_ray* rays, uint64_t n, lt_hip_shade* out,
+                                  uint64_t out_bytes) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  PathsCall call{};
+  if (const int rc = check_paths(ctx, desc, rays, n, out, out_bytes, false, call)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint64_t rayBytes = n * sizeof(lt_hip_shade_ray);
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, call.outBytes, call.outBytes));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = enqueue_paths(ctx, call, desc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
+  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (const int rc = finish_pending(ctx)) return rc;
+  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, call.outBytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+extern "C" int lt_hip_shade_paths_device(lt_hip_context* ctx, const lt_hip_paths_desc* desc, const lt_hip_shade_ray* rays, uint64_t n, lt_hip_shade* out,
+                                         uint64_t out_bytes, void* hip_stream) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  PathsCall call{};
+  if (const int rc = check_paths(ctx, desc, rays, n, out, out_bytes, true, call)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return enqueue_paths(ctx, call, desc, rays, n, out, (hipStream_t)hip_stream);
 }
 
 extern "C" int lt_hip_untile(lt_hip_context* ctx, const float* gathered, uint64_t floats_per_rank, uint32_t n_ranks, uint32_t width,

@@ -410,6 +410,56 @@ class RendererHIP:
                                                      ctypes.c_void_p(handle)))
         return out
 
+    # -- shaded paths -----------------------------------------------------------------------------------
+    def shade_paths(self, rays, program="global_illumination", gi_max_depth=0, frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR,
+                    portable_math=False, strict_math=False, coherent=False, stream=None):
+        """Shades caller-supplied rays with a global-illumination program (lt_hip_shade_paths): for each ray what a render of
+        `program` (global_illumination, global_illumination25: an LT_PROGRAM_* id or a kernel path) leaves in a pixel whose
+        camera ray it is, for frames frame_first .. frame_first + frame_count - 1 folded by the running mean, with paths of at most
+        gi_max_depth bounces (0: the reference's 16), and the primitive the ray itself hit (-1: none).
+        rays and the result: shade_rays' contract -- an (n, 8) float32 array (make_shade_rays) or a SHADE_RAY_DTYPE array in, a
+        SHADE_DTYPE array out; or a contiguous (n, 8) float32 torch tensor on this context's GPU in, enqueued on `stream` (default:
+        the current torch stream), an (n, 4) float32 tensor out (column 3 holds int32 bits).  coherent is accepted and changes
+        nothing."""
+        if not isinstance(program, int):
+            program = C.program_from_path(str(program))
+        d = C.PathsDesc()
+        d.struct_size = ctypes.sizeof(C.PathsDesc)
+        d.program = program
+        d.kernel_mode = kernel_mode
+        d.frame_first, d.frame_count = frame_first, frame_count
+        d.gi_max_depth = gi_max_depth
+        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
+                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
+        if isinstance(rays, np.ndarray):
+            if rays.dtype == SHADE_RAY_DTYPE and rays.ndim == 1:
+                rays = rays.view(np.float32).reshape(-1, 8)
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an (n, 8) float32 array (make_shade_rays) or a SHADE_RAY_DTYPE array")
+            rays = np.ascontiguousarray(rays)
+            n = rays.shape[0]
+            out = np.zeros(n, dtype=SHADE_DTYPE)
+            self._check(self._L.lt_hip_shade_paths(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
+                                                   out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+            return out
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError("rays must be a numpy array or a torch tensor")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
+        dev = torch.device("cuda", self.device)
+        if rays.device != dev:
+            raise ValueError("rays must be on %s, the context's device" % dev)
+        n = rays.shape[0]
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        self._check(self._L.lt_hip_shade_paths_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
+                                                      ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                                                      ctypes.c_void_p(handle)))
+        return out
+
     def stats(self):
         s = C.Stats()
         self._check(self._L.lt_hip_get_stats(self._ctx, ctypes.byref(s)))
