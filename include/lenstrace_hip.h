@@ -417,6 +417,60 @@ int lt_hip_shade_paths(lt_hip_context* ctx, const lt_hip_paths_desc* desc, const
 int lt_hip_shade_paths_device(lt_hip_context* ctx, const lt_hip_paths_desc* desc, const lt_hip_shade_ray* rays, uint64_t n,
                               lt_hip_shade* out, uint64_t out_bytes, void* hip_stream);
 
+/* Surface queries: what every `shade` of the reference computes first at a hit (accumulator.cl:243-274) -- the point its next ray
+ * starts from, the interpolated vertex normal, the primitive's material, whether the primitive is a light -- for a caller that
+ * writes its own integrator, sensor model, lightmap baker or denoiser front end on top of the queries.  Per-pixel feature images
+ * (position, normal, ids, depth) are a surface query over the camera's rays.
+ *   t, prim, u, v   the lt_hip_hit of the same ray, bit for bit: what lt_hip_trace_rays / LT_TRACE_CLOSEST writes for the same
+ *                   ray, desc and scene.
+ *   position        A*b.x + B*b.y + C*b.z of the primitive's positionA/B/C with b = ((float)(1.0 - u - v), u, v), b.x evaluated
+ *                   in double -- NOT origin + t * direction.  As shipped (no flavour flag) the expression is contracted as the
+ *                   reference's build contracts it, fma(C, b.z, fma(A, b.x, B * b.y)); LT_RENDER_FLAG_STRICT_MATH and
+ *                   LT_RENDER_FLAG_PORTABLE_MATH round the three products and the two sums separately, (A*b.x + B*b.y) + C*b.z.
+ *   normal          the same interpolation of normalA/B/C, not normalised (the reference never normalises it).
+ *   material        Primitive::materialIndex.
+ *   flags           LT_SURFACE_LIGHT when prim is one of LightContainer.primitives[0 .. count - 1] (accumulator.cl:233-237).
+ * A miss has position = normal = +0, material = -1, flags = 0. */
+typedef struct lt_hip_surface {
+  float t; int32_t prim; float u, v;
+  float position[3]; int32_t material;
+  float normal[3]; uint32_t flags;
+} lt_hip_surface;                       /* 48 B */
+#define LT_SURFACE_LIGHT 1u
+
+/* lt_hip_trace_surface: from rays to surface records in one call.  desc is lt_hip_trace_rays' own: kind must be LT_TRACE_CLOSEST
+ * (LT_TRACE_ANY: LT_ERR_INVALID_ARGUMENT), program selects the triangle epsilon, flags are STRICT or PORTABLE and
+ * LT_TRACE_FLAG_COHERENT (honoured: the packet walk).  Host memory, synchronous.  Errors, their order and the alignment rule of
+ * the device entry point are lt_hip_trace_rays'; LT_ERR_BUFFER_TOO_SMALL when out_bytes < 48 n.  A failed call writes nothing to
+ * out; n == 0 launches nothing.  lt_hip_get_stats then reports rays = n, kernel_launches and kernel_ms.
+ * (lens_trace_amd/csrc/lt_query.hip) */
+int lt_hip_trace_surface(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                         lt_hip_surface* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_trace_surface_device(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                                lt_hip_surface* out, uint64_t out_bytes, void* hip_stream);
+
+/* lt_hip_surface_at: the same record from hit records the caller already has -- above all the K records per ray of
+ * lt_hip_trace_hits, so that the surfaces behind the first one get positions and normals.  t, u and v are copied bit for bit.  A
+ * record whose prim is not one of the scene's primitives (negative, or >= their number) gives the miss form: t as given,
+ * prim = -1, u = v = +0, position = normal = +0, material = -1, flags = 0.  lt_hip_trace_surface equals lt_hip_trace_rays followed
+ * by lt_hip_surface_at with the same flavour, byte for byte.
+ * flags: LT_RENDER_FLAG_STRICT_MATH or LT_RENDER_FLAG_PORTABLE_MATH only; the flavour decides fused or separate multiply-adds and
+ * nothing else.  Host memory, synchronous.  LT_ERR_INVALID_ARGUMENT: null ctx / desc, struct_size too small, STRICT with PORTABLE,
+ * any other flag, n >= 2^32, a null pointer with n > 0 (and, device entry point, pointers that are not 16-byte aligned);
+ * LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when out_bytes < 48 n.  A failed call writes nothing to out; n == 0 launches nothing.
+ * lt_hip_get_stats then reports kernel_launches = 1 and kernel_ms. */
+typedef struct lt_hip_surface_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_surface_desc) */
+  uint32_t flags;
+} lt_hip_surface_desc;          /* 8 B */
+
+int lt_hip_surface_at(lt_hip_context* ctx, const lt_hip_surface_desc* desc, const lt_hip_hit* hits, uint64_t n,
+                      lt_hip_surface* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_surface_at_device(lt_hip_context* ctx, const lt_hip_surface_desc* desc, const lt_hip_hit* hits, uint64_t n,
+                             lt_hip_surface* out, uint64_t out_bytes, void* hip_stream);
+
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
 

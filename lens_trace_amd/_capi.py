@@ -24,6 +24,7 @@ TRACE_CLOSEST, TRACE_ANY = 0, 1      # lt_hip_trace_desc::kind
 TRACE_FLAG_COHERENT = 0x100          # runs of 64 consecutive rays are coherent: walked as packets
 TRACE_FIRST_K, TRACE_COUNT = 0, 1    # lt_hip_multihit_desc::kind (lt_hip_trace_hits only)
 TRACE_MAX_HITS = 8                   # LT_TRACE_MAX_HITS
+SURFACE_LIGHT = 1                    # lt_hip_surface::flags: the primitive is in the light list
 
 # every symbol include/lenstrace_hip.h declares
 EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last_error", "lt_hip_program_from_path",
@@ -31,7 +32,8 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_set_scene", "lt_hip_output_floats", "lt_hip_render", "lt_hip_render_scene", "lt_hip_render_device", "lt_hip_untile",
            "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure",
            "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device",
-           "lt_hip_shade_rays", "lt_hip_shade_rays_device", "lt_hip_shade_paths", "lt_hip_shade_paths_device"]
+           "lt_hip_shade_rays", "lt_hip_shade_rays_device", "lt_hip_shade_paths", "lt_hip_shade_paths_device",
+           "lt_hip_trace_surface", "lt_hip_trace_surface_device", "lt_hip_surface_at", "lt_hip_surface_at_device"]
 
 
 class RenderDesc(ctypes.Structure):
@@ -93,6 +95,15 @@ class PathsDesc(ctypes.Structure):   # lt_hip_paths_desc
                 ("reserved", ctypes.c_uint32)]
 
 
+class Surface(ctypes.Structure):   # lt_hip_surface
+    _fields_ = [("t", ctypes.c_float), ("prim", ctypes.c_int32), ("u", ctypes.c_float), ("v", ctypes.c_float),
+                ("position", ctypes.c_float * 3), ("material", ctypes.c_int32), ("normal", ctypes.c_float * 3), ("flags", ctypes.c_uint32)]
+
+
+class SurfaceDesc(ctypes.Structure):   # lt_hip_surface_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 def _np_dtypes():
     import numpy as np
     ray = np.dtype([("origin", "<f4", (3,)), ("tmax", "<f4"), ("direction", "<f4", (3,)), ("ignore", "<i4")])
@@ -111,6 +122,15 @@ def _np_shade_dtypes():
 
 
 SHADE_RAY_DTYPE, SHADE_DTYPE = _np_shade_dtypes()   # numpy views of lt_hip_shade_ray (32 bytes) and lt_hip_shade (16 bytes)
+
+
+def _np_surface_dtype():
+    import numpy as np
+    return np.dtype([("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4"), ("position", "<f4", (3,)), ("material", "<i4"),
+                     ("normal", "<f4", (3,)), ("flags", "<u4")])
+
+
+SURFACE_DTYPE = _np_surface_dtype()   # numpy view of lt_hip_surface (48 bytes)
 
 
 class LensTraceError(RuntimeError):
@@ -169,6 +189,11 @@ def load():
     if hasattr(L, "lt_hip_shade_paths"):
         L.lt_hip_shade_paths.argtypes = [vp, ctypes.POINTER(PathsDesc), vp, u64, vp, u64]
         L.lt_hip_shade_paths_device.argtypes = [vp, ctypes.POINTER(PathsDesc), vp, u64, vp, u64, vp]
+    if hasattr(L, "lt_hip_trace_surface"):
+        L.lt_hip_trace_surface.argtypes = [vp, ctypes.POINTER(TraceDesc), vp, u64, vp, u64]
+        L.lt_hip_trace_surface_device.argtypes = [vp, ctypes.POINTER(TraceDesc), vp, u64, vp, u64, vp]
+        L.lt_hip_surface_at.argtypes = [vp, ctypes.POINTER(SurfaceDesc), vp, u64, vp, u64]
+        L.lt_hip_surface_at_device.argtypes = [vp, ctypes.POINTER(SurfaceDesc), vp, u64, vp, u64, vp]
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

@@ -292,6 +292,8 @@ struct lt_hip_context {
   uint32_t* d_query_ctl = nullptr;
   void* d_query_rays = nullptr;
   uint64_t query_rays_bytes = 0;
+  uint4* d_surface_hits = nullptr;   // lt_hip_trace_surface*: the closest hits between its two launches
+  uint64_t surface_hits_records = 0;
   void* d_query_out = nullptr;
   uint64_t query_out_bytes = 0;
   hipEvent_t query_ev = nullptr;
@@ -413,6 +415,7 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_shadowCtl) (void)hipFree(ctx->d_shadowCtl);
   if (ctx->d_query_ctl) (void)hipFree(ctx->d_query_ctl);
   if (ctx->d_query_rays) (void)hipFree(ctx->d_query_rays);
+  if (ctx->d_surface_hits) (void)hipFree(ctx->d_surface_hits);
   if (ctx->d_query_out) (void)hipFree(ctx->d_query_out);
   if (ctx->query_ev) (void)hipEventDestroy(ctx->query_ev);
   if (ctx->d_shade_ctl) (void)hipFree(ctx->d_shade_ctl);
@@ -2004,10 +2007,11 @@ struct TraceCall {
 static_assert(sizeof(lt_hip_ray) == 32 && sizeof(lt_hip_hit) == 16 && sizeof(lt_hip_trace_desc) == 16, "ray query records (include/lenstrace_hip.h)");
 
 static int check_trace(lt_hip_context* ctx, const lt_hip_trace_desc* d, const lt_hip_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
-                       bool device, TraceCall& tc) {
+                       bool device, TraceCall& tc, bool surface = false) {
   if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_trace_rays: desc is NULL");
   if (d->struct_size < sizeof(lt_hip_trace_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_trace_desc (struct_size)");
   if (d->kind != LT_TRACE_CLOSEST && d->kind != LT_TRACE_ANY) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown trace kind");
+  if (surface && d->kind != LT_TRACE_CLOSEST) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "surface queries take LT_TRACE_CLOSEST");
   if (d->program >= LT_PROGRAM_USER_BASE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take a built-in program (it selects the triangle epsilon)");
   if (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL) return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
   if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
@@ -2019,7 +2023,7 @@ static int check_trace(lt_hip_context* ctx, const lt_hip_trace_desc* d, const lt
   if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
   if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "ray query before lt_hip_set_scene");
   tc.anyHit = d->kind == LT_TRACE_ANY;
-  tc.outBytes = n * (tc.anyHit ? sizeof(uint32_t) : sizeof(lt_hip_hit));
+  tc.outBytes = n * (surface ? sizeof(lt_hip_surface) : tc.anyHit ? sizeof(uint32_t) : sizeof(lt_hip_hit));
   if (out_bytes < tc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
   tc.eps = (d->program == LT_PROGRAM_BASIC || d->program == LT_PROGRAM_CUSTOM_OPENCL) ? lt_query::kEpsFloat7
            : d->program == LT_PROGRAM_BASIC_LIGHTING ? lt_query::kEpsDouble7 : lt_query::kEpsDouble4;
@@ -2177,6 +2181,131 @@ extern "C" int lt_hip_trace_hits_device(lt_hip_context* ctx, const lt_hip_multih
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   return enqueue_hits(ctx, hc, rays, n, out, (hipStream_t)hip_stream);
+}
+
+// lt_hip_trace_surface / lt_hip_trace_surface_device: closest hits with the surface record behind them -- lt_hip_trace_rays'
+// launch into a scratch buffer of the context, then lt_hip_surface_at's over it (lt_query.hip).  By definition the call equals
+// those two, and the one-kernel form -- the query kernels writing the record themselves -- was slower than the pair on incoherent
+// rays.  check_trace's rules with 48-byte records and no LT_TRACE_ANY; the same staging and read-back.
+static_assert(sizeof(lt_hip_surface) == 48 && sizeof(lt_hip_surface_desc) == 8, "surface records (include/lenstrace_hip.h)");
+
+static int enqueue_surface(lt_hip_context* ctx, const TraceCall& tc, const void* rays, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  if (!ctx->d_query_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_query_ctl, 8 * kQueueStride * sizeof(uint32_t)));
+  // (growing frees the old buffer, which waits for the calls that use it)
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_surface_hits, ctx->surface_hits_records, n, n * sizeof(lt_hip_hit)));
+  if (!ctx->query_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->query_ev, hipEventDisableTiming));
+  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->query_ev, 0));   // (the counters and the hit records are the previous query's until it is done)
+  lt_query::Params qp{};
+  qp.rays = (const float4*)rays;
+  qp.hits = ctx->d_surface_hits;
+  qp.n = (uint32_t)n;
+  qp.next = ctx->d_query_ctl;
+  qp.refill = k.trace_refill;
+  const SceneDev sc = scene_dev(ctx, k, tc.devlibm);
+  ctx->mean_pairs = 0;
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  LT_HIP_CHECK(ctx, lt_query::launch(sc, qp, tc.eps, false, tc.coherent, (uint32_t)ctx->cu_count, s));
+  LT_HIP_CHECK(ctx, lt_query::launch_surface_at(sc, ctx->d_surface_hits, (uint4*)out, (uint32_t)n, tc.devlibm == 2, (uint32_t)ctx->cu_count, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->query_ev, s));
+  ctx->last = lt_hip_stats{};
+  ctx->last.kernel_launches = 2;
+  ctx->last.rays = n;
+  ctx->pending = true;
+  ctx->pending_stats = false;
+  ctx->pending_query = true;
+  return LT_OK;
+}
+
+extern "C" int lt_hip_trace_surface(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, lt_hip_surface* out,
+                                    uint64_t out_bytes) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  TraceCall tc{};
+  if (const int rc = check_trace(ctx, desc, rays, n, out, out_bytes, false, tc, true)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint64_t rayBytes = n * sizeof(lt_hip_ray);
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, tc.outBytes, tc.outBytes));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = enqueue_surface(ctx, tc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
+  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (const int rc = finish_pending(ctx)) return rc;
+  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, tc.outBytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+extern "C" int lt_hip_trace_surface_device(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, lt_hip_surface* out,
+                                           uint64_t out_bytes, void* hip_stream) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  TraceCall tc{};
+  if (const int rc = check_trace(ctx, desc, rays, n, out, out_bytes, true, tc, true)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return enqueue_surface(ctx, tc, rays, n, out, (hipStream_t)hip_stream);
+}
+
+// lt_hip_surface_at / lt_hip_surface_at_device: the surface record of hit records the caller has (lt_query.hip,
+// lt_surface_at_kernel).  check_trace's rules where they apply: every argument error is found before anything is enqueued.
+static int check_surface_at(lt_hip_context* ctx, const lt_hip_surface_desc* d, const lt_hip_hit* hits, uint64_t n, const void* out, uint64_t out_bytes,
+                            bool device, bool& shipped) {
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_surface_at: desc is NULL");
+  if (d->struct_size < sizeof(lt_hip_surface_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_surface_desc (struct_size)");
+  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_surface_at takes LT_RENDER_FLAG_STRICT_MATH and LT_RENDER_FLAG_PORTABLE_MATH only");
+  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 hit records per call");
+  if (n > 0 && (!hits || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "hits or out is NULL");
+  if (device && n > 0 && (((uintptr_t)hits | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device hits and out must be 16-byte aligned");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_surface_at before lt_hip_set_scene");
+  if (out_bytes < n * sizeof(lt_hip_surface)) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
+  shipped = (d->flags & (LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH)) == 0;
+  return LT_OK;
+}
+
+static int enqueue_surface_at(lt_hip_context* ctx, bool shipped, const void* hits, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  const SceneDev sc = scene_dev(ctx, k, shipped ? 2 : 1);
+  ctx->mean_pairs = 0;
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  LT_HIP_CHECK(ctx, lt_query::launch_surface_at(sc, (const uint4*)hits, (uint4*)out, (uint32_t)n, shipped, (uint32_t)ctx->cu_count, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
+  ctx->last = lt_hip_stats{};
+  ctx->last.kernel_launches = 1;
+  ctx->pending = true;
+  ctx->pending_stats = false;
+  ctx->pending_query = true;
+  return LT_OK;
+}
+
+extern "C" int lt_hip_surface_at(lt_hip_context* ctx, const lt_hip_surface_desc* desc, const lt_hip_hit* hits, uint64_t n, lt_hip_surface* out,
+                                 uint64_t out_bytes) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  bool shipped = true;
+  if (const int rc = check_surface_at(ctx, desc, hits, n, out, out_bytes, false, shipped)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint64_t hitBytes = n * sizeof(lt_hip_hit), outBytes = n * sizeof(lt_hip_surface);
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, hitBytes, hitBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, outBytes, outBytes));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, hits, hitBytes, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = enqueue_surface_at(ctx, shipped, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
+  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (const int rc = finish_pending(ctx)) return rc;
+  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, outBytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+extern "C" int lt_hip_surface_at_device(lt_hip_context* ctx, const lt_hip_surface_desc* desc, const lt_hip_hit* hits, uint64_t n, lt_hip_surface* out,
+                                        uint64_t out_bytes, void* hip_stream) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  bool shipped = true;
+  if (const int rc = check_surface_at(ctx, desc, hits, n, out, out_bytes, true, shipped)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return enqueue_surface_at(ctx, shipped, hits, n, out, (hipStream_t)hip_stream);
 }
 
 // lt_hip_shade_rays / lt_hip_shade_rays_device: the colour a program's `shade` returns for caller-supplied rays (lt_shade.hip).

@@ -16,6 +16,8 @@
 //                           the 64 qualify, per lane otherwise.
 // And the multi-hit queries (lt_hip_trace_hits): lt_query_hits_kernel, lt_query_kernel's loop with another leaf action -- every
 // accepted primitive goes into a per-lane list sorted by t (the first K hits), or is counted.
+// And the surface queries (lt_hip_surface_at; lt_hip_trace_surface is a closest-hit query and this): lt_surface_at_kernel turns hit
+// records into what every `shade` of the reference computes first at a hit.  Nothing is walked.
 #include "lt_query.hpp"
 
 using namespace lt;
@@ -368,6 +370,36 @@ __global__ __launch_bounds__(kBlock, 8) void lt_query_hits_kernel(SceneDev sc, l
   }
 }
 
+// lt_hip_surface from lt_hip_hit: one record per lane -- a 16-byte load, the primitive's 76 bytes gathered, three 16-byte stores --
+// in a grid-stride loop.  The reference's own steps (acc.cl:233-247): the primitive, b = (1.0 - u - v in double, u, v),
+// A*b.x + B*b.y + C*b.z of the positions and of the normals -- as shipped (Math<2>: fused) or with every product and sum rounded
+// (strict and portable: bary3 knows no other difference) --, the material, the scan of the light list.  A primitive that is none of
+// the scene's (one unsigned compare: -1 included) gives the miss form.
+template <bool SHIPPED>
+__global__ __launch_bounds__(256) void lt_surface_at_kernel(SceneDev sc, const uint4* __restrict__ hits, uint4* __restrict__ out, uint32_t n) {
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    uint4 hit = hits[i];
+    uint4 pos = make_uint4(0u, 0u, 0u, 0xffffffffu), nrm = make_uint4(0u, 0u, 0u, 0u);
+    if (hit.y >= sc.n_prims) {
+      hit = make_uint4(hit.x, 0xffffffffu, 0u, 0u);
+    } else {
+      const int prim = (int)hit.y;
+      const float* pr = prim_ptr(sc, prim);
+      const V3 b = barycentrics(__uint_as_float(hit.z), __uint_as_float(hit.w));
+      const V3 p3 = bary3<SHIPPED ? 2 : 0>(pr + 0, pr + 3, pr + 6, b);
+      const V3 n3 = bary3<SHIPPED ? 2 : 0>(pr + 9, pr + 12, pr + 15, b);
+      pos = make_uint4(__float_as_uint(p3.x), __float_as_uint(p3.y), __float_as_uint(p3.z), (uint32_t)prim_material(pr));
+      nrm = make_uint4(__float_as_uint(n3.x), __float_as_uint(n3.y), __float_as_uint(n3.z), is_light(sc.lights, prim) ? 1u : 0u);
+    }
+    uint4* const o = out + 3 * (size_t)i;
+    o[0] = hit;
+    o[1] = pos;
+    o[2] = nrm;
+    if (n - i <= stride) break;   // (i + stride may wrap: n goes up to 2^32 - 1)
+  }
+}
+
 namespace lt_query {
 
 template <int PROGRAM, bool ANYHIT>
@@ -397,6 +429,15 @@ hipError_t launch(const SceneDev& sc, const Params& p, Epsilon eps, bool anyHit,
       anyHit ? launch_one<kAccumulator, true>(sc, p, coherent, cuCount, s) : launch_one<kAccumulator, false>(sc, p, coherent, cuCount, s);
       break;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_surface_at(const SceneDev& sc, const uint4* hits, uint4* out, uint32_t n, bool shipped, uint32_t cuCount, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint32_t blocks = (uint32_t)(((uint64_t)n + 255u) / 256u), resident = cuCount * 8u;   // 2048 lanes per CU
+  const dim3 grid(blocks < resident ? blocks : resident);
+  if (shipped) hipLaunchKernelGGL((lt_surface_at_kernel<true>), grid, dim3(256), 0, s, sc, hits, out, n);
+  else hipLaunchKernelGGL((lt_surface_at_kernel<false>), grid, dim3(256), 0, s, sc, hits, out, n);
   return hipGetLastError();
 }
 

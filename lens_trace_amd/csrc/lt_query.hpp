@@ -40,4 +40,10 @@ struct HitsParams {
 // Enqueues lt_query_hits_kernel on `s`.  Returns the first HIP error.
 hipError_t launch_hits(const lt::SceneDev& sc, const HitsParams& p, Epsilon eps, uint32_t cuCount, hipStream_t s);
 
+// Surface queries (lt_hip_surface_at, and lt_hip_trace_surface behind its closest-hit query): lt_surface_at_kernel over n hit
+// records (lt_hip_hit) gives n 48-byte records lt_hip_surface -- the hit record, then (position.xyz, material), then (normal.xyz,
+// flags) -- interpolated as shipped (fused multiply-adds) or with every product and sum rounded (the strict and portable
+// flavours); a record whose primitive is not the scene's gives the miss form.  Enqueues on `s`; returns the first HIP error.
+hipError_t launch_surface_at(const lt::SceneDev& sc, const uint4* hits, uint4* out, uint32_t n, bool shipped, uint32_t cuCount, hipStream_t s);
+
 }  // namespace lt_query

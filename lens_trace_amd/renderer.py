@@ -75,6 +75,7 @@ def make_desc(program, W, H, depth, camera28, kernel_mode=KERNEL_MODE_LINEAR, fr
 
 FLT_MAX = float(np.finfo(np.float32).max)   # the reference's payload start (acc.cl: RayPayload.t = FLT_MAX)
 RAY_DTYPE, HIT_DTYPE = C.RAY_DTYPE, C.HIT_DTYPE
+SURFACE_DTYPE = C.SURFACE_DTYPE
 
 
 def make_rays(origins, directions, tmax=FLT_MAX, ignore=-1):
@@ -356,6 +357,88 @@ class RendererHIP:
             stream = torch.cuda.current_stream(dev)
         handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
         self._check(self._L.lt_hip_trace_hits_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
+                                                     ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                                                     ctypes.c_void_p(handle)))
+        return out
+
+    # -- surface queries -------------------------------------------------------------------------------
+    def trace_surface(self, rays, program="accumulator", coherent=False, portable_math=False, strict_math=False, stream=None):
+        """Closest hits with the surface behind them (lt_hip_trace_surface): for each ray trace_rays' record (t, prim, u, v), the
+        position A*b.x + B*b.y + C*b.z the reference's shade starts its next ray from, the interpolated vertex normal (not
+        normalised), the primitive's material index and flags (C.SURFACE_LIGHT: the primitive is in the light list); on a miss
+        position = normal = 0, material = -1, flags = 0.  Rays, program and coherent as trace_rays takes them.  A numpy array goes
+        to the host entry point and an (n,) SURFACE_DTYPE array comes back; a contiguous (n, 8) float32 torch tensor on this
+        context's GPU is enqueued on `stream` (default: the current torch stream) and an (n, 12) float32 tensor comes back
+        (columns 1, 7 and 11 hold integer bits: .view(torch.int32))."""
+        if not isinstance(program, int):
+            program = C.program_from_path(str(program))
+        d = C.TraceDesc()
+        d.struct_size = ctypes.sizeof(C.TraceDesc)
+        d.program = program
+        d.kind = C.TRACE_CLOSEST
+        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
+                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
+        if isinstance(rays, np.ndarray):
+            if rays.dtype == RAY_DTYPE and rays.ndim == 1:
+                rays = rays.view(np.float32).reshape(-1, 8)
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an (n, 8) float32 array (make_rays) or a RAY_DTYPE array")
+            rays = np.ascontiguousarray(rays)
+            n = rays.shape[0]
+            out = np.zeros(n, dtype=SURFACE_DTYPE)
+            self._check(self._L.lt_hip_trace_surface(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
+                                                     out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+            return out
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError("rays must be a numpy array or a torch tensor")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
+        dev = torch.device("cuda", self.device)
+        if rays.device != dev:
+            raise ValueError("rays must be on %s, the context's device" % dev)
+        n = rays.shape[0]
+        out = torch.empty((n, 12), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        self._check(self._L.lt_hip_trace_surface_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
+                                                        ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                                                        ctypes.c_void_p(handle)))
+        return out
+
+    def surface_at(self, hits, portable_math=False, strict_math=False, stream=None):
+        """The surface records of hit records the caller has (lt_hip_surface_at) -- above all trace_hits' K per ray: t, u and v
+        copied, position, normal, material and flags as trace_surface gives them; a record whose prim is none of the scene's
+        primitives gives the miss form (prim = -1, u = v = 0).  hits: a HIT_DTYPE array of any shape -- then the host entry point
+        runs and a SURFACE_DTYPE array of the same shape comes back; or a contiguous (..., 4) float32 torch tensor on this
+        context's GPU -- then the call is enqueued on `stream` (default: the current torch stream) and a (..., 12) float32 tensor
+        comes back."""
+        d = C.SurfaceDesc()
+        d.struct_size = ctypes.sizeof(C.SurfaceDesc)
+        d.flags = (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) | (C.RENDER_FLAG_STRICT_MATH if strict_math else 0)
+        if isinstance(hits, np.ndarray):
+            if hits.dtype != HIT_DTYPE:
+                raise ValueError("hits must be a HIT_DTYPE array")
+            flat = np.ascontiguousarray(hits).reshape(-1)
+            out = np.zeros(flat.shape[0], dtype=SURFACE_DTYPE)
+            self._check(self._L.lt_hip_surface_at(self._ctx, ctypes.byref(d), flat.ctypes.data_as(ctypes.c_void_p), flat.shape[0],
+                                                  out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+            return out.reshape(hits.shape)
+        import torch
+        if not isinstance(hits, torch.Tensor):
+            raise TypeError("hits must be a numpy array or a torch tensor")
+        if hits.dtype != torch.float32 or hits.dim() < 1 or hits.shape[-1] != 4 or not hits.is_contiguous():
+            raise ValueError("hits must be a contiguous (..., 4) float32 tensor")
+        dev = torch.device("cuda", self.device)
+        if hits.device != dev:
+            raise ValueError("hits must be on %s, the context's device" % dev)
+        n = hits.numel() // 4
+        out = torch.empty(tuple(hits.shape[:-1]) + (12,), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        self._check(self._L.lt_hip_surface_at_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(hits.data_ptr()), n,
                                                      ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
                                                      ctypes.c_void_p(handle)))
         return out
