@@ -267,7 +267,7 @@ struct lt_hip_context {
   hipEvent_t cal_ev[12] = {};
   std::map<std::vector<uint32_t>, int> shadow_modes;
   std::map<std::vector<uint32_t>, uint32_t> shadow_groups;   // ... and the frames per work item it was timed with (launch_walk)
-  unsigned long long* d_groupWalks = nullptr;   // LT_DEBUG_SHADOW_FRAMES: waves whose two frames walked together / apart (launch_walk)   // (program, W, H, tile geometry) -> the walk timed faster for it on the resident scene
+  unsigned long long* d_groupWalks = nullptr;   // LT_DEBUG_SHADOW_FRAMES: waves whose two frames walked together / apart / together per one-mixed-axis form (launch_walk)   // (program, W, H, tile geometry) -> the walk timed faster for it on the resident scene
   void* d_shadowq = nullptr;         // accumulator's queued shadow rays (shadow mode 3): origin+tmax, direction, (pixel, primitive, frame), occluded: 52 bytes per slot
   uint64_t shadowq_slots = 0;
   uint32_t* d_shadowCtl = nullptr;   // ... the trace launch's eight work counters (kQueueStride apart) and, behind them, the queue's length
@@ -1593,16 +1593,17 @@ static int launch_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& sc, uint32_
                         ? std::min(std::min(group, c.k.shadow_frames), fp.fusedFrames) : 1u;
   if (mode != 3u) {
     if (c.k.debug_shadow_frames && fp.shadowFrames > 1u) {   // (a debugging aid: counts the waves of each kind, and waits for them)
-      if (!ctx->d_groupWalks) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_groupWalks, 2 * sizeof(unsigned long long)));
-      LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_groupWalks, 0, 2 * sizeof(unsigned long long), c.s));
+      if (!ctx->d_groupWalks) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_groupWalks, 14 * sizeof(unsigned long long)));
+      LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_groupWalks, 0, 14 * sizeof(unsigned long long), c.s));
       SceneDev sd = sc;
       sd.groupWalks = ctx->d_groupWalks;
       launch_builtin(c, sd, fp, grid, out, ctx->d_stats, queues);
-      unsigned long long h[2];
+      unsigned long long h[14];   // together, apart, then the together-walks of each one-mixed-axis form (traverse_shadow2)
       LT_HIP_CHECK(ctx, hipMemcpyAsync(h, ctx->d_groupWalks, sizeof(h), hipMemcpyDeviceToHost, c.s));
       LT_HIP_CHECK(ctx, hipStreamSynchronize(c.s));
-      fprintf(stderr, "shadow-ray frame groups: %u (walk %u, %u frames): %llu waves walked both frames together, %llu apart\n", fp.shadowFrames,
-              mode, fp.fusedFrames, h[0], h[1]);
+      fprintf(stderr, "shadow-ray frame groups: %u (walk %u, %u frames): %llu waves walked both frames together, %llu apart; of those together, "
+              "one mixed axis: x %llu %llu %llu %llu, y %llu %llu %llu %llu, z %llu %llu %llu %llu\n", fp.shadowFrames, mode, fp.fusedFrames, h[0],
+              h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13]);
       return LT_OK;
     }
     if (c.k.debug_shadow_frames) fprintf(stderr, "shadow-ray frame groups: %u (walk %u, %u frames)\n", fp.shadowFrames, mode, fp.fusedFrames);

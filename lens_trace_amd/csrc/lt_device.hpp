@@ -112,7 +112,7 @@ struct SceneDev {
   uint32_t fastRcp;         // != 0: intersectTriangle's 1 / det as the reference's as-shipped build computes it (Math<2>::rcp), in every walk
   float shadowSpread;       // shadowPackets == 2: a wave's shadow rays walk as a packet iff every origin lies within sqrt(shadowSpread) x its
                             // own ray's length of the first lane's origin (one surface patch looking at one light), else per lane
-  unsigned long long* groupWalks;   // LT_DEBUG_SHADOW_FRAMES, else null: [0] waves whose two frames' shadow rays walked together, [1] apart
+  unsigned long long* groupWalks;   // LT_DEBUG_SHADOW_FRAMES, else null: [0] waves whose two frames' shadow rays walked together, [1] apart, [2 + k] together in the one-mixed-axis form 8 + k (14 words)
 };
 
 typedef float F4v __attribute__((ext_vector_type(4)));
@@ -480,11 +480,31 @@ __device__ __forceinline__ bool box_test_finite(float lox, float loy, float loz,
 // tell apart.  NEG < 0: signs unknown, box_test_finite's min / max form.
 // The wave's lane mask of a slab test, as the AND of the two compares' masks: `ballot(a && b)` makes the compiler
 // materialise the bool in a VGPR and compare it again (two vector instructions per test); two ballots and a scalar AND do not.
+// NEG = 8 .. 19 (the two-frame walk's one-mixed-axis forms, traverse_shadow2): 8 + 4 * (the axis whose signs are mixed) + the signs
+// along the other two axes in x, y, z order; the mixed axis takes the min / max form, the others the octant form.
+__host__ __device__ constexpr int packet_neg_mode(int NEG, int a) {   // axis a of NEG: 0 positive, 1 negative, 2 mixed / unknown
+  if (NEG < 0) return 2;
+  if (NEG < 8) return (NEG >> a) & 1;
+  const int m = (NEG - 8) >> 2;
+  return a == m ? 2 : ((NEG - 8) >> (a - (a > m ? 1 : 0))) & 1;
+}
+template <int MODE>   // one axis of a slab test: the near and far one of its products for the box's min and max
+__device__ __forceinline__ void slab_axis(float tLo, float tHi, float& tNear, float& tFar) {
+  if (MODE == 2) { tNear = __builtin_fminf(tLo, tHi); tFar = __builtin_fmaxf(tLo, tHi); }
+  else { tNear = MODE ? tHi : tLo; tFar = MODE ? tLo : tHi; }
+}
 template <int NEG>   // NEG < 0: signs unknown (box_test_finite's min / max form)
 __device__ __forceinline__ unsigned long long box_mask(float lox, float loy, float loz, float hix, float hiy, float hiz, const Ray& ray,
                                                        float ix, float iy, float iz) {
   float tEnter, tExit;
-  if (NEG >= 0) {
+  if (NEG >= 8) {
+    float nx, fx, ny, fy, nz, fz;
+    slab_axis<packet_neg_mode(NEG, 0)>((lox - ray.o.x) * ix, (hix - ray.o.x) * ix, nx, fx);
+    slab_axis<packet_neg_mode(NEG, 1)>((loy - ray.o.y) * iy, (hiy - ray.o.y) * iy, ny, fy);
+    slab_axis<packet_neg_mode(NEG, 2)>((loz - ray.o.z) * iz, (hiz - ray.o.z) * iz, nz, fz);
+    tEnter = __builtin_fmaxf(__builtin_fmaxf(nx, ny), nz);
+    tExit = __builtin_fminf(__builtin_fminf(fx, fy), fz);
+  } else if (NEG >= 0) {
     const float nearX = (NEG & 1) ? hix : lox, farX = (NEG & 1) ? lox : hix;
     const float nearY = (NEG & 2) ? hiy : loy, farY = (NEG & 2) ? loy : hiy;
     const float nearZ = (NEG & 4) ? hiz : loz, farZ = (NEG & 4) ? loz : hiz;
@@ -845,7 +865,14 @@ template <int NEG>
 __device__ __forceinline__ unsigned long long box_mask_cheap(float lox, float loy, float loz, float hix, float hiy, float hiz, float ix, float iy,
                                                             float iz, const PacketRayC& pr) {
   float tEnter, tExit;
-  if (NEG >= 0) {
+  if (NEG >= 8) {   // one mixed axis (packet_neg_mode)
+    float nx, fx, ny, fy, nz, fz;
+    slab_axis<packet_neg_mode(NEG, 0)>(__builtin_fmaf(lox, ix, -pr.px), __builtin_fmaf(hix, ix, -pr.px), nx, fx);
+    slab_axis<packet_neg_mode(NEG, 1)>(__builtin_fmaf(loy, iy, -pr.py), __builtin_fmaf(hiy, iy, -pr.py), ny, fy);
+    slab_axis<packet_neg_mode(NEG, 2)>(__builtin_fmaf(loz, iz, -pr.pz), __builtin_fmaf(hiz, iz, -pr.pz), nz, fz);
+    tEnter = __builtin_fmaxf(__builtin_fmaxf(nx, ny), nz);
+    tExit = __builtin_fminf(__builtin_fminf(fx, fy), fz);
+  } else if (NEG >= 0) {
     const float nearX = (NEG & 1) ? hix : lox, farX = (NEG & 1) ? lox : hix;
     const float nearY = (NEG & 2) ? hiy : loy, farY = (NEG & 2) ? loy : hiy;
     const float nearZ = (NEG & 4) ? hiz : loz, farZ = (NEG & 4) ? loz : hiz;
@@ -1102,8 +1129,9 @@ __device__ inline void traverse(const SceneDev& sc, const Ray& ray, bool useIgno
 
 // Two frames' shadow rays of one camera hit (shade_lighting2: one origin, the primitive `ignore` under it; pl[j].t = frame j's
 // tmax).  One walk for both (packet_walk2) when each frame's rays would walk as a packet in traverse -- finite, of ordinary
-// magnitudes, walk 1 or walk 2 with the spread test passed for that frame's tmax -- and all 128 rays share one direction-sign
-// octant: true.  Otherwise false, and nothing is walked: the caller renders each frame as it does alone (render_square), so that
+// magnitudes, walk 1 or walk 2 with the spread test passed for that frame's tmax -- and the 128 rays' direction signs are mixed
+// along at most one axis (one octant, or a one-mixed-axis form: what a receiver within an area light's extent along one axis
+// sees): true.  Otherwise false, and nothing is walked: the caller renders each frame as it does alone (render_square), so that
 // the kernel holds one copy of traverse and its walks, not two.
 template <int PROGRAM, class CFG>
 __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2], int ignore, Hit (&pl)[2], Stack<CFG::kDeep>& st, Counters& c) {
@@ -1129,12 +1157,27 @@ __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2],
 #pragma unroll
       for (int a = 0; a < 3; a++) sign[j][a] = __builtin_amdgcn_ballot_w64(inv[j][a] < 0.0f);
     }
+    // The form of the walk: 0 .. 7 = all 128 rays in one octant; 8 + 4 * a + k = axis a mixed (some frame's ballot neither empty nor
+    // full, or the two frames' ballots different) and the other two axes of one sign each, k as in packet_neg_mode; two or three
+    // mixed axes: apart.
+    uint32_t neg = 0u, mixed = 0u;
 #pragma unroll
-    for (int a = 0; a < 3; a++) ok = ok && (sign[0][a] == 0ull || sign[0][a] == all) && sign[1][a] == sign[0][a];
-    if (sc.groupWalks != nullptr && (int)__lane_id() == __ffsll((long long)all) - 1) atomicAdd(&sc.groupWalks[ok ? 0 : 1], 1ull);
+    for (int a = 0; a < 3; a++) {
+      neg |= sign[0][a] != 0ull ? 1u << a : 0u;
+      mixed |= (sign[0][a] == 0ull || sign[0][a] == all) && sign[1][a] == sign[0][a] ? 0u : 1u << a;
+    }
+    ok = ok && (mixed & (mixed - 1u)) == 0u;
+    uint32_t form = neg;
+    if (mixed == 1u) form = 8u + (neg >> 1);
+    else if (mixed == 2u) form = 12u + ((neg & 1u) | (neg >> 1 & 2u));
+    else if (mixed == 4u) form = 16u + (neg & 3u);
+    if (sc.groupWalks != nullptr && (int)__lane_id() == __ffsll((long long)all) - 1) {
+      atomicAdd(&sc.groupWalks[ok ? 0 : 1], 1ull);
+      if (ok && form >= 8u) atomicAdd(&sc.groupWalks[form - 6u], 1ull);
+    }
     if (ok) {
       int* const row = st.lds - __lane_id();
-      switch ((sign[0][0] != 0ull ? 1 : 0) | (sign[0][1] != 0ull ? 2 : 0) | (sign[0][2] != 0ull ? 4 : 0)) {
+      switch (form) {
         case 0: packet_walk2<PROGRAM, 0>(sc, ray, inv, ignore, pl, row); break;
         case 1: packet_walk2<PROGRAM, 1>(sc, ray, inv, ignore, pl, row); break;
         case 2: packet_walk2<PROGRAM, 2>(sc, ray, inv, ignore, pl, row); break;
@@ -1142,7 +1185,19 @@ __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2],
         case 4: packet_walk2<PROGRAM, 4>(sc, ray, inv, ignore, pl, row); break;
         case 5: packet_walk2<PROGRAM, 5>(sc, ray, inv, ignore, pl, row); break;
         case 6: packet_walk2<PROGRAM, 6>(sc, ray, inv, ignore, pl, row); break;
-        default: packet_walk2<PROGRAM, 7>(sc, ray, inv, ignore, pl, row); break;
+        case 7: packet_walk2<PROGRAM, 7>(sc, ray, inv, ignore, pl, row); break;
+        case 8: packet_walk2<PROGRAM, 8>(sc, ray, inv, ignore, pl, row); break;
+        case 9: packet_walk2<PROGRAM, 9>(sc, ray, inv, ignore, pl, row); break;
+        case 10: packet_walk2<PROGRAM, 10>(sc, ray, inv, ignore, pl, row); break;
+        case 11: packet_walk2<PROGRAM, 11>(sc, ray, inv, ignore, pl, row); break;
+        case 12: packet_walk2<PROGRAM, 12>(sc, ray, inv, ignore, pl, row); break;
+        case 13: packet_walk2<PROGRAM, 13>(sc, ray, inv, ignore, pl, row); break;
+        case 14: packet_walk2<PROGRAM, 14>(sc, ray, inv, ignore, pl, row); break;
+        case 15: packet_walk2<PROGRAM, 15>(sc, ray, inv, ignore, pl, row); break;
+        case 16: packet_walk2<PROGRAM, 16>(sc, ray, inv, ignore, pl, row); break;
+        case 17: packet_walk2<PROGRAM, 17>(sc, ray, inv, ignore, pl, row); break;
+        case 18: packet_walk2<PROGRAM, 18>(sc, ray, inv, ignore, pl, row); break;
+        default: packet_walk2<PROGRAM, 19>(sc, ray, inv, ignore, pl, row); break;
       }
     }
   }

@@ -248,6 +248,73 @@ typedef unsigned long long lt_u64;
 #define LT_BC_LT_NF_G(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_G(LX, LY, LZ, HX, HY, HZ, OUT, S)
 #define LT_BX_LT_NF_G(LX, LY, LZ, HX, HY, HZ) LT_ASM_BOXX_G(LX, LY, LZ, HX, HY, HZ)
 #define LT_BXL_LT_NF_G(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_G_LATE(LX, LY, LZ, HX, HY, HZ, S)
+// ... and for the two-frame walk of a group whose 128 rays have mixed signs along ONE axis A and one sign along each of the other
+// two, B and C (shadow rays towards an area light from a receiver that lies within the light's extent along A only): axis A as
+// in the sign-generic form -- both products, v_min / v_max -- and B, C as in the octant form, the near / far bound named by the
+// operand order: 13 and 18 instructions.  Per lane these are LT_NF_G's floats: where every ray of the wave has one sign along
+// an axis, min / max of that axis' two products IS the octant form's near / far product (the monotonicity argument above; the
+// sign of a zero aside, which max3 / min3, `+ mg`, max(0+, .) and the compares cannot tell apart), so the conservative-test proof
+// at the head of the file and the reference's exact leaf test hold as they do for LT_NF_G, and the two-frame argument in front
+// of LT_ASM_TESTS2 speaks of lanes and frames, not of octants.  The late leaf test leaves t3 (the triangle's t) alone.
+#define LT_ASM_BOXC_M(A, B, C, LA, HA, NB, NC, FB, FC, OUT, S)       \
+  "v_fma_f32 %[t0], " LA ", %[i" A S "], -%[p" A S "]\n"   \
+  "v_fma_f32 %[t1], " HA ", %[i" A S "], -%[p" A S "]\n"   \
+  "v_fma_f32 %[t2], " NB ", %[i" B S "], -%[p" B S "]\n"   \
+  "v_fma_f32 %[t3], " NC ", %[i" C S "], -%[p" C S "]\n"   \
+  "v_min_f32_e32 %[t4], %[t0], %[t1]\n"               \
+  "v_max_f32_e32 %[t0], %[t0], %[t1]\n"               \
+  "v_max3_f32 %[t4], %[t4], %[t2], %[t3]\n"           \
+  "v_fma_f32 %[t1], " FB ", %[i" B S "], -%[p" B S "]\n"   \
+  "v_fma_f32 %[t2], " FC ", %[i" C S "], -%[p" C S "]\n"   \
+  "v_min3_f32 %[t0], %[t0], %[t1], %[t2]\n"           \
+  "v_add_f32_e32 %[t0], %[t0], %[mg" S "]\n"          \
+  "v_max_f32_e32 %[t4], 1, %[t4]\n"                   \
+  "v_cmp_ge_f32_e64 " OUT ", %[t0], %[t4]\n"
+#define LT_ASM_BOXX_M_LATE(A, B, C, LA, HA, NB, NC, FB, FC, S)       \
+  "v_sub_f32_e32 %[t4], " LA ", %[o" A "]\n"          \
+  "v_sub_f32_e32 %[t5], " HA ", %[o" A "]\n"          \
+  "v_mul_f32_e32 %[t4], %[t4], %[i" A S "]\n"         \
+  "v_mul_f32_e32 %[t5], %[t5], %[i" A S "]\n"         \
+  "v_min_f32_e32 %[t6], %[t4], %[t5]\n"               \
+  "v_max_f32_e32 %[t7], %[t4], %[t5]\n"               \
+  "v_sub_f32_e32 %[t4], " NB ", %[o" B "]\n"          \
+  "v_sub_f32_e32 %[t5], " NC ", %[o" C "]\n"          \
+  "v_mul_f32_e32 %[t4], %[t4], %[i" B S "]\n"         \
+  "v_mul_f32_e32 %[t5], %[t5], %[i" C S "]\n"         \
+  "v_max3_f32 %[t6], %[t6], %[t4], %[t5]\n"           \
+  "v_sub_f32_e32 %[t4], " FB ", %[o" B "]\n"          \
+  "v_sub_f32_e32 %[t5], " FC ", %[o" C "]\n"          \
+  "v_mul_f32_e32 %[t4], %[t4], %[i" B S "]\n"         \
+  "v_mul_f32_e32 %[t5], %[t5], %[i" C S "]\n"         \
+  "v_min3_f32 %[t7], %[t7], %[t4], %[t5]\n"           \
+  "v_max_f32_e32 %[t6], 1, %[t6]\n"                   \
+  "v_cmpx_ge_f32_e64 " LT_R_HML ", %[t7], %[t6]\n"
+// LT_NF_<A><k>: A = the mixed axis, k = the signs along the other two axes in x, y, z order (bit 0: the first of them negative,
+// bit 1: the second), the form index 8 + 4 * axis + k of traverse_shadow2 (lt_device.hpp: packet_neg_mode).
+#define LT_BC_LT_NF_X0(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("x", "y", "z", LX, HX, LY, LZ, HY, HZ, OUT, S)
+#define LT_BC_LT_NF_X1(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("x", "y", "z", LX, HX, HY, LZ, LY, HZ, OUT, S)
+#define LT_BC_LT_NF_X2(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("x", "y", "z", LX, HX, LY, HZ, HY, LZ, OUT, S)
+#define LT_BC_LT_NF_X3(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("x", "y", "z", LX, HX, HY, HZ, LY, LZ, OUT, S)
+#define LT_BC_LT_NF_Y0(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("y", "x", "z", LY, HY, LX, LZ, HX, HZ, OUT, S)
+#define LT_BC_LT_NF_Y1(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("y", "x", "z", LY, HY, HX, LZ, LX, HZ, OUT, S)
+#define LT_BC_LT_NF_Y2(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("y", "x", "z", LY, HY, LX, HZ, HX, LZ, OUT, S)
+#define LT_BC_LT_NF_Y3(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("y", "x", "z", LY, HY, HX, HZ, LX, LZ, OUT, S)
+#define LT_BC_LT_NF_Z0(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("z", "x", "y", LZ, HZ, LX, LY, HX, HY, OUT, S)
+#define LT_BC_LT_NF_Z1(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("z", "x", "y", LZ, HZ, HX, LY, LX, HY, OUT, S)
+#define LT_BC_LT_NF_Z2(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("z", "x", "y", LZ, HZ, LX, HY, HX, LY, OUT, S)
+#define LT_BC_LT_NF_Z3(LX, LY, LZ, HX, HY, HZ, OUT, S) LT_ASM_BOXC_M("z", "x", "y", LZ, HZ, HX, HY, LX, LY, OUT, S)
+#define LT_BXL_LT_NF_X0(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("x", "y", "z", LX, HX, LY, LZ, HY, HZ, S)
+#define LT_BXL_LT_NF_X1(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("x", "y", "z", LX, HX, HY, LZ, LY, HZ, S)
+#define LT_BXL_LT_NF_X2(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("x", "y", "z", LX, HX, LY, HZ, HY, LZ, S)
+#define LT_BXL_LT_NF_X3(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("x", "y", "z", LX, HX, HY, HZ, LY, LZ, S)
+#define LT_BXL_LT_NF_Y0(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("y", "x", "z", LY, HY, LX, LZ, HX, HZ, S)
+#define LT_BXL_LT_NF_Y1(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("y", "x", "z", LY, HY, HX, LZ, LX, HZ, S)
+#define LT_BXL_LT_NF_Y2(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("y", "x", "z", LY, HY, LX, HZ, HX, LZ, S)
+#define LT_BXL_LT_NF_Y3(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("y", "x", "z", LY, HY, HX, HZ, LX, LZ, S)
+#define LT_BXL_LT_NF_Z0(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("z", "x", "y", LZ, HZ, LX, LY, HX, HY, S)
+#define LT_BXL_LT_NF_Z1(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("z", "x", "y", LZ, HZ, HX, LY, LX, HY, S)
+#define LT_BXL_LT_NF_Z2(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("z", "x", "y", LZ, HZ, LX, HY, HX, LY, S)
+#define LT_BXL_LT_NF_Z3(LX, LY, LZ, HX, HY, HZ, S) LT_ASM_BOXX_M_LATE("z", "x", "y", LZ, HZ, HX, HY, LX, LY, S)
 #define LT_BC(NF, LOHI, OUT, S) LT_BC_##NF(LOHI, OUT, S)
 #define LT_BX(NF, LOHI) LT_BX_##NF(LOHI)
 #define LT_BXL(NF, LOHI, S) LT_BXL_##NF(LOHI, S)
@@ -456,6 +523,8 @@ typedef unsigned long long lt_u64;
 // frame's rays entered, and there a lane either passes the leaf's exact tests or fails them, as it would have had its own walk
 // reached that leaf -- a finite ray reaches a leaf of the reference's traversal iff it passes the slab test of the leaf's own box
 // (lt_retree.hpp).  An any-hit caller reads "accepted or not" only, so the order in which a frame meets its leaves is free.
+// (Nothing in this argument asks for one octant: the walk exists for the eight octant forms and for the twelve forms with mixed
+// signs along one axis, LT_ASM_BOXC_M / LT_ASM_BOXX_M_LATE, whose tests compute LT_NF_G's floats lane for lane.)
 // Interior record: a child is pushed iff its hit mask is non-zero and a stack entry carries no lane mask, so once frame 0's test
 // (EXEC = `open`) has let a lane into a child, frame 1's test of that child has no reader: it runs (EXEC = `open_1`, writing the mask
 // itself: nothing to OR) only for the children frame 0 missed -- the set of pushed children is that of testing both frames always.
@@ -612,8 +681,9 @@ __device__ __forceinline__ lt_u64 packet_anyhit_walk(const void* pairs, float ox
   return open;
 }
 
-// The any-hit walk of two frames' rays from one origin (LT_ASM_WALK2), one octant NEG >= 0 for both: on return open0 / open1 hold
-// the lanes whose ray of that frame found no occluder.  The second frame's ray: inverse direction i?1, direction d?1, tmax1.
+// The any-hit walk of two frames' rays from one origin (LT_ASM_WALK2), one octant NEG = 0 .. 7 for both, or one mixed axis and
+// one sign along each of the other two for both (NEG = 8 .. 19): on return open0 / open1 hold the lanes whose ray of that frame
+// found no occluder.  The second frame's ray: inverse direction i?1, direction d?1, tmax1.
 template <int NEG>
 __device__ __forceinline__ void packet_anyhit_walk2(const void* pairs, float ox, float oy, float oz, float ix, float iy, float iz, float dx,
                                                     float dy, float dz, float dw, float tmax, float ix1, float iy1, float iz1, float dx1,
@@ -641,7 +711,19 @@ __device__ __forceinline__ void packet_anyhit_walk2(const void* pairs, float ox,
   else if constexpr (NEG == 4) LT_ANYHIT2_INSTANCE(LT_NF_4);
   else if constexpr (NEG == 5) LT_ANYHIT2_INSTANCE(LT_NF_5);
   else if constexpr (NEG == 6) LT_ANYHIT2_INSTANCE(LT_NF_6);
-  else LT_ANYHIT2_INSTANCE(LT_NF_7);
+  else if constexpr (NEG == 7) LT_ANYHIT2_INSTANCE(LT_NF_7);
+  else if constexpr (NEG == 8) LT_ANYHIT2_INSTANCE(LT_NF_X0);    // one mixed axis: 8 + 4 * axis + the other two axes' signs
+  else if constexpr (NEG == 9) LT_ANYHIT2_INSTANCE(LT_NF_X1);
+  else if constexpr (NEG == 10) LT_ANYHIT2_INSTANCE(LT_NF_X2);
+  else if constexpr (NEG == 11) LT_ANYHIT2_INSTANCE(LT_NF_X3);
+  else if constexpr (NEG == 12) LT_ANYHIT2_INSTANCE(LT_NF_Y0);
+  else if constexpr (NEG == 13) LT_ANYHIT2_INSTANCE(LT_NF_Y1);
+  else if constexpr (NEG == 14) LT_ANYHIT2_INSTANCE(LT_NF_Y2);
+  else if constexpr (NEG == 15) LT_ANYHIT2_INSTANCE(LT_NF_Y3);
+  else if constexpr (NEG == 16) LT_ANYHIT2_INSTANCE(LT_NF_Z0);
+  else if constexpr (NEG == 17) LT_ANYHIT2_INSTANCE(LT_NF_Z1);
+  else if constexpr (NEG == 18) LT_ANYHIT2_INSTANCE(LT_NF_Z2);
+  else LT_ANYHIT2_INSTANCE(LT_NF_Z3);
 #undef LT_ANYHIT2_INSTANCE
 }
 
