@@ -252,9 +252,13 @@ int lt_hip_own_wide(const void* own_nodes, uint64_t node_bytes, uint32_t n_prims
  * device-side preparation, lens_trace_amd/csrc/lt_prep.hip, against the host-side one, lt_retree.hpp, with it).
  * what: 0 = the own tree (32-byte nodes, pre-order), 1 = the leaf order table (8 x uint32 per primitive), 2 = the per-lane
  * walks' array (64-byte grid header, then 64-byte records: groups, leaf records by primitive offset, the sentinel),
- * 3 = four uint32: own-tree height, group-tree height, groups, 1 if the device prepared the scene (0: the host).
- * out == NULL: only *out_bytes (the size) is set.  LT_ERR_NO_SCENE without a scene; *out_bytes = 0 when the scene has no such
- * structure (it then walks the caller's tree). */
+ * 3 = four uint32: own-tree height, group-tree height, groups, 1 if the device prepared the scene (0: the host),
+ * 4 = the packet walks' records (64 bytes per node of the own tree: an interior node's two children -- box pushed outwards,
+ * reference with bit 31 set for a leaf, 0.0f -- or a leaf's triangle A, B - A, C - A, its box bit for bit, its primitive offset),
+ * 5 = the traversal triangles (48 bytes per primitive: A, B - A, C - A, three zero floats).
+ * out == NULL: only *out_bytes (the size) is set.  LT_ERR_NO_SCENE without a scene; *out_bytes = 0 for kinds 0, 1, 2 and 4 when
+ * the scene has no such structure (it then walks the caller's tree); kinds 3 and 5 are always there.  In kind 2 the leaf records of
+ * primitive offsets that no leaf names are written by nobody. */
 int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* out, uint64_t capacity, uint64_t* out_bytes);
 
 /* Ray queries over the resident scene (the scene of the last lt_hip_set_scene).  Each ray is traced as the reference traces

@@ -180,6 +180,14 @@ struct SceneHash {
   bool operator==(const SceneHash& o) const { return memcmp(buf, o.buf, sizeof(buf)) == 0; }
 };
 
+// LT_DEBUG_POISON=<byte>: a buffer's bytes before its first use, chosen by the caller instead of left to the allocator (fresh
+// memory is zero pages, a pooled buffer holds the last scene's content).  The wait behind the fill orders it before the work of
+// every stream.  A test switch: whatever reads a word that nothing wrote shows up as a difference between two byte values.
+static hipError_t lt_debug_poison(void* p, size_t bytes, int byte) {
+  const hipError_t e = hipMemset(p, byte, bytes);
+  return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
+
 // Device buffers of scenes gone by, kept for the next scene of the same shape: an animation hands over buffers of the same sizes
 // frame after frame, and a hipFree / hipMalloc pair per buffer (a dozen of them, each a device-wide wait) was a tenth of
 // lt_hip_set_scene.  Exact sizes only; at most kSpareCap bytes lie idle (LT_SCENE_POOL_BYTES, 0: every buffer goes straight
@@ -188,8 +196,13 @@ struct ScenePool {
   std::multimap<size_t, void*> spare;
   std::map<void*, size_t> sizes;   // of every buffer this pool handed out
   size_t spareBytes = 0, cap = (size_t)8 << 30;
+  int poison = -1;   // LT_DEBUG_POISON: every buffer handed out is filled with this byte first (lt_debug_poison)
   hipError_t get(void** p, size_t bytes) {
     if (bytes == 0) bytes = 4;
+    const hipError_t e = take(p, bytes);
+    return e == hipSuccess && poison >= 0 ? lt_debug_poison(*p, bytes, poison) : e;
+  }
+  hipError_t take(void** p, size_t bytes) {
     auto it = spare.find(bytes);
     if (it != spare.end()) {
       *p = it->second;
@@ -351,6 +364,7 @@ extern "C" int lt_hip_create(int device_index, lt_hip_context** out_ctx) {
   ctx->device = device_index;
   ctx->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   if (const char* e = getenv("LT_SCENE_POOL_BYTES")) ctx->pool.cap = (size_t)strtoull(e, nullptr, 10);
+  if (const char* e = getenv("LT_DEBUG_POISON")) ctx->pool.poison = (int)(strtoul(e, nullptr, 0) & 0xffu);
   auto bail = [&](const char* what, hipError_t er) {
     std::string m = std::string(what) + ": " + hipGetErrorString(er);
     delete ctx;
@@ -1077,13 +1091,14 @@ struct RenderKnobs {
 // Grows a scratch buffer of the context to `need` units (`bytes` bytes): frees the old one, allocates, records the capacity
 // (0 while there is no buffer).
 template <class T>
-static hipError_t grow_scratch(T*& buf, uint64_t& capacity, uint64_t need, uint64_t bytes) {
+static hipError_t grow_scratch(const lt_hip_context* ctx, T*& buf, uint64_t& capacity, uint64_t need, uint64_t bytes) {
   if (capacity >= need) return hipSuccess;
   hipError_t e = buf ? hipFree(buf) : hipSuccess;
   if (e != hipSuccess) return e;
   buf = nullptr;
   e = hipMalloc((void**)&buf, bytes);
   capacity = e == hipSuccess ? need : 0;
+  if (e == hipSuccess && ctx->pool.poison >= 0) e = lt_debug_poison(buf, bytes, ctx->pool.poison);
   return e;
 }
 
@@ -1221,11 +1236,18 @@ static void launch_program(const RenderCall& c, const SceneDev& sc, const FrameP
 constexpr uint32_t kGiCtlWords = (8 + 19 * (kMaxStack + 2)) * kQueueStride;   // (the trace launches' counters come in eights: one per eighth of their queue)
 
 static int ensure_gi_buffers(lt_hip_context* ctx, uint64_t pixels) {
-  if (!ctx->d_giCtl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_giCtl, kGiCtlWords * sizeof(uint32_t)));
+  const int poison = ctx->pool.poison;
+  if (!ctx->d_giCtl) {
+    LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_giCtl, kGiCtlWords * sizeof(uint32_t)));
+    if (poison >= 0) LT_HIP_CHECK(ctx, lt_debug_poison(ctx->d_giCtl, kGiCtlWords * sizeof(uint32_t), poison));
+  }
   if (ctx->gi_pixels >= pixels) return LT_OK;
   for (void*& b : ctx->d_gi) { if (b) LT_HIP_CHECK(ctx, hipFree(b)); b = nullptr; }
   ctx->gi_pixels = 0;
-  for (int i = 0; i < 17; i++) LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_gi[i], pixels * 16));
+  for (int i = 0; i < 17; i++) {
+    LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_gi[i], pixels * 16));
+    if (poison >= 0) LT_HIP_CHECK(ctx, lt_debug_poison(ctx->d_gi[i], pixels * 16, poison));
+  }
   ctx->gi_pixels = pixels;
   return LT_OK;
 }
@@ -1396,7 +1418,7 @@ static int ensure_square_order(lt_hip_context* ctx, const lt_hip_render_desc* d,
     std::copy(rest.begin(), rest.end(), ord.begin() + pos);
   }
   ctx->order_key.clear();
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_order, ctx->order_capacity, n, n * sizeof(uint32_t)));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_order, ctx->order_capacity, n, n * sizeof(uint32_t)));
   // (rare path: image size, tiling or camera rotation changed)  No launch of an earlier call, on whatever stream, may still
   // be reading the old order; and `ord` must outlive the copy.
   LT_HIP_CHECK(ctx, hipDeviceSynchronize());
@@ -1531,7 +1553,7 @@ static int plan_fusion(lt_hip_context* ctx, const RenderKnobs& k, const lt_hip_r
       chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)(gi25Sets ? 25u : frames), k.fused_bytes / scratchPerFrame, 0xffffffffull / nblocks,
                                                                   giWavefront ? 0xffffffffull / std::max<uint64_t>(giSlots, 1) : ~0ull}));
     // a device that cannot spare the scratch memory gets shorter launches, down to one sample per launch
-    while ((chunk > 1 || gi25Sets) && grow_scratch(ctx->d_samples, ctx->d_samples_bytes, chunk * frameBytes, chunk * frameBytes) != hipSuccess) {
+    while ((chunk > 1 || gi25Sets) && grow_scratch(ctx, ctx->d_samples, ctx->d_samples_bytes, chunk * frameBytes, chunk * frameBytes) != hipSuccess) {
       (void)hipGetLastError();
       if (chunk == 1) return fail(ctx, LT_ERR_HIP, "out of device memory for one sample image");
       chunk /= 2;
@@ -1612,7 +1634,7 @@ static int launch_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& sc, uint32_
   }
   if (c.k.debug_shadow_frames) fprintf(stderr, "shadow-ray frame groups: %u (walk %u, %u frames)\n", fp.shadowFrames, mode, fp.fusedFrames);
   const uint64_t slots = c.nblocks * fp.fusedFrames * kBlock;
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_shadowq, ctx->shadowq_slots, slots, slots * 52));   // (origin + tmax, direction, pixel / primitive / frame: 48 bytes; its fate: 4)
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_shadowq, ctx->shadowq_slots, slots, slots * 52));   // (origin + tmax, direction, pixel / primitive / frame: 48 bytes; its fate: 4)
   if (!ctx->d_shadowCtl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_shadowCtl, 9 * kQueueStride * sizeof(uint32_t)));
   LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_shadowCtl, 0, 8 * kQueueStride * sizeof(uint32_t), c.s));
   LT_HIP_CHECK(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->d_shadowCtl + 8 * kQueueStride), (int)(uint32_t)slots, 1, c.s));
@@ -1686,7 +1708,7 @@ static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const Sc
   for (uint32_t xcd = 0; xcd < 8; xcd++) squares += camera_hit_squares(fp, xcd);
   if (c.k.debug_camera_hits) fprintf(stderr, "camera-hit pass: %llu of %llu squares\n", (unsigned long long)squares, (unsigned long long)c.nblocks);
   if (squares == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_camhits, ctx->camhits_slots, c.nblocks * kBlock, c.nblocks * kBlock * sizeof(uint4)));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_camhits, ctx->camhits_slots, c.nblocks * kBlock, c.nblocks * kBlock * sizeof(uint4)));
   fp.cameraHits = ctx->d_camhits;
   FrameParams fh = fp;
   fh.fusedFrames = 1;
@@ -1717,7 +1739,7 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   if (stats) LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_stats, 0, 8 * sizeof(unsigned long long), s));
   if (k.persistent) {   // (persistent wavefronts by default; LT_PERSISTENT=0 selects one-square-per-workgroup dispatch: A/B measurements)
     const uint64_t queueBytes = ((uint64_t)frames + 1) * 8 * kQueueStride * sizeof(uint32_t);   // (the last eight: the camera-hit pass's)
-    LT_HIP_CHECK(ctx, grow_scratch(ctx->d_queues, ctx->queue_frames, (uint64_t)frames + 1, queueBytes));
+    LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_queues, ctx->queue_frames, (uint64_t)frames + 1, queueBytes));
     LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_queues, 0, queueBytes, s));
     if (k.square_order)
       if (const int rc = ensure_square_order(ctx, d, p, fp.sinYaw == 0.0f, s, &fp.order, fp.orderHead)) return rc;
@@ -1918,7 +1940,7 @@ static int render_to_host(lt_hip_context* ctx, const lt_hip_render_desc* desc, f
   if (out_bytes < rb.need) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "outputBufferSize smaller than W*H*depth floats");
   if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_render before lt_hip_set_scene");
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_out, ctx->d_out_bytes, rb.need, rb.need ? rb.need : 4));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_out, ctx->d_out_bytes, rb.need, rb.need ? rb.need : 4));
   // a running mean continues from the caller's buffer when accumulate_base > 0
   if (desc->frame_count && desc->accumulate && desc->accumulate_base > 0)
     LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_out, out_host, rb.need, hipMemcpyHostToDevice, ctx->stream));
@@ -2070,8 +2092,8 @@ extern "C" int lt_hip_trace_rays(lt_hip_context* ctx, const lt_hip_trace_desc* d
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const uint64_t rayBytes = n * sizeof(lt_hip_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, tc.outBytes, tc.outBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, tc.outBytes, tc.outBytes));
   LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
   if (const int rc = enqueue_trace(ctx, tc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2164,8 +2186,8 @@ extern "C" int lt_hip_trace_hits(lt_hip_context* ctx, const lt_hip_multihit_desc
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const uint64_t rayBytes = n * sizeof(lt_hip_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, hc.outBytes, hc.outBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, hc.outBytes, hc.outBytes));
   LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
   if (const int rc = enqueue_hits(ctx, hc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2194,7 +2216,7 @@ static int enqueue_surface(lt_hip_context* ctx, const TraceCall& tc, const void*
   const RenderKnobs k;
   if (!ctx->d_query_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_query_ctl, 8 * kQueueStride * sizeof(uint32_t)));
   // (growing frees the old buffer, which waits for the calls that use it)
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_surface_hits, ctx->surface_hits_records, n, n * sizeof(lt_hip_hit)));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_surface_hits, ctx->surface_hits_records, n, n * sizeof(lt_hip_hit)));
   if (!ctx->query_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->query_ev, hipEventDisableTiming));
   else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->query_ev, 0));   // (the counters and the hit records are the previous query's until it is done)
   lt_query::Params qp{};
@@ -2227,8 +2249,8 @@ extern "C" int lt_hip_trace_surface(lt_hip_context* ctx, const lt_hip_trace_desc
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const uint64_t rayBytes = n * sizeof(lt_hip_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, tc.outBytes, tc.outBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, tc.outBytes, tc.outBytes));
   LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
   if (const int rc = enqueue_surface(ctx, tc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2289,8 +2311,8 @@ extern "C" int lt_hip_surface_at(lt_hip_context* ctx, const lt_hip_surface_desc*
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const uint64_t hitBytes = n * sizeof(lt_hip_hit), outBytes = n * sizeof(lt_hip_surface);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, hitBytes, hitBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, outBytes, outBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, hitBytes, hitBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, outBytes, outBytes));
   LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, hits, hitBytes, hipMemcpyHostToDevice, ctx->stream));
   if (const int rc = enqueue_surface_at(ctx, shipped, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2387,8 +2409,8 @@ extern "C" int lt_hip_shade_rays(lt_hip_context* ctx, const lt_hip_shade_desc* d
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const uint64_t rayBytes = n * sizeof(lt_hip_shade_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, call.outBytes, call.outBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, call.outBytes, call.outBytes));
   LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
   if (const int rc = enqueue_shade(ctx, call, desc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2549,7 +2571,7 @@ static int enqueue_paths(lt_hip_context* ctx, const PathsCall& call, const lt_hi
   const uint64_t ranges = (n + raysAtMost - 1) / raysAtMost;
   const uint32_t raysPerSet = (uint32_t)((n + ranges - 1) / ranges);   // (ranges of equal size: a short last one costs its launches all the same)
   if (const int rc = ensure_gi_buffers(ctx, (uint64_t)raysPerSet * framesPerSet * perFrame)) return rc;
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_paths_hits, ctx->paths_hits_rays, (uint64_t)raysPerSet, (uint64_t)raysPerSet * sizeof(uint4)));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_paths_hits, ctx->paths_hits_rays, (uint64_t)raysPerSet, (uint64_t)raysPerSet * sizeof(uint4)));
   if (!ctx->paths_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->paths_ev, hipEventDisableTiming));
   else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->paths_ev, 0));   // (the control block and the scratch are the previous call's until it is done)
   SceneDev sc = scene_dev(ctx, k, call.devlibm);
@@ -2612,8 +2634,8 @@ extern "C" int lt_hip_shade_paths(lt_hip_context* ctx, const lt_hip_paths_desc* 
   if (n == 0) return LT_OK;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const uint64_t rayBytes = n * sizeof(lt_hip_shade_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx->d_query_out, ctx->query_out_bytes, call.outBytes, call.outBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, call.outBytes, call.outBytes));
   LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
   if (const int rc = enqueue_paths(ctx, call, desc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2657,7 +2679,7 @@ extern "C" int lt_hip_synchronize(lt_hip_context* ctx, void* hip_stream) {
 
 extern "C" int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* out, uint64_t capacity, uint64_t* out_bytes) {
   if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  if (!out_bytes || what < 0 || what > 3) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_read_scene_structure: bad arguments");
+  if (!out_bytes || what < 0 || what > 5) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_read_scene_structure: bad arguments");
   if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "no scene uploaded");
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const bool own = ctx->d_nodes2 && ctx->d_wide && ctx->d_rank8;
@@ -2668,6 +2690,8 @@ extern "C" int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* 
   else if (own && what == 0) { src = ctx->d_nodes2; bytes = (uint64_t)ctx->n_nodes2 * 32; }
   else if (own && what == 1) { src = ctx->d_rank8; bytes = (uint64_t)ctx->n_prims * 32; }
   else if (own && what == 2) { src = ctx->d_wide; bytes = ((uint64_t)ctx->n_wide + ctx->n_prims + 1) * 64 + 64; }
+  else if (own && what == 4 && ctx->d_pairs2) { src = ctx->d_pairs2; bytes = (uint64_t)ctx->n_nodes2 * 64; }
+  else if (what == 5) { src = ctx->d_tris; bytes = (uint64_t)ctx->n_prims * 48; }
   *out_bytes = bytes;
   if (!out || bytes == 0) return LT_OK;
   if (capacity < bytes) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_read_scene_structure: buffer too small");

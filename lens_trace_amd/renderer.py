@@ -249,7 +249,9 @@ class RendererHIP:
 
     def scene_structure(self, what):
         """lt_hip_read_scene_structure: 0 own tree (NODE_DTYPE array), 1 leaf order table (n_prims x 8 uint32), 2 the per-lane walks'
-        array (bytes), 3 (own height, group-tree height, groups, prepared on the device).  None when the scene has no such structure."""
+        array (bytes), 3 (own height, group-tree height, groups, prepared on the device), 4 the packet walks' records (bytes, 64 per
+        node of the own tree), 5 the traversal triangles (bytes, 48 per primitive).  None when the scene has no such structure
+        (kinds 0, 1, 2 and 4 of a scene that walks the caller's tree)."""
         from . import scene as sc
         n = ctypes.c_uint64(0)
         self._check(self._L.lt_hip_read_scene_structure(self._ctx, what, None, ctypes.c_uint64(0), ctypes.byref(n)))

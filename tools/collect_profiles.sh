@@ -20,12 +20,14 @@ rm -rf "$OUT"      # (a pass directory must hold ONE run: the summaries average 
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 B="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-soup --no-e2e $EXTRA"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B > $OUT/stats.log 2>&1
+# every pass under a time limit of its own; a pass that fails ends the collection (nothing more is started on the GPU behind it)
+LIMIT="timeout -k 10 ${LT_PROFILE_PASS_SECONDS:-300}"
+$LIMIT rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B > $OUT/stats.log 2>&1 || { echo "stats pass FAILED (see $OUT/stats.log)"; tail -3 $OUT/stats.log; exit 1; }
 echo "stats pass done"
 B1="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-soup --no-e2e $EXTRA"
 pass() {   # name, counters...
   local name=$1; shift
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -- $B1 > $OUT/$name.log 2>&1 || { echo "pass $name FAILED (see $OUT/$name.log)"; tail -3 $OUT/$name.log; return 0; }
+  $LIMIT rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -- $B1 > $OUT/$name.log 2>&1 || { echo "pass $name FAILED (see $OUT/$name.log)"; tail -3 $OUT/$name.log; exit 1; }
   echo "pass $name done"
 }
 pass fetch FETCH_SIZE
