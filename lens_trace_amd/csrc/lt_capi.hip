@@ -2019,142 +2019,220 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
 }
 
 // ---------------------------------------------------------------------------------- ray queries
-// lt_hip_trace_rays / lt_hip_trace_rays_device: caller-supplied rays against the resident scene (lt_query.hip).  Every argument
-// error is found before anything is enqueued, so that a failed call writes nothing to `out`.
-struct TraceCall {
-  lt_query::Epsilon eps;
-  bool anyHit, coherent;
-  int devlibm;
-  uint64_t outBytes;   // what n results take
-};
+// Six families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
+// lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at (lt_query.hip), lt_hip_shade_rays (lt_shade.hip)
+// and lt_hip_shade_paths (lt_paths.hip).  Every argument error is found before anything is enqueued, so that a failed call writes
+// nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
+// check_ray_buffers), the course of an entry point with the host form's staging (run_ray_call) and the events and statistics
+// around the launches (begin_ray_launches, end_ray_launches).  A family has its check (the rules about its descriptor, at their
+// place in the order), its launches (enqueue_*) and two one-line entry points.
 static_assert(sizeof(lt_hip_ray) == 32 && sizeof(lt_hip_hit) == 16 && sizeof(lt_hip_trace_desc) == 16, "ray query records (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_multihit_desc) == 24 && LT_TRACE_MAX_HITS == lt_query::kMaxHits, "multi-hit records (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_surface) == 48 && sizeof(lt_hip_surface_desc) == 8, "surface records (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_shade_ray) == 32 && sizeof(lt_hip_shade) == 16 && sizeof(lt_hip_shade_desc) == 24, "shaded-ray records (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_paths_desc) == 32, "path-shading descriptor (include/lenstrace_hip.h)");
 
-static int check_trace(lt_hip_context* ctx, const lt_hip_trace_desc* d, const lt_hip_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
-                       bool device, TraceCall& tc, bool surface = false) {
-  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_trace_rays: desc is NULL");
-  if (d->struct_size < sizeof(lt_hip_trace_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_trace_desc (struct_size)");
-  if (d->kind != LT_TRACE_CLOSEST && d->kind != LT_TRACE_ANY) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown trace kind");
-  if (surface && d->kind != LT_TRACE_CLOSEST) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "surface queries take LT_TRACE_CLOSEST");
-  if (d->program >= LT_PROGRAM_USER_BASE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take a built-in program (it selects the triangle epsilon)");
-  if (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL) return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
-  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only");
-  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
+// What every family's check leaves for its launches: the math flavour (SceneDev: 0 portable, 1 strict, 2 as shipped) and the bytes
+// of one result.
+struct RayCall {
+  int devlibm;
+  uint64_t outRecord;
+};
+
+// The nouns of a family's error texts: the call, its records, what a batch of them is, the input pointer.
+struct RayWording { const char *call, *records, *batch, *in; };
+constexpr RayWording kQueryWording{"ray query", "rays", "query", "rays"};
+constexpr RayWording kSurfaceAtWording{"lt_hip_surface_at", "hit records", "call", "hits"};
+constexpr RayWording kShadeWording{"lt_hip_shade_rays", "rays", "call", "rays"};
+constexpr RayWording kPathsWording{"lt_hip_shade_paths", "rays", "call", "rays"};
+
+// The flags of a call: the two math flags and, `coherent`, LT_TRACE_FLAG_COHERENT; `who`: the family's "... take(s)".
+static int check_ray_flags(lt_hip_context* ctx, uint32_t flags, bool coherent, const char* who, RayCall& call) {
+  const uint32_t allowed = LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | (coherent ? LT_TRACE_FLAG_COHERENT : 0u);
+  if (flags & ~allowed)
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(who) + (coherent ? " LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only"
+                                                                        : " LT_RENDER_FLAG_STRICT_MATH and LT_RENDER_FLAG_PORTABLE_MATH only"));
+  if ((flags & LT_RENDER_FLAG_PORTABLE_MATH) && (flags & LT_RENDER_FLAG_STRICT_MATH))
     return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
-  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 rays per query");
-  if (n > 0 && (!rays || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "rays or out is NULL");
-  if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
-  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "ray query before lt_hip_set_scene");
-  tc.anyHit = d->kind == LT_TRACE_ANY;
-  tc.outBytes = n * (surface ? sizeof(lt_hip_surface) : tc.anyHit ? sizeof(uint32_t) : sizeof(lt_hip_hit));
-  if (out_bytes < tc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
-  tc.eps = (d->program == LT_PROGRAM_BASIC || d->program == LT_PROGRAM_CUSTOM_OPENCL) ? lt_query::kEpsFloat7
-           : d->program == LT_PROGRAM_BASIC_LIGHTING ? lt_query::kEpsDouble7 : lt_query::kEpsDouble4;
-  tc.coherent = (d->flags & LT_TRACE_FLAG_COHERENT) != 0;
-  tc.devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
+  call.devlibm = (flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
   return LT_OK;
 }
 
-// Enqueues the query on `s` between the context's timing events; lt_hip_get_stats reports it (finish_pending).
-static int enqueue_trace(lt_hip_context* ctx, const TraceCall& tc, const void* rays, uint64_t n, void* out, hipStream_t s) {
-  const RenderKnobs k;
-  if (!ctx->d_query_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_query_ctl, 8 * kQueueStride * sizeof(uint32_t)));
-  if (!ctx->query_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->query_ev, hipEventDisableTiming));
-  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->query_ev, 0));   // (the counters are the previous query's until it is done)
-  lt_query::Params qp{};
-  qp.rays = (const float4*)rays;
-  qp.hits = tc.anyHit ? nullptr : (uint4*)out;
-  qp.occluded = tc.anyHit ? (uint32_t*)out : nullptr;
-  qp.n = (uint32_t)n;
-  qp.next = ctx->d_query_ctl;
-  qp.refill = k.trace_refill;
-  const SceneDev sc = scene_dev(ctx, k, tc.devlibm);
+// The records of a call and the room for its results (call.outRecord bytes each), once the descriptor has passed.
+static int check_ray_buffers(lt_hip_context* ctx, const RayWording& w, const void* in, uint64_t n, const void* out, uint64_t out_bytes, bool device,
+                             const RayCall& call) {
+  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("at most 2^32 - 1 ") + w.records + " per " + w.batch);
+  if (n > 0 && (!in || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(w.in) + " or out is NULL");
+  if (device && n > 0 && (((uintptr_t)in | (uintptr_t)out) & 15u))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("device ") + w.in + " and out must be 16-byte aligned");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, std::string(w.call) + " before lt_hip_set_scene");
+  if (out_bytes < n * call.outRecord) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
+  return LT_OK;
+}
+
+// The program of a query: a built-in one, for the triangle epsilon of its intersect.
+static int query_epsilon(lt_hip_context* ctx, int program, lt_query::Epsilon& eps) {
+  if (program >= LT_PROGRAM_USER_BASE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take a built-in program (it selects the triangle epsilon)");
+  if (program < LT_PROGRAM_BASIC || program > LT_PROGRAM_CUSTOM_OPENCL) return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
+  eps = (program == LT_PROGRAM_BASIC || program == LT_PROGRAM_CUSTOM_OPENCL) ? lt_query::kEpsFloat7
+        : program == LT_PROGRAM_BASIC_LIGHTING ? lt_query::kEpsDouble7 : lt_query::kEpsDouble4;
+  return LT_OK;
+}
+
+// The program of a shade family: a built-in one; `noUserPrograms`: the family's text for a user program the context knows.
+static int check_shade_program(lt_hip_context* ctx, int program, const char* noUserPrograms) {
+  const bool userProgram = program >= LT_PROGRAM_USER_BASE;
+  if (userProgram ? (size_t)(program - LT_PROGRAM_USER_BASE) >= ctx->user_programs.size()
+                  : (program < LT_PROGRAM_BASIC || program > LT_PROGRAM_CUSTOM_OPENCL))
+    return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
+  if (userProgram) return fail(ctx, LT_ERR_INVALID_ARGUMENT, noUserPrograms);
+  return LT_OK;
+}
+
+// Every entry point: the family's check, then -- n > 0 -- its launches.  The device form enqueues them on the caller's stream.
+// The host form stages the records and the results in two buffers of the context that all the families share, runs on the
+// context's stream and waits.
+template <class Call, class Desc, class Record>
+static int run_ray_call(lt_hip_context* ctx, const Desc* desc, const Record* in, uint64_t n, void* out, uint64_t out_bytes, bool device,
+                        void* hip_stream,
+                        int (*check)(lt_hip_context*, const Desc*, const Record*, uint64_t, const void*, uint64_t, bool, Call&),
+                        int (*enqueue)(lt_hip_context*, const Call&, const void*, uint64_t, void*, hipStream_t)) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  Call call{};
+  if (const int rc = check(ctx, desc, in, n, out, out_bytes, device, call)) return rc;
+  if (n == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (device) return enqueue(ctx, call, in, n, out, (hipStream_t)hip_stream);
+  const uint64_t inBytes = n * sizeof(Record), outBytes = n * call.outRecord;
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, inBytes, inBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, outBytes, outBytes));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, in, inBytes, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = enqueue(ctx, call, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
+  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (const int rc = finish_pending(ctx)) return rc;
+  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, outBytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+// The eight work counters of a family's kernels (kQueueStride apart), allocated at its first call.
+static hipError_t ensure_ray_counters(uint32_t*& ctl) {
+  return ctl ? hipSuccess : hipMalloc((void**)&ctl, 8 * kQueueStride * sizeof(uint32_t));
+}
+
+// Around the launches of a call on `s`.  `ev`: the event behind the family's last call, or null (lt_hip_surface_at: it has no
+// state of its own) -- the counters and the scratch are the previous call's until it is done, on whichever stream that was.  The
+// context's timing events bracket the launches; lt_hip_get_stats reports them (finish_pending).
+static int begin_ray_launches(lt_hip_context* ctx, hipEvent_t* ev, hipStream_t s) {
+  if (ev && !*ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  else if (ev) LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, *ev, 0));
   ctx->mean_pairs = 0;
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
-  LT_HIP_CHECK(ctx, lt_query::launch(sc, qp, tc.eps, tc.anyHit, tc.coherent, (uint32_t)ctx->cu_count, s));
+  return LT_OK;
+}
+
+static int end_ray_launches(lt_hip_context* ctx, hipEvent_t ev, hipStream_t s, uint32_t launches, uint64_t rays, uint64_t shadowRays) {
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->query_ev, s));
+  if (ev) LT_HIP_CHECK(ctx, hipEventRecord(ev, s));
   ctx->last = lt_hip_stats{};
-  ctx->last.kernel_launches = 1;
-  if (tc.anyHit) ctx->last.shadow_rays = n;
-  else ctx->last.rays = n;
+  ctx->last.kernel_launches = launches;
+  ctx->last.rays = rays;
+  ctx->last.shadow_rays = shadowRays;
   ctx->pending = true;
   ctx->pending_stats = false;
   ctx->pending_query = true;
   return LT_OK;
 }
 
+// lt_hip_trace_rays*: closest or any hit of each ray.  lt_hip_trace_surface* (`surface`): closest hits with the surface record
+// behind them -- lt_hip_trace_rays' launch into a scratch buffer of the context, then lt_hip_surface_at's over it.  By definition
+// the call equals those two, and the one-kernel form -- the query kernels writing the record themselves -- was slower than the pair
+// on incoherent rays.
+struct TraceCall : RayCall {
+  lt_query::Epsilon eps;
+  bool anyHit, coherent, surface;
+};
+
+template <bool SURFACE>
+static int check_trace(lt_hip_context* ctx, const lt_hip_trace_desc* d, const lt_hip_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
+                       bool device, TraceCall& tc) {
+  tc.surface = SURFACE;
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_trace_rays: desc is NULL");
+  if (d->struct_size < sizeof(lt_hip_trace_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_trace_desc (struct_size)");
+  if (d->kind != LT_TRACE_CLOSEST && d->kind != LT_TRACE_ANY) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown trace kind");
+  if (tc.surface && d->kind != LT_TRACE_CLOSEST) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "surface queries take LT_TRACE_CLOSEST");
+  if (const int rc = query_epsilon(ctx, d->program, tc.eps)) return rc;
+  if (const int rc = check_ray_flags(ctx, d->flags, true, "ray queries take", tc)) return rc;
+  tc.anyHit = d->kind == LT_TRACE_ANY;
+  tc.coherent = (d->flags & LT_TRACE_FLAG_COHERENT) != 0;
+  tc.outRecord = tc.surface ? sizeof(lt_hip_surface) : tc.anyHit ? sizeof(uint32_t) : sizeof(lt_hip_hit);
+  return check_ray_buffers(ctx, kQueryWording, rays, n, out, out_bytes, device, tc);
+}
+
+static int enqueue_trace(lt_hip_context* ctx, const TraceCall& tc, const void* rays, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_query_ctl));
+  // (growing frees the old buffer, which waits for the calls that use it)
+  if (tc.surface) LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_surface_hits, ctx->surface_hits_records, n, n * sizeof(lt_hip_hit)));
+  lt_query::Params qp{};
+  qp.rays = (const float4*)rays;
+  qp.hits = tc.surface ? ctx->d_surface_hits : tc.anyHit ? nullptr : (uint4*)out;
+  qp.occluded = tc.anyHit ? (uint32_t*)out : nullptr;
+  qp.n = (uint32_t)n;
+  qp.next = ctx->d_query_ctl;
+  qp.refill = k.trace_refill;
+  const SceneDev sc = scene_dev(ctx, k, tc.devlibm);
+  if (const int rc = begin_ray_launches(ctx, &ctx->query_ev, s)) return rc;
+  LT_HIP_CHECK(ctx, lt_query::launch(sc, qp, tc.eps, tc.anyHit, tc.coherent, (uint32_t)ctx->cu_count, s));
+  if (tc.surface)
+    LT_HIP_CHECK(ctx, lt_query::launch_surface_at(sc, ctx->d_surface_hits, (uint4*)out, (uint32_t)n, tc.devlibm == 2, (uint32_t)ctx->cu_count, s));
+  return end_ray_launches(ctx, ctx->query_ev, s, tc.surface ? 2 : 1, tc.anyHit ? 0 : n, tc.anyHit ? n : 0);
+}
+
 extern "C" int lt_hip_trace_rays(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, void* out,
                                  uint64_t out_bytes) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  TraceCall tc{};
-  if (const int rc = check_trace(ctx, desc, rays, n, out, out_bytes, false, tc)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint64_t rayBytes = n * sizeof(lt_hip_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, tc.outBytes, tc.outBytes));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
-  if (const int rc = enqueue_trace(ctx, tc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
-  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (const int rc = finish_pending(ctx)) return rc;
-  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, tc.outBytes, hipMemcpyDeviceToHost));
-  return LT_OK;
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, false, nullptr, check_trace<false>, enqueue_trace);
 }
 
 extern "C" int lt_hip_trace_rays_device(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, void* out,
                                         uint64_t out_bytes, void* hip_stream) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  TraceCall tc{};
-  if (const int rc = check_trace(ctx, desc, rays, n, out, out_bytes, true, tc)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return enqueue_trace(ctx, tc, rays, n, out, (hipStream_t)hip_stream);
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, true, hip_stream, check_trace<false>, enqueue_trace);
 }
 
-// lt_hip_trace_hits / lt_hip_trace_hits_device: the first K hits of each ray, or their number (lt_query.hip,
-// lt_query_hits_kernel).  check_trace's rules with the descriptor's two further fields; the same staging and read-back.
-struct HitsCall {
+extern "C" int lt_hip_trace_surface(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, lt_hip_surface* out,
+                                    uint64_t out_bytes) {
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, false, nullptr, check_trace<true>, enqueue_trace);
+}
+
+extern "C" int lt_hip_trace_surface_device(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, lt_hip_surface* out,
+                                           uint64_t out_bytes, void* hip_stream) {
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, true, hip_stream, check_trace<true>, enqueue_trace);
+}
+
+// lt_hip_trace_hits*: the first K hits of each ray, or their number (lt_query_hits_kernel).
+struct HitsCall : RayCall {
   lt_query::Epsilon eps;
   uint32_t maxHits;    // 0: count
-  int devlibm;
-  uint64_t outBytes;
 };
-static_assert(sizeof(lt_hip_multihit_desc) == 24 && LT_TRACE_MAX_HITS == lt_query::kMaxHits, "multi-hit records (include/lenstrace_hip.h)");
 
 static int check_hits(lt_hip_context* ctx, const lt_hip_multihit_desc* d, const lt_hip_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
                       bool device, HitsCall& hc) {
   if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_trace_hits: desc is NULL");
   if (d->struct_size < sizeof(lt_hip_multihit_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_multihit_desc (struct_size)");
   if (d->kind != LT_TRACE_FIRST_K && d->kind != LT_TRACE_COUNT) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown multi-hit kind");
-  if (d->program >= LT_PROGRAM_USER_BASE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take a built-in program (it selects the triangle epsilon)");
-  if (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL) return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
-  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "ray queries take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only");
-  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (const int rc = query_epsilon(ctx, d->program, hc.eps)) return rc;
+  if (const int rc = check_ray_flags(ctx, d->flags, true, "ray queries take", hc)) return rc;
   if (d->kind == LT_TRACE_FIRST_K && (d->max_hits < 1 || d->max_hits > LT_TRACE_MAX_HITS))
     return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_TRACE_FIRST_K takes max_hits in 1 .. LT_TRACE_MAX_HITS");
   if (d->kind == LT_TRACE_COUNT && d->max_hits != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_TRACE_COUNT takes max_hits = 0");
   if (d->reserved != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_multihit_desc::reserved must be 0");
-  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 rays per query");
-  if (n > 0 && (!rays || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "rays or out is NULL");
-  if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
-  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "ray query before lt_hip_set_scene");
   hc.maxHits = d->max_hits;
-  hc.outBytes = d->kind == LT_TRACE_COUNT ? n * sizeof(uint32_t) : n * d->max_hits * sizeof(lt_hip_hit);
-  if (out_bytes < hc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
-  hc.eps = (d->program == LT_PROGRAM_BASIC || d->program == LT_PROGRAM_CUSTOM_OPENCL) ? lt_query::kEpsFloat7
-           : d->program == LT_PROGRAM_BASIC_LIGHTING ? lt_query::kEpsDouble7 : lt_query::kEpsDouble4;
-  hc.devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
-  return LT_OK;
+  hc.outRecord = d->kind == LT_TRACE_COUNT ? sizeof(uint32_t) : d->max_hits * sizeof(lt_hip_hit);
+  return check_ray_buffers(ctx, kQueryWording, rays, n, out, out_bytes, device, hc);
 }
 
 static int enqueue_hits(lt_hip_context* ctx, const HitsCall& hc, const void* rays, uint64_t n, void* out, hipStream_t s) {
   const RenderKnobs k;
-  if (!ctx->d_query_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_query_ctl, 8 * kQueueStride * sizeof(uint32_t)));
-  if (!ctx->query_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->query_ev, hipEventDisableTiming));
-  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->query_ev, 0));   // (the counters are the previous query's until it is done)
+  LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_query_ctl));
   lt_query::HitsParams qp{};
   qp.rays = (const float4*)rays;
   qp.hits = hc.maxHits ? (uint4*)out : nullptr;
@@ -2164,217 +2242,78 @@ static int enqueue_hits(lt_hip_context* ctx, const HitsCall& hc, const void* ray
   qp.next = ctx->d_query_ctl;
   qp.refill = k.trace_refill;
   const SceneDev sc = scene_dev(ctx, k, hc.devlibm);
-  ctx->mean_pairs = 0;
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  if (const int rc = begin_ray_launches(ctx, &ctx->query_ev, s)) return rc;
   LT_HIP_CHECK(ctx, lt_query::launch_hits(sc, qp, hc.eps, (uint32_t)ctx->cu_count, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->query_ev, s));
-  ctx->last = lt_hip_stats{};
-  ctx->last.kernel_launches = 1;
-  ctx->last.rays = n;
-  ctx->pending = true;
-  ctx->pending_stats = false;
-  ctx->pending_query = true;
-  return LT_OK;
+  return end_ray_launches(ctx, ctx->query_ev, s, 1, n, 0);
 }
 
 extern "C" int lt_hip_trace_hits(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, const lt_hip_ray* rays, uint64_t n, void* out,
                                  uint64_t out_bytes) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  HitsCall hc{};
-  if (const int rc = check_hits(ctx, desc, rays, n, out, out_bytes, false, hc)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint64_t rayBytes = n * sizeof(lt_hip_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, hc.outBytes, hc.outBytes));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
-  if (const int rc = enqueue_hits(ctx, hc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
-  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (const int rc = finish_pending(ctx)) return rc;
-  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, hc.outBytes, hipMemcpyDeviceToHost));
-  return LT_OK;
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, false, nullptr, check_hits, enqueue_hits);
 }
 
 extern "C" int lt_hip_trace_hits_device(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, const lt_hip_ray* rays, uint64_t n, void* out,
                                         uint64_t out_bytes, void* hip_stream) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  HitsCall hc{};
-  if (const int rc = check_hits(ctx, desc, rays, n, out, out_bytes, true, hc)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return enqueue_hits(ctx, hc, rays, n, out, (hipStream_t)hip_stream);
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, true, hip_stream, check_hits, enqueue_hits);
 }
 
-// lt_hip_trace_surface / lt_hip_trace_surface_device: closest hits with the surface record behind them -- lt_hip_trace_rays'
-// launch into a scratch buffer of the context, then lt_hip_surface_at's over it (lt_query.hip).  By definition the call equals
-// those two, and the one-kernel form -- the query kernels writing the record themselves -- was slower than the pair on incoherent
-// rays.  check_trace's rules with 48-byte records and no LT_TRACE_ANY; the same staging and read-back.
-static_assert(sizeof(lt_hip_surface) == 48 && sizeof(lt_hip_surface_desc) == 8, "surface records (include/lenstrace_hip.h)");
-
-static int enqueue_surface(lt_hip_context* ctx, const TraceCall& tc, const void* rays, uint64_t n, void* out, hipStream_t s) {
-  const RenderKnobs k;
-  if (!ctx->d_query_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_query_ctl, 8 * kQueueStride * sizeof(uint32_t)));
-  // (growing frees the old buffer, which waits for the calls that use it)
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_surface_hits, ctx->surface_hits_records, n, n * sizeof(lt_hip_hit)));
-  if (!ctx->query_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->query_ev, hipEventDisableTiming));
-  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->query_ev, 0));   // (the counters and the hit records are the previous query's until it is done)
-  lt_query::Params qp{};
-  qp.rays = (const float4*)rays;
-  qp.hits = ctx->d_surface_hits;
-  qp.n = (uint32_t)n;
-  qp.next = ctx->d_query_ctl;
-  qp.refill = k.trace_refill;
-  const SceneDev sc = scene_dev(ctx, k, tc.devlibm);
-  ctx->mean_pairs = 0;
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
-  LT_HIP_CHECK(ctx, lt_query::launch(sc, qp, tc.eps, false, tc.coherent, (uint32_t)ctx->cu_count, s));
-  LT_HIP_CHECK(ctx, lt_query::launch_surface_at(sc, ctx->d_surface_hits, (uint4*)out, (uint32_t)n, tc.devlibm == 2, (uint32_t)ctx->cu_count, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->query_ev, s));
-  ctx->last = lt_hip_stats{};
-  ctx->last.kernel_launches = 2;
-  ctx->last.rays = n;
-  ctx->pending = true;
-  ctx->pending_stats = false;
-  ctx->pending_query = true;
-  return LT_OK;
-}
-
-extern "C" int lt_hip_trace_surface(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, lt_hip_surface* out,
-                                    uint64_t out_bytes) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  TraceCall tc{};
-  if (const int rc = check_trace(ctx, desc, rays, n, out, out_bytes, false, tc, true)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint64_t rayBytes = n * sizeof(lt_hip_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, tc.outBytes, tc.outBytes));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
-  if (const int rc = enqueue_surface(ctx, tc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
-  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (const int rc = finish_pending(ctx)) return rc;
-  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, tc.outBytes, hipMemcpyDeviceToHost));
-  return LT_OK;
-}
-
-extern "C" int lt_hip_trace_surface_device(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n, lt_hip_surface* out,
-                                           uint64_t out_bytes, void* hip_stream) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  TraceCall tc{};
-  if (const int rc = check_trace(ctx, desc, rays, n, out, out_bytes, true, tc, true)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return enqueue_surface(ctx, tc, rays, n, out, (hipStream_t)hip_stream);
-}
-
-// lt_hip_surface_at / lt_hip_surface_at_device: the surface record of hit records the caller has (lt_query.hip,
-// lt_surface_at_kernel).  check_trace's rules where they apply: every argument error is found before anything is enqueued.
+// lt_hip_surface_at*: the surface record of hit records the caller has (lt_surface_at_kernel).  The kernel keeps nothing in the
+// context: the call waits for no event and records none.
 static int check_surface_at(lt_hip_context* ctx, const lt_hip_surface_desc* d, const lt_hip_hit* hits, uint64_t n, const void* out, uint64_t out_bytes,
-                            bool device, bool& shipped) {
+                            bool device, RayCall& call) {
   if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_surface_at: desc is NULL");
   if (d->struct_size < sizeof(lt_hip_surface_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_surface_desc (struct_size)");
-  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_surface_at takes LT_RENDER_FLAG_STRICT_MATH and LT_RENDER_FLAG_PORTABLE_MATH only");
-  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
-  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 hit records per call");
-  if (n > 0 && (!hits || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "hits or out is NULL");
-  if (device && n > 0 && (((uintptr_t)hits | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device hits and out must be 16-byte aligned");
-  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_surface_at before lt_hip_set_scene");
-  if (out_bytes < n * sizeof(lt_hip_surface)) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
-  shipped = (d->flags & (LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH)) == 0;
-  return LT_OK;
+  if (const int rc = check_ray_flags(ctx, d->flags, false, "lt_hip_surface_at takes", call)) return rc;
+  call.outRecord = sizeof(lt_hip_surface);
+  return check_ray_buffers(ctx, kSurfaceAtWording, hits, n, out, out_bytes, device, call);
 }
 
-static int enqueue_surface_at(lt_hip_context* ctx, bool shipped, const void* hits, uint64_t n, void* out, hipStream_t s) {
+static int enqueue_surface_at(lt_hip_context* ctx, const RayCall& call, const void* hits, uint64_t n, void* out, hipStream_t s) {
   const RenderKnobs k;
+  const bool shipped = call.devlibm == 2;
   const SceneDev sc = scene_dev(ctx, k, shipped ? 2 : 1);
-  ctx->mean_pairs = 0;
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  if (const int rc = begin_ray_launches(ctx, nullptr, s)) return rc;
   LT_HIP_CHECK(ctx, lt_query::launch_surface_at(sc, (const uint4*)hits, (uint4*)out, (uint32_t)n, shipped, (uint32_t)ctx->cu_count, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
-  ctx->last = lt_hip_stats{};
-  ctx->last.kernel_launches = 1;
-  ctx->pending = true;
-  ctx->pending_stats = false;
-  ctx->pending_query = true;
-  return LT_OK;
+  return end_ray_launches(ctx, nullptr, s, 1, 0, 0);
 }
 
 extern "C" int lt_hip_surface_at(lt_hip_context* ctx, const lt_hip_surface_desc* desc, const lt_hip_hit* hits, uint64_t n, lt_hip_surface* out,
                                  uint64_t out_bytes) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  bool shipped = true;
-  if (const int rc = check_surface_at(ctx, desc, hits, n, out, out_bytes, false, shipped)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint64_t hitBytes = n * sizeof(lt_hip_hit), outBytes = n * sizeof(lt_hip_surface);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, hitBytes, hitBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, outBytes, outBytes));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, hits, hitBytes, hipMemcpyHostToDevice, ctx->stream));
-  if (const int rc = enqueue_surface_at(ctx, shipped, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
-  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (const int rc = finish_pending(ctx)) return rc;
-  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, outBytes, hipMemcpyDeviceToHost));
-  return LT_OK;
+  return run_ray_call(ctx, desc, hits, n, out, out_bytes, false, nullptr, check_surface_at, enqueue_surface_at);
 }
 
 extern "C" int lt_hip_surface_at_device(lt_hip_context* ctx, const lt_hip_surface_desc* desc, const lt_hip_hit* hits, uint64_t n, lt_hip_surface* out,
                                         uint64_t out_bytes, void* hip_stream) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  bool shipped = true;
-  if (const int rc = check_surface_at(ctx, desc, hits, n, out, out_bytes, true, shipped)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return enqueue_surface_at(ctx, shipped, hits, n, out, (hipStream_t)hip_stream);
+  return run_ray_call(ctx, desc, hits, n, out, out_bytes, true, hip_stream, check_surface_at, enqueue_surface_at);
 }
 
-// lt_hip_shade_rays / lt_hip_shade_rays_device: the colour a program's `shade` returns for caller-supplied rays (lt_shade.hip).
-// check_trace's rules: every argument error is found before anything is enqueued.
-struct ShadeCall {
+// lt_hip_shade_rays*: the colour a program's `shade` returns for caller-supplied rays (lt_shade.hip).
+struct ShadeCall : RayCall {
   int program;         // lt::Program
-  int devlibm;
-  uint64_t outBytes;
+  const lt_hip_shade_desc* desc;
 };
-static_assert(sizeof(lt_hip_shade_ray) == 32 && sizeof(lt_hip_shade) == 16 && sizeof(lt_hip_shade_desc) == 24, "shaded-ray records (include/lenstrace_hip.h)");
 
 static int check_shade(lt_hip_context* ctx, const lt_hip_shade_desc* d, const lt_hip_shade_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
                        bool device, ShadeCall& sc) {
   if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_rays: desc is NULL");
   if (d->struct_size < sizeof(lt_hip_shade_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_shade_desc (struct_size)");
-  const bool userProgram = d->program >= LT_PROGRAM_USER_BASE;
-  if (userProgram ? (size_t)(d->program - LT_PROGRAM_USER_BASE) >= ctx->user_programs.size()
-                  : (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL))
-    return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
-  if (userProgram) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_rays does not take user programs");
+  if (const int rc = check_shade_program(ctx, d->program, "lt_hip_shade_rays does not take user programs")) return rc;
   if (d->program == LT_PROGRAM_GLOBAL_ILLUMINATION || d->program == LT_PROGRAM_GLOBAL_ILLUMINATION_25)
     return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_rays does not take the global-illumination programs (their pipeline is indexed by pixel)");
   if (d->kernel_mode != LT_KERNEL_MODE_LINEAR && d->kernel_mode != LT_KERNEL_MODE_TILE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown kernel mode");
-  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "shaded rays take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only");
-  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (const int rc = check_ray_flags(ctx, d->flags, true, "shaded rays take", sc)) return rc;
   if (d->frame_count == 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_desc::frame_count must be at least 1");
-  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 rays per call");
-  if (n > 0 && (!rays || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "rays or out is NULL");
-  if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
-  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_shade_rays before lt_hip_set_scene");
-  sc.outBytes = n * sizeof(lt_hip_shade);
-  if (out_bytes < sc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
   sc.program = d->program == LT_PROGRAM_BASIC ? kBasic : d->program == LT_PROGRAM_BASIC_LIGHTING ? kBasicLighting
                : d->program == LT_PROGRAM_ACCUMULATOR ? kAccumulator : kCustom;
-  sc.devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
-  return LT_OK;
+  sc.desc = d;
+  sc.outRecord = sizeof(lt_hip_shade);
+  return check_ray_buffers(ctx, kShadeWording, rays, n, out, out_bytes, device, sc);
 }
 
-// Enqueues the kernel on `s` between the context's timing events; lt_hip_get_stats reports it (finish_pending).
-static int enqueue_shade(lt_hip_context* ctx, const ShadeCall& call, const lt_hip_shade_desc* d, const void* rays, uint64_t n, void* out, hipStream_t s) {
+static int enqueue_shade(lt_hip_context* ctx, const ShadeCall& call, const void* rays, uint64_t n, void* out, hipStream_t s) {
   const RenderKnobs k;
-  if (!ctx->d_shade_ctl) LT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_shade_ctl, 8 * kQueueStride * sizeof(uint32_t)));
-  if (!ctx->shade_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->shade_ev, hipEventDisableTiming));
-  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->shade_ev, 0));   // (the counters are the previous call's until it is done)
+  const lt_hip_shade_desc* const d = call.desc;
+  LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_shade_ctl));
   lt_shade::Params sp{};
   sp.rays = (const float4*)rays;
   sp.out = (uint4*)out;
@@ -2387,85 +2326,43 @@ static int enqueue_shade(lt_hip_context* ctx, const ShadeCall& call, const lt_hi
   sp.frameCount = d->frame_count;
   sp.clampOutput = d->kernel_mode == LT_KERNEL_MODE_LINEAR;
   const SceneDev sc = scene_dev(ctx, k, call.devlibm);
-  ctx->mean_pairs = 0;
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  if (const int rc = begin_ray_launches(ctx, &ctx->shade_ev, s)) return rc;
   LT_HIP_CHECK(ctx, lt_shade::launch(sc, sp, call.program, call.devlibm, (uint32_t)ctx->cu_count, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->shade_ev, s));
-  ctx->last = lt_hip_stats{};
-  ctx->last.kernel_launches = 1;
-  ctx->last.rays = n;
-  ctx->pending = true;
-  ctx->pending_stats = false;
-  ctx->pending_query = true;
-  return LT_OK;
+  return end_ray_launches(ctx, ctx->shade_ev, s, 1, n, 0);
 }
 
 extern "C" int lt_hip_shade_rays(lt_hip_context* ctx, const lt_hip_shade_desc* desc, const lt_hip_shade_ray* rays, uint64_t n, lt_hip_shade* out,
                                  uint64_t out_bytes) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  ShadeCall call{};
-  if (const int rc = check_shade(ctx, desc, rays, n, out, out_bytes, false, call)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint64_t rayBytes = n * sizeof(lt_hip_shade_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, call.outBytes, call.outBytes));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
-  if (const int rc = enqueue_shade(ctx, call, desc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
-  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (const int rc = finish_pending(ctx)) return rc;
-  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, call.outBytes, hipMemcpyDeviceToHost));
-  return LT_OK;
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, false, nullptr, check_shade, enqueue_shade);
 }
 
 extern "C" int lt_hip_shade_rays_device(lt_hip_context* ctx, const lt_hip_shade_desc* desc, const lt_hip_shade_ray* rays, uint64_t n, lt_hip_shade* out,
                                         uint64_t out_bytes, void* hip_stream) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  ShadeCall call{};
-  if (const int rc = check_shade(ctx, desc, rays, n, out, out_bytes, true, call)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return enqueue_shade(ctx, call, desc, rays, n, out, (hipStream_t)hip_stream);
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, true, hip_stream, check_shade, enqueue_shade);
 }
 
-// lt_hip_shade_paths / lt_hip_shade_paths_device: the global-illumination programs over caller-supplied rays (lt_paths.hip).
-// check_shade's rules and order: every argument error is found before anything is enqueued.
-struct PathsCall {
+// lt_hip_shade_paths*: the global-illumination programs over caller-supplied rays (lt_paths.hip).  check_shade's rules and order.
+struct PathsCall : RayCall {
   bool gi25;
-  int devlibm;
-  uint64_t outBytes;
+  const lt_hip_paths_desc* desc;
 };
-static_assert(sizeof(lt_hip_paths_desc) == 32, "path-shading descriptor (include/lenstrace_hip.h)");
 
 static int check_paths(lt_hip_context* ctx, const lt_hip_paths_desc* d, const lt_hip_shade_ray* rays, uint64_t n, const void* out, uint64_t out_bytes,
                        bool device, PathsCall& pc) {
   if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_paths: desc is NULL");
   if (d->struct_size < sizeof(lt_hip_paths_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_paths_desc (struct_size)");
-  const bool userProgram = d->program >= LT_PROGRAM_USER_BASE;
-  if (userProgram ? (size_t)(d->program - LT_PROGRAM_USER_BASE) >= ctx->user_programs.size()
-                  : (d->program < LT_PROGRAM_BASIC || d->program > LT_PROGRAM_CUSTOM_OPENCL))
-    return fail(ctx, LT_ERR_UNKNOWN_PROGRAM, "unknown program");
-  if (userProgram) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_paths does not take user programs (nor does lt_hip_shade_rays)");
+  if (const int rc = check_shade_program(ctx, d->program, "lt_hip_shade_paths does not take user programs (nor does lt_hip_shade_rays)")) return rc;
   if (d->program != LT_PROGRAM_GLOBAL_ILLUMINATION && d->program != LT_PROGRAM_GLOBAL_ILLUMINATION_25)
     return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_shade_paths takes the global-illumination programs only: this program's entry point is lt_hip_shade_rays");
   if (d->kernel_mode != LT_KERNEL_MODE_LINEAR && d->kernel_mode != LT_KERNEL_MODE_TILE) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "unknown kernel mode");
-  if (d->flags & ~(uint32_t)(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "shaded paths take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only");
-  if ((d->flags & LT_RENDER_FLAG_PORTABLE_MATH) && (d->flags & LT_RENDER_FLAG_STRICT_MATH))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, "LT_RENDER_FLAG_PORTABLE_MATH and LT_RENDER_FLAG_STRICT_MATH exclude each other");
+  if (const int rc = check_ray_flags(ctx, d->flags, true, "shaded paths take", pc)) return rc;
   if (d->frame_count == 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_paths_desc::frame_count must be at least 1");
   if (d->gi_max_depth < 0 || d->gi_max_depth > 64) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "gi_max_depth out of range");
   if (d->reserved != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_paths_desc::reserved must be 0");
-  if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "at most 2^32 - 1 rays per call");
-  if (n > 0 && (!rays || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "rays or out is NULL");
-  if (device && n > 0 && (((uintptr_t)rays | (uintptr_t)out) & 15u)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "device rays and out must be 16-byte aligned");
-  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "lt_hip_shade_paths before lt_hip_set_scene");
-  pc.outBytes = n * sizeof(lt_hip_shade);
-  if (out_bytes < pc.outBytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "out is smaller than n results");
   pc.gi25 = d->program == LT_PROGRAM_GLOBAL_ILLUMINATION_25;
-  pc.devlibm = (d->flags & LT_RENDER_FLAG_PORTABLE_MATH) ? 0 : (d->flags & LT_RENDER_FLAG_STRICT_MATH) ? 1 : 2;
-  return LT_OK;
+  pc.desc = d;
+  pc.outRecord = sizeof(lt_hip_shade);
+  return check_ray_buffers(ctx, kPathsWording, rays, n, out, out_bytes, device, pc);
 }
 
 // Path slots of one set when neither LT_PATHS_SLOTS nor LT_FUSED_BYTES says otherwise (DESIGN.md 5.11 has the timings of the
@@ -2559,8 +2456,9 @@ static int launch_paths_set(lt_hip_context* ctx, const RenderKnobs& k, const Sce
 // into SETS of at most `cap` path slots: ranges of rays with all their frames, or -- one ray's frames alone exceed the cap --
 // ranges of frames as well; a frame's 25 samples stay together.  A range of rays walks its camera rays once, ahead of its sets;
 // between the sets of a range the running mean waits in the caller's record (lt_paths::Params::folded).
-static int enqueue_paths(lt_hip_context* ctx, const PathsCall& call, const lt_hip_paths_desc* d, const void* rays, uint64_t n, void* out, hipStream_t s) {
+static int enqueue_paths(lt_hip_context* ctx, const PathsCall& call, const void* rays, uint64_t n, void* out, hipStream_t s) {
   const RenderKnobs k;
+  const lt_hip_paths_desc* const d = call.desc;
   const uint32_t perFrame = call.gi25 ? 25u : 1u, frames = d->frame_count;
   uint64_t cap = std::min<uint64_t>(kPathsSlots, k.fused_bytes / (17 * 16));
   if (const char* e = getenv("LT_PATHS_SLOTS")) cap = strtoull(e, nullptr, 10);   // (tests, A/B measurements; no result depends on it)
@@ -2572,8 +2470,6 @@ static int enqueue_paths(lt_hip_context* ctx, const PathsCall& call, const lt_hi
   const uint32_t raysPerSet = (uint32_t)((n + ranges - 1) / ranges);   // (ranges of equal size: a short last one costs its launches all the same)
   if (const int rc = ensure_gi_buffers(ctx, (uint64_t)raysPerSet * framesPerSet * perFrame)) return rc;
   LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_paths_hits, ctx->paths_hits_rays, (uint64_t)raysPerSet, (uint64_t)raysPerSet * sizeof(uint4)));
-  if (!ctx->paths_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->paths_ev, hipEventDisableTiming));
-  else LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->paths_ev, 0));   // (the control block and the scratch are the previous call's until it is done)
   SceneDev sc = scene_dev(ctx, k, call.devlibm);
   sc.shadowPackets = 0u;   // (every shadow ray of these launches walks per lane)
   lt_paths::Params pp{};
@@ -2584,8 +2480,7 @@ static int enqueue_paths(lt_hip_context* ctx, const PathsCall& call, const lt_hi
   pp.giMaxDepth = d->gi_max_depth ? d->gi_max_depth : 16;
   pp.clampOutput = d->kernel_mode == LT_KERNEL_MODE_LINEAR;
   uint32_t launches = 0;
-  ctx->mean_pairs = 0;
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  if (const int rc = begin_ray_launches(ctx, &ctx->paths_ev, s)) return rc;   // (waits for the previous call: the control block and the scratch are its)
   for (uint64_t r0 = 0; r0 < n; r0 += raysPerSet) {
     pp.ray0 = (uint32_t)r0;
     pp.nRays = (uint32_t)std::min<uint64_t>(raysPerSet, n - r0);
@@ -2615,43 +2510,17 @@ static int enqueue_paths(lt_hip_context* ctx, const PathsCall& call, const lt_hi
       if (rc) return rc;
     }
   }
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
-  LT_HIP_CHECK(ctx, hipEventRecord(ctx->paths_ev, s));
-  ctx->last = lt_hip_stats{};
-  ctx->last.kernel_launches = launches;
-  ctx->last.rays = n;
-  ctx->pending = true;
-  ctx->pending_stats = false;
-  ctx->pending_query = true;
-  return LT_OK;
+  return end_ray_launches(ctx, ctx->paths_ev, s, launches, n, 0);
 }
 
 extern "C" int lt_hip_shade_paths(lt_hip_context* ctx, const lt_hip_paths_desc* desc, const lt_hip_shade_ray* rays, uint64_t n, lt_hip_shade* out,
                                   uint64_t out_bytes) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  PathsCall call{};
-  if (const int rc = check_paths(ctx, desc, rays, n, out, out_bytes, false, call)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint64_t rayBytes = n * sizeof(lt_hip_shade_ray);
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, rayBytes, rayBytes));
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, call.outBytes, call.outBytes));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, rayBytes, hipMemcpyHostToDevice, ctx->stream));
-  if (const int rc = enqueue_paths(ctx, call, desc, ctx->d_query_rays, n, ctx->d_query_out, ctx->stream)) return rc;
-  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (const int rc = finish_pending(ctx)) return rc;
-  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_query_out, call.outBytes, hipMemcpyDeviceToHost));
-  return LT_OK;
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, false, nullptr, check_paths, enqueue_paths);
 }
 
 extern "C" int lt_hip_shade_paths_device(lt_hip_context* ctx, const lt_hip_paths_desc* desc, const lt_hip_shade_ray* rays, uint64_t n, lt_hip_shade* out,
                                          uint64_t out_bytes, void* hip_stream) {
-  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  PathsCall call{};
-  if (const int rc = check_paths(ctx, desc, rays, n, out, out_bytes, true, call)) return rc;
-  if (n == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return enqueue_paths(ctx, call, desc, rays, n, out, (hipStream_t)hip_stream);
+  return run_ray_call(ctx, desc, rays, n, out, out_bytes, true, hip_stream, check_paths, enqueue_paths);
 }
 
 extern "C" int lt_hip_untile(lt_hip_context* ctx, const float* gathered, uint64_t floats_per_rank, uint32_t n_ranks, uint32_t width,

@@ -151,6 +151,29 @@ def reference_camera_rays(camera28, W, H):
     return o, d, fx, fy
 
 
+def ray_records(rays, record_dtype, names):
+    """A numpy batch of 32-byte ray records as a contiguous (n, 8) float32 array: an (n, 8) float32 array as it is, a 1-D array of
+    `record_dtype` viewed as one.  names: (the function that packs such records, the dtype's name), for the error's text."""
+    if rays.dtype == record_dtype and rays.ndim == 1:
+        rays = rays.view(np.float32).reshape(-1, 8)
+    if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("rays must be an (n, 8) float32 array (%s) or a %s array" % names)
+    return np.ascontiguousarray(rays)
+
+
+_QUERY_RAYS = (RAY_DTYPE, ("make_rays", "RAY_DTYPE"))
+_SHADE_RAYS = (SHADE_RAY_DTYPE, ("make_shade_rays", "SHADE_RAY_DTYPE"))
+
+
+def _program_id(program):
+    return program if isinstance(program, int) else C.program_from_path(str(program))
+
+
+def _ray_flags(coherent, portable_math, strict_math):
+    return ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
+            (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
+
+
 class RendererHIP:
     """One context per GPU.  `device` is the HIP ordinal."""
 
@@ -268,6 +291,42 @@ class RendererHIP:
         return buf
 
     # -- ray queries ------------------------------------------------------------------------------------
+    def _host_call(self, name, d, records, out):
+        """lt_hip_<name> over a contiguous numpy array of records; fills and returns `out`, one result per record."""
+        self._check(getattr(self._L, "lt_hip_" + name)(self._ctx, ctypes.byref(d), records.ctypes.data_as(ctypes.c_void_p), records.shape[0],
+                                                       out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+        return out
+
+    def _device_call(self, name, d, records, what, lead, width, result, stream):
+        """lt_hip_<name>_device over a contiguous (`lead`, width) float32 tensor of records on this context's GPU (lead "n": two
+        dimensions, "...": any number), enqueued on `stream`; returns a new tensor of dtype result[0] whose last dimension is
+        replaced by the shape result[1]."""
+        import torch
+        if not isinstance(records, torch.Tensor):
+            raise TypeError("%s must be a numpy array or a torch tensor" % what)
+        dims_ok = records.dim() == 2 if lead == "n" else records.dim() >= 1
+        if records.dtype != torch.float32 or not dims_ok or records.shape[-1] != width or not records.is_contiguous():
+            raise ValueError("%s must be a contiguous (%s, %d) float32 tensor" % (what, lead, width))
+        dev = torch.device("cuda", self.device)
+        if records.device != dev:
+            raise ValueError("%s must be on %s, the context's device" % (what, dev))
+        out = torch.empty(tuple(records.shape[:-1]) + result[1], dtype=getattr(torch, result[0]), device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        self._check(getattr(self._L, "lt_hip_" + name + "_device")(self._ctx, ctypes.byref(d), ctypes.c_void_p(records.data_ptr()),
+                                                                   records.numel() // width, ctypes.c_void_p(out.data_ptr()),
+                                                                   out.numel() * out.element_size(), ctypes.c_void_p(handle)))
+        return out
+
+    def _ray_call(self, name, d, rays, kind, host_result, device_result, stream):
+        """Rays through lt_hip_<name>: a numpy batch (kind: ray_records' arguments) gives numpy -- host_result: (dtype, shape per
+        ray) --, a torch tensor gives torch -- device_result: the same with the dtype's name."""
+        if isinstance(rays, np.ndarray):
+            rays = ray_records(rays, *kind)
+            return self._host_call(name, d, rays, np.zeros((rays.shape[0],) + host_result[1], dtype=host_result[0]))
+        return self._device_call(name, d, rays, "rays", "n", 8, device_result, stream)
+
     def trace_rays(self, rays, any_hit=False, program="accumulator", coherent=False, portable_math=False, strict_math=False, stream=None):
         """Traces caller-supplied rays against the scene of the last set_scene / render (lt_hip_trace_rays): as the reference's
         intersect / intersectIgnorePrimitiveIndex would, with the triangle epsilon of `program` (an LT_PROGRAM_* id or a kernel path).
@@ -276,42 +335,10 @@ class RendererHIP:
         (n, 8) float32 torch tensor on this context's GPU -- then the query is enqueued on `stream` (default: the current torch
         stream) and torch comes back: an (n, 4) float32 tensor of lt_hip_hit records (column 1 holds int32 bits: .view(torch.int32))
         or an (n,) int32 tensor of occluded words.  coherent: runs of 64 consecutive rays are coherent (LT_TRACE_FLAG_COHERENT)."""
-        if not isinstance(program, int):
-            program = C.program_from_path(str(program))
-        d = C.TraceDesc()
-        d.struct_size = ctypes.sizeof(C.TraceDesc)
-        d.program = program
-        d.kind = C.TRACE_ANY if any_hit else C.TRACE_CLOSEST
-        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
-                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
-        if isinstance(rays, np.ndarray):
-            if rays.dtype == RAY_DTYPE and rays.ndim == 1:
-                rays = rays.view(np.float32).reshape(-1, 8)
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-                raise ValueError("rays must be an (n, 8) float32 array (make_rays) or a RAY_DTYPE array")
-            rays = np.ascontiguousarray(rays)
-            n = rays.shape[0]
-            out = np.zeros(n, dtype=np.uint32 if any_hit else HIT_DTYPE)
-            self._check(self._L.lt_hip_trace_rays(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
-                                                  out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
-            return out
-        import torch
-        if not isinstance(rays, torch.Tensor):
-            raise TypeError("rays must be a numpy array or a torch tensor")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
-        dev = torch.device("cuda", self.device)
-        if rays.device != dev:
-            raise ValueError("rays must be on %s, the context's device" % dev)
-        n = rays.shape[0]
-        out = torch.empty((n,) if any_hit else (n, 4), dtype=torch.int32 if any_hit else torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        self._check(self._L.lt_hip_trace_rays_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
-                                                     ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
-                                                     ctypes.c_void_p(handle)))
-        return out
+        d = C.TraceDesc(ctypes.sizeof(C.TraceDesc), _program_id(program), C.TRACE_ANY if any_hit else C.TRACE_CLOSEST,
+                        _ray_flags(coherent, portable_math, strict_math))
+        return self._ray_call("trace_rays", d, rays, _QUERY_RAYS, (np.uint32, ()) if any_hit else (HIT_DTYPE, ()),
+                              ("int32", ()) if any_hit else ("float32", (4,)), stream)
 
     def trace_hits(self, rays, max_hits=4, count=False, program="accumulator", portable_math=False, strict_math=False, coherent=False,
                    stream=None):
@@ -322,46 +349,13 @@ class RendererHIP:
         (t = tmax, prim -1), or (n,) uint32 counts; a torch tensor on this context's GPU is enqueued on `stream` (default: the
         current torch stream) and torch comes back: (n, max_hits, 4) float32 (column 1: int32 bits) or (n,) int32 counts.
         coherent is accepted and changes nothing: these queries have no packet walk."""
-        if not isinstance(program, int):
-            program = C.program_from_path(str(program))
-        d = C.MultiHitDesc()
-        d.struct_size = ctypes.sizeof(C.MultiHitDesc)
-        d.program = program
-        d.kind = C.TRACE_COUNT if count else C.TRACE_FIRST_K
-        d.max_hits = 0 if count else max_hits
-        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
-                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
+        d = C.MultiHitDesc(ctypes.sizeof(C.MultiHitDesc), _program_id(program), C.TRACE_COUNT if count else C.TRACE_FIRST_K,
+                           _ray_flags(coherent, portable_math, strict_math), 0 if count else max_hits)
         if not count and not 1 <= max_hits <= C.TRACE_MAX_HITS:
             raise ValueError("max_hits must be in 1..%d" % C.TRACE_MAX_HITS)
         k = 0 if count else int(max_hits)
-        if isinstance(rays, np.ndarray):
-            if rays.dtype == RAY_DTYPE and rays.ndim == 1:
-                rays = rays.view(np.float32).reshape(-1, 8)
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-                raise ValueError("rays must be an (n, 8) float32 array (make_rays) or a RAY_DTYPE array")
-            rays = np.ascontiguousarray(rays)
-            n = rays.shape[0]
-            out = np.zeros(n, dtype=np.uint32) if count else np.zeros((n, k), dtype=HIT_DTYPE)
-            self._check(self._L.lt_hip_trace_hits(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
-                                                  out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
-            return out
-        import torch
-        if not isinstance(rays, torch.Tensor):
-            raise TypeError("rays must be a numpy array or a torch tensor")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
-        dev = torch.device("cuda", self.device)
-        if rays.device != dev:
-            raise ValueError("rays must be on %s, the context's device" % dev)
-        n = rays.shape[0]
-        out = torch.empty((n,) if count else (n, k, 4), dtype=torch.int32 if count else torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        self._check(self._L.lt_hip_trace_hits_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
-                                                     ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
-                                                     ctypes.c_void_p(handle)))
-        return out
+        return self._ray_call("trace_hits", d, rays, _QUERY_RAYS, (np.uint32, ()) if count else (HIT_DTYPE, (k,)),
+                              ("int32", ()) if count else ("float32", (k, 4)), stream)
 
     # -- surface queries -------------------------------------------------------------------------------
     def trace_surface(self, rays, program="accumulator", coherent=False, portable_math=False, strict_math=False, stream=None):
@@ -372,42 +366,8 @@ class RendererHIP:
         to the host entry point and an (n,) SURFACE_DTYPE array comes back; a contiguous (n, 8) float32 torch tensor on this
         context's GPU is enqueued on `stream` (default: the current torch stream) and an (n, 12) float32 tensor comes back
         (columns 1, 7 and 11 hold integer bits: .view(torch.int32))."""
-        if not isinstance(program, int):
-            program = C.program_from_path(str(program))
-        d = C.TraceDesc()
-        d.struct_size = ctypes.sizeof(C.TraceDesc)
-        d.program = program
-        d.kind = C.TRACE_CLOSEST
-        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
-                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
-        if isinstance(rays, np.ndarray):
-            if rays.dtype == RAY_DTYPE and rays.ndim == 1:
-                rays = rays.view(np.float32).reshape(-1, 8)
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-                raise ValueError("rays must be an (n, 8) float32 array (make_rays) or a RAY_DTYPE array")
-            rays = np.ascontiguousarray(rays)
-            n = rays.shape[0]
-            out = np.zeros(n, dtype=SURFACE_DTYPE)
-            self._check(self._L.lt_hip_trace_surface(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
-                                                     out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
-            return out
-        import torch
-        if not isinstance(rays, torch.Tensor):
-            raise TypeError("rays must be a numpy array or a torch tensor")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
-        dev = torch.device("cuda", self.device)
-        if rays.device != dev:
-            raise ValueError("rays must be on %s, the context's device" % dev)
-        n = rays.shape[0]
-        out = torch.empty((n, 12), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        self._check(self._L.lt_hip_trace_surface_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
-                                                        ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
-                                                        ctypes.c_void_p(handle)))
-        return out
+        d = C.TraceDesc(ctypes.sizeof(C.TraceDesc), _program_id(program), C.TRACE_CLOSEST, _ray_flags(coherent, portable_math, strict_math))
+        return self._ray_call("trace_surface", d, rays, _QUERY_RAYS, (SURFACE_DTYPE, ()), ("float32", (12,)), stream)
 
     def surface_at(self, hits, portable_math=False, strict_math=False, stream=None):
         """The surface records of hit records the caller has (lt_hip_surface_at) -- above all trace_hits' K per ray: t, u and v
@@ -416,34 +376,13 @@ class RendererHIP:
         runs and a SURFACE_DTYPE array of the same shape comes back; or a contiguous (..., 4) float32 torch tensor on this
         context's GPU -- then the call is enqueued on `stream` (default: the current torch stream) and a (..., 12) float32 tensor
         comes back."""
-        d = C.SurfaceDesc()
-        d.struct_size = ctypes.sizeof(C.SurfaceDesc)
-        d.flags = (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) | (C.RENDER_FLAG_STRICT_MATH if strict_math else 0)
+        d = C.SurfaceDesc(ctypes.sizeof(C.SurfaceDesc), _ray_flags(False, portable_math, strict_math))
         if isinstance(hits, np.ndarray):
             if hits.dtype != HIT_DTYPE:
                 raise ValueError("hits must be a HIT_DTYPE array")
             flat = np.ascontiguousarray(hits).reshape(-1)
-            out = np.zeros(flat.shape[0], dtype=SURFACE_DTYPE)
-            self._check(self._L.lt_hip_surface_at(self._ctx, ctypes.byref(d), flat.ctypes.data_as(ctypes.c_void_p), flat.shape[0],
-                                                  out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
-            return out.reshape(hits.shape)
-        import torch
-        if not isinstance(hits, torch.Tensor):
-            raise TypeError("hits must be a numpy array or a torch tensor")
-        if hits.dtype != torch.float32 or hits.dim() < 1 or hits.shape[-1] != 4 or not hits.is_contiguous():
-            raise ValueError("hits must be a contiguous (..., 4) float32 tensor")
-        dev = torch.device("cuda", self.device)
-        if hits.device != dev:
-            raise ValueError("hits must be on %s, the context's device" % dev)
-        n = hits.numel() // 4
-        out = torch.empty(tuple(hits.shape[:-1]) + (12,), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        self._check(self._L.lt_hip_surface_at_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(hits.data_ptr()), n,
-                                                     ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
-                                                     ctypes.c_void_p(handle)))
-        return out
+            return self._host_call("surface_at", d, flat, np.zeros(flat.shape[0], dtype=SURFACE_DTYPE)).reshape(hits.shape)
+        return self._device_call("surface_at", d, hits, "hits", "...", 4, ("float32", (12,)), stream)
 
     # -- shaded rays ------------------------------------------------------------------------------------
     def shade_rays(self, rays, program="accumulator", frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR, portable_math=False,
@@ -457,43 +396,9 @@ class RendererHIP:
         context's GPU -- then the call is enqueued on `stream` (default: the current torch stream) and an (n, 4) float32 tensor
         comes back (column 3 holds int32 bits: .view(torch.int32)).  coherent is accepted and changes nothing: there is no
         packet path."""
-        if not isinstance(program, int):
-            program = C.program_from_path(str(program))
-        d = C.ShadeDesc()
-        d.struct_size = ctypes.sizeof(C.ShadeDesc)
-        d.program = program
-        d.kernel_mode = kernel_mode
-        d.frame_first, d.frame_count = frame_first, frame_count
-        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
-                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
-        if isinstance(rays, np.ndarray):
-            if rays.dtype == SHADE_RAY_DTYPE and rays.ndim == 1:
-                rays = rays.view(np.float32).reshape(-1, 8)
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-                raise ValueError("rays must be an (n, 8) float32 array (make_shade_rays) or a SHADE_RAY_DTYPE array")
-            rays = np.ascontiguousarray(rays)
-            n = rays.shape[0]
-            out = np.zeros(n, dtype=SHADE_DTYPE)
-            self._check(self._L.lt_hip_shade_rays(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
-                                                  out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
-            return out
-        import torch
-        if not isinstance(rays, torch.Tensor):
-            raise TypeError("rays must be a numpy array or a torch tensor")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
-        dev = torch.device("cuda", self.device)
-        if rays.device != dev:
-            raise ValueError("rays must be on %s, the context's device" % dev)
-        n = rays.shape[0]
-        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        self._check(self._L.lt_hip_shade_rays_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
-                                                     ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
-                                                     ctypes.c_void_p(handle)))
-        return out
+        d = C.ShadeDesc(ctypes.sizeof(C.ShadeDesc), _program_id(program), kernel_mode, _ray_flags(coherent, portable_math, strict_math),
+                        frame_first, frame_count)
+        return self._ray_call("shade_rays", d, rays, _SHADE_RAYS, (SHADE_DTYPE, ()), ("float32", (4,)), stream)
 
     # -- shaded paths -----------------------------------------------------------------------------------
     def shade_paths(self, rays, program="global_illumination", gi_max_depth=0, frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR,
@@ -506,44 +411,9 @@ class RendererHIP:
         SHADE_DTYPE array out; or a contiguous (n, 8) float32 torch tensor on this context's GPU in, enqueued on `stream` (default:
         the current torch stream), an (n, 4) float32 tensor out (column 3 holds int32 bits).  coherent is accepted and changes
         nothing."""
-        if not isinstance(program, int):
-            program = C.program_from_path(str(program))
-        d = C.PathsDesc()
-        d.struct_size = ctypes.sizeof(C.PathsDesc)
-        d.program = program
-        d.kernel_mode = kernel_mode
-        d.frame_first, d.frame_count = frame_first, frame_count
-        d.gi_max_depth = gi_max_depth
-        d.flags = ((C.TRACE_FLAG_COHERENT if coherent else 0) | (C.RENDER_FLAG_PORTABLE_MATH if portable_math else 0) |
-                   (C.RENDER_FLAG_STRICT_MATH if strict_math else 0))
-        if isinstance(rays, np.ndarray):
-            if rays.dtype == SHADE_RAY_DTYPE and rays.ndim == 1:
-                rays = rays.view(np.float32).reshape(-1, 8)
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-                raise ValueError("rays must be an (n, 8) float32 array (make_shade_rays) or a SHADE_RAY_DTYPE array")
-            rays = np.ascontiguousarray(rays)
-            n = rays.shape[0]
-            out = np.zeros(n, dtype=SHADE_DTYPE)
-            self._check(self._L.lt_hip_shade_paths(self._ctx, ctypes.byref(d), rays.ctypes.data_as(ctypes.c_void_p), n,
-                                                   out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
-            return out
-        import torch
-        if not isinstance(rays, torch.Tensor):
-            raise TypeError("rays must be a numpy array or a torch tensor")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
-        dev = torch.device("cuda", self.device)
-        if rays.device != dev:
-            raise ValueError("rays must be on %s, the context's device" % dev)
-        n = rays.shape[0]
-        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        self._check(self._L.lt_hip_shade_paths_device(self._ctx, ctypes.byref(d), ctypes.c_void_p(rays.data_ptr()), n,
-                                                      ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
-                                                      ctypes.c_void_p(handle)))
-        return out
+        d = C.PathsDesc(ctypes.sizeof(C.PathsDesc), _program_id(program), kernel_mode, _ray_flags(coherent, portable_math, strict_math),
+                        frame_first, frame_count, gi_max_depth)
+        return self._ray_call("shade_paths", d, rays, _SHADE_RAYS, (SHADE_DTYPE, ()), ("float32", (4,)), stream)
 
     def stats(self):
         s = C.Stats()

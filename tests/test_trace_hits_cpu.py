@@ -164,3 +164,30 @@ def test_expected_records_pad_with_the_rays_own_tmax_bits():
     assert rec.shape == (2, 2) and rec[0, 0].tolist() == (1.5, 7, 0.25, 0.5)
     assert rec[0, 1]["prim"] == -1 and rec[0, 1]["t"] == np.float32(FLT_MAX) and rec[0, 1]["u"] == 0
     assert rec["t"].view(np.uint32)[1].tolist() == [0x7fc12345] * 2 and (rec["prim"][1] == -1).all()
+
+
+# ------------------------------------------------------------------------------------------- the wrappers' numpy ray batches
+def test_ray_records_normalises_numpy_batches_and_refuses_the_rest():
+    import pytest
+    from lens_trace_amd.renderer import RAY_DTYPE, SHADE_RAY_DTYPE, make_shade_rays, ray_records
+    rng = np.random.default_rng(3)
+    n = 7
+    packed = {"RAY_DTYPE": make_rays(rng.normal(size=(n, 3)), rng.normal(size=(n, 3)), 9.0, np.arange(n)),
+              "SHADE_RAY_DTYPE": make_shade_rays(rng.normal(size=(n, 3)), rng.normal(size=(n, 3)), 0.25, rng.uniform(size=n))}
+    for (name, rays), dtype, maker in zip(packed.items(), (RAY_DTYPE, SHADE_RAY_DTYPE), ("make_rays", "make_shade_rays")):
+        names = (maker, name)
+        text = "rays must be an (n, 8) float32 array (%s) or a %s array" % names
+        wide = np.repeat(rays, 2, axis=0)
+        wide[1::2] = -1.0
+        cases = (rays.reshape(-1).view(dtype), rays, wide[::2], np.asfortranarray(rays), np.zeros((0, 8), dtype=np.float32))
+        assert cases[0].shape == (n,) and not cases[2].flags.c_contiguous and not cases[3].flags.c_contiguous
+        for a, want in zip(cases, (rays, rays, rays, rays, rays[:0])):
+            got = ray_records(a, dtype, names)
+            assert got.dtype == np.float32 and got.shape == want.shape and got.flags.c_contiguous
+            assert got.tobytes() == want.tobytes()
+        other = SHADE_RAY_DTYPE if dtype is RAY_DTYPE else RAY_DTYPE
+        for bad in (rays.astype(np.float64), rays.reshape(-1), rays[:, :7], rays.reshape(n, 2, 4), rays.reshape(-1).view(other),
+                    rays.reshape(-1).view(dtype).reshape(n, 1), rays.view(np.int32)):
+            with pytest.raises(ValueError) as e:
+                ray_records(bad, dtype, names)
+            assert str(e.value) == text
