@@ -221,7 +221,8 @@ int lt_hip_render_device(lt_hip_context* ctx, const lt_hip_render_desc* desc, fl
                          uint64_t out_bytes, void* hip_stream);
 
 /* Scatters a gathered stack of per-rank tile buffers (rank r holds tiles r, r+n_ranks, ...) into the
- * reference's row-major image.  All pointers are device memory; runs on hip_stream. */
+ * reference's row-major image.  All pointers are device memory; runs on hip_stream.  The image: at most 2^31 - 1 pixels, as for
+ * the render calls (LT_ERR_INVALID_ARGUMENT, "image too large"). */
 int lt_hip_untile(lt_hip_context* ctx, const float* gathered, uint64_t floats_per_rank, uint32_t n_ranks,
                   uint32_t width, uint32_t height, uint32_t depth, uint32_t tile_w, uint32_t tile_h,
                   float* image_out, void* hip_stream);
@@ -287,9 +288,10 @@ typedef struct lt_hip_trace_desc {
 
 /* Host memory, synchronous.  LT_ERR_INVALID_ARGUMENT: null ctx / desc, a null pointer with n > 0, an unknown kind, n >= 2^32, a
  * user program, STRICT with PORTABLE, any other flag, struct_size too small (and, device entry point, pointers that are not
- * 16-byte aligned); LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when out_bytes < n records.  A failed call writes nothing to out;
- * n == 0 launches nothing.  lt_hip_get_stats then reports rays = n (closest) or shadow_rays = n (any), kernel_launches and
- * kernel_ms. */
+ * 16-byte aligned); with LT_TRACE_FLAG_COHERENT also n > 2^32 - 64 (one workgroup per 64 rays: from 2^32 - 63 rays on that is
+ * 2^32 work-items, more than a launch can hold; lt_hip_trace_surface likewise); LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when
+ * out_bytes < n records.  A failed call writes nothing to out; n == 0 launches nothing.  lt_hip_get_stats then reports rays = n
+ * (closest) or shadow_rays = n (any), kernel_launches and kernel_ms. */
 int lt_hip_trace_rays(lt_hip_context* ctx, const lt_hip_trace_desc* desc, const lt_hip_ray* rays, uint64_t n,
                       void* out, uint64_t out_bytes);
 /* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */

@@ -1121,7 +1121,8 @@ static int plan_tiles(const lt_hip_render_desc* d, TilePlan& p, std::string& msg
   p.tilesX = (d->width + p.tileW - 1) / p.tileW;
   p.tilesY = (d->height + p.tileH - 1) / p.tileH;
   const uint32_t total = p.tilesX * p.tilesY;
-  p.tilesInCall = p.tileFirst < total ? (total - p.tileFirst + p.tileStride - 1) / p.tileStride : 0;
+  // (in 64 bits: a tile_stride near 2^32 -- "this tile alone" -- would wrap the sum to a count of 0)
+  p.tilesInCall = p.tileFirst < total ? (uint32_t)(((uint64_t)total - p.tileFirst + p.tileStride - 1) / p.tileStride) : 0;
   p.bptx = (p.tileW + 7) / 8;
   p.bpty = (p.tileH + 7) / 8;
   p.floats = (uint64_t)p.tilesInCall * p.tileW * p.tileH * d->depth;
@@ -1530,7 +1531,8 @@ static int plan_fusion(lt_hip_context* ctx, const RenderKnobs& k, const lt_hip_r
   const bool giWavefront = giProgram && !stats && nblocks > 0 && (k.gi_wavefront >= 0 ? k.gi_wavefront != 0 : (ctx->n_prims >= 1024u || giManyLongPaths));
   const uint64_t giPixels = (uint64_t)p.tilesInCall * p.tileW * p.tileH;
   const uint64_t giSlots = std::max<uint64_t>(giPixels, nblocks * kBlock);   // (a direct-mapped path queue has a slot per lane of every square)
-  if (giWavefront && giSlots > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "too many pixels for the GI path queues");
+  // (the stages' grids round the slots of a launch up to whole blocks of 256: 2^32 - 256 slots are the most a launch holds)
+  if (giWavefront && giSlots > 0xffffff00ull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "too many pixels for the GI path queues");
   // Several samples of a running mean in ONE launch.  A launch cannot end before its slowest wavefront does -- one 8x8 square
   // is a dependent chain of several hundred node fetches, ~0.3-0.6 ms on the 1 M-triangle scene, 1.9 ms for the squares on
   // the image's centre column -- so a launch per sample pays that drain once per sample: 0.65 ms of a 4.5 ms launch for the
@@ -1549,9 +1551,11 @@ static int plan_fusion(lt_hip_context* ctx, const RenderKnobs& k, const lt_hip_r
   if (gi25Sets || ((giFusable || (k.persistent && !giWavefront)) && !stats && frames > 1 && d->accumulate && nblocks > 0)) {
     const uint64_t frameBytes = p.floats * sizeof(float);
     const uint64_t scratchPerFrame = frameBytes + (giWavefront ? giSlots * 16 * 17 : 0);
-    if (k.fused_frames && frameBytes > 0)
+    // (lt_running_mean_kernel runs one thread per float of a sample image, 256 to a block: 2^32 - 256 floats are the most one
+    // launch holds.  Under the default LT_FUSED_BYTES two such images do not fit the scratch anyway; a larger cap must not fuse them.)
+    if (k.fused_frames && frameBytes > 0 && p.floats <= 0xffffff00ull)
       chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)(gi25Sets ? 25u : frames), k.fused_bytes / scratchPerFrame, 0xffffffffull / nblocks,
-                                                                  giWavefront ? 0xffffffffull / std::max<uint64_t>(giSlots, 1) : ~0ull}));
+                                                                  giWavefront ? 0xffffff00ull / std::max<uint64_t>(giSlots, 1) : ~0ull}));
     // a device that cannot spare the scratch memory gets shorter launches, down to one sample per launch
     while ((chunk > 1 || gi25Sets) && grow_scratch(ctx, ctx->d_samples, ctx->d_samples_bytes, chunk * frameBytes, chunk * frameBytes) != hipSuccess) {
       (void)hipGetLastError();
@@ -1753,8 +1757,10 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   // out differently.  shadow_mode[program] keeps the most recent verdict for callers without a geometry of their own: the GI pipeline)
   const std::vector<uint32_t> shadowKey = {(uint32_t)d->program, d->width, d->height, p.tileW, p.tileH, p.tileFirst, p.tileStride,
                                            firstFrames == 1u ? 1u : firstFrames < 8u ? 2u : 8u};
+  // (the slots: a 32-bit index, and lt_shadow_resolve_kernel strides over them with `i += stride` in 32 bits -- its grid of 8 blocks
+  // of 256 threads per CU: the count stays one stride below 2^32, or the sum would wrap and the loop never end)
   const bool queueOk = d->program == LT_PROGRAM_ACCUMULATOR && k.persistent && !stats && ctx->d_rank8 != nullptr && !meanInLaunch &&
-                       nblocks * firstFrames * kBlock < 0xffffffffull;
+                       nblocks * firstFrames * kBlock + (uint64_t)ctx->cu_count * 2048u <= 0xffffffffull;
   int shadowMode = choose_shadow_walk(ctx, k, d, shadowKey, queueOk || nblocks == 0);
   // frames per work item of walks 1 and 2 (launch_walk): LT_SHADOW_FRAMES where the walk is forced, else what it was timed with
   uint32_t shadowGroup = k.shadow_frames;
@@ -2037,6 +2043,7 @@ static_assert(sizeof(lt_hip_paths_desc) == 32, "path-shading descriptor (include
 struct RayCall {
   int devlibm;
   uint64_t outRecord;
+  bool chunkGrid = false;   // the call launches one 64-lane workgroup per 64 records (lt_query_packet_kernel)
 };
 
 // The nouns of a family's error texts: the call, its records, what a batch of them is, the input pointer.
@@ -2062,6 +2069,10 @@ static int check_ray_flags(lt_hip_context* ctx, uint32_t flags, bool coherent, c
 static int check_ray_buffers(lt_hip_context* ctx, const RayWording& w, const void* in, uint64_t n, const void* out, uint64_t out_bytes, bool device,
                              const RayCall& call) {
   if (n > 0xffffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("at most 2^32 - 1 ") + w.records + " per " + w.batch);
+  // A grid of ceil(n / 64) workgroups of 64 lanes has 2^32 work-items from n = 2^32 - 63 on, one more than a dispatch's 32-bit
+  // grid size holds: the launch would fail.  Every other kernel of these calls runs a grid of the chip's size.
+  if (call.chunkGrid && n > 0xffffffc0ull)
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("at most 2^32 - 64 ") + w.records + " per " + w.batch + " with LT_TRACE_FLAG_COHERENT");
   if (n > 0 && (!in || !out)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(w.in) + " or out is NULL");
   if (device && n > 0 && (((uintptr_t)in | (uintptr_t)out) & 15u))
     return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("device ") + w.in + " and out must be 16-byte aligned");
@@ -2164,6 +2175,7 @@ static int check_trace(lt_hip_context* ctx, const lt_hip_trace_desc* d, const lt
   if (const int rc = check_ray_flags(ctx, d->flags, true, "ray queries take", tc)) return rc;
   tc.anyHit = d->kind == LT_TRACE_ANY;
   tc.coherent = (d->flags & LT_TRACE_FLAG_COHERENT) != 0;
+  tc.chunkGrid = tc.coherent;
   tc.outRecord = tc.surface ? sizeof(lt_hip_surface) : tc.anyHit ? sizeof(uint32_t) : sizeof(lt_hip_hit);
   return check_ray_buffers(ctx, kQueryWording, rays, n, out, out_bytes, device, tc);
 }
@@ -2462,7 +2474,9 @@ static int enqueue_paths(lt_hip_context* ctx, const PathsCall& call, const void*
   const uint32_t perFrame = call.gi25 ? 25u : 1u, frames = d->frame_count;
   uint64_t cap = std::min<uint64_t>(kPathsSlots, k.fused_bytes / (17 * 16));
   if (const char* e = getenv("LT_PATHS_SLOTS")) cap = strtoull(e, nullptr, 10);   // (tests, A/B measurements; no result depends on it)
-  cap = std::min<uint64_t>(std::max<uint64_t>(cap, perFrame), 0xffffffffull);
+  // (lt_paths_primary_kernel runs one lane per slot, 64 to a block, the stage and resolve kernels one per ray, 256 to a block: a
+  // launch holds 2^32 - 1 work-items, so a set has at most 2^32 - 256 slots)
+  cap = std::min<uint64_t>(std::max<uint64_t>(cap, perFrame), 0xffffff00ull);
   const uint64_t perRay = (uint64_t)frames * perFrame;
   const uint32_t framesPerSet = perRay <= cap ? frames : (uint32_t)(cap / perFrame);
   const uint64_t raysAtMost = std::min<uint64_t>(n, std::max<uint64_t>(1, cap / ((uint64_t)framesPerSet * perFrame)));
@@ -2528,6 +2542,8 @@ extern "C" int lt_hip_untile(lt_hip_context* ctx, const float* gathered, uint64_
   if (!ctx) return LT_ERR_INVALID_ARGUMENT;
   if (!gathered || !image_out || !n_ranks || !width || !height || depth < 1 || !tile_w || !tile_h)
     return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_untile: bad argument");
+  // (the images the render calls take, plan_tiles: lt_untile_kernel's tile index and its grid of one thread per pixel are 32-bit)
+  if ((uint64_t)width * height > 0x7fffffffull) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_untile: image too large");
   const uint32_t tilesX = (width + tile_w - 1) / tile_w, tilesY = (height + tile_h - 1) / tile_h;
   const uint64_t maxTilesPerRank = ((uint64_t)tilesX * tilesY + n_ranks - 1) / n_ranks;
   if (floats_per_rank < maxTilesPerRank * tile_w * tile_h * depth) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "lt_hip_untile: floats_per_rank too small");

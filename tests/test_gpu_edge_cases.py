@@ -281,5 +281,14 @@ def test_render_desc_errors_keep_their_codes_and_order():
             got, msg = call(*args)
             assert got == code and text in msg, (args[1:], got, msg, code, text)
         assert call(desc())[0] == C.LT_OK                                    # (the context is none the worse)
+        # the largest image: 2^31 - 1 pixels for the render calls and for lt_hip_untile alike (32-bit tile and pixel indices)
+        big = make_desc(C.PROGRAM_BASIC, 46341, 46341, 3, cam, tile=(8, 8, 0, 2 ** 32 - 1))
+        got, msg = call(big)
+        assert got == C.LT_ERR_INVALID_ARGUMENT and "image too large" in msg
+        vp = ctypes.c_void_p
+        assert L.lt_hip_untile(ctx, vp(buf.data_ptr()), 192, 1, 46341, 46341, 3, 8, 8, vp(buf.data_ptr()), vp(stream)) == C.LT_ERR_INVALID_ARGUMENT
+        assert L.lt_hip_last_error(ctx) == b"lt_hip_untile: image too large"
+        assert L.lt_hip_untile(ctx, vp(buf.data_ptr()), 192, 1, 46340, 46340, 3, 8, 8, vp(buf.data_ptr()), vp(stream)) == C.LT_ERR_BUFFER_TOO_SMALL
+        torch.cuda.synchronize()
     finally:
         r.close()

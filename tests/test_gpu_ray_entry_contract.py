@@ -70,6 +70,11 @@ QUERY_USER = "ray queries take a built-in program (it selects the triangle epsil
 QUERY_FLAGS = "ray queries take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH and LT_TRACE_FLAG_COHERENT only"
 QUERY_TAIL = common("rays", "query", "rays or out is NULL", "device rays and out must be 16-byte aligned", "ray query before lt_hip_set_scene")
 HEAD = [("ctx", INVALID, None, {"ctx": "null"}, {})]
+# lt_hip_trace_rays and lt_hip_trace_surface with LT_TRACE_FLAG_COHERENT launch one workgroup of 64 lanes per 64 rays: 2^32 - 63 rays
+# are 2^26 workgroups, 2^32 work-items, one more than a launch holds.  The first n refused, behind the check of n >= 2^32.
+COHERENT_N = ("coherent_n", INVALID, "at most 2^32 - 64 rays per query with LT_TRACE_FLAG_COHERENT",
+              [{"n": 2 ** 32 - 63, "flags": C.TRACE_FLAG_COHERENT}, {"n": 2 ** 32 - 1, "flags": C.TRACE_FLAG_COHERENT | C.RENDER_FLAG_PORTABLE_MATH}], {})
+TRACE_TAIL = QUERY_TAIL[:1] + [COHERENT_N] + QUERY_TAIL[1:]
 
 
 def trace_checks(surface):
@@ -83,7 +88,7 @@ def trace_checks(surface):
         ("program", UNKNOWN, "unknown program", [{"program": 6}, {"program": -1}], {}),
         ("flags", INVALID, QUERY_FLAGS, [{"flags": C.RENDER_FLAG_STATS}, {"flags": 0x200}], {"exclude": {"flags": BOTH | C.RENDER_FLAG_STATS}}),
         ("exclude", INVALID, EXCLUDE, {"flags": BOTH}, {}),
-    ] + QUERY_TAIL
+    ] + TRACE_TAIL
 
 
 HITS_CHECKS = HEAD + [
@@ -254,6 +259,21 @@ def test_every_check_gives_its_code_and_text_and_the_earlier_of_two_wins(context
         assert call({"n": 0, "inp": "odd", "out": "odd"})[0] == 0
         torch.cuda.synchronize()
     assert call.untouched(), family
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_the_coherent_limit_narrows_the_packet_grid_alone(contexts, device):
+    """n = 2^32 - 64 with LT_TRACE_FLAG_COHERENT, and n = 2^32 - 1 without it or in a family that has no packet kernel, pass every
+    check about n: such a call goes on to the next thing wrong with it, the room for its results."""
+    small = (TOO_SMALL, "out is smaller than n results")
+    for family in ("trace_rays", "trace_surface"):
+        call = Caller(*contexts, family, device)
+        assert call({"n": 2 ** 32 - 64, "flags": C.TRACE_FLAG_COHERENT}) == small, family
+        assert call({"n": 2 ** 32 - 1}) == small, family
+        assert call({"n": 2 ** 32 - 63, "flags": C.TRACE_FLAG_COHERENT})[0] == INVALID, family
+    for family in ("trace_hits", "shade_rays", "shade_paths"):
+        assert Caller(*contexts, family, device)({"n": 2 ** 32 - 1, "flags": C.TRACE_FLAG_COHERENT}) == small, family
+    assert Caller(*contexts, "surface_at", device)({"n": 2 ** 32 - 1}) == small
 
 
 # ---------------------------------------------------------------------------------------------- 2 - 4: the calls themselves

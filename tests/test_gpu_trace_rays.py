@@ -22,6 +22,7 @@ from lens_trace_amd.renderer import FLT_MAX, HIT_DTYPE, RendererHIP, make_rays
 from oracle import pyoracle as po
 from tests.conftest import GOLDEN, fuzz_scene
 from tests.conftest import oracle_props as RenderPropertiesHIP
+from tests.query_edges import Oracle, on_triangle, random_rays, root_box, same_hits   # noqa: F401 (other test files take them from here)
 from tests.test_gpu_own_hierarchy import doubled_scene
 
 pytestmark = pytest.mark.gpu
@@ -37,104 +38,7 @@ def renderer():
     r.close()
 
 
-# ------------------------------------------------------------------------------------------------------- rays and the oracle
-def root_box(s):
-    nv = s.node_view
-    return nv["boundsMin"][0].astype(np.float64), nv["boundsMax"][0].astype(np.float64)
-
-
-def on_triangle(s, prims, rng):
-    pv = s.prim_view
-    b = rng.dirichlet([1, 1, 1], len(prims)).astype(np.float32)
-    A, B, Cc = (pv[k][prims].astype(np.float32) for k in ("positionA", "positionB", "positionC"))
-    return (A * b[:, :1] + B * b[:, 1:2]) + Cc * b[:, 2:3]
-
-
-def random_rays(s, rng, n):
-    """n rays of every kind the contract names, rounded up to whole chunks of 64, then 4 chunks of 64 coherent rays that start on
-    a multiple of 64 (so that the packet kernel walks them as packets)."""
-    n = -(-n // 64) * 64
-    lo, hi = root_box(s)
-    ext = np.maximum(hi - lo, 1e-3)
-    o = rng.uniform(lo - 0.5 * ext, hi + 0.5 * ext, (n, 3))
-    d = rng.normal(0, 1, (n, 3))
-    k = rng.integers(0, 10, n)
-    axis = rng.integers(0, 3, n)
-    sign = rng.choice([-1.0, 1.0], (n, 3))
-    rows = np.arange(n)
-    par = k == 0                                           # axis-parallel: two signed zeros
-    d[par] = 0.0 * sign[par]
-    d[rows[par], axis[par]] = sign[par, 0]
-    one = k == 1                                           # one signed zero
-    d[rows[one], axis[one]] = 0.0 * sign[one, 1]
-    bad = np.flatnonzero(k == 2)                           # a non-finite component of the origin or the direction
-    val = rng.choice([np.inf, -np.inf, np.nan], len(bad))
-    half = rng.integers(0, 2, len(bad)) == 1
-    o[bad[half], axis[bad[half]]] = val[half]
-    d[bad[~half], axis[bad[~half]]] = val[~half]
-    big = np.flatnonzero(k == 3)                           # beyond 2^40, or a direction whose inverse is beyond 2^60
-    half = rng.integers(0, 2, len(big)) == 1
-    o[big[half]] = (o[big[half]] - (lo + hi) / 2) * 2.0 ** 41
-    d[big[~half], axis[big[~half]]] = 1e-20
-    tmax = rng.choice(np.array([FLT_MAX, np.inf, 0.0, -1.0, np.nan, -0.0], dtype=np.float64), n)
-    rnd = rng.integers(0, 3, n) == 0
-    tmax[rnd] = rng.uniform(0, 2 * np.linalg.norm(ext), rnd.sum())
-    tmax[rng.integers(0, 2, n) == 0] = FLT_MAX
-    ign = np.full(n, -1, dtype=np.int64)
-    start = np.flatnonzero(k >= 8)                          # rays that start on a triangle and ignore it
-    prims = rng.integers(0, s.n_prims, len(start))
-    o[start] = on_triangle(s, prims, rng)
-    ign[start] = prims
-    ign[k == 4] = rng.integers(-5, s.n_prims + 3, (k == 4).sum())
-    rays = [make_rays(o, d, tmax.astype(np.float32), ign)]
-    for c in range(4):                                     # coherent chunks: one origin, a small cone
-        oc = np.tile(rng.uniform(lo - 0.5 * ext, hi + 0.5 * ext), (64, 1))
-        dc = ((lo + hi) / 2 - oc[0]) + rng.normal(0, 0.05 * np.linalg.norm(ext), (64, 3))
-        ic = np.full(64, -1)
-        if c == 3:
-            p = rng.integers(0, s.n_prims, 64)
-            oc, ic = on_triangle(s, p, rng), p
-        rays.append(make_rays(oc, dc, np.float32(FLT_MAX), ic))
-    return np.concatenate(rays)
-
-
-class Oracle:
-    def __init__(self, s):
-        self.L = po.lib()
-        self.nodes, self.prims = np.ascontiguousarray(s.nodes), np.ascontiguousarray(s.prims)
-        self.np_, self.pp = self.nodes.ctypes.data_as(ctypes.c_void_p), self.prims.ctypes.data_as(ctypes.c_void_p)
-
-    def trace(self, rays, program):
-        """(closest-hit records as HIT_DTYPE, occluded words) of the reference for each ray (origin.w = 1, direction.w = +0)"""
-        n = len(rays)
-        hits = np.zeros(n, dtype=HIT_DTYPE)
-        occ = np.zeros(n, dtype=np.uint32)
-        o = np.ones(4, dtype=np.float32)
-        d = np.zeros(4, dtype=np.float32)
-        tuv = np.zeros(3, dtype=np.float32)
-        prim = ctypes.c_int(0)
-        ign = rays[:, 7].view(np.int32)
-        op, dp, tp = o.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p), tuv.ctypes.data_as(ctypes.c_void_p)
-        for i in range(n):
-            o[:3] = rays[i, 0:3]
-            d[:3] = rays[i, 4:7]
-            g = int(ign[i])
-            h = self.L.lt_oracle_trace(C.PROGRAM_ACCUMULATOR if program is None else program, self.np_, self.pp, op, dp,
-                                       ctypes.c_float(rays[i, 3]), 1 if g >= 0 else 0, max(g, 0), ctypes.byref(prim), tp)
-            hits[i] = (tuv[0], prim.value if h else -1, tuv[1], tuv[2])
-            occ[i] = 1 if h else 0
-        return hits, occ
-
-
-def same_hits(a, b):
-    """bit for bit, except that any two NaN t are equal (the oracle's tmax passes through a C float)"""
-    a, b = np.asarray(a).view(np.uint32).reshape(-1, 4), np.asarray(b).view(np.uint32).reshape(-1, 4)
-    ta, tb = a[:, 0].view(np.float32), b[:, 0].view(np.float32)
-    both_nan = np.isnan(ta) & np.isnan(tb)
-    ok = (a[:, 1:] == b[:, 1:]).all(axis=1) & ((a[:, 0] == b[:, 0]) | both_nan)
-    return np.flatnonzero(~ok)
-
-
+# (rays and the oracle: root_box, on_triangle, random_rays, Oracle and same_hits live in tests/query_edges.py, importable without a GPU)
 def check_scene(r, s, rays, want=None, flavours_any=True):
     """Every epsilon program, both kinds, both kernels: portable = the oracle bit for bit; any == (closest prim >= 0) in every
     flavour."""
