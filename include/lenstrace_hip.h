@@ -477,6 +477,52 @@ int lt_hip_surface_at(lt_hip_context* ctx, const lt_hip_surface_desc* desc, cons
 int lt_hip_surface_at_device(lt_hip_context* ctx, const lt_hip_surface_desc* desc, const lt_hip_hit* hits, uint64_t n,
                              lt_hip_surface* out, uint64_t out_bytes, void* hip_stream);
 
+/* Nearest-point queries: for each point the closest primitive of the resident scene, the squared distance and where on the
+ * primitive -- for lightmap bakers, sensor models, clearance and collision checks that would otherwise build a second hierarchy.
+ * The result is an lt_hip_hit with t = the squared distance, prim, u, v: lt_hip_surface_at turns it straight into the closest
+ * point (position), normal, material and light flag.  A miss has prim = -1, t = max_d2 with the bits given, u = v = +0.
+ *
+ * Candidates: the leaves of the caller's LinearBVHNode array, each with its one primitive (primitivesOffset), as every ray query
+ * enumerates them; a leaf with primitiveCount > 1 contributes that one primitive once.
+ * Distance of a point P to a candidate:  d2 = max(tri(P; A, e1, e2), box(P; the leaf's box)),  a NaN tri staying a NaN.
+ *   tri   on the traversal triangle as the scene stores it, A, e1 = fl(B - A), e2 = fl(C - A), with ap = P - A: four points of the
+ *         triangle are tried in this order and the first of the smallest squared distance (by `<`) is kept -- the closest point
+ *         of edge AB, (u, v) = (t, 0) with t = (e1.ap) / (e1.e1); of edge AC, (0, t) with t = (e2.ap) / (e2.e2); of edge BC,
+ *         (1 - t, t) with t = ((ap - e1).f) / (f.f), f = e2 - e1; each t held to [0, 1] (t > 0 else 0, then t > 1 gives 1: a NaN
+ *         counts as 0), so the vertices are the edges' ends; and the foot of the perpendicular, from e2's part at right angles
+ *         to e1, g = e2 - k e1 with k = (e1.e2) / (e1.e1): v = (ap.g) / (g.g), u = (e1.ap) / (e1.e1) - v k, where u >= 0, v >= 0
+ *         and u + v <= 1.  The point is A + u e1 + v e2 and the squared distance that of r = (ap - u e1) - v e2 per component.
+ *         Dot products and squared lengths are (x x' + y y') + z z'.  Every operation is one IEEE float32 operation rounded once,
+ *         in this order: nothing is contracted, `/` is the correctly rounded quotient, subnormals are kept
+ *         (lens_trace_amd/csrc/lt_nearest.hpp is the expression sequence; tests/nearest.py restates it in numpy).
+ *   box   the squared distance from P to the leaf's own box as the caller gave it: per axis g = max(lo - P, P - hi, +0), then
+ *         (g.x g.x + g.y g.y) + g.z g.z.
+ * Selection: a candidate is accepted iff d2 < max_d2 by the float `<` -- a NaN d2 or a NaN max_d2 never; 0, -0 and negative
+ * max_d2 give a miss, inf accepts every finite d2.  Among the accepted the smallest d2 wins, the lowest primitive offset among
+ * equal d2.  A point with a component that is not finite is a miss.  The answer is a function of the scene and the point alone:
+ * whichever hierarchy is walked, the bits are these.
+ *
+ * flags: 0.  Host memory, synchronous.  LT_ERR_INVALID_ARGUMENT: null ctx / desc, struct_size too small, flags != 0, n >= 2^32, a
+ * null pointer with n > 0 (and, device entry point, pointers that are not 16-byte aligned); LT_ERR_NO_SCENE;
+ * LT_ERR_BUFFER_TOO_SMALL when out_bytes < 16 n.  A failed call writes nothing to out; n == 0 launches nothing.
+ * lt_hip_get_stats then reports rays = n, kernel_launches = 1 and kernel_ms.  (lens_trace_amd/csrc/lt_nearest.hip) */
+typedef struct lt_hip_point { float p[3]; float max_d2; } lt_hip_point;      /* 16 B */
+typedef struct lt_hip_nearest_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_nearest_desc) */
+  uint32_t flags;               /* 0 */
+} lt_hip_nearest_desc;          /* 8 B */
+
+int lt_hip_nearest_points(lt_hip_context* ctx, const lt_hip_nearest_desc* desc, const lt_hip_point* points, uint64_t n,
+                          lt_hip_hit* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_nearest_points_device(lt_hip_context* ctx, const lt_hip_nearest_desc* desc, const lt_hip_point* points, uint64_t n,
+                                 lt_hip_hit* out, uint64_t out_bytes, void* hip_stream);
+/* The same answers on the host, without a context or a GPU, from the caller's buffers: nodes (LinearBVHNode, 32 bytes each) and
+ * prims (Primitive, 76 bytes each).  LT_ERR_INVALID_ARGUMENT (a null or mis-sized buffer, n >= 2^32), LT_ERR_BAD_SCENE (a leaf
+ * whose offset lies outside prims), LT_ERR_BUFFER_TOO_SMALL (out_bytes < 16 n); a failed call writes nothing. */
+int lt_hip_nearest_points_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                               const lt_hip_point* points, uint64_t n, lt_hip_hit* out, uint64_t out_bytes);
+
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
 

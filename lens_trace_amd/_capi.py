@@ -33,7 +33,8 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure",
            "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device",
            "lt_hip_shade_rays", "lt_hip_shade_rays_device", "lt_hip_shade_paths", "lt_hip_shade_paths_device",
-           "lt_hip_trace_surface", "lt_hip_trace_surface_device", "lt_hip_surface_at", "lt_hip_surface_at_device"]
+           "lt_hip_trace_surface", "lt_hip_trace_surface_device", "lt_hip_surface_at", "lt_hip_surface_at_device",
+           "lt_hip_nearest_points", "lt_hip_nearest_points_device", "lt_hip_nearest_points_host"]
 
 
 class RenderDesc(ctypes.Structure):
@@ -104,6 +105,14 @@ class SurfaceDesc(ctypes.Structure):   # lt_hip_surface_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class Point(ctypes.Structure):   # lt_hip_point
+    _fields_ = [("p", ctypes.c_float * 3), ("max_d2", ctypes.c_float)]
+
+
+class NearestDesc(ctypes.Structure):   # lt_hip_nearest_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 def _np_dtypes():
     import numpy as np
     ray = np.dtype([("origin", "<f4", (3,)), ("tmax", "<f4"), ("direction", "<f4", (3,)), ("ignore", "<i4")])
@@ -131,6 +140,14 @@ def _np_surface_dtype():
 
 
 SURFACE_DTYPE = _np_surface_dtype()   # numpy view of lt_hip_surface (48 bytes)
+
+
+def _np_point_dtype():
+    import numpy as np
+    return np.dtype([("p", "<f4", (3,)), ("max_d2", "<f4")])
+
+
+POINT_DTYPE = _np_point_dtype()   # numpy view of lt_hip_point (16 bytes)
 
 
 class LensTraceError(RuntimeError):
@@ -194,6 +211,10 @@ def load():
         L.lt_hip_trace_surface_device.argtypes = [vp, ctypes.POINTER(TraceDesc), vp, u64, vp, u64, vp]
         L.lt_hip_surface_at.argtypes = [vp, ctypes.POINTER(SurfaceDesc), vp, u64, vp, u64]
         L.lt_hip_surface_at_device.argtypes = [vp, ctypes.POINTER(SurfaceDesc), vp, u64, vp, u64, vp]
+    if hasattr(L, "lt_hip_nearest_points"):
+        L.lt_hip_nearest_points.argtypes = [vp, ctypes.POINTER(NearestDesc), vp, u64, vp, u64]
+        L.lt_hip_nearest_points_device.argtypes = [vp, ctypes.POINTER(NearestDesc), vp, u64, vp, u64, vp]
+        L.lt_hip_nearest_points_host.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64]
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

@@ -5,6 +5,7 @@
 #include "lt_own16.hpp"
 #include "lt_prep.hpp"
 #include "lt_query.hpp"
+#include "lt_nearest.hpp"
 #include "lt_shade.hpp"
 #include "lt_paths.hpp"
 
@@ -2025,9 +2026,9 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
 }
 
 // ---------------------------------------------------------------------------------- ray queries
-// Six families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
-// lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at (lt_query.hip), lt_hip_shade_rays (lt_shade.hip)
-// and lt_hip_shade_paths (lt_paths.hip).  Every argument error is found before anything is enqueued, so that a failed call writes
+// Seven families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
+// lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at (lt_query.hip), lt_hip_shade_rays (lt_shade.hip),
+// lt_hip_shade_paths (lt_paths.hip) and lt_hip_nearest_points (lt_nearest.hip).  Every argument error is found before anything is enqueued, so that a failed call writes
 // nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
 // check_ray_buffers), the course of an entry point with the host form's staging (run_ray_call) and the events and statistics
 // around the launches (begin_ray_launches, end_ray_launches).  A family has its check (the rules about its descriptor, at their
@@ -2037,6 +2038,7 @@ static_assert(sizeof(lt_hip_multihit_desc) == 24 && LT_TRACE_MAX_HITS == lt_quer
 static_assert(sizeof(lt_hip_surface) == 48 && sizeof(lt_hip_surface_desc) == 8, "surface records (include/lenstrace_hip.h)");
 static_assert(sizeof(lt_hip_shade_ray) == 32 && sizeof(lt_hip_shade) == 16 && sizeof(lt_hip_shade_desc) == 24, "shaded-ray records (include/lenstrace_hip.h)");
 static_assert(sizeof(lt_hip_paths_desc) == 32, "path-shading descriptor (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_point) == 16 && sizeof(lt_hip_nearest_desc) == 8, "nearest-point records (include/lenstrace_hip.h)");
 
 // What every family's check leaves for its launches: the math flavour (SceneDev: 0 portable, 1 strict, 2 as shipped) and the bytes
 // of one result.
@@ -2052,6 +2054,7 @@ constexpr RayWording kQueryWording{"ray query", "rays", "query", "rays"};
 constexpr RayWording kSurfaceAtWording{"lt_hip_surface_at", "hit records", "call", "hits"};
 constexpr RayWording kShadeWording{"lt_hip_shade_rays", "rays", "call", "rays"};
 constexpr RayWording kPathsWording{"lt_hip_shade_paths", "rays", "call", "rays"};
+constexpr RayWording kNearestWording{"lt_hip_nearest_points", "points", "call", "points"};
 
 // The flags of a call: the two math flags and, `coherent`, LT_TRACE_FLAG_COHERENT; `who`: the family's "... take(s)".
 static int check_ray_flags(lt_hip_context* ctx, uint32_t flags, bool coherent, const char* who, RayCall& call) {
@@ -2297,6 +2300,76 @@ extern "C" int lt_hip_surface_at(lt_hip_context* ctx, const lt_hip_surface_desc*
 extern "C" int lt_hip_surface_at_device(lt_hip_context* ctx, const lt_hip_surface_desc* desc, const lt_hip_hit* hits, uint64_t n, lt_hip_surface* out,
                                         uint64_t out_bytes, void* hip_stream) {
   return run_ray_call(ctx, desc, hits, n, out, out_bytes, true, hip_stream, check_surface_at, enqueue_surface_at);
+}
+
+// lt_hip_nearest_points*: the closest primitive of each point (lt_nearest_kernel).  The work counters are the ray queries': the
+// call takes its turn behind them (ctx->query_ev).
+static int check_nearest(lt_hip_context* ctx, const lt_hip_nearest_desc* d, const lt_hip_point* points, uint64_t n, const void* out, uint64_t out_bytes,
+                         bool device, RayCall& call) {
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_nearest_points: desc is NULL");
+  if (d->struct_size < sizeof(lt_hip_nearest_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "bad lt_hip_nearest_desc (struct_size)");
+  if (d->flags != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_nearest_points takes no flags");
+  call.devlibm = 2;
+  call.outRecord = sizeof(lt_hip_hit);
+  return check_ray_buffers(ctx, kNearestWording, points, n, out, out_bytes, device, call);
+}
+
+static int enqueue_nearest(lt_hip_context* ctx, const RayCall& call, const void* points, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_query_ctl));
+  lt_nearest::Params qp{};
+  qp.points = (const float4*)points;
+  qp.hits = (uint4*)out;
+  qp.n = (uint32_t)n;
+  qp.next = ctx->d_query_ctl;
+  qp.refill = k.trace_refill;
+  const SceneDev sc = scene_dev(ctx, k, call.devlibm);
+  if (const int rc = begin_ray_launches(ctx, &ctx->query_ev, s)) return rc;
+  LT_HIP_CHECK(ctx, lt_nearest::launch(sc, qp, (uint32_t)ctx->cu_count, s));
+  return end_ray_launches(ctx, ctx->query_ev, s, 1, n, 0);
+}
+
+extern "C" int lt_hip_nearest_points(lt_hip_context* ctx, const lt_hip_nearest_desc* desc, const lt_hip_point* points, uint64_t n, lt_hip_hit* out,
+                                     uint64_t out_bytes) {
+  return run_ray_call(ctx, desc, points, n, out, out_bytes, false, nullptr, check_nearest, enqueue_nearest);
+}
+
+extern "C" int lt_hip_nearest_points_device(lt_hip_context* ctx, const lt_hip_nearest_desc* desc, const lt_hip_point* points, uint64_t n,
+                                            lt_hip_hit* out, uint64_t out_bytes, void* hip_stream) {
+  return run_ray_call(ctx, desc, points, n, out, out_bytes, true, hip_stream, check_nearest, enqueue_nearest);
+}
+
+// The same answers without a context or a GPU: every leaf of `nodes` (LinearBVHNode) with its one primitive of `prims` (Primitive,
+// 76 bytes), the arithmetic of lt_nearest.hpp on the traversal triangle A, fl(B - A), fl(C - A).  Nothing is written unless
+// every leaf's offset lies inside `prims`.
+extern "C" int lt_hip_nearest_points_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const lt_hip_point* points,
+                                          uint64_t n, lt_hip_hit* out, uint64_t out_bytes) {
+  if (!nodes || !prims || node_bytes == 0 || node_bytes % 32 || node_bytes > 0xffffffffull * 32 || prim_bytes % 76) return LT_ERR_INVALID_ARGUMENT;
+  if (n > 0xffffffffull || (n > 0 && (!points || !out))) return LT_ERR_INVALID_ARGUMENT;
+  const lt_retree::Node* nd = (const lt_retree::Node*)nodes;
+  const uint64_t n_nodes = node_bytes / 32, n_prims = prim_bytes / 76;
+  for (uint64_t i = 0; i < n_nodes; i++)
+    if (nd[i].cnt != 0 && (nd[i].off < 0 || (uint64_t)nd[i].off >= n_prims)) return LT_ERR_BAD_SCENE;
+  if (out_bytes < n * sizeof(lt_hip_hit)) return LT_ERR_BUFFER_TOO_SMALL;
+  const float* pr = (const float*)prims;
+  for (uint64_t j = 0; j < n; j++) {
+    const float px = points[j].p[0], py = points[j].p[1], pz = points[j].p[2];
+    lt_nearest::Best best{points[j].max_d2, 0.0f, 0.0f, -1};
+    if (!lt_nearest::no_walk(px, py, pz, best.t)) {
+      for (uint64_t i = 0; i < n_nodes; i++) {
+        if (nd[i].cnt == 0) continue;
+        const float* p = pr + 19 * (size_t)nd[i].off;
+        const lt_nearest::Tri t = lt_nearest::tri(px, py, pz, p[0], p[1], p[2], p[3] - p[0], p[4] - p[1], p[5] - p[2], p[6] - p[0], p[7] - p[1], p[8] - p[2]);
+        const float box = lt_nearest::box_d2(px, py, pz, nd[i].lo[0], nd[i].lo[1], nd[i].lo[2], nd[i].hi[0], nd[i].hi[1], nd[i].hi[2]);
+        best.offer(lt_nearest::candidate_d2(t.d2, box), t.u, t.v, nd[i].off);
+      }
+    }
+    memcpy(&out[j].t, &best.t, sizeof(float));   // (max_d2's bits on a miss, a NaN's payload included)
+    out[j].prim = best.prim;
+    out[j].u = best.u;
+    out[j].v = best.v;
+  }
+  return LT_OK;
 }
 
 // lt_hip_shade_rays*: the colour a program's `shade` returns for caller-supplied rays (lt_shade.hip).

@@ -161,6 +161,52 @@ def ray_records(rays, record_dtype, names):
     return np.ascontiguousarray(rays)
 
 
+POINT_DTYPE = C.POINT_DTYPE
+
+
+def make_points(points, max_d2=np.inf):
+    """Packs points for RendererHIP.nearest_points: (n, 3) positions and max_d2 (a candidate counts only if its squared distance
+    is below it: a scalar or an (n,) array) into an (n, 4) float32 array of lt_hip_point records."""
+    p = np.asarray(points, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("points must have shape (n, 3)")
+    m = np.asarray(max_d2, dtype=np.float32)
+    if m.shape not in ((), (p.shape[0],)):
+        raise ValueError("max_d2 must be a scalar or have shape (n,)")
+    out = np.empty((p.shape[0], 4), dtype=np.float32)
+    out[:, 0:3] = p
+    out[:, 3] = m
+    return out
+
+
+def point_records(points, max_d2=np.inf):
+    """A numpy batch of points as a contiguous (n, 4) float32 array of lt_hip_point records: a 1-D POINT_DTYPE array or an (n, 4)
+    float32 array as it is (max_d2 must then be left alone), an (n, 3) array packed with max_d2 (make_points)."""
+    if points.dtype == POINT_DTYPE and points.ndim == 1:
+        points = points.view(np.float32).reshape(-1, 4)
+    elif points.ndim == 2 and points.shape[1] == 3:
+        return make_points(points, max_d2)
+    if points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != 4:
+        raise ValueError("points must be an (n, 3) array, an (n, 4) float32 array (make_points) or a POINT_DTYPE array")
+    if not (np.ndim(max_d2) == 0 and np.isposinf(max_d2)):
+        raise ValueError("ready lt_hip_point records carry their own max_d2")
+    return np.ascontiguousarray(points)
+
+
+def nearest_points_host(scene: Scene, points, max_d2=np.inf):
+    """lt_hip_nearest_points_host: RendererHIP.nearest_points' answers computed on the host from the scene's own buffers, leaf by
+    leaf -- no context, no GPU.  points as nearest_points takes numpy batches; returns a HIT_DTYPE array."""
+    pts = point_records(np.asarray(points), max_d2)
+    nodes, prims = np.ascontiguousarray(scene.nodes), np.ascontiguousarray(scene.prims)
+    out = np.zeros(pts.shape[0], dtype=HIT_DTYPE)
+    vp = ctypes.c_void_p
+    rc = C.load().lt_hip_nearest_points_host(nodes.ctypes.data_as(vp), nodes.nbytes, prims.ctypes.data_as(vp), prims.nbytes,
+                                             pts.ctypes.data_as(vp), pts.shape[0], out.ctypes.data_as(vp), out.nbytes)
+    if rc:
+        raise C.LensTraceError(rc, "lt_hip_nearest_points_host failed")
+    return out
+
+
 _QUERY_RAYS = (RAY_DTYPE, ("make_rays", "RAY_DTYPE"))
 _SHADE_RAYS = (SHADE_RAY_DTYPE, ("make_shade_rays", "SHADE_RAY_DTYPE"))
 
@@ -383,6 +429,30 @@ class RendererHIP:
             flat = np.ascontiguousarray(hits).reshape(-1)
             return self._host_call("surface_at", d, flat, np.zeros(flat.shape[0], dtype=SURFACE_DTYPE)).reshape(hits.shape)
         return self._device_call("surface_at", d, hits, "hits", "...", 4, ("float32", (12,)), stream)
+
+    # -- nearest-point queries -------------------------------------------------------------------------
+    def nearest_points(self, points, max_d2=np.inf, stream=None):
+        """The closest primitive of each point (lt_hip_nearest_points; include/lenstrace_hip.h defines the distance and the
+        selection): records (t = the squared distance, prim, u, v) that surface_at turns into the closest point, its normal and
+        material; a miss -- nothing with a squared distance below max_d2 -- has prim = -1 and t = max_d2.
+        points: an (n, 3) numpy array with max_d2 a scalar or an (n,) array, or ready lt_hip_point records (an (n, 4) float32 array
+        from make_points, or a POINT_DTYPE array) -- then the host entry point runs and a HIT_DTYPE array comes back; or a
+        contiguous float32 torch tensor on this context's GPU, (n, 3) with max_d2 a scalar or an (n,) tensor, or (n, 4) records --
+        then the call is enqueued on `stream` (default: the current torch stream) and an (n, 4) float32 tensor of lt_hip_hit
+        records comes back (column 1 holds int32 bits: .view(torch.int32))."""
+        d = C.NearestDesc(ctypes.sizeof(C.NearestDesc), 0)
+        if isinstance(points, np.ndarray):
+            pts = point_records(points, max_d2)
+            return self._host_call("nearest_points", d, pts, np.zeros(pts.shape[0], dtype=HIT_DTYPE))
+        import torch
+        if isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[1] == 3:
+            m = torch.as_tensor(max_d2, dtype=torch.float32, device=points.device)
+            if m.shape not in ((), (points.shape[0],)):
+                raise ValueError("max_d2 must be a scalar or have shape (n,)")
+            # (the records are packed by torch, on the call's stream when it is a torch stream, else on the current one)
+            with torch.cuda.stream(stream if isinstance(stream, torch.cuda.Stream) else None):
+                points = torch.cat([points, m.expand(points.shape[0]).unsqueeze(1)], dim=1).contiguous()
+        return self._device_call("nearest_points", d, points, "points", "n", 4, ("float32", (4,)), stream)
 
     # -- shaded rays ------------------------------------------------------------------------------------
     def shade_rays(self, rays, program="accumulator", frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR, portable_math=False,
