@@ -523,6 +523,49 @@ int lt_hip_nearest_points_device(lt_hip_context* ctx, const lt_hip_nearest_desc*
 int lt_hip_nearest_points_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
                                const lt_hip_point* points, uint64_t n, lt_hip_hit* out, uint64_t out_bytes);
 
+/* k-nearest queries: the K closest primitives of each point, or how many lie within its radius -- the contact set of a collision
+ * or clearance check, the second and third nearest surfaces at thin walls and inner corners, point-to-mesh registration.
+ *
+ * The candidate sequence of a point {p, max_d2}: candidates, d2, (u, v) and acceptance (d2 < max_d2 by the float `<`) are exactly
+ * those of lt_hip_nearest_points; every accepted candidate appears once; the order is ascending d2 by `<`, ascending primitive
+ * offset among equal d2 (`==`), and ascending node index in the caller's array among equal d2 and equal offset (only scenes whose
+ * leaves name one primitive twice have such candidates).  A point with a component that is not finite, or with a max_d2 nothing
+ * is below (0, -0, negative, NaN), has the empty sequence.  The sequence is a function of the scene and the point alone.
+ *   LT_NEAREST_FIRST_K  the first max_k entries as max_k consecutive lt_hip_hit records per point, point-major: record
+ *                       i * max_k + j is entry j of point i (t = d2, prim, u, v).  Unused slots hold the miss record: t = max_d2
+ *                       with the bits given, prim = -1, u = v = +0.  With max_k = 1 the call is lt_hip_nearest_points byte for
+ *                       byte.  Every record feeds lt_hip_surface_at as lt_hip_nearest_points' do.
+ *   LT_NEAREST_COUNT    one uint32 per point: the length of the whole sequence, i.e. the number of candidates within the radius.
+ *                       max_d2 = inf accepts every finite d2, which makes the call a visit of every leaf for every point: give
+ *                       a finite radius.
+ *
+ * flags: 0.  max_k: 1 .. LT_NEAREST_MAX_K for LT_NEAREST_FIRST_K, 0 for LT_NEAREST_COUNT.  Host memory, synchronous.  Errors in
+ * lt_hip_nearest_points' order: LT_ERR_INVALID_ARGUMENT for a null ctx / desc, struct_size too small, flags != 0, an unknown kind,
+ * max_k outside its range for the kind, n >= 2^32, a null pointer with n > 0 (and, device entry point, pointers that are not
+ * 16-byte aligned); LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when out_bytes < 16 max_k n (FIRST_K) or 4 n (COUNT).  A failed call
+ * writes nothing to out; n == 0 launches nothing.  lt_hip_get_stats then reports rays = n, kernel_launches = 1 and kernel_ms.
+ * (lens_trace_amd/csrc/lt_nearest.hip) */
+#define LT_NEAREST_FIRST_K 0
+#define LT_NEAREST_COUNT   1
+#define LT_NEAREST_MAX_K   8
+typedef struct lt_hip_nearest_k_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_nearest_k_desc) */
+  uint32_t flags;               /* 0 */
+  int32_t kind;                 /* LT_NEAREST_FIRST_K / LT_NEAREST_COUNT */
+  uint32_t max_k;               /* FIRST_K: 1 .. LT_NEAREST_MAX_K; COUNT: 0 */
+} lt_hip_nearest_k_desc;        /* 16 B */
+
+int lt_hip_nearest_k(lt_hip_context* ctx, const lt_hip_nearest_k_desc* desc, const lt_hip_point* points, uint64_t n,
+                     void* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_nearest_k_device(lt_hip_context* ctx, const lt_hip_nearest_k_desc* desc, const lt_hip_point* points, uint64_t n,
+                            void* out, uint64_t out_bytes, void* hip_stream);
+/* The same answers on the host, without a context or a GPU, from the caller's buffers, as lt_hip_nearest_points_host takes them.
+ * LT_ERR_INVALID_ARGUMENT (a null desc, struct_size, flags, kind or max_k as above, a null or mis-sized buffer, n >= 2^32),
+ * LT_ERR_BAD_SCENE (a leaf whose offset lies outside prims), LT_ERR_BUFFER_TOO_SMALL; a failed call writes nothing. */
+int lt_hip_nearest_k_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                          const lt_hip_nearest_k_desc* desc, const lt_hip_point* points, uint64_t n, void* out, uint64_t out_bytes);
+
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
 

@@ -24,6 +24,8 @@ TRACE_CLOSEST, TRACE_ANY = 0, 1      # lt_hip_trace_desc::kind
 TRACE_FLAG_COHERENT = 0x100          # runs of 64 consecutive rays are coherent: walked as packets
 TRACE_FIRST_K, TRACE_COUNT = 0, 1    # lt_hip_multihit_desc::kind (lt_hip_trace_hits only)
 TRACE_MAX_HITS = 8                   # LT_TRACE_MAX_HITS
+NEAREST_FIRST_K, NEAREST_COUNT = 0, 1   # lt_hip_nearest_k_desc::kind
+NEAREST_MAX_K = 8                    # LT_NEAREST_MAX_K
 SURFACE_LIGHT = 1                    # lt_hip_surface::flags: the primitive is in the light list
 
 # every symbol include/lenstrace_hip.h declares
@@ -34,7 +36,8 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device",
            "lt_hip_shade_rays", "lt_hip_shade_rays_device", "lt_hip_shade_paths", "lt_hip_shade_paths_device",
            "lt_hip_trace_surface", "lt_hip_trace_surface_device", "lt_hip_surface_at", "lt_hip_surface_at_device",
-           "lt_hip_nearest_points", "lt_hip_nearest_points_device", "lt_hip_nearest_points_host"]
+           "lt_hip_nearest_points", "lt_hip_nearest_points_device", "lt_hip_nearest_points_host",
+           "lt_hip_nearest_k", "lt_hip_nearest_k_device", "lt_hip_nearest_k_host"]
 
 
 class RenderDesc(ctypes.Structure):
@@ -111,6 +114,10 @@ class Point(ctypes.Structure):   # lt_hip_point
 
 class NearestDesc(ctypes.Structure):   # lt_hip_nearest_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class NearestKDesc(ctypes.Structure):   # lt_hip_nearest_k_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("kind", ctypes.c_int32), ("max_k", ctypes.c_uint32)]
 
 
 def _np_dtypes():
@@ -215,6 +222,10 @@ def load():
         L.lt_hip_nearest_points.argtypes = [vp, ctypes.POINTER(NearestDesc), vp, u64, vp, u64]
         L.lt_hip_nearest_points_device.argtypes = [vp, ctypes.POINTER(NearestDesc), vp, u64, vp, u64, vp]
         L.lt_hip_nearest_points_host.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64]
+    if hasattr(L, "lt_hip_nearest_k"):
+        L.lt_hip_nearest_k.argtypes = [vp, ctypes.POINTER(NearestKDesc), vp, u64, vp, u64]
+        L.lt_hip_nearest_k_device.argtypes = [vp, ctypes.POINTER(NearestKDesc), vp, u64, vp, u64, vp]
+        L.lt_hip_nearest_k_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(NearestKDesc), vp, u64, vp, u64]
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

@@ -2026,9 +2026,9 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
 }
 
 // ---------------------------------------------------------------------------------- ray queries
-// Seven families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
+// Eight families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
 // lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at (lt_query.hip), lt_hip_shade_rays (lt_shade.hip),
-// lt_hip_shade_paths (lt_paths.hip) and lt_hip_nearest_points (lt_nearest.hip).  Every argument error is found before anything is enqueued, so that a failed call writes
+// lt_hip_shade_paths (lt_paths.hip), lt_hip_nearest_points and lt_hip_nearest_k (lt_nearest.hip).  Every argument error is found before anything is enqueued, so that a failed call writes
 // nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
 // check_ray_buffers), the course of an entry point with the host form's staging (run_ray_call) and the events and statistics
 // around the launches (begin_ray_launches, end_ray_launches).  A family has its check (the rules about its descriptor, at their
@@ -2039,6 +2039,7 @@ static_assert(sizeof(lt_hip_surface) == 48 && sizeof(lt_hip_surface_desc) == 8, 
 static_assert(sizeof(lt_hip_shade_ray) == 32 && sizeof(lt_hip_shade) == 16 && sizeof(lt_hip_shade_desc) == 24, "shaded-ray records (include/lenstrace_hip.h)");
 static_assert(sizeof(lt_hip_paths_desc) == 32, "path-shading descriptor (include/lenstrace_hip.h)");
 static_assert(sizeof(lt_hip_point) == 16 && sizeof(lt_hip_nearest_desc) == 8, "nearest-point records (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_nearest_k_desc) == 16 && LT_NEAREST_MAX_K == lt_nearest::kMaxK, "k-nearest records (include/lenstrace_hip.h)");
 
 // What every family's check leaves for its launches: the math flavour (SceneDev: 0 portable, 1 strict, 2 as shipped) and the bytes
 // of one result.
@@ -2055,6 +2056,7 @@ constexpr RayWording kSurfaceAtWording{"lt_hip_surface_at", "hit records", "call
 constexpr RayWording kShadeWording{"lt_hip_shade_rays", "rays", "call", "rays"};
 constexpr RayWording kPathsWording{"lt_hip_shade_paths", "rays", "call", "rays"};
 constexpr RayWording kNearestWording{"lt_hip_nearest_points", "points", "call", "points"};
+constexpr RayWording kNearestKWording{"lt_hip_nearest_k", "points", "call", "points"};
 
 // The flags of a call: the two math flags and, `coherent`, LT_TRACE_FLAG_COHERENT; `who`: the family's "... take(s)".
 static int check_ray_flags(lt_hip_context* ctx, uint32_t flags, bool coherent, const char* who, RayCall& call) {
@@ -2368,6 +2370,107 @@ extern "C" int lt_hip_nearest_points_host(const void* nodes, uint64_t node_bytes
     out[j].prim = best.prim;
     out[j].u = best.u;
     out[j].v = best.v;
+  }
+  return LT_OK;
+}
+
+// lt_hip_nearest_k*: the first K entries of each point's candidate sequence, or its length (lt_nearest_k_kernel).  The descriptor's
+// rules, for the context's entry points and the host form alike; null when it passes.
+static const char* nearest_k_desc_error(const lt_hip_nearest_k_desc* d) {
+  if (!d) return "lt_hip_nearest_k: desc is NULL";
+  if (d->struct_size < sizeof(lt_hip_nearest_k_desc)) return "bad lt_hip_nearest_k_desc (struct_size)";
+  if (d->flags != 0) return "lt_hip_nearest_k takes no flags";
+  if (d->kind != LT_NEAREST_FIRST_K && d->kind != LT_NEAREST_COUNT) return "unknown nearest kind";
+  if (d->kind == LT_NEAREST_FIRST_K && (d->max_k < 1 || d->max_k > LT_NEAREST_MAX_K)) return "LT_NEAREST_FIRST_K takes max_k in 1 .. LT_NEAREST_MAX_K";
+  if (d->kind == LT_NEAREST_COUNT && d->max_k != 0) return "LT_NEAREST_COUNT takes max_k = 0";
+  return nullptr;
+}
+
+struct NearestKCall : RayCall {
+  uint32_t maxK;   // 0: count
+};
+
+static int check_nearest_k(lt_hip_context* ctx, const lt_hip_nearest_k_desc* d, const lt_hip_point* points, uint64_t n, const void* out,
+                           uint64_t out_bytes, bool device, NearestKCall& call) {
+  if (const char* why = nearest_k_desc_error(d)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, why);
+  call.devlibm = 2;
+  call.maxK = d->max_k;
+  call.outRecord = d->kind == LT_NEAREST_COUNT ? sizeof(uint32_t) : (uint64_t)d->max_k * sizeof(lt_hip_hit);
+  return check_ray_buffers(ctx, kNearestKWording, points, n, out, out_bytes, device, call);
+}
+
+static int enqueue_nearest_k(lt_hip_context* ctx, const NearestKCall& call, const void* points, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_query_ctl));
+  lt_nearest::KParams qp{};
+  qp.points = (const float4*)points;
+  qp.hits = call.maxK ? (uint4*)out : nullptr;
+  qp.counts = call.maxK ? nullptr : (uint32_t*)out;
+  qp.n = (uint32_t)n;
+  qp.maxK = call.maxK;
+  qp.next = ctx->d_query_ctl;
+  qp.refill = k.trace_refill;
+  const SceneDev sc = scene_dev(ctx, k, call.devlibm);
+  if (const int rc = begin_ray_launches(ctx, &ctx->query_ev, s)) return rc;
+  LT_HIP_CHECK(ctx, lt_nearest::launch_k(sc, qp, (uint32_t)ctx->cu_count, s));
+  return end_ray_launches(ctx, ctx->query_ev, s, 1, n, 0);
+}
+
+extern "C" int lt_hip_nearest_k(lt_hip_context* ctx, const lt_hip_nearest_k_desc* desc, const lt_hip_point* points, uint64_t n, void* out,
+                                uint64_t out_bytes) {
+  return run_ray_call(ctx, desc, points, n, out, out_bytes, false, nullptr, check_nearest_k, enqueue_nearest_k);
+}
+
+extern "C" int lt_hip_nearest_k_device(lt_hip_context* ctx, const lt_hip_nearest_k_desc* desc, const lt_hip_point* points, uint64_t n, void* out,
+                                       uint64_t out_bytes, void* hip_stream) {
+  return run_ray_call(ctx, desc, points, n, out, out_bytes, true, hip_stream, check_nearest_k, enqueue_nearest_k);
+}
+
+// The same answers without a context or a GPU: lt_hip_nearest_points_host's scan of the caller's leaves in node order into the
+// kernel's sinks (lt_nearest.hpp: KList, KCount), u and v from the same tri() once more for the survivors.
+extern "C" int lt_hip_nearest_k_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const lt_hip_nearest_k_desc* desc,
+                                     const lt_hip_point* points, uint64_t n, void* out, uint64_t out_bytes) {
+  if (nearest_k_desc_error(desc)) return LT_ERR_INVALID_ARGUMENT;
+  if (!nodes || !prims || node_bytes == 0 || node_bytes % 32 || node_bytes > 0xffffffffull * 32 || prim_bytes % 76) return LT_ERR_INVALID_ARGUMENT;
+  if (n > 0xffffffffull || (n > 0 && (!points || !out))) return LT_ERR_INVALID_ARGUMENT;
+  const lt_retree::Node* nd = (const lt_retree::Node*)nodes;
+  const uint64_t n_nodes = node_bytes / 32, n_prims = prim_bytes / 76;
+  for (uint64_t i = 0; i < n_nodes; i++)
+    if (nd[i].cnt != 0 && (nd[i].off < 0 || (uint64_t)nd[i].off >= n_prims)) return LT_ERR_BAD_SCENE;
+  const uint32_t maxK = desc->max_k;
+  if (out_bytes < n * (maxK ? (uint64_t)maxK * sizeof(lt_hip_hit) : sizeof(uint32_t))) return LT_ERR_BUFFER_TOO_SMALL;
+  const float* pr = (const float*)prims;
+  auto triangle = [&](float px, float py, float pz, int32_t off) {
+    const float* p = pr + 19 * (size_t)off;
+    return lt_nearest::tri(px, py, pz, p[0], p[1], p[2], p[3] - p[0], p[4] - p[1], p[5] - p[2], p[6] - p[0], p[7] - p[1], p[8] - p[2]);
+  };
+  for (uint64_t j = 0; j < n; j++) {
+    const float px = points[j].p[0], py = points[j].p[1], pz = points[j].p[2];
+    int entries[2 * LT_NEAREST_MAX_K];
+    lt_nearest::KList<1> list{entries, maxK};
+    lt_nearest::KCount count{points[j].max_d2, 0u};
+    list.reset(points[j].max_d2);
+    if (!lt_nearest::no_walk(px, py, pz, points[j].max_d2)) {
+      for (uint64_t i = 0; i < n_nodes; i++) {
+        if (nd[i].cnt == 0) continue;
+        const float d2 = lt_nearest::candidate_d2(triangle(px, py, pz, nd[i].off).d2,
+                                                  lt_nearest::box_d2(px, py, pz, nd[i].lo[0], nd[i].lo[1], nd[i].lo[2], nd[i].hi[0], nd[i].hi[1], nd[i].hi[2]));
+        if (maxK) list.offer(d2, 0.0f, 0.0f, nd[i].off); else count.offer(d2, 0.0f, 0.0f, nd[i].off);
+      }
+    }
+    if (!maxK) { ((uint32_t*)out)[j] = count.n; continue; }
+    lt_hip_hit* rec = (lt_hip_hit*)out + j * maxK;
+    for (uint32_t e = 0; e < maxK; e++) {
+      const int bits = list.d2_bits(e);
+      memcpy(&rec[e].t, &bits, sizeof(float));   // (max_d2's bits in an unused slot, a NaN's payload included)
+      rec[e].prim = list.prim(e);
+      rec[e].u = rec[e].v = 0.0f;
+      if (rec[e].prim >= 0) {
+        const lt_nearest::Tri t = triangle(px, py, pz, rec[e].prim);
+        rec[e].u = t.u;
+        rec[e].v = t.v;
+      }
+    }
   }
   return LT_OK;
 }

@@ -9,6 +9,9 @@
 // leaf's own box and the offset.  Nothing is dropped that could hold a candidate with d2 <= best (or, before the first one, with
 // d2 < max_d2): every bound on the way to a leaf is <= that leaf's box_d2 <= its d2, as floats, without margins.
 // A scene without an own tree is scanned leaf by leaf in the caller's node order.
+//
+// And the k-nearest queries (lt_hip_nearest_k): lt_nearest_k_kernel, the same loop and step with another sink -- the first K
+// candidates by (d2, offset) in a per-lane list in LDS, or their number -- and "best" read as "K-th best" (DESIGN 5.15).
 #include "lt_nearest.hpp"
 
 using namespace lt;
@@ -27,8 +30,10 @@ __device__ __forceinline__ void put_nearest(const lt_nearest::Params& qp, uint32
 struct Grid { float O[3], S[3]; };   // the 16-bit grid of the group slots (wide[-2], wide[-1])
 
 // One step of the walk for one lane: the record `e` (a group, or a leaf: bit 31) is fetched and dealt with, the next entry that
-// can still hold the answer popped into `e`.  Returns true when the stack is empty.
-__device__ __forceinline__ bool nearest_step(const SceneDev& sc, const Grid& g, uint32_t emptyLink, float px, float py, float pz, lt_nearest::Best& best,
+// can still hold the answer popped into `e`.  Returns true when the stack is empty.  SINK: what takes the candidates and says
+// which bounds it still reaches -- lt_nearest::Best, or lt_hip_nearest_k's LaneList (the first K) and lt_nearest::KCount.
+template <class SINK>
+__device__ __forceinline__ bool nearest_step(const SceneDev& sc, const Grid& g, uint32_t emptyLink, float px, float py, float pz, SINK& best,
                                              int* col, int* deep, uint32_t& e, int& sp) {
   const uint4* rec = (const uint4*)((const char*)sc.wide + ((size_t)(e & 0x7fffffffu) << 6));
   const uint4 s0 = rec[0], s1 = rec[1], s2 = rec[2], s3 = rec[3];
@@ -77,13 +82,14 @@ __device__ __forceinline__ bool nearest_step(const SceneDev& sc, const Grid& g, 
 }
 
 // A scene without an own tree: every leaf of the caller's node array in index order; the triangle may be skipped when the leaf's
-// box alone is already beyond the best (d2 >= box_d2).
-__device__ __forceinline__ void nearest_scan(const SceneDev& sc, float px, float py, float pz, lt_nearest::Best& best) {
+// box alone is already beyond what the sink still takes (d2 >= box_d2).
+template <class SINK>
+__device__ __forceinline__ void nearest_scan(const SceneDev& sc, float px, float py, float pz, SINK& best) {
   for (uint32_t i = 0; i < sc.n_nodes; i++) {
     const float4 a = sc.nodes[2 * (size_t)i], b = sc.nodes[2 * (size_t)i + 1];
     if ((__float_as_uint(b.w) & 0xffffu) == 0u) continue;
     const float box = lt_nearest::box_d2(px, py, pz, a.x, a.y, a.z, a.w, b.x, b.y);
-    if (best.prim >= 0 && box > best.t) continue;
+    if (!best.reaches(box)) continue;
     const int32_t prim = __float_as_int(b.z);
     const float4 t0 = sc.tris[3 * (size_t)prim], t1 = sc.tris[3 * (size_t)prim + 1], t2 = sc.tris[3 * (size_t)prim + 2];
     const lt_nearest::Tri t = lt_nearest::tri(px, py, pz, t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x);
@@ -184,7 +190,159 @@ __global__ __launch_bounds__(kBlock, 8) void lt_nearest_kernel(SceneDev sc, lt_n
   }
 }
 
+namespace {
+
+// The lane's KList with its last entry in registers: every slot and every popped entry asks reaches(), and a candidate enters
+// the list iff it comes before that entry -- the others never touch LDS.
+struct LaneList {
+  lt_nearest::KList<kBlock> list;
+  float lastD2;
+  int32_t lastPrim;
+  __device__ __forceinline__ void reset(float max_d2) { list.reset(max_d2); lastD2 = max_d2; lastPrim = -1; }
+  __device__ __forceinline__ void offer(float d2, float u, float v, int32_t p) {
+    if (!lt_nearest::before(d2, p, lastD2, lastPrim)) return;
+    list.offer(d2, u, v, p);
+    lastD2 = list.d2(list.k - 1u);
+    lastPrim = list.prim(list.k - 1u);
+  }
+  __device__ __forceinline__ bool reaches(float bound) const { return lt_nearest::last_reaches(bound, lastD2, lastPrim); }
+};
+
+// A point's K records: d2 and the primitive from the list, u and v from lt_nearest::tri run once more on the traversal triangle
+// and the same point -- the same function on the same operands as in the walk's leaf record, hence the same bits.  Empty entries
+// are the miss record already (max_d2's bits, -1); their u and v are +0.
+__device__ __forceinline__ void put_nearest_k(const SceneDev& sc, const lt_nearest::KList<kBlock>& list, float px, float py, float pz, uint4* out) {
+  for (uint32_t j = 0; j < list.k; j++) {
+    const int prim = list.prim(j);
+    float u = 0.0f, v = 0.0f;
+    if (prim >= 0) {
+      const float4 t0 = sc.tris[3 * (size_t)prim], t1 = sc.tris[3 * (size_t)prim + 1], t2 = sc.tris[3 * (size_t)prim + 2];
+      const lt_nearest::Tri t = lt_nearest::tri(px, py, pz, t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x);
+      u = t.u; v = t.v;
+    }
+    out[j] = make_uint4((uint32_t)list.d2_bits(j), (uint32_t)prim, __float_as_uint(u), __float_as_uint(v));
+  }
+}
+
+}  // namespace
+
+// lt_hip_nearest_k: lt_nearest_kernel's claim, stage and refill loop with another sink.  COUNT counts a point's accepted
+// candidates in a register and keeps every subtree whose bound is below max_d2.  Otherwise the candidates go into the lane's
+// KList of qp.maxK entries, 2 maxK LDS rows behind the stage, which the lane resets when it takes a new point -- its neighbours'
+// lists stay as they are -- and writes out when its walk is done; a subtree is kept while its bound reaches the list's last
+// entry (KList::reaches).  A step pops one stack entry and pushes at most four whatever the sink keeps, so the
+// stack is lt_nearest_kernel's.
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock, 8) void lt_nearest_k_kernel(SceneDev sc, lt_nearest::KParams qp) {
+  using u64 = unsigned long long;
+  extern __shared__ int lds_stack[];   // [2 kNearEntries stack rows][kNearStage rows of staged points][2 maxK list rows], 64 lanes each
+  int* const col = lds_stack + threadIdx.x;
+  int* const stage = lds_stack + 2 * kNearEntries * kBlock;
+  const uint32_t total = qp.n;
+  const uint32_t lane = threadIdx.x;
+  const bool ownTree = sc.wide != nullptr && sc.rank8 != nullptr;
+  const uint32_t emptyLink = 0x80000000u | (sc.nWide + sc.n_prims);
+  Grid g{};
+  if (ownTree) {
+    const F8v fr = *(ConstF8)((unsigned long long)sc.wide - 32ull);   // origin.xyz - step.xyz -
+    g = Grid{{fr.s0, fr.s1, fr.s2}, {fr.s4, fr.s5, fr.s6}};
+  }
+  const uint32_t share = total / (gridDim.x * 4u) / (uint32_t)kBlock * (uint32_t)kBlock;
+  const uint32_t claim = share < (uint32_t)kBlock ? (uint32_t)kBlock : (share > (uint32_t)kNearClaim ? (uint32_t)kNearClaim : share);
+  bool active = false;
+  uint32_t stageCount = 0u, stageTaken = 0u, claimNext = 0u, claimEnd = 0u, sweep = 0u;
+  const uint32_t home = __builtin_amdgcn_s_getreg((3u << 11) | 20u) & 7u;   // HW_REG_XCC_ID
+  bool drained = false;
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  LaneList list{{col + (2 * kNearEntries + kNearStage) * kBlock, COUNT ? 0u : qp.maxK}, 0.0f, -1};
+  lt_nearest::KCount count{0.0f, 0u};
+  uint32_t idx = 0u, e = 0u;
+  int sp = 0;
+  int deep[2 * kNearDeep];
+  for (;;) {
+    const u64 idle = __builtin_amdgcn_ballot_w64(!active);
+    const uint32_t nIdle = (uint32_t)__popcll(idle);
+    if ((nIdle >= qp.refill || nIdle == (uint32_t)kBlock) && (stageTaken < stageCount || !drained)) {
+      if (stageTaken == stageCount) {
+        while (claimNext == claimEnd && sweep < 8u) {
+          const uint32_t part = (home + sweep) & 7u;
+          const uint32_t lo = (uint32_t)((uint64_t)total * part / 8u / kBlock * kBlock), hi = part == 7u ? total : (uint32_t)((uint64_t)total * (part + 1u) / 8u / kBlock * kBlock);
+          uint32_t got = 0u;
+          if (lane == 0u) got = atomicAdd(&qp.next[part * kQueueStride], claim);
+          got = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
+          if (got >= hi - lo) { sweep++; continue; }
+          claimNext = lo + got;
+          claimEnd = hi - claimNext < claim ? hi : claimNext + claim;
+        }
+        const uint32_t base = claimNext;
+        const uint32_t batch = claimEnd - base < (uint32_t)kBlock ? claimEnd - base : (uint32_t)kBlock;
+        claimNext = base + batch;
+        drained = claimNext == claimEnd && sweep >= 8u;
+        stageTaken = 0u;
+        stageCount = batch;
+        if (lane < batch) {   // the caller's record: one coalesced 16-byte load
+          const float4 a = qp.points[(size_t)(base + lane)];
+          stage[0 * kBlock + lane] = __float_as_int(a.x); stage[1 * kBlock + lane] = __float_as_int(a.y); stage[2 * kBlock + lane] = __float_as_int(a.z);
+          stage[3 * kBlock + lane] = __float_as_int(a.w);   // max_d2
+          stage[4 * kBlock + lane] = (int)(base + lane);
+        }
+      }
+      const uint32_t take = nIdle < stageCount - stageTaken ? nIdle : stageCount - stageTaken;
+      const uint32_t mine = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));   // idle lanes below this one
+      if (!active && mine < take) {
+        const uint32_t s = stageTaken + mine;
+        idx = (uint32_t)stage[4 * kBlock + s];
+        px = __int_as_float(stage[0 * kBlock + s]); py = __int_as_float(stage[1 * kBlock + s]); pz = __int_as_float(stage[2 * kBlock + s]);
+        const float maxD2 = __int_as_float(stage[3 * kBlock + s]);
+        if (COUNT) count = lt_nearest::KCount{maxD2, 0u}; else list.reset(maxD2);
+        if (lt_nearest::no_walk(px, py, pz, maxD2)) {
+          if (COUNT) qp.counts[idx] = 0u; else put_nearest_k(sc, list.list, px, py, pz, qp.hits + (size_t)idx * qp.maxK);
+        } else if (ownTree) {
+          e = 0u;   // the root's group
+          sp = 0;
+          active = true;
+        } else if (COUNT) {
+          nearest_scan(sc, px, py, pz, count);
+          qp.counts[idx] = count.n;
+        } else {
+          nearest_scan(sc, px, py, pz, list);
+          put_nearest_k(sc, list.list, px, py, pz, qp.hits + (size_t)idx * qp.maxK);
+        }
+      }
+      stageTaken += take;
+    }
+    if (__builtin_amdgcn_ballot_w64(active) == 0ull) {
+      if (drained && stageTaken == stageCount) break;
+      continue;
+    }
+    if (active) {
+      const bool done = COUNT ? nearest_step(sc, g, emptyLink, px, py, pz, count, col, deep, e, sp)
+                              : nearest_step(sc, g, emptyLink, px, py, pz, list, col, deep, e, sp);
+      if (done) {
+        if (COUNT) qp.counts[idx] = count.n; else put_nearest_k(sc, list.list, px, py, pz, qp.hits + (size_t)idx * qp.maxK);
+        active = false;
+      }
+    }
+  }
+}
+
 namespace lt_nearest {
+
+hipError_t launch_k(const SceneDev& sc, const KParams& p, uint32_t cuCount, hipStream_t s) {
+  if (p.n == 0) return hipSuccess;
+  if (p.maxK > kMaxK) return hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(p.next, 0, 8 * kQueueStride * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  const uint32_t chunks = (uint32_t)(((uint64_t)p.n + kBlock - 1) / kBlock);
+  const uint32_t rows = (uint32_t)(2 * kNearEntries + kNearStage) + 2u * p.maxK;
+  // every wave slot the list rows leave: 160 KB of LDS per CU, at most 32 waves
+  const uint32_t fit = 160u * 1024u / (rows * kBlock * (uint32_t)sizeof(int)), perCu = fit < 32u ? fit : 32u;
+  const uint32_t resident = cuCount * perCu;
+  const dim3 grid(chunks < resident ? chunks : resident);
+  if (p.maxK == 0u) hipLaunchKernelGGL((lt_nearest_k_kernel<true>), grid, dim3(kBlock), rows * kBlock * (uint32_t)sizeof(int), s, sc, p);
+  else hipLaunchKernelGGL((lt_nearest_k_kernel<false>), grid, dim3(kBlock), rows * kBlock * (uint32_t)sizeof(int), s, sc, p);
+  return hipGetLastError();
+}
 
 hipError_t launch(const SceneDev& sc, const Params& p, uint32_t cuCount, hipStream_t s) {
   if (p.n == 0) return hipSuccess;

@@ -117,6 +117,54 @@ struct Best {
   LT_NEAR_HD bool reaches(float bound) const { return bound < t || (prim >= 0 && bound == t); }
 };
 
+// The order of a point's candidate sequence (lt_hip_nearest_k): ascending d2 by `<`, ascending primitive offset among equal d2.
+// Whether the candidate {d2, p} comes before the list entry {ed2, ep}; ep = -1 is the miss entry {max_d2, -1}, which every
+// accepted candidate (d2 < max_d2) comes before and nothing else does -- so the order is the acceptance too.  Best::offer is
+// this with a list of one.  Equal d2 and equal offset: not before, i.e. behind what is there.
+LT_NEAR_HD inline bool before(float d2, int32_t p, float ed2, int32_t ep) { return d2 < ed2 || (d2 == ed2 && ep >= 0 && p < ep); }
+
+// KList::reaches from the list's last entry {lastD2, lastPrim}, for a walk that keeps that entry in registers.
+LT_NEAR_HD inline bool last_reaches(float bound, float lastD2, int32_t lastPrim) { return bound < lastD2 || (lastPrim >= 0 && bound == lastD2); }
+
+// The first k entries of a point's candidate sequence, sorted by `before`: entry j is the two words col[2 j STRIDE] (d2's bits) and
+// col[(2 j + 1) STRIDE] (the primitive offset) -- the kernel's lists are columns of LDS rows (STRIDE = 64 lanes), the host form's
+// an array (STRIDE = 1).  Empty entries are the miss entry.  u and v are not kept: tri() gives them again for the survivors.
+template <int STRIDE>
+struct KList {
+  int* col;
+  uint32_t k;   // 1 .. LT_NEAREST_MAX_K
+  LT_NEAR_HD int d2_bits(uint32_t j) const { return col[2 * j * STRIDE]; }
+  LT_NEAR_HD float d2(uint32_t j) const { return __builtin_bit_cast(float, col[2 * j * STRIDE]); }
+  LT_NEAR_HD int32_t prim(uint32_t j) const { return col[(2 * j + 1) * STRIDE]; }
+  LT_NEAR_HD void reset(float max_d2) {
+    for (uint32_t j = 0; j < k; j++) { col[2 * j * STRIDE] = __builtin_bit_cast(int, max_d2); col[(2 * j + 1) * STRIDE] = -1; }
+  }
+  // Inserts from the end; the entry pushed past the end is dropped.  (Best::offer's signature: u and v are not kept.)
+  LT_NEAR_HD void offer(float cd2, float, float, int32_t p) {
+    uint32_t j = k;
+    while (j > 0u) {
+      const int eb = d2_bits(j - 1u);
+      const int32_t ep = prim(j - 1u);
+      if (!before(cd2, p, __builtin_bit_cast(float, eb), ep)) break;
+      if (j < k) { col[2 * j * STRIDE] = eb; col[(2 * j + 1) * STRIDE] = ep; }
+      j--;
+    }
+    if (j < k) { col[2 * j * STRIDE] = __builtin_bit_cast(int, cd2); col[(2 * j + 1) * STRIDE] = p; }
+  }
+  // Whether a subtree (or leaf) whose every candidate has d2 >= bound may still hold one of the first k: while the list is not
+  // full (its last entry is the miss entry), bound < max_d2; once it is, bound <= the k-th d2 -- equality stays reachable, a
+  // lower offset at the same d2 displaces the k-th entry.  Best::reaches with the k-th best.
+  LT_NEAR_HD bool reaches(float bound) const { return last_reaches(bound, d2(k - 1u), prim(k - 1u)); }
+};
+
+// The length of the whole sequence: the candidates within the radius.
+struct KCount {
+  float max_d2;
+  uint32_t n;
+  LT_NEAR_HD void offer(float cd2, float, float, int32_t) { if (cd2 < max_d2) n++; }
+  LT_NEAR_HD bool reaches(float bound) const { return bound < max_d2; }
+};
+
 // A point that needs no walk: a component that is not finite, or a max_d2 nothing is below (0, -0, negative, NaN).
 LT_NEAR_HD inline bool no_walk(float px, float py, float pz, float max_d2) {
   const float inf = __builtin_inff();
@@ -142,6 +190,23 @@ struct Params {
 
 // Enqueues lt_nearest_kernel on `s`.  Returns the first HIP error.
 hipError_t launch(const lt::SceneDev& sc, const Params& p, uint32_t cuCount, hipStream_t s);
+
+constexpr uint32_t kMaxK = 8;   // LT_NEAREST_MAX_K
+
+// lt_hip_nearest_k: the first maxK entries of each point's candidate sequence as maxK lt_hip_hit records per point, or -- maxK = 0 --
+// the sequence's length, one uint32 per point.
+struct KParams {
+  const float4* points;
+  uint4* hits;        // [n * maxK], point-major; null when counting
+  uint32_t* counts;   // [n]; null unless counting
+  uint32_t n;
+  uint32_t maxK;      // 0: count
+  uint32_t* next;
+  uint32_t refill;
+};
+
+// Enqueues lt_nearest_k_kernel on `s`.  Returns the first HIP error.
+hipError_t launch_k(const lt::SceneDev& sc, const KParams& p, uint32_t cuCount, hipStream_t s);
 
 }  // namespace lt_nearest
 #endif

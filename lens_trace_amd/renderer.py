@@ -207,6 +207,27 @@ def nearest_points_host(scene: Scene, points, max_d2=np.inf):
     return out
 
 
+def _nearest_k_desc(k, count):
+    if not count and not 1 <= k <= C.NEAREST_MAX_K:
+        raise ValueError("k must be in 1..%d" % C.NEAREST_MAX_K)
+    return C.NearestKDesc(ctypes.sizeof(C.NearestKDesc), 0, C.NEAREST_COUNT if count else C.NEAREST_FIRST_K, 0 if count else int(k))
+
+
+def nearest_k_host(scene: Scene, points, k=4, count=False, max_d2=np.inf):
+    """lt_hip_nearest_k_host: RendererHIP.nearest_k's answers computed on the host from the scene's own buffers, leaf by leaf -- no
+    context, no GPU.  points as nearest_k takes numpy batches; returns an (n, k) HIT_DTYPE array or, count, (n,) uint32."""
+    d = _nearest_k_desc(k, count)
+    pts = point_records(np.asarray(points), max_d2)
+    nodes, prims = np.ascontiguousarray(scene.nodes), np.ascontiguousarray(scene.prims)
+    out = np.zeros(pts.shape[0], dtype=np.uint32) if count else np.zeros((pts.shape[0], int(k)), dtype=HIT_DTYPE)
+    vp = ctypes.c_void_p
+    rc = C.load().lt_hip_nearest_k_host(nodes.ctypes.data_as(vp), nodes.nbytes, prims.ctypes.data_as(vp), prims.nbytes, ctypes.byref(d),
+                                        pts.ctypes.data_as(vp), pts.shape[0], out.ctypes.data_as(vp), out.nbytes)
+    if rc:
+        raise C.LensTraceError(rc, "lt_hip_nearest_k_host failed")
+    return out
+
+
 _QUERY_RAYS = (RAY_DTYPE, ("make_rays", "RAY_DTYPE"))
 _SHADE_RAYS = (SHADE_RAY_DTYPE, ("make_shade_rays", "SHADE_RAY_DTYPE"))
 
@@ -444,6 +465,12 @@ class RendererHIP:
         if isinstance(points, np.ndarray):
             pts = point_records(points, max_d2)
             return self._host_call("nearest_points", d, pts, np.zeros(pts.shape[0], dtype=HIT_DTYPE))
+        return self._device_call("nearest_points", d, self._point_tensor(points, max_d2, stream), "points", "n", 4, ("float32", (4,)), stream)
+
+    @staticmethod
+    def _point_tensor(points, max_d2, stream):
+        """A torch batch of points as lt_hip_point records: (n, 3) positions are packed with max_d2, anything else is left to
+        _device_call's checks."""
         import torch
         if isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[1] == 3:
             m = torch.as_tensor(max_d2, dtype=torch.float32, device=points.device)
@@ -452,7 +479,23 @@ class RendererHIP:
             # (the records are packed by torch, on the call's stream when it is a torch stream, else on the current one)
             with torch.cuda.stream(stream if isinstance(stream, torch.cuda.Stream) else None):
                 points = torch.cat([points, m.expand(points.shape[0]).unsqueeze(1)], dim=1).contiguous()
-        return self._device_call("nearest_points", d, points, "points", "n", 4, ("float32", (4,)), stream)
+        return points
+
+    def nearest_k(self, points, k=4, count=False, max_d2=np.inf, stream=None):
+        """The `k` (1..C.NEAREST_MAX_K) closest primitives of each point, nearest first, or with count=True how many lie within
+        max_d2 (lt_hip_nearest_k; include/lenstrace_hip.h defines the candidate sequence: nearest_points' candidates by squared
+        distance, the lower primitive offset first among equal ones).  Points and max_d2 as nearest_points takes them.  A numpy
+        batch goes to the host entry point and numpy comes back: an (n, k) HIT_DTYPE array whose unused slots are miss records
+        (t = max_d2, prim -1), or (n,) uint32 counts; a torch tensor on this context's GPU is enqueued on `stream` (default: the
+        current torch stream) and torch comes back: (n, k, 4) float32 (column 1: int32 bits) or (n,) int32 counts.  A count with
+        max_d2 = inf visits every leaf for every point."""
+        d = _nearest_k_desc(k, count)
+        k = 0 if count else int(k)
+        if isinstance(points, np.ndarray):
+            pts = point_records(points, max_d2)
+            return self._host_call("nearest_k", d, pts, np.zeros(pts.shape[0], dtype=np.uint32) if count else np.zeros((pts.shape[0], k), dtype=HIT_DTYPE))
+        return self._device_call("nearest_k", d, self._point_tensor(points, max_d2, stream), "points", "n", 4,
+                                 ("int32", ()) if count else ("float32", (k, 4)), stream)
 
     # -- shaded rays ------------------------------------------------------------------------------------
     def shade_rays(self, rays, program="accumulator", frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR, portable_math=False,
