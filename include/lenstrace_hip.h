@@ -566,6 +566,73 @@ int lt_hip_nearest_k_device(lt_hip_context* ctx, const lt_hip_nearest_k_desc* de
 int lt_hip_nearest_k_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
                           const lt_hip_nearest_k_desc* desc, const lt_hip_point* points, uint64_t n, void* out, uint64_t out_bytes);
 
+/* Box-overlap queries: the primitives an axis-aligned box touches, their number, or whether there is any -- for voxelisers and
+ * occupancy grids, the broad phase of a collision check against a volume, region selection, binning a scene into bricks.
+ *
+ * Record: lt_hip_box {lo[3], pad0, hi[3], pad1}; the pads are ignored.  A box is EMPTY, and touches nothing, when any of its six
+ * bounds is not finite or lo[k] <= hi[k] fails on some axis; lo == hi is a valid point box.
+ * Candidates: the leaves of the caller's LinearBVHNode array, each with its one primitive, exactly as the nearest queries take
+ * them; a leaf with primitiveCount > 1 contributes that one primitive once.
+ * A candidate touches the box q iff both hold:
+ *   boxes_meet     q meets the leaf's own box as the caller gave it: per axis q.lo <= leaf.hi && leaf.lo <= q.hi.  A NaN bound
+ *                  makes it false.
+ *   tri_meets_box  the traversal triangle as the scene stores it, A, e1 = fl(B - A), e2 = fl(C - A), is separated from q by none
+ *                  of 13 axes.  Every operation is one IEEE float32 operation rounded once, in the order given; nothing is
+ *                  contracted, subnormals are kept.  A compare with a NaN is false, which reads "not separated".  min and max of
+ *                  three are chains of compares: m = first; if (second < m) m = second; if (third < m) m = third (`>` for max).
+ *     box axes (3)   un-centred, on the vertices A, fl(A + e1), fl(A + e2): axis k separates iff min > hi[k] or max < lo[k].
+ *                    Compares only: a vertex exactly on a face touches the cells on both sides.
+ *     centring       per axis c = 0.5 lo + 0.5 hi, h = 0.5 hi - 0.5 lo (two products, then the sum or difference; h >= 0),
+ *                    v0 = A - c, v1 = v0 + e1, v2 = v0 + e2.
+ *     plane (1)      n = e1 x e2: n.x = e1.y e2.z - e1.z e2.y, n.y = e1.z e2.x - e1.x e2.z, n.z = e1.x e2.y - e1.y e2.x;
+ *                    d = (n.x v0.x + n.y v0.y) + n.z v0.z; r = (|n.x| h.x + |n.y| h.y) + |n.z| h.z; separates iff d > r or d < -r.
+ *     edge axes (9)  the edges f0 = e1, f1 = e2 - e1, f2 = -e2 in that order, each crossed with the unit axes x, y, z in that
+ *                    order.  The projections of v0, v1, v2 (in that order, all three) and the box's radius are
+ *                      x:  p = v.z f.y - v.y f.z,   r = h.z |f.y| + h.y |f.z|
+ *                      y:  p = v.x f.z - v.z f.x,   r = h.x |f.z| + h.z |f.x|
+ *                      z:  p = v.y f.x - v.x f.y,   r = h.y |f.x| + h.x |f.y|
+ *                    and the axis separates iff min(p) > r or max(p) < -r.  A point triangle or a needle gives zero axes, which
+ *                    separate nothing; the other axes decide.
+ *                  (lens_trace_amd/csrc/lt_overlap.hpp is the expression sequence; tests/overlap.py restates it in numpy.)
+ * The sequence of a box: every touching candidate once, by ascending primitive offset, then ascending node index in the caller's
+ * array (only scenes whose leaves name one primitive twice have a second key).  An empty box has the empty sequence.  The
+ * sequence is a function of the scene and the box alone: whichever hierarchy is walked, the words are these.
+ *   LT_OVERLAP_FIRST_K  the first max_k entries as max_k consecutive int32 primitive offsets per box, box-major: word
+ *                       i * max_k + j is entry j of box i.  Unused slots hold -1.  No subtree can be skipped because of its
+ *                       offsets, so this costs what LT_OVERLAP_COUNT costs.
+ *   LT_OVERLAP_COUNT    one uint32 per box: the length of the sequence.
+ *   LT_OVERLAP_ANY      one uint32 per box: 1 iff the sequence is not empty (the walk may stop at the first touch).
+ *
+ * flags: 0.  max_k: 1 .. LT_OVERLAP_MAX_K for LT_OVERLAP_FIRST_K, 0 for the other kinds.  Host memory, synchronous.  Errors in
+ * lt_hip_nearest_k's order: LT_ERR_INVALID_ARGUMENT for a null ctx / desc, struct_size too small, flags != 0, an unknown kind,
+ * max_k outside its range for the kind, n >= 2^32, a null pointer with n > 0 (and, device entry point, pointers that are not
+ * 16-byte aligned); LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when out_bytes < 4 max_k n (FIRST_K) or 4 n (COUNT, ANY).  A failed
+ * call writes nothing to out; n == 0 launches nothing.  lt_hip_get_stats then reports rays = n, kernel_launches = 1 and
+ * kernel_ms.  (lens_trace_amd/csrc/lt_overlap.hip) */
+#define LT_OVERLAP_FIRST_K 0
+#define LT_OVERLAP_COUNT   1
+#define LT_OVERLAP_ANY     2
+#define LT_OVERLAP_MAX_K   8
+typedef struct lt_hip_box { float lo[3]; uint32_t pad0; float hi[3]; uint32_t pad1; } lt_hip_box;   /* 32 B */
+typedef struct lt_hip_overlap_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_overlap_desc) */
+  uint32_t flags;               /* 0 */
+  int32_t kind;                 /* LT_OVERLAP_FIRST_K / LT_OVERLAP_COUNT / LT_OVERLAP_ANY */
+  uint32_t max_k;               /* FIRST_K: 1 .. LT_OVERLAP_MAX_K; COUNT, ANY: 0 */
+} lt_hip_overlap_desc;          /* 16 B */
+
+int lt_hip_overlap_boxes(lt_hip_context* ctx, const lt_hip_overlap_desc* desc, const lt_hip_box* boxes, uint64_t n,
+                         void* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_overlap_boxes_device(lt_hip_context* ctx, const lt_hip_overlap_desc* desc, const lt_hip_box* boxes, uint64_t n,
+                                void* out, uint64_t out_bytes, void* hip_stream);
+/* The same answers on the host, without a context or a GPU, from the caller's buffers, as lt_hip_nearest_k_host takes them: a scan
+ * of the caller's leaves in node order.  LT_ERR_INVALID_ARGUMENT (a null desc, struct_size, flags, kind or max_k as above, a null
+ * or mis-sized buffer, n >= 2^32), LT_ERR_BAD_SCENE (a leaf whose offset lies outside prims), LT_ERR_BUFFER_TOO_SMALL; a failed
+ * call writes nothing. */
+int lt_hip_overlap_boxes_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                              const lt_hip_overlap_desc* desc, const lt_hip_box* boxes, uint64_t n, void* out, uint64_t out_bytes);
+
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
 

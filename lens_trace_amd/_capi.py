@@ -26,6 +26,8 @@ TRACE_FIRST_K, TRACE_COUNT = 0, 1    # lt_hip_multihit_desc::kind (lt_hip_trace_
 TRACE_MAX_HITS = 8                   # LT_TRACE_MAX_HITS
 NEAREST_FIRST_K, NEAREST_COUNT = 0, 1   # lt_hip_nearest_k_desc::kind
 NEAREST_MAX_K = 8                    # LT_NEAREST_MAX_K
+OVERLAP_FIRST_K, OVERLAP_COUNT, OVERLAP_ANY = 0, 1, 2   # lt_hip_overlap_desc::kind
+OVERLAP_MAX_K = 8                    # LT_OVERLAP_MAX_K
 SURFACE_LIGHT = 1                    # lt_hip_surface::flags: the primitive is in the light list
 
 # every symbol include/lenstrace_hip.h declares
@@ -37,7 +39,8 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_shade_rays", "lt_hip_shade_rays_device", "lt_hip_shade_paths", "lt_hip_shade_paths_device",
            "lt_hip_trace_surface", "lt_hip_trace_surface_device", "lt_hip_surface_at", "lt_hip_surface_at_device",
            "lt_hip_nearest_points", "lt_hip_nearest_points_device", "lt_hip_nearest_points_host",
-           "lt_hip_nearest_k", "lt_hip_nearest_k_device", "lt_hip_nearest_k_host"]
+           "lt_hip_nearest_k", "lt_hip_nearest_k_device", "lt_hip_nearest_k_host",
+           "lt_hip_overlap_boxes", "lt_hip_overlap_boxes_device", "lt_hip_overlap_boxes_host"]
 
 
 class RenderDesc(ctypes.Structure):
@@ -120,6 +123,14 @@ class NearestKDesc(ctypes.Structure):   # lt_hip_nearest_k_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("kind", ctypes.c_int32), ("max_k", ctypes.c_uint32)]
 
 
+class Box(ctypes.Structure):   # lt_hip_box
+    _fields_ = [("lo", ctypes.c_float * 3), ("pad0", ctypes.c_uint32), ("hi", ctypes.c_float * 3), ("pad1", ctypes.c_uint32)]
+
+
+class OverlapDesc(ctypes.Structure):   # lt_hip_overlap_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("kind", ctypes.c_int32), ("max_k", ctypes.c_uint32)]
+
+
 def _np_dtypes():
     import numpy as np
     ray = np.dtype([("origin", "<f4", (3,)), ("tmax", "<f4"), ("direction", "<f4", (3,)), ("ignore", "<i4")])
@@ -155,6 +166,14 @@ def _np_point_dtype():
 
 
 POINT_DTYPE = _np_point_dtype()   # numpy view of lt_hip_point (16 bytes)
+
+
+def _np_box_dtype():
+    import numpy as np
+    return np.dtype([("lo", "<f4", (3,)), ("pad0", "<u4"), ("hi", "<f4", (3,)), ("pad1", "<u4")])
+
+
+BOX_DTYPE = _np_box_dtype()   # numpy view of lt_hip_box (32 bytes)
 
 
 class LensTraceError(RuntimeError):
@@ -226,6 +245,10 @@ def load():
         L.lt_hip_nearest_k.argtypes = [vp, ctypes.POINTER(NearestKDesc), vp, u64, vp, u64]
         L.lt_hip_nearest_k_device.argtypes = [vp, ctypes.POINTER(NearestKDesc), vp, u64, vp, u64, vp]
         L.lt_hip_nearest_k_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(NearestKDesc), vp, u64, vp, u64]
+    if hasattr(L, "lt_hip_overlap_boxes"):
+        L.lt_hip_overlap_boxes.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
+        L.lt_hip_overlap_boxes_device.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64, vp]
+        L.lt_hip_overlap_boxes_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

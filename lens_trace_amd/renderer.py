@@ -228,6 +228,61 @@ def nearest_k_host(scene: Scene, points, k=4, count=False, max_d2=np.inf):
     return out
 
 
+BOX_DTYPE = C.BOX_DTYPE
+
+
+def make_boxes(lo, hi):
+    """Packs boxes for RendererHIP.overlap_boxes: (n, 3) lower and upper corners into an (n, 8) float32 array of lt_hip_box
+    records (lo, pad, hi, pad; the pads are zero and ignored)."""
+    lo = np.asarray(lo, dtype=np.float32)
+    hi = np.asarray(hi, dtype=np.float32)
+    if lo.ndim != 2 or lo.shape[1] != 3 or hi.shape != lo.shape:
+        raise ValueError("lo and hi must both have shape (n, 3)")
+    out = np.zeros((lo.shape[0], 8), dtype=np.float32)
+    out[:, 0:3] = lo
+    out[:, 4:7] = hi
+    return out
+
+
+def box_records(boxes):
+    """A numpy batch of boxes as a contiguous (n, 8) float32 array of lt_hip_box records: a 1-D BOX_DTYPE array or an (n, 8)
+    float32 array (make_boxes)."""
+    if boxes.dtype == BOX_DTYPE and boxes.ndim == 1:
+        boxes = np.ascontiguousarray(boxes).view(np.float32).reshape(-1, 8)
+    if boxes.dtype != np.float32 or boxes.ndim != 2 or boxes.shape[1] != 8:
+        raise ValueError("boxes must be an (n, 8) float32 array (make_boxes) or a BOX_DTYPE array")
+    return np.ascontiguousarray(boxes)
+
+
+def _overlap_desc(k, count, any):
+    if count and any:
+        raise ValueError("count and any exclude each other")
+    if (count or any) and k is not None:
+        raise ValueError("k goes with neither count nor any")
+    if not (count or any):
+        k = 4 if k is None else k
+        if not 1 <= k <= C.OVERLAP_MAX_K:
+            raise ValueError("k must be in 1..%d" % C.OVERLAP_MAX_K)
+    kind = C.OVERLAP_COUNT if count else C.OVERLAP_ANY if any else C.OVERLAP_FIRST_K
+    return C.OverlapDesc(ctypes.sizeof(C.OverlapDesc), 0, kind, 0 if (count or any) else int(k))
+
+
+def overlap_boxes_host(scene: Scene, boxes, k=None, count=False, any=False):
+    """lt_hip_overlap_boxes_host: RendererHIP.overlap_boxes' answers computed on the host from the scene's own buffers, leaf by
+    leaf -- no context, no GPU.  boxes as overlap_boxes takes numpy batches; returns an (n, k) int32 array or, count / any, (n,)
+    uint32."""
+    d = _overlap_desc(k, count, any)
+    bx = box_records(np.asarray(boxes))
+    nodes, prims = np.ascontiguousarray(scene.nodes), np.ascontiguousarray(scene.prims)
+    out = np.zeros((bx.shape[0], d.max_k), dtype=np.int32) if d.max_k else np.zeros(bx.shape[0], dtype=np.uint32)
+    vp = ctypes.c_void_p
+    rc = C.load().lt_hip_overlap_boxes_host(nodes.ctypes.data_as(vp), nodes.nbytes, prims.ctypes.data_as(vp), prims.nbytes, ctypes.byref(d),
+                                            bx.ctypes.data_as(vp), bx.shape[0], out.ctypes.data_as(vp), out.nbytes)
+    if rc:
+        raise C.LensTraceError(rc, "lt_hip_overlap_boxes_host failed")
+    return out
+
+
 _QUERY_RAYS = (RAY_DTYPE, ("make_rays", "RAY_DTYPE"))
 _SHADE_RAYS = (SHADE_RAY_DTYPE, ("make_shade_rays", "SHADE_RAY_DTYPE"))
 
@@ -496,6 +551,23 @@ class RendererHIP:
             return self._host_call("nearest_k", d, pts, np.zeros(pts.shape[0], dtype=np.uint32) if count else np.zeros((pts.shape[0], k), dtype=HIT_DTYPE))
         return self._device_call("nearest_k", d, self._point_tensor(points, max_d2, stream), "points", "n", 4,
                                  ("int32", ()) if count else ("float32", (k, 4)), stream)
+
+    # -- box-overlap queries ---------------------------------------------------------------------------
+    def overlap_boxes(self, boxes, k=None, count=False, any=False, stream=None):
+        """The primitives each axis-aligned box touches (lt_hip_overlap_boxes; include/lenstrace_hip.h defines "touches": the
+        leaf's box meets the box and the triangle passes the 13-axis test): the `k` (1..C.OVERLAP_MAX_K, default 4) lowest
+        primitive offsets in ascending order, -1 in unused slots; with count=True how many there are; with any=True 1 or 0.  A box
+        with a bound that is not finite or with lo > hi on an axis touches nothing.
+        boxes: an (n, 8) float32 array of lt_hip_box records (make_boxes) or a BOX_DTYPE array -- then the host entry point runs
+        and numpy comes back: (n, k) int32 or (n,) uint32; or a contiguous (n, 8) float32 torch tensor on this context's GPU --
+        then the call is enqueued on `stream` (default: the current torch stream) and torch comes back: (n, k) int32 or (n,)
+        int32."""
+        d = _overlap_desc(k, count, any)
+        if isinstance(boxes, np.ndarray):
+            bx = box_records(boxes)
+            out = np.zeros((bx.shape[0], d.max_k), dtype=np.int32) if d.max_k else np.zeros(bx.shape[0], dtype=np.uint32)
+            return self._host_call("overlap_boxes", d, bx, out)
+        return self._device_call("overlap_boxes", d, boxes, "boxes", "n", 8, ("int32", (d.max_k,) if d.max_k else ()), stream)
 
     # -- shaded rays ------------------------------------------------------------------------------------
     def shade_rays(self, rays, program="accumulator", frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR, portable_math=False,
