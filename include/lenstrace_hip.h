@@ -269,7 +269,10 @@ int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* out, uint64
  * basic_lighting.cl:4: 1e-7 in double; the three others: 1e-4 in double).  Kept as the reference has them: no t > 0 test, no
  * tmin, `t < tmax` with tmax as given (0, negative, inf and NaN included).  The kernel sets origin.w = 1, direction.w = +0.
  * The walk may follow the backend's own hierarchy: results are the same bit for bit (equal t from two triangles: the
- * reference's first leaf wins).  lens_trace_amd/csrc/lt_query.hip. */
+ * reference's first leaf wins).  lens_trace_amd/csrc/lt_query.hip.
+ * Streams: the ray, point and box queries (lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_nearest_points,
+ * lt_hip_nearest_k, lt_hip_overlap_boxes, host and _device forms) share the context's work counters, so calls of these entry
+ * points are ordered among themselves on any streams (each waits for the one enqueued before it). */
 typedef struct lt_hip_ray { float origin[3]; float tmax; float direction[3]; int32_t ignore; } lt_hip_ray;   /* 32 B, ignore -1 = none */
 typedef struct lt_hip_hit { float t; int32_t prim; float u, v; } lt_hip_hit;   /* 16 B; a miss: prim = -1, t = tmax, u = v = 0 */
 

@@ -1,15 +1,16 @@
-"""GPU (-m gpu): what the twelve ray entry points (lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at,
-lt_hip_shade_rays, lt_hip_shade_paths, each with its _device form) have in common -- the part of lens_trace_amd/csrc/lt_capi.hip
-behind its `ray queries` banner that is host code alone.  Cornell box, a few hundred rays at the most.
+"""GPU (-m gpu): what the eighteen ray entry points (lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at,
+lt_hip_shade_rays, lt_hip_shade_paths, lt_hip_nearest_points, lt_hip_nearest_k, lt_hip_overlap_boxes, each with its _device form)
+have in common -- the part of lens_trace_amd/csrc/lt_capi.hip behind its `ray queries` banner that is host code alone.  Cornell
+box, a few hundred records at the most.
 
 1. messages and precedence: every argument check of every entry point, in the order the library makes them, with its return code
    and the text of lt_hip_last_error; every two neighbouring checks violated in one call give the earlier one's; the output keeps
    its fill pattern throughout;
 2. the host and the device form of a family give the same bytes at n = 1, 63, 64, 65 and 130, and lt_hip_get_stats the same
    figures;
-3. the host forms share two staging buffers: a sequence of calls with records of 16, 32 and 48 bytes on one context gives what
-   each call gives on a fresh context;
-4. the device forms of all six families back to back on one caller stream give the host forms' results."""
+3. the host forms share two staging buffers: a sequence of calls with records of 4, 16, 32, 48 and 128 bytes on one context
+   gives what each call gives on a fresh context;
+4. the device forms of all nine families back to back on one caller stream give the host forms' results."""
 import ctypes
 import os
 
@@ -17,7 +18,9 @@ import numpy as np
 import pytest
 
 from lens_trace_amd import _capi as C
-from lens_trace_amd.renderer import HIT_DTYPE, RendererHIP, make_shade_rays
+from lens_trace_amd.renderer import HIT_DTYPE, RendererHIP, make_shade_rays, nearest_points_host, overlap_boxes_host
+from tests import nearest_k as nk
+from tests import overlap as ov
 from tests import shade_rays as F
 from tests.test_gpu_trace_rays import random_rays
 
@@ -143,8 +146,45 @@ PATHS_CHECKS = shade_checks(
      ("reserved", INVALID, "lt_hip_paths_desc::reserved must be 0", {"reserved": 1}, {})])
 
 
+# The point and box families have no program and no flags: the descriptor's own rules (one function per family, for the context's
+# entry points and the GPU-free form alike) come first, in the order of the fields' dependence -- flags, kind, then max_k as the
+# kind reads it.  Not violated together:
+#   * "kind" with "first_k" or "count": an unknown kind is neither of the kinds whose max_k is checked; its neighbour is "n";
+#   * "first_k" with "count": the two are about max_k under kinds that exclude each other; "first_k" is paired with "n" instead.
+def plain_checks(name, struct, small_size, noun, more):
+    return HEAD + [
+        ("desc", INVALID, "%s: desc is NULL" % name, {"desc_null": True}, {"size": None}),
+        ("size", INVALID, "bad %s (struct_size)" % struct, {"struct_size": small_size}, {}),
+        ("flags", INVALID, "%s takes no flags" % name, [{"flags": 1}, {"flags": C.RENDER_FLAG_STRICT_MATH}, {"flags": C.TRACE_FLAG_COHERENT}], {}),
+    ] + more + common(noun, "call", "%s or out is NULL" % noun, "device %s and out must be 16-byte aligned" % noun, "%s before lt_hip_set_scene" % name)
+
+
+NEAREST_CHECKS = plain_checks("lt_hip_nearest_points", "lt_hip_nearest_desc", 4, "points", [])
+NEAREST_K_CHECKS = plain_checks("lt_hip_nearest_k", "lt_hip_nearest_k_desc", 12, "points", [
+    ("kind", INVALID, "unknown nearest kind", [{"kind": 2}, {"kind": -1}], {"first_k": None, "n": {"kind": 2, "n": 2 ** 32}}),
+    ("first_k", INVALID, "LT_NEAREST_FIRST_K takes max_k in 1 .. LT_NEAREST_MAX_K",
+     [{"kind": C.NEAREST_FIRST_K, "max_k": 0}, {"kind": C.NEAREST_FIRST_K, "max_k": C.NEAREST_MAX_K + 1}],
+     {"count": None, "n": {"kind": C.NEAREST_FIRST_K, "max_k": 0, "n": 2 ** 32}}),
+    ("count", INVALID, "LT_NEAREST_COUNT takes max_k = 0", {"kind": C.NEAREST_COUNT, "max_k": 1}, {}),
+])
+OVERLAP_CHECKS = plain_checks("lt_hip_overlap_boxes", "lt_hip_overlap_desc", 12, "boxes", [
+    ("kind", INVALID, "unknown overlap kind", [{"kind": 3}, {"kind": -1}], {"first_k": None, "n": {"kind": 3, "n": 2 ** 32}}),
+    ("first_k", INVALID, "LT_OVERLAP_FIRST_K takes max_k in 1 .. LT_OVERLAP_MAX_K",
+     [{"kind": C.OVERLAP_FIRST_K, "max_k": 0}, {"kind": C.OVERLAP_FIRST_K, "max_k": C.OVERLAP_MAX_K + 1}],
+     {"count": None, "n": {"kind": C.OVERLAP_FIRST_K, "max_k": 0, "n": 2 ** 32}}),
+    ("count", INVALID, "LT_OVERLAP_COUNT and LT_OVERLAP_ANY take max_k = 0",
+     [{"kind": C.OVERLAP_COUNT, "max_k": 1}, {"kind": C.OVERLAP_ANY, "max_k": 1}], {}),
+])
+
+
 def result_bytes(family, call):
     """bytes of one result record of the call"""
+    if family == "nearest_points":
+        return 16
+    if family == "nearest_k":
+        return 4 if call["kind"] == C.NEAREST_COUNT else 16 * call["max_k"]
+    if family == "overlap_boxes":
+        return 4 * call["max_k"] if call["kind"] == C.OVERLAP_FIRST_K else 4
     if family == "trace_rays":
         return 4 if call["kind"] == C.TRACE_ANY else 16
     if family == "trace_hits":
@@ -162,6 +202,9 @@ FAMILIES = {
                    SHADE_CHECKS),
     "shade_paths": (C.PathsDesc, {"program": C.PROGRAM_GLOBAL_ILLUMINATION, "kernel_mode": C.KERNEL_MODE_LINEAR, "flags": 0, "frame_first": 0,
                                   "frame_count": 1, "gi_max_depth": 2, "reserved": 0}, 32, PATHS_CHECKS),
+    "nearest_points": (C.NearestDesc, {"flags": 0}, 16, NEAREST_CHECKS),
+    "nearest_k": (C.NearestKDesc, {"flags": 0, "kind": C.NEAREST_FIRST_K, "max_k": 2}, 16, NEAREST_K_CHECKS),
+    "overlap_boxes": (C.OverlapDesc, {"flags": 0, "kind": C.OVERLAP_FIRST_K, "max_k": 2}, 32, OVERLAP_CHECKS),
 }
 ENTRY_POINTS = [(f, device) for f in FAMILIES for device in (False, True)]
 
@@ -289,6 +332,12 @@ VARIANTS = {
     "surface_at": ("surface_at", {}, "hits", 1, None),
     "shade_rays": ("shade_rays", {"frame_count": 2}, "shade", 1, "rays"),
     "shade_paths": ("shade_paths", {"gi_max_depth": 2, "frame_count": 2}, "shade", 2 + 1 + 2 + 1, "rays"),
+    "nearest_points": ("nearest_points", {}, "points", 1, "rays"),
+    "nearest_k": ("nearest_k", {"k": 3}, "points", 1, "rays"),
+    "nearest_k_count": ("nearest_k", {"count": True}, "points", 1, "rays"),
+    "overlap_boxes": ("overlap_boxes", {"k": 3}, "boxes", 1, "rays"),
+    "overlap_count": ("overlap_boxes", {"count": True}, "boxes", 1, "rays"),
+    "overlap_any": ("overlap_boxes", {"any": True}, "boxes", 1, "rays"),
 }
 
 
@@ -302,7 +351,8 @@ def renderer():
 
 @pytest.fixture(scope="module")
 def inputs(renderer):
-    """130 records of each kind of input: lt_hip_ray, lt_hip_shade_ray, and lt_hip_hit as (n, 1) of trace_hits"""
+    """130 records of each kind of input: lt_hip_ray, lt_hip_shade_ray, lt_hip_hit as (n, 1) of trace_hits, lt_hip_point and
+    lt_hip_box (tests/nearest_k.py's and tests/overlap.py's families, shuffled: hits and misses among any 63 of them)"""
     s = F.scene(SCENE)
     rng = np.random.default_rng(5)
     q = random_rays(s, rng, 130)
@@ -310,7 +360,13 @@ def inputs(renderer):
     shade = make_shade_rays(q[:, 0:3], q[:, 4:7], rng.uniform(-0.5, 0.5, len(q)), rng.uniform(-0.5, 0.5, len(q)))
     hits = renderer.trace_hits(q, max_hits=1)
     assert hits.shape == (130, 1) and hits.dtype == HIT_DTYPE and (hits["prim"] >= 0).any() and (hits["prim"] < 0).any()
-    return {"rays": F.frozen(q), "shade": F.frozen(shade), "hits": F.frozen(hits)}
+    points = np.concatenate(list(nk.families(s, seed=5, n=48).values()))
+    points = np.ascontiguousarray(points[rng.permutation(len(points))[:130]])
+    boxes = np.concatenate(list(ov.families(s, seed=5, n=48).values()))
+    boxes = np.ascontiguousarray(boxes[rng.permutation(len(boxes))[:130]])
+    near, touched = nearest_points_host(s, points[:63])["prim"], overlap_boxes_host(s, boxes[:63], any=True)
+    assert (near >= 0).sum() >= 8 and (near < 0).sum() >= 8 and (touched == 1).sum() >= 8 and (touched == 0).sum() >= 8
+    return {"rays": F.frozen(q), "shade": F.frozen(shade), "hits": F.frozen(hits), "points": F.frozen(points), "boxes": F.frozen(boxes)}
 
 
 def words(a):
@@ -365,8 +421,10 @@ def test_host_and_device_forms_agree_and_report_the_same(renderer, inputs, varia
     assert (words(host) != 0).any()
 
 
-SEQUENCE = (("trace_rays", 130), ("shade_rays", 1), ("trace_surface", 65), ("surface_at", 65), ("trace_hits", 64), ("shade_paths", 63), ("trace_rays", 1))
-SEQUENCE_ARGS = {"trace_hits": {"max_hits": 8}}
+SEQUENCE = (("trace_rays", 130), ("shade_rays", 1), ("trace_surface", 65), ("surface_at", 65), ("trace_hits", 64), ("shade_paths", 63), ("trace_rays", 1),
+            # records of 16 bytes in with 128 out, and of 32 in with 4 out
+            ("nearest_k", 130), ("overlap_any", 65), ("nearest_points", 64), ("overlap_boxes", 63), ("trace_rays", 1))
+SEQUENCE_ARGS = {"trace_hits": {"max_hits": 8}, "nearest_k": {"k": 8}, "overlap_boxes": {"k": 8}}
 
 
 def sequence_call(r, variant, inputs, n):

@@ -387,18 +387,20 @@ def batch(which):
 _plain = {}
 
 
-def plain_and_poisoned(which, poison, what, call):
-    """call(context) in a context with the switch and in one without it (that result kept per `what`): (poisoned, plain)"""
+def plain_and_poisoned(which, poison, what, call, resident=None):
+    """call(context) in a context with the switch and in one without it (that result kept per `what`): (poisoned, plain).  The
+    scene is walk_scene(which), or `resident` (tests/test_gpu_query_shapes.py's scenes, which it names `which`)."""
+    s = walk_scene(which) if resident is None else resident
     if (which, what) not in _plain:
         r = context()
         try:
-            r.set_scene(walk_scene(which))
+            r.set_scene(s)
             _plain[which, what] = call(r)
         finally:
             r.close()
     r = context(poison)
     try:
-        r.set_scene(walk_scene(which))
+        r.set_scene(s)
         return call(r), _plain[which, what]
     finally:
         r.close()
