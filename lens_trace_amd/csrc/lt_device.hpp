@@ -964,6 +964,38 @@ __device__ __forceinline__ bool packet_ray_ok(const Ray& ray, float ix, float iy
 // ray[0] and ray[1] share their origin, both frames' rays of the wave lie in the octant NEG.  On return pl[j].hitType is 1 where
 // frame j's ray met an occluder.  The plain-C++ form first (-DLT_NO_ASM_WALKS): packet_walk_cpp's any-hit walk with a `live` mask
 // per frame and a child pushed when some lane of either frame enters it (frame 1 is asked only where frame 0 does not).
+//
+// Its leaf is LT_ASM_WALK2's: tvec = o - A once per record, then one frame's test after the other (leaf2_frame:
+// intersect_triangle_anyhit given tvec).  The dot products are dot4's fma chains without the `a.w * b.w` term, which is zero in
+// each of the four; lt_walk_asm.hpp says, in front of LT_ASM_TESTS2, why no accept of THIS walk can depend on it (eps > 0, rays
+// from normalize4, nothing returned but the accept).
+//
+// The two-frame walk's triangle epsilon: accumulator.cl's `(double)fabs(det) < 1e-4` as a float compare (intersect_triangle_data).
+// Both forms of its leaf lean on eps > 0 (a det of -0 never reaches 1 / det) and on shade_lighting2's rays, so the walk is
+// kAccumulator's only: another program asks for the one-frame leaf's terms back first.
+template <int PROGRAM>
+struct Walk2Eps {
+  static_assert(PROGRAM == kAccumulator, "the two-frame walk's leaf drops dot4's zero-valued w terms: sound for accumulator's eps and rays only");
+  static constexpr uint32_t kBits = 0x38d1b718u;
+  static_assert(kBits > 0u && kBits < 0x7f800000u, "eps must be a positive finite float");
+};
+template <int PROGRAM>
+__device__ __forceinline__ float walk2_eps() { return __uint_as_float(Walk2Eps<PROGRAM>::kBits); }
+__device__ __forceinline__ float dot_xyz(V4 a, V4 b) { return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x)); }
+__device__ __forceinline__ bool leaf2_frame(V4 v0v1, V4 v0v2, V4 tvec, V4 d, float eps, float tmax, bool active, bool fastRcp) {
+  const V4 pvec = cross4(d, v0v2);
+  const float det = dot_xyz(v0v1, pvec);
+  bool ok = active && !(__builtin_fabsf(det) < eps);
+  const float invDet = fastRcp ? Math<2>::rcp(det) : 1.0f / det;
+  const float u = dot_xyz(tvec, pvec) * invDet;
+  ok = ok && !(u < 0.0f || u > 1.0f);
+  if (__builtin_amdgcn_ballot_w64(ok) == 0ull) return false;
+  const V4 qvec = cross4(tvec, v0v1);
+  const float v = dot_xyz(d, qvec) * invDet;
+  ok = ok && !(v < 0.0f || u + v > 1.0f);
+  const float tt = dot_xyz(v0v2, qvec) * invDet;
+  return ok && (tt < tmax);
+}
 template <int PROGRAM, int NEG>
 __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave) {
   using u64 = unsigned long long;
@@ -978,6 +1010,7 @@ __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2],
     live[j] = __builtin_amdgcn_ballot_w64(true);
   }
   const bool fast = sc.fastRcp != 0u;
+  const float eps = walk2_eps<PROGRAM>();
   uint32_t cur = 0u;
   int sp = 0;
   for (;;) {
@@ -992,13 +1025,14 @@ __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2],
       if (hmR != 0ull) ldsWave[sp++] = __float_as_int(r.se);
     } else {
       const int prim = __float_as_int(r.sf);
-      const float4 t0 = make_float4(r.s0, r.s1, r.s2, r.s3), t1 = make_float4(r.s4, r.s5, r.s6, r.s7), t2 = make_float4(r.s8, 0.0f, 0.0f, 0.0f);
+      const V4 A = mk4(r.s0, r.s1, r.s2, 1.0f), v0v1 = mk4(r.s3, r.s4, r.s5, 0.0f), v0v2 = mk4(r.s6, r.s7, r.s8, 0.0f);
+      const V4 tvec = sub4(ray[0].o, A);   // (ray[1].o is the same point)
 #pragma unroll
       for (int j = 0; j < 2; j++) {
         const u64 m = box_mask<NEG>(r.s9, r.sa, r.sb, r.sc, r.sd, r.se, ray[j], inv[j][0], inv[j][1], inv[j][2]) & live[j];
         if (m != 0ull) {
           const bool active = ((m >> lane) & 1ull) != 0ull && prim != ign;
-          live[j] &= ~__builtin_amdgcn_ballot_w64(intersect_triangle_anyhit<PROGRAM>(t0, t1, t2, ray[j], pl[j].t, active, fast));
+          live[j] &= ~__builtin_amdgcn_ballot_w64(leaf2_frame(v0v1, v0v2, tvec, ray[j].d, eps, pl[j].t, active, fast));
         }
       }
       if ((live[0] | live[1]) == 0ull) break;
@@ -1013,13 +1047,12 @@ __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2],
 template <int PROGRAM, int NEG>
 __device__ __forceinline__ void packet_walk2(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave) {
 #ifndef LT_NO_ASM_WALKS
-  const float eps = (PROGRAM == kBasic || PROGRAM == kCustom) ? 0.0000001f
-                    : (PROGRAM == kBasicLighting) ? __uint_as_float(0x33d6bf95u) : __uint_as_float(0x38d1b718u);
+  const float eps = walk2_eps<PROGRAM>();
   const uint32_t ldsrow = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) int*)ldsWave);
   unsigned long long open0 = __builtin_amdgcn_ballot_w64(true), open1 = open0;
   packet_anyhit_walk2<NEG>((const void*)sc.ownPairs, ray[0].o.x, ray[0].o.y, ray[0].o.z, inv[0][0], inv[0][1], inv[0][2], ray[0].d.x, ray[0].d.y,
-                           ray[0].d.z, ray[0].d.w, pl[0].t, inv[1][0], inv[1][1], inv[1][2], ray[1].d.x, ray[1].d.y, ray[1].d.z, ray[1].d.w,
-                           pl[1].t, ign, eps, sc.fastRcp, open0, open1, ldsrow);
+                           ray[0].d.z, pl[0].t, inv[1][0], inv[1][1], inv[1][2], ray[1].d.x, ray[1].d.y, ray[1].d.z, pl[1].t, ign, eps,
+                           sc.fastRcp, open0, open1, ldsrow);
   pl[0].hitType = ((open0 >> __lane_id()) & 1ull) != 0ull ? pl[0].hitType : 1;
   pl[1].hitType = ((open1 >> __lane_id()) & 1ull) != 0ull ? pl[1].hitType : 1;
 #else

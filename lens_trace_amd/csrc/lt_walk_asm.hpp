@@ -529,9 +529,32 @@ typedef unsigned long long lt_u64;
 // (EXEC = `open`) has let a lane into a child, frame 1's test of that child has no reader: it runs (EXEC = `open_1`, writing the mask
 // itself: nothing to OR) only for the children frame 0 missed -- the set of pushed children is that of testing both frames always.
 // A frame with no lane left looking has its tests branched over (frame 0's masks are then zeroed out of line: LT_ASM_TESTS2_ZERO).
-// Leaf: each frame's complete test in turn (the triangle's tvec / qvec and the box's (bound - o) depend on the origin only, but qvec
-// is only computed for the lanes past the u test, mostly none; recomputing them keeps every value what the one-frame walk computes
-// and costs no register); the walk ends when both masks are empty.
+// Leaf: tvec = o - A depends on the origin and the triangle only and every frame's u test needs it, so it is computed ONCE per
+// record, for the lanes open in either frame (LT_ASM_TRI2_TVEC: LT_ASM_TRI_PART1's three instructions, the same bits whatever
+// EXEC is), and kept in three registers of its own across both frames' tests; then each frame's test in turn under its own `open`
+// (LT_ASM_TRI2_PART1 / PART2: pvec, det, 1 / det, u, qvec, v, t, the late box test, the accept, narrowed test by test as in
+// the one-frame walk).  qvec = cross(tvec, e1) and the numerator of t, e2 . qvec, depend on the origin only as well, but stay
+// behind each frame's u test: on the 1 M-triangle wall 0.93 of a leaf record's two frame tests get past it (measured, DESIGN
+// 5.1), so computing them up front for both costs what it saves, and four more registers; and the box's (bound - o) is reached by
+// fewer than one frame test in ten.  The walk ends when both masks are empty.
+//
+// The two-frame leaf also drops the four instructions that restate dot4's `a.w * b.w` term in the one-frame leaf -- `x + 0`
+// after det, tvec . pvec and e2 . qvec, and `+ 0 * dw` in d . qvec.  They can change no accept HERE, term by term:
+//   * x + 0 differs from x for x = -0 only (NaN and +-inf pass through).
+//       - det: a zero of either sign is rejected by !(|det| < eps), because this walk's eps is 0x38d1b718 > 0 (packet_walk2
+//         asserts its program); for every lane that survives, |det| >= eps, so 1 / det is finite and non-zero, the same bits.
+//       - tvec . pvec and e2 . qvec: u, t = (that) * invDet become -0 instead of +0 at most; so may v and u + v.  They enter
+//         !(u < 0), !(u > 1), !(v < 0), !(u + v > 1) and t < tmax only, and no compare tells -0 from +0.
+//       - the walk returns the accept masks and nothing else: no u, v or t leaves it.
+//   * 0 * dw: every ray of this walk is shade_lighting2's normalize4(light - position), whose w is (1 - 1) * s = +0 * s with
+//     s = rsqrt(l2) -- in all three math flavours (Math<0 / 1 / 2>::rsqrt differ in s's last bits only; normalize4 rescales
+//     so that l2 is an ordinary positive float whenever the vector holds no NaN, and returns an all-zero vector as it is).
+//     So s is finite and positive, dw = +0 and the term adds +0 -- or the vector holds a NaN, s is NaN, dx, dy and dz are NaN,
+//     and d . qvec is NaN with or without the term.  (Were s 0 or inf, d would be 0 or infinite with it, det +-0, +-inf or
+//     NaN, and the accept would still not depend on the term: the test enumerates those too.)
+// Neither holds for the one-frame walks: the closest-hit walk hands out u, v and t, lt_query.hip feeds caller-made dw through
+// the any-hit walk, and kBasic's eps compares are not this one (tests/test_leaf2_zero_terms_cpu.py enumerates the cases and
+// shows the accept changing once eps is 0 or dw arbitrary).  They keep LT_ASM_TRI_PART1 / PART2 as they are.
 // LT_ASM_TESTS2's S: a suffix for its labels, distinct in every expansion inside one asm block (%= is unique per block only);
 // LT_ASM_TESTS2_ZERO(S), placed where control cannot fall into it, is the expansion's out-of-line part.
 #define LT_ASM_TESTS2(NF, L, R, S)                                                                                              \
@@ -556,12 +579,85 @@ typedef unsigned long long lt_u64;
   "s_mov_b64 " LT_R_HMR ", 0\n"                                                                                                 \
   "s_branch .Lt2second" S "%=\n"
 
+// tvec for the lanes open in either frame (a leaf is only popped while some lane is)
+#define LT_ASM_TRI2_TVEC                                                                                                        \
+  "s_or_b64 exec, %[open], %[open_1]\n"                                                                                         \
+  "v_subrev_f32_e32 %[tvx], " LT_R_AX ", %[ox]\n"   /* tvec = o - A */                                                          \
+  "v_subrev_f32_e32 %[tvy], " LT_R_AY ", %[oy]\n"                                                                               \
+  "v_subrev_f32_e32 %[tvz], " LT_R_AZ ", %[oz]\n"
+
+// one frame's det, 1 / det, u (EXEC narrowed by the det and u tests); leaves: t0 = invDet, t1 = u.  tvec . pvec fills the wait
+// for v_rcp where LT_ASM_TRI_PART1 computes tvec, and pvec's registers then serve the division.
+#define LT_ASM_TRI2_PART1(S)                                                                                                    \
+  "v_mul_f32_e64 %[t4], %[dz" S "], -" LT_R_E2Y "\n"     /* pvec = cross(d, e2) */                                              \
+  "v_mul_f32_e64 %[t5], %[dx" S "], -" LT_R_E2Z "\n"                                                                            \
+  "v_fmac_f32_e32 %[t4], " LT_R_E2Z ", %[dy" S "]\n"                                                                            \
+  "v_fmac_f32_e32 %[t5], " LT_R_E2X ", %[dz" S "]\n"                                                                            \
+  "v_mul_f32_e64 %[t6], %[dy" S "], -" LT_R_E2X "\n"                                                                            \
+  "v_mul_f32_e32 %[t0], " LT_R_E1X ", %[t4]\n"                                                                                  \
+  "v_fmac_f32_e32 %[t6], " LT_R_E2Y ", %[dx" S "]\n"                                                                            \
+  "v_fmac_f32_e32 %[t0], " LT_R_E1Y ", %[t5]\n"                                                                                 \
+  "v_fmac_f32_e32 %[t0], " LT_R_E1Z ", %[t6]\n"     /* det */                                                                   \
+  "s_cmp_lg_u32 %[fast], 0\n"                                                                                                   \
+  "s_cbranch_scc1 .LfastRcp" S "%=\n"                                                                                           \
+  "v_div_scale_f32 %[t1], " LT_R_HML ", %[t0], %[t0], 1.0\n"                                                                    \
+  "v_rcp_f32_e32 %[t2], %[t1]\n"                                                                                                \
+  "v_cmpx_nlt_f32_e64 " LT_R_HML ", |%[t0]|, %[eps]\n" /* !(fabs(det) < epsilon) */                                             \
+  "v_mul_f32_e32 %[t7], %[tvx], %[t4]\n"            /* tvec . pvec */                                                           \
+  "v_fmac_f32_e32 %[t7], %[tvy], %[t5]\n"                                                                                       \
+  "v_fmac_f32_e32 %[t7], %[tvz], %[t6]\n"                                                                                       \
+  "v_fma_f32 %[t3], -%[t1], %[t2], 1.0\n"                                                                                       \
+  "v_fmac_f32_e32 %[t2], %[t3], %[t2]\n"                                                                                        \
+  "v_div_scale_f32 %[t3], vcc, 1.0, %[t0], 1.0\n"                                                                               \
+  "v_mul_f32_e32 %[t4], %[t3], %[t2]\n"                                                                                         \
+  "v_fma_f32 %[t5], -%[t1], %[t4], %[t3]\n"                                                                                     \
+  "v_fmac_f32_e32 %[t4], %[t5], %[t2]\n"                                                                                        \
+  "v_fma_f32 %[t1], -%[t1], %[t4], %[t3]\n"                                                                                     \
+  "v_div_fmas_f32 %[t1], %[t1], %[t2], %[t4]\n"                                                                                 \
+  "v_div_fixup_f32 %[t0], %[t1], %[t0], 1.0\n"      /* invDet = 1 / det, correctly rounded */                                   \
+  "s_branch .LrcpDone" S "%=\n"                                                                                                 \
+  ".LfastRcp" S "%=:\n"                             /* the as-shipped build's 1 / det: ldexp(rcp(frexp_mant), -frexp_exp) */    \
+  "v_frexp_mant_f32_e32 %[t1], %[t0]\n"                                                                                         \
+  "v_rcp_f32_e32 %[t1], %[t1]\n"                                                                                                \
+  "v_cmpx_nlt_f32_e64 " LT_R_HML ", |%[t0]|, %[eps]\n"                                                                          \
+  "v_mul_f32_e32 %[t7], %[tvx], %[t4]\n"                                                                                        \
+  "v_fmac_f32_e32 %[t7], %[tvy], %[t5]\n"                                                                                       \
+  "v_fmac_f32_e32 %[t7], %[tvz], %[t6]\n"                                                                                       \
+  "v_frexp_exp_i32_f32_e32 %[t2], %[t0]\n"                                                                                      \
+  "v_sub_u32_e32 %[t2], 0, %[t2]\n"                                                                                             \
+  "v_ldexp_f32 %[t0], %[t1], %[t2]\n"                                                                                           \
+  ".LrcpDone" S "%=:\n"                                                                                                         \
+  "v_mul_f32_e32 %[t1], %[t7], %[t0]\n"             /* u */                                                                     \
+  "v_cmpx_ngt_f32_e64 " LT_R_HML ", 0, %[t1]\n"     /* !(u < 0) */                                                              \
+  "v_cmpx_nlt_f32_e64 " LT_R_HML ", 1.0, %[t1]\n"   /* !(u > 1) */                                                              \
+  "s_cbranch_execz .LleafEnd" S "%=\n"
+
+// one frame's qvec, v, u + v, t (EXEC narrowed by the v and u + v tests); leaves: t3 = t
+#define LT_ASM_TRI2_PART2(S)                                                                                                    \
+  "v_mul_f32_e64 %[t4], %[tvz], -" LT_R_E1Y "\n"    /* qvec = cross(tvec, e1) */                                                \
+  "v_fmac_f32_e32 %[t4], " LT_R_E1Z ", %[tvy]\n"                                                                                \
+  "v_mul_f32_e64 %[t5], %[tvx], -" LT_R_E1Z "\n"                                                                                \
+  "v_mul_f32_e64 %[t6], %[tvy], -" LT_R_E1X "\n"                                                                                \
+  "v_fmac_f32_e32 %[t5], " LT_R_E1X ", %[tvz]\n"                                                                                \
+  "v_fmac_f32_e32 %[t6], " LT_R_E1Y ", %[tvx]\n"                                                                                \
+  "v_mul_f32_e32 %[t2], %[dx" S "], %[t4]\n"                                                                                    \
+  "v_fmac_f32_e32 %[t2], %[dy" S "], %[t5]\n"                                                                                   \
+  "v_fmac_f32_e32 %[t2], %[dz" S "], %[t6]\n"                                                                                   \
+  "v_mul_f32_e32 %[t2], %[t2], %[t0]\n"             /* v */                                                                     \
+  "v_add_f32_e32 %[t7], %[t1], %[t2]\n"             /* u + v */                                                                 \
+  "v_mul_f32_e32 %[t3], " LT_R_E2X ", %[t4]\n"      /* the numerator of t */                                                    \
+  "v_fmac_f32_e32 %[t3], " LT_R_E2Y ", %[t5]\n"                                                                                 \
+  "v_fmac_f32_e32 %[t3], " LT_R_E2Z ", %[t6]\n"                                                                                 \
+  "v_cmpx_ngt_f32_e64 " LT_R_HML ", 0, %[t2]\n"     /* !(v < 0) */                                                              \
+  "v_cmpx_nlt_f32_e64 " LT_R_HML ", 1.0, %[t7]\n"   /* !(u + v > 1) */                                                          \
+  "v_mul_f32_e32 %[t3], %[t3], %[t0]\n"             /* t */
+
 #define LT_ASM_LEAF2(NF, S)                                                                                                     \
   "s_mov_b64 exec, %[open" S "]\n"                                                                                              \
   "s_cbranch_execz .LleafEnd" S "%=\n"                                                                                          \
   LT_ASM_IGNORE_ANYHIT                                                                                                          \
-  LT_ASM_TRI_PART1(S)                                                                                                           \
-  LT_ASM_TRI_PART2(S)                                                                                                           \
+  LT_ASM_TRI2_PART1(S)                                                                                                          \
+  LT_ASM_TRI2_PART2(S)                                                                                                          \
   "s_cbranch_execz .LleafEnd" S "%=\n"                                                                                          \
   LT_BXL(NF, LT_LOHI_LEAF, S)                                                                                                   \
   "v_cmpx_lt_f32_e64 " LT_R_HML ", %[t3], %[tmax" S "]\n" /* t < payload.t: accepted */                                         \
@@ -623,6 +719,7 @@ typedef unsigned long long lt_u64;
   "s_lshl_b32 " LT_R_TMPLO ", " LT_R_CUR ", 6\n"                                                                                \
   "s_load_dwordx16 " LT_R_REC0 ", %[pairs], " LT_R_TMPLO "\n"                                                                   \
   "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
+  LT_ASM_TRI2_TVEC                                                                                                              \
   LT_ASM_LEAF2(NF, "")                                                                                                          \
   LT_ASM_LEAF2(NF, "_1")                                                                                                        \
   "s_or_b64 " LT_R_TMPM ", %[open], %[open_1]\n"    /* SCC = some lane of some frame still looking */                           \
@@ -683,26 +780,27 @@ __device__ __forceinline__ lt_u64 packet_anyhit_walk(const void* pairs, float ox
 
 // The any-hit walk of two frames' rays from one origin (LT_ASM_WALK2), one octant NEG = 0 .. 7 for both, or one mixed axis and
 // one sign along each of the other two for both (NEG = 8 .. 19): on return open0 / open1 hold the lanes whose ray of that frame
-// found no occluder.  The second frame's ray: inverse direction i?1, direction d?1, tmax1.
+// found no occluder.  The second frame's ray: inverse direction i?1, direction d?1, tmax1.  (No direction `w`: the leaf of this
+// walk has no use for it -- see the argument in front of LT_ASM_TESTS2 -- and eps must be positive.)
 template <int NEG>
 __device__ __forceinline__ void packet_anyhit_walk2(const void* pairs, float ox, float oy, float oz, float ix, float iy, float iz, float dx,
-                                                    float dy, float dz, float dw, float tmax, float ix1, float iy1, float iz1, float dx1,
-                                                    float dy1, float dz1, float dw1, float tmax1, int ign, float eps, uint32_t fast,
-                                                    lt_u64& open0, lt_u64& open1, uint32_t ldsrow) {
+                                                    float dy, float dz, float tmax, float ix1, float iy1, float iz1, float dx1, float dy1,
+                                                    float dz1, float tmax1, int ign, float eps, uint32_t fast, lt_u64& open0, lt_u64& open1,
+                                                    uint32_t ldsrow) {
   const PacketRay pr = packet_ray(ox, oy, oz, ix, iy, iz), pr1 = packet_ray(ox, oy, oz, ix1, iy1, iz1);
   int stk = 0;
-  float t0, t1, t2, t3, t4, t5, t6, t7, t8, t9, t10;
+  float t0, t1, t2, t3, t4, t5, t6, t7, tvx, tvy, tvz;
 #define LT_ANYHIT2_INSTANCE(NF)                                                                                                          \
   asm volatile(LT_ASM_WALK2(NF)                                                                                                          \
                : [open] "+s"(open0), [open_1] "+s"(open1), [stk] "+v"(stk), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),             \
-                 [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6), [t7] "=&v"(t7), [t8] "=&v"(t8), [t9] "=&v"(t9),         \
-                 [t10] "=&v"(t10)                                                                                                        \
+                 [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6), [t7] "=&v"(t7), [tvx] "=&v"(tvx), [tvy] "=&v"(tvy),     \
+                 [tvz] "=&v"(tvz)                                                                                                        \
                : [pairs] "s"(pairs), [ox] "v"(ox), [oy] "v"(oy), [oz] "v"(oz), [ign] "v"(ign), [eps] "s"(eps), [fast] "s"(fast),          \
                  [ldsrow] "s"(ldsrow),                                                                                                   \
                  [ix] "v"(ix), [iy] "v"(iy), [iz] "v"(iz), [px] "v"(pr.px), [py] "v"(pr.py), [pz] "v"(pr.pz), [mg] "v"(pr.mg),             \
-                 [dx] "v"(dx), [dy] "v"(dy), [dz] "v"(dz), [dw] "v"(dw), [tmax] "v"(tmax),                                                \
+                 [dx] "v"(dx), [dy] "v"(dy), [dz] "v"(dz), [tmax] "v"(tmax),                                                              \
                  [ix_1] "v"(ix1), [iy_1] "v"(iy1), [iz_1] "v"(iz1), [px_1] "v"(pr1.px), [py_1] "v"(pr1.py), [pz_1] "v"(pr1.pz),           \
-                 [mg_1] "v"(pr1.mg), [dx_1] "v"(dx1), [dy_1] "v"(dy1), [dz_1] "v"(dz1), [dw_1] "v"(dw1), [tmax_1] "v"(tmax1)              \
+                 [mg_1] "v"(pr1.mg), [dx_1] "v"(dx1), [dy_1] "v"(dy1), [dz_1] "v"(dz1), [tmax_1] "v"(tmax1)                               \
                : LT_ASM_CLOBBERS)
   if constexpr (NEG == 0) LT_ANYHIT2_INSTANCE(LT_NF_0);
   else if constexpr (NEG == 1) LT_ANYHIT2_INSTANCE(LT_NF_1);
