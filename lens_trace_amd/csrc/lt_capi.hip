@@ -165,6 +165,50 @@ __global__ void lt_running_mean_kernel(const float* __restrict__ samples, uint32
   out[i] = acc;
 }
 
+// The same fold, four consecutive floats per thread: for launches whose every float is folded (depth == 3, no padded tiles), from
+// a `first` that is a multiple of four floats into an `out` aligned to 16 bytes (launch_running_mean).  A thread reads each frame's
+// four floats in one load (the sample images lie `stride` floats apart, whatever that is modulo four: the loads ask for no more than
+// the floats' own alignment) and has four frames' loads in flight before the first divide that depends on them; per float the
+// expression and the order of the frames are lt_running_mean_kernel's.  The thread whose four floats would pass `floats` folds what
+// is left of them one by one.
+struct __attribute__((packed, aligned(4))) MeanQuad { float v[4]; };
+__global__ __launch_bounds__(256) void lt_running_mean4_kernel(const float* __restrict__ samples, uint32_t n, uint64_t stride, float* __restrict__ out,
+                                                               uint64_t first, uint64_t floats, int32_t base) {
+  const uint64_t i = first + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4u;
+  if (i >= floats) return;
+  auto fold = [&](float acc, float c, int32_t N) {
+    if (N <= 0) return c;
+    const float nf = (float)N, n1 = (float)(N + 1);
+    return (c + (acc * nf)) / n1;
+  };
+  if (i + 4u > floats) {
+    for (uint64_t j = i; j < floats; j++) {
+      float acc = base > 0 ? out[j] : 0.0f;
+      for (uint32_t f = 0; f < n; f++) acc = fold(acc, samples[(uint64_t)f * stride + j], base + (int32_t)f);
+      out[j] = acc;
+    }
+    return;
+  }
+  float4 acc = base > 0 ? *(const float4*)(out + i) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  uint32_t f = 0;
+  for (; f + 4u <= n; f += 4u) {
+    MeanQuad c[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) c[u] = *(const MeanQuad*)(samples + (uint64_t)(f + u) * stride + i);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int32_t N = base + (int32_t)(f + u);
+      acc.x = fold(acc.x, c[u].v[0], N); acc.y = fold(acc.y, c[u].v[1], N); acc.z = fold(acc.z, c[u].v[2], N); acc.w = fold(acc.w, c[u].v[3], N);
+    }
+  }
+  for (; f < n; f++) {
+    const MeanQuad c = *(const MeanQuad*)(samples + (uint64_t)f * stride + i);
+    const int32_t N = base + (int32_t)f;
+    acc.x = fold(acc.x, c.v[0], N); acc.y = fold(acc.y, c.v[1], N); acc.z = fold(acc.z, c.v[2], N); acc.w = fold(acc.w, c.v[3], N);
+  }
+  *(float4*)(out + i) = acc;
+}
+
 // The walks' slab tests compare against the smallest positive float (`tExit >= max(tEnter, 0x00000001)`: "tExit > 0" in one
 // instruction) and their conservative tests carry a 2^-140 margin: both need float32 denormals to be KEPT, which is hipcc's
 // default for gfx950 and what this library and its run-time compiled user programs are built with.  A build with
@@ -1476,6 +1520,16 @@ struct ReadBack {
 static int launch_running_mean(lt_hip_context* ctx, hipStream_t s, const FrameParams& fp, uint64_t floats, uint32_t nf, int32_t base,
                                bool paddedTiles, float* out, ReadBack* rb) {
   const uint32_t threads = 256;
+  // four floats per thread (lt_running_mean4_kernel) where every float of the range is folded and `out` takes 16-byte stores; the
+  // pieces' bounds are multiples of 4096 bytes, so a piece that starts aligned is followed by aligned ones
+  const bool quads = fp.depth == 3u && !paddedTiles && (uintptr_t)out % 16u == 0u;
+  auto launch = [&](uint64_t lo, uint64_t hi) {
+    if (quads && lo % 4u == 0u)
+      lt_running_mean4_kernel<<<dim3((uint32_t)((hi - lo + 4u * threads - 1) / (4u * threads))), dim3(threads), 0, s>>>(ctx->d_samples, nf, floats, out, lo, hi, base);
+    else
+      lt_running_mean_kernel<<<dim3((uint32_t)((hi - lo + threads - 1) / threads)), dim3(threads), 0, s>>>(ctx->d_samples, nf, floats, out, lo, hi, base, fp,
+                                                                                                       paddedTiles ? 1 : 0);
+  };
   while (ctx->mean_events.size() < 2 * (size_t)(ctx->mean_pairs + 1)) {
     hipEvent_t e;
     LT_HIP_CHECK(ctx, hipEventCreate(&e));
@@ -1489,15 +1543,12 @@ static int launch_running_mean(lt_hip_context* ctx, hipStream_t s, const FramePa
     const uint64_t per = rb->piece / sizeof(float);
     for (int k = 0; k < 8; k++) {
       const uint64_t lo = std::min(floats, (uint64_t)k * per), hi = std::min(floats, lo + per);
-      if (hi > lo)
-        lt_running_mean_kernel<<<dim3((uint32_t)((hi - lo + threads - 1) / threads)), dim3(threads), 0, s>>>(ctx->d_samples, nf, floats, out, lo, hi, base, fp,
-                                                                                                         paddedTiles ? 1 : 0);
+      if (hi > lo) launch(lo, hi);
       LT_HIP_CHECK(ctx, hipEventRecord(ctx->fold_ev[k], s));
     }
     rb->foldPieced = true;
   } else {
-    lt_running_mean_kernel<<<dim3((uint32_t)((floats + threads - 1) / threads)), dim3(threads), 0, s>>>(ctx->d_samples, nf, floats, out, 0ull, floats,
-                                                                                                    base, fp, paddedTiles ? 1 : 0);
+    launch(0ull, floats);
   }
   LT_HIP_CHECK(ctx, hipGetLastError());
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->mean_events[2 * ctx->mean_pairs + 1], s));

@@ -1459,10 +1459,22 @@ __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float 
     return true;
   }
   if (pl.hitType != 1) return true;
-  const float* pr = prim_ptr(sc, pl.prim);
   float rnd[4];
+  // The four randoms sit behind a wave-uniform branch that the compiler cannot resolve.  Left in straight-line code, the nine
+  // double-precision coefficients of the sine's polynomials are hoisted out of the kernel's work loop into 18 registers, which do
+  // not fit beside the walk: they are spilled, and every step of every polynomial then waits for a scratch load in front of the
+  // fma that needs it (some three dozen reloads per work item).  Behind the branch they are made where they are used.  The other arm
+  // is never taken -- shadowPackets is 0 .. 3 -- and were it taken, traverse_shadow2 below would refuse that same value and the
+  // caller would not read `out`.
+  uint32_t opaque = sc.shadowPackets;
+  asm volatile("" : "+s"(opaque));
+  if (opaque == 0xffffffffu) {
 #pragma unroll
-  for (int i = 0; i < 4; i++) rnd[i] = random_<CFG::kDevLibm>(fx, fy, (float)(s + (uint32_t)i));
+    for (int i = 0; i < 4; i++) rnd[i] = __uint_as_float(opaque + (uint32_t)i);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++) rnd[i] = random_<CFG::kDevLibm>(fx, fy, (float)(s + (uint32_t)i));
+  }
   V4 lightPosition[2];
 #pragma unroll
   for (int j = 0; j < 2; j++) {
@@ -1477,11 +1489,17 @@ __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float 
   }
   asm volatile("" ::: "memory");
 
-  const V3 b = barycentrics(pl.u, pl.v);
-  const V3 p3 = bary3<CFG::kDevLibm>(pr + 0, pr + 3, pr + 6, b);
-  const V4 position = mk4(p3.x, p3.y, p3.z, 1.0f);
-  const V3 n3 = bary3<CFG::kDevLibm>(pr + 9, pr + 12, pr + 15, b);
-  const V4 normal = mk4(n3.x, n3.y, n3.z, 0.0f);
+  // (the primitive's address is made where it is used, here and behind the walk: held from the top it is two registers that live
+  // through the randoms and the walk)
+  V4 position, normal;
+  {
+    const float* pr = prim_ptr(sc, pl.prim);
+    const V3 b = barycentrics(pl.u, pl.v);
+    const V3 p3 = bary3<CFG::kDevLibm>(pr + 0, pr + 3, pr + 6, b);
+    position = mk4(p3.x, p3.y, p3.z, 1.0f);
+    const V3 n3 = bary3<CFG::kDevLibm>(pr + 9, pr + 12, pr + 15, b);
+    normal = mk4(n3.x, n3.y, n3.z, 0.0f);
+  }
   Ray ray[2];
   Hit spl[2];
   float ndotl[2];
@@ -1495,7 +1513,7 @@ __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float 
   asm volatile("" : "+v"(ndotl[0]), "+v"(ndotl[1]));
   if (!traverse_shadow2<kAccumulator, CFG>(sc, ray, pl.prim, spl, st, c)) return false;
   asm volatile("" ::: "memory");
-  const Material* m = sc.mats + prim_material(pr);
+  const Material* m = sc.mats + prim_material(prim_ptr(sc, pl.prim));
 #pragma unroll
   for (int j = 0; j < 2; j++)
     if (spl[j].hitType == 0) out[j] = V3{m->diffuse[0] * ndotl[j], m->diffuse[1] * ndotl[j], m->diffuse[2] * ndotl[j]};
