@@ -216,7 +216,13 @@ int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint64_t node_by
                         const lt_hip_render_desc* desc, float* out_host, uint64_t out_bytes);
 
 /* Same, but the pixels stay in HBM: out_device is device memory of the context's GPU, the work is enqueued
- * on hip_stream (a hipStream_t, NULL = default stream) and NOT waited for. */
+ * on hip_stream (a hipStream_t, NULL = default stream) and NOT waited for.
+ * Streams: a render's scratch is the context's -- work counters, sample images and the camera hits that accumulator keeps from one
+ * call to the next for as long as scene, camera, image and tile set stay what they were (lt_hip_camera_hit_passes).  A render
+ * enqueued on another stream than the render before it on this context waits (hipStreamWaitEvent, on the device; the host does not
+ * wait) for that render's last launch before its own first: a call that reuses the hits starts after the launch that wrote them, a
+ * call that overwrites them after their last reader.  Renders on one stream are ordered by the stream, and no wait is added.  The
+ * output buffers are the caller's to order. */
 int lt_hip_render_device(lt_hip_context* ctx, const lt_hip_render_desc* desc, float* out_device,
                          uint64_t out_bytes, void* hip_stream);
 
@@ -401,8 +407,9 @@ int lt_hip_shade_rays_device(lt_hip_context* ctx, const lt_hip_shade_desc* desc,
  * tests and measurements; LT_FUSED_BYTES bounds it as it bounds a render's sets).
  * Streams: the scratch and its control block are the context's, shared with the programs' renders.  Calls of this entry point are
  * ordered among themselves on any streams (each waits for the one enqueued before it).  A call and a global-illumination
- * lt_hip_render_device on two different streams are NOT ordered by the library, exactly as two such renders on two streams are
- * not: order them (one stream, an event, lt_hip_synchronize) or use two contexts.  (lens_trace_amd/csrc/lt_paths.hip) */
+ * lt_hip_render_device on two different streams are NOT ordered by the library (renders are ordered among themselves, see
+ * lt_hip_render_device, and so are calls of this entry point, but not the one with the other): order them (one stream, an event,
+ * lt_hip_synchronize) or use two contexts.  (lens_trace_amd/csrc/lt_paths.hip) */
 typedef struct lt_hip_paths_desc {
   uint32_t struct_size;         /* >= sizeof(lt_hip_paths_desc) */
   int32_t program;              /* LT_PROGRAM_GLOBAL_ILLUMINATION or LT_PROGRAM_GLOBAL_ILLUMINATION_25 */
@@ -638,6 +645,12 @@ int lt_hip_overlap_boxes_host(const void* nodes, uint64_t node_bytes, const void
 
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
+
+/* Camera-hit passes launched on ctx since it was created.  accumulator walks the camera rays of a call of two or more frames in a
+ * pass ahead of its render launches and keeps the hits: a call with the same scene, camera, image, tile set and math flavour as the
+ * one before it -- a progressive caller moving frame_first on -- launches no pass and this number stays.  LT_CAMERA_HITS_KEEP=0:
+ * every such call launches one.  Waits for nothing; 0 for a null ctx. */
+uint64_t lt_hip_camera_hit_passes(const lt_hip_context* ctx);
 
 #ifdef __cplusplus
 }

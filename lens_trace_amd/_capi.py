@@ -41,6 +41,7 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_nearest_points", "lt_hip_nearest_points_device", "lt_hip_nearest_points_host",
            "lt_hip_nearest_k", "lt_hip_nearest_k_device", "lt_hip_nearest_k_host",
            "lt_hip_overlap_boxes", "lt_hip_overlap_boxes_device", "lt_hip_overlap_boxes_host"]
+# (lt_hip_camera_hit_passes returns a uint64_t count, not a status: bound in load() beside these)
 
 
 class RenderDesc(ctypes.Structure):
@@ -249,6 +250,9 @@ def load():
         L.lt_hip_overlap_boxes.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
         L.lt_hip_overlap_boxes_device.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64, vp]
         L.lt_hip_overlap_boxes_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
+    if hasattr(L, "lt_hip_camera_hit_passes"):
+        L.lt_hip_camera_hit_passes.argtypes = [vp]
+        L.lt_hip_camera_hit_passes.restype = u64
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

@@ -23,6 +23,7 @@
 #include <thread>
 #include <type_traits>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -333,6 +334,12 @@ struct lt_hip_context {
   float* d_samples = nullptr;        // un-accumulated sample images of a fused multi-sample launch
   uint4* d_camhits = nullptr;        // the camera-hit pass's hits (FrameParams::cameraHits): 16 bytes per lane of every square of a call
   uint64_t camhits_slots = 0;
+  std::vector<unsigned char> camhits_key;   // what d_camhits holds the hits of, every square's (camera_hits_key); empty: nothing to reuse
+  uint64_t camhit_passes = 0;        // camera-hit passes launched so far (lt_hip_camera_hit_passes)
+  uint64_t scene_generation = 0;     // goes up whenever a resident scene buffer or an array derived from one is written or given back
+  hipEvent_t render_ev = nullptr;    // behind the last launch of the last render call, on render_stream: a render on another stream waits for it
+  hipStream_t render_stream = nullptr;
+  bool render_ev_recorded = false;
   uint64_t d_samples_bytes = 0;
   uint32_t* d_order = nullptr;       // persistent mode: hand-out order of the squares (slow-path squares first), cached
   uint64_t order_capacity = 0;
@@ -445,6 +452,7 @@ extern "C" int lt_hip_create(int device_index, lt_hip_context** out_ctx) {
 }
 
 static void free_scene(lt_hip_context* ctx) {
+  ctx->scene_generation++;
   for (void** p : {&ctx->d_nodes, &ctx->d_tris, &ctx->d_prims, &ctx->d_mats, &ctx->d_lights, &ctx->d_nodes2, &ctx->d_pairs2, &ctx->d_rank8, &ctx->d_wide}) {
     if (*p) ctx->pool.put(*p);
     *p = nullptr;
@@ -470,6 +478,7 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_queues) (void)hipFree(ctx->d_queues);
   if (ctx->d_samples) (void)hipFree(ctx->d_samples);
   if (ctx->d_camhits) (void)hipFree(ctx->d_camhits);
+  if (ctx->render_ev) (void)hipEventDestroy(ctx->render_ev);
   if (ctx->d_groupWalks) (void)hipFree(ctx->d_groupWalks);
   if (ctx->d_shadowq) (void)hipFree(ctx->d_shadowq);
   if (ctx->d_shadowCtl) (void)hipFree(ctx->d_shadowCtl);
@@ -839,6 +848,7 @@ struct OwnBuild {
 // Makes the per-lane walks' group records and the own structures resident -- or, when the walks cannot use them, gives all of them
 // back (the renderer takes them all or none): the scene then walks the caller's tree.  The leaf records are remake_leaf_records'.
 static int install_own_structures(lt_hip_context* ctx, const OwnBuild& b, uint32_t n_prims) {
+  ctx->scene_generation++;
   ctx->d_nodes2 = b.d_nodes2;
   ctx->d_rank8 = b.d_rank8;
   // (the walk's stack: at most three waiting entries per level of groups and the four of the last one; the records' links: 31 bits)
@@ -873,6 +883,7 @@ static int install_own_structures(lt_hip_context* ctx, const OwnBuild& b, uint32
 // What is made from the resident primitives: the traversal triangles and, with the own structures, the leaf records of both walks
 // (the packet walks' pairs, the per-lane walks' records behind the groups).  Both builds run it, and an edit of the primitives.
 static int remake_leaf_records(lt_hip_context* ctx, uint32_t n_prims) {
+  ctx->scene_generation++;
   hipLaunchKernelGGL(lt_retile_kernel, dim3((n_prims + 255) / 256), dim3(256), 0, ctx->stream, (const float*)ctx->d_prims, (float4*)ctx->d_tris, n_prims);
   if (ctx->d_nodes2 && ctx->d_pairs2 && ctx->d_wide) {
     const uint32_t n2 = ctx->n_nodes2;
@@ -896,6 +907,7 @@ static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const Scen
   ctx->scene_hash = hash;
   memcpy(ctx->scene_sizes, sizes, sizeof(ctx->scene_sizes));
   ctx->scene_uploads++;
+  ctx->scene_generation++;   // (every path that wrote a scene buffer ends here; those that write without it -- a failed edit -- count below)
   // The shadow-ray walk timed fastest for a scene (render_on_stream) is kept for a scene of the same shape -- the next pose of an
   // animation, an edited material: it is a matter of speed, never of pixels, and timing it again costs five frames -- and forgotten
   // when the sizes change (another scene).
@@ -1007,6 +1019,7 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
       if (badMaterial && why != kTooManyLights) why = badMaterial;
       if (why) return fail(ctx, LT_ERR_BAD_SCENE, why);
       LT_HIP_CHECK(ctx, hipDeviceSynchronize());   // (nothing of an earlier call may still be reading what is about to change)
+      ctx->scene_generation++;
       if (primsChanged) {
         LT_HIP_CHECK(ctx, hipMemcpy(ctx->d_prims, prims, prim_bytes, hipMemcpyHostToDevice));
         const int rc = remake_leaf_records(ctx, n_prims);
@@ -1120,6 +1133,7 @@ struct RenderKnobs {
   bool debug_camera_hits = getenv("LT_DEBUG_CAMERA_HITS") != nullptr;   // launch_camera_hits prints the squares of its pass to stderr
   bool pinned_readback = !env_off("LT_PINNED_READBACK");   // off: lt_hip_render reads back in one copy (readback_piece)
   bool camera_hits = !env_off("LT_CAMERA_HITS");   // off: every launch walks its camera rays (launch_camera_hits)
+  bool camera_hits_keep = !env_off("LT_CAMERA_HITS_KEEP");   // off: a call's camera hits are not kept for the next one (camera_hits_key)
   uint32_t shadow_frames = 2;           // LT_SHADOW_FRAMES=1..2: frames per work item whose shadow rays walk together (launch_walk)
   bool debug_shadow_frames = getenv("LT_DEBUG_SHADOW_FRAMES") != nullptr;   // launch_walk prints the frame groups of every render launch
                                                                             // and, where there are groups, how many waves walked them together
@@ -1752,29 +1766,83 @@ static int calibrate_shadow_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& s
   return LT_OK;
 }
 
+// What the stored camera hits are a function of, and nothing else: every input that camera_hit_square and square_pixel read.  Made
+// from the FrameParams the pass is launched with -- not from the desc, so that a field added later is in it without being asked --
+// with what changes from frame to frame or launch to launch cleared; the camera's bytes as frame_params takes them, without the frame
+// counter at byte 24; the hand-out order the hits are indexed by (ensure_square_order's key and head counts); the math flavour; the
+// scene generation; and the allocation the hits live in.
+// FrameParams, field by field: camx .. yaw, width, height (camera_ray), tileW .. totalSquares (square_pixel), order, orderHead and
+// persistent (the hand-out), ldsRows (the walk's stack) are in the key; depth, clampOutput, giMaxDepth, pixelCounters and squareMajor do
+// not reach a camera hit and are in it all the same; frameCount, accumulateN, fusedFrames, frameStride, shadowFrames, storeHeadHits and
+// the cameraHits pointer are cleared.
+static_assert(sizeof(FrameParams) == 184 && offsetof(FrameParams, storeHeadHits) + sizeof(uint32_t) == sizeof(FrameParams),
+              "FrameParams changed: say in camera_hits_key whether the new field is part of the key or cleared");
+static std::vector<unsigned char> camera_hits_key(const lt_hip_context* ctx, const FrameParams& pass, const lt_hip_render_desc* d, int devlibm) {
+  FrameParams f = pass;
+  f.frameCount = 0; f.accumulateN = 0; f.fusedFrames = 0; f.frameStride = 0; f.shadowFrames = 0; f.storeHeadHits = 0; f.cameraHits = nullptr;
+  std::vector<unsigned char> key;
+  auto put = [&](const void* p, size_t n) { key.insert(key.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
+  put(&f, sizeof(f));   // (no padding inside: the assertion above and the fields' natural alignment)
+  put(d->camera, 24);
+  const uint64_t words[4] = {(uint64_t)devlibm, ctx->scene_generation, (uint64_t)(uintptr_t)ctx->d_camhits, ctx->order_key.size()};
+  put(words, sizeof(words));
+  put(ctx->order_key.data(), ctx->order_key.size() * sizeof(uint32_t));
+  put(ctx->order_head, sizeof(ctx->order_head));
+  return key;
+}
+
 // The camera-hit pass (lt_camera_hits_kernel, FrameParams::cameraHits): a camera ray is the same in every frame of a call, and so is
 // its walk -- 1 002 530-triangle wall, 4K, 16 frames: 6.4 of the 17 ms of accumulator's launch were its 16 walks of each camera
 // ray (`basic`, nothing but those walks).  So a call of accumulator that renders two or more frames walks each camera ray once,
 // before its render launches, which read the hits and shade from them; its head squares (ensure_square_order: 1.9 ms for one on the
 // wall, a floor under the pass's length) stay out and are walked by the render launches, where they start first and overlap.  A
-// one-frame call keeps the walk in its launch (the pass would add a launch and its drain).  Nothing is kept from one call to the
-// next.  Not the counting kernels: their walks are what their ray, node and triangle counts count.  Run after ev0 (render_ms holds it),
-// not counted in kernel_launches.  LT_CAMERA_HITS=0: every launch walks its camera rays.
-static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const SceneDev& sc, FrameParams& fp, uint32_t* queues, uint32_t resident) {
+// one-frame call keeps the walk in its launch (the pass would add a launch and its drain).
+// The hits are kept from one call to the next: a progressive caller leaves the camera where it is and moves frame_first on, and the
+// hits do not depend on the frame.  The first launch of a call whose pass ran has its head squares' first-frame items store what they
+// walk (FrameParams::storeHeadHits), and once that launch is enqueued the context remembers what the hits belong to (camera_hits_key;
+// `pendingKey`: the caller records it then).  A later call with the same key launches no pass and hands its render launches orderHead
+// all zero: every square, the head squares too, is then a stored item in frame groups, at the position it always had -- fp.order is
+// unchanged, and so are the XCDs' shares.  Anything else in the key -- another camera, image, tile set, scene, math flavour, a
+// reallocation -- and the call runs its pass as before; a call that fails after it has begun to overwrite the hits leaves nothing to
+// reuse.  Calls that take no hits (one frame, the counting kernels, other programs, LT_PERSISTENT=0, LT_CAMERA_HITS=0) neither read
+// nor disturb them.  LT_CAMERA_HITS_KEEP=0: nothing is kept, every call runs its pass.
+// Not the counting kernels: their walks are what their ray, node and triangle counts count.  Run after ev0 (render_ms holds it),
+// not counted in kernel_launches (lt_hip_camera_hit_passes counts the passes).  LT_CAMERA_HITS=0: every launch walks its camera rays.
+static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const SceneDev& sc, FrameParams& fp, uint32_t* queues, uint32_t resident,
+                              std::vector<unsigned char>& pendingKey) {
   uint64_t squares = 0;   // those of the pass: every square but the head squares (the kernel's own count, lt_kernel.hpp)
   for (uint32_t xcd = 0; xcd < 8; xcd++) squares += camera_hit_squares(fp, xcd);
-  if (c.k.debug_camera_hits) fprintf(stderr, "camera-hit pass: %llu of %llu squares\n", (unsigned long long)squares, (unsigned long long)c.nblocks);
-  if (squares == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_camhits, ctx->camhits_slots, c.nblocks * kBlock, c.nblocks * kBlock * sizeof(uint4)));
-  fp.cameraHits = ctx->d_camhits;
+  if (squares == 0) {
+    if (c.k.debug_camera_hits) fprintf(stderr, "camera-hit pass: none (every square is a head square)\n");
+    return LT_OK;
+  }
   FrameParams fh = fp;
   fh.fusedFrames = 1;
+  if (c.k.camera_hits_keep && !ctx->camhits_key.empty() && ctx->camhits_slots >= c.nblocks * kBlock &&
+      ctx->camhits_key == camera_hits_key(ctx, fh, c.d, c.devlibm)) {
+    // (the same words as below for the pass these hits came from, so that a reader of the log sees which squares it walked)
+    if (c.k.debug_camera_hits)
+      fprintf(stderr, "camera-hit pass: %llu of %llu squares, kept from an earlier call (no pass launched: %llu so far)\n", (unsigned long long)squares,
+              (unsigned long long)c.nblocks, (unsigned long long)ctx->camhit_passes);
+    fp.cameraHits = ctx->d_camhits;
+    for (uint32_t& h : fp.orderHead) h = 0u;
+    return LT_OK;
+  }
+  if (c.k.debug_camera_hits) fprintf(stderr, "camera-hit pass: %llu of %llu squares\n", (unsigned long long)squares, (unsigned long long)c.nblocks);
+  ctx->camhits_key.clear();   // (from here on the hits are being overwritten, or their buffer replaced)
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_camhits, ctx->camhits_slots, c.nblocks * kBlock, c.nblocks * kBlock * sizeof(uint4)));
+  fp.cameraHits = fh.cameraHits = ctx->d_camhits;
   with_math(c.devlibm, [&](auto m) {
     hipLaunchKernelGGL((lt_camera_hits_kernel<Config<false, false, decltype(m)::value>>), dim3((uint32_t)std::min<uint64_t>(squares, resident)), dim3(kBlock),
                        c.lds, c.s, sc, fh, queues);
     return 0;
   });
   LT_HIP_CHECK(ctx, hipGetLastError());
+  ctx->camhit_passes++;
+  if (c.k.camera_hits_keep) {
+    fp.storeHeadHits = 1u;
+    pendingKey = camera_hits_key(ctx, fh, c.d, c.devlibm);
+  }
   return LT_OK;
 }
 
@@ -1793,6 +1861,11 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   const uint32_t frames = d->frame_count ? d->frame_count : 1;
   const uint64_t nblocks = p.squares();
 
+  // The scratch of a render -- work counters, sample images, shadow queue, the camera hits and what they are kept for -- is the
+  // context's: a render enqueued on another stream than the one before it waits for that one's last launch (the writer of the hits a
+  // reusing call reads; the last reader of hits about to be overwritten).  One stream: no waits.
+  if (!ctx->render_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->render_ev, hipEventDisableTiming));
+  if (ctx->render_ev_recorded && s != ctx->render_stream) LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->render_ev, 0));
   if (stats) LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_stats, 0, 8 * sizeof(unsigned long long), s));
   if (k.persistent) {   // (persistent wavefronts by default; LT_PERSISTENT=0 selects one-square-per-workgroup dispatch: A/B measurements)
     const uint64_t queueBytes = ((uint64_t)frames + 1) * 8 * kQueueStride * sizeof(uint32_t);   // (the last eight: the camera-hit pass's)
@@ -1838,8 +1911,9 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   const uint32_t resident = (uint32_t)ctx->cu_count * 32u;   // every wave slot of the chip, once
   ctx->mean_pairs = 0;
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  std::vector<unsigned char> hitsKey;   // (launch_camera_hits: what the hits will belong to once the first launch has stored the head squares')
   if (k.camera_hits && k.persistent && !stats && frames > 1 && nblocks > 0 && d->program == LT_PROGRAM_ACCUMULATOR)
-    if (const int rc = launch_camera_hits(ctx, call, sc, fp, ctx->d_queues + (size_t)frames * 8 * kQueueStride, resident)) return rc;
+    if (const int rc = launch_camera_hits(ctx, call, sc, fp, ctx->d_queues + (size_t)frames * 8 * kQueueStride, resident, hitsKey)) return rc;
   for (uint32_t f = 0, launchIndex = 0; f < frames && nblocks > 0; launchIndex++) {
     const uint32_t nf = fused ? std::min(fu.chunk, frames - f) : 1u;   // frames of this launch
     fp.frameCount = d->frame_count ? d->frame_first + f : camFrame;
@@ -1868,12 +1942,19 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
     }
     LT_HIP_CHECK(ctx, hipGetLastError());
     call.launches++;
+    if (fp.storeHeadHits) {   // the pass and the launch that stores the head squares' hits are enqueued: the hits are whole
+      ctx->camhits_key.swap(hitsKey);
+      fp.storeHeadHits = 0u;
+    }
     if (fused)
       if (const int rc = launch_running_mean(ctx, s, fp, p.floats, nf, (int32_t)(d->accumulate_base + f), paddedTiles, out_device, f + nf >= frames ? rb : nullptr))
         return rc;
     f += nf;
   }
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
+  LT_HIP_CHECK(ctx, hipEventRecord(ctx->render_ev, s));
+  ctx->render_stream = s;
+  ctx->render_ev_recorded = true;
   ctx->last = lt_hip_stats{};
   ctx->last.frames = frames;
   ctx->last.kernel_launches = call.launches;
@@ -2911,6 +2992,8 @@ extern "C" int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* 
   LT_HIP_CHECK(ctx, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
   return LT_OK;
 }
+
+extern "C" uint64_t lt_hip_camera_hit_passes(const lt_hip_context* ctx) { return ctx ? ctx->camhit_passes : 0; }
 
 extern "C" int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out) {
   if (!ctx || !out) return LT_ERR_INVALID_ARGUMENT;

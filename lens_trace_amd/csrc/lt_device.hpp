@@ -1398,14 +1398,18 @@ __device__ inline V3 shade_custom(const SceneDev& sc, const Ray& ray, Stack<CFG:
 // The hit of a camera ray (acc.cl:229-231): walked, or -- hitRow != null, a non-counting kernel -- read from the call's
 // camera-hit pass (FrameParams::cameraHits; hitRow: the square's 64 slots, wave-uniform).  Same bits either way: the pass walks
 // the same ray with the same walk over the same lanes of the square.  (t is not stored: no shading code reads it.)
+// storeRow != null (a walked hit, FrameParams::storeHeadHits): the hit goes into the lane's slot of it, in the pass's format.
 template <int PROGRAM, class CFG>
-__device__ __forceinline__ Hit camera_hit(const SceneDev& sc, const Ray& cameraRay, const uint4* hitRow, Stack<CFG::kDeep>& st, Counters& c) {
+__device__ __forceinline__ Hit camera_hit(const SceneDev& sc, const Ray& cameraRay, const uint4* hitRow, Stack<CFG::kDeep>& st, Counters& c,
+                                          uint4* storeRow = nullptr) {
   Hit pl{0, 0, kFltMax, 0.0f, 0.0f};
   if (!CFG::kStats && hitRow != nullptr) {
     const uint4 h = hitRow[__lane_id()];
     pl.prim = (int)h.x; pl.hitType = (int)h.y; pl.u = __uint_as_float(h.z); pl.v = __uint_as_float(h.w);
   } else {
     traverse_camera<PROGRAM, CFG::kDeep, CFG::kStats>(sc, cameraRay, pl, st, c);
+    if (!CFG::kStats && storeRow != nullptr)
+      storeRow[__lane_id()] = make_uint4((uint32_t)pl.prim, (uint32_t)pl.hitType, __float_as_uint(pl.u), __float_as_uint(pl.v));
   }
   return pl;
 }
@@ -1635,11 +1639,17 @@ struct FrameParams {
   // that renders two or more frames walks every camera ray once, ahead of its render launches (lt_camera_hits_kernel): the hit
   // of lane l of the square at hand-out position p at cameraHits[p * 64 + l], (primitive, hitType, u, v) -- every square but the
   // head squares of the XCDs' shares, which the render launches walk themselves.  Null: every launch walks its camera rays.
+  // A call that finds the hits of an earlier call with the same camera still there (lt_capi.hip: camera_hits_key) runs no pass and
+  // passes orderHead all zero: every position of `order` is then a stored square.
   uint4* cameraHits;
   // ... and then a work item of accumulator over stored hits covers shadowFrames consecutive frames of its square (1 or 2; the last
   // item of a square covers what is left): the frames' shadow rays leave the same points, and two of them walk together
   // (shade_pixel2).  The host sets it for shadow walks 1 and 2 (LT_SHADOW_FRAMES); 1 everywhere else.
   uint32_t shadowFrames;
+  // != 0 (cameraHits set, the first launch of a call whose pass ran): an item of the launch's first frame that walks its own camera
+  // rays -- a head square's -- stores what it found in its 64 slots of cameraHits, as the pass would have: a later call with the same
+  // camera then finds every square's hits there (lt_capi.hip: CameraHitsKey).
+  uint32_t storeHeadHits;
 };
 
 // Camera ray of pixel (x,y): acc.cl:304-312.
@@ -1687,10 +1697,11 @@ __device__ V3 user_shade(const SceneDev& sc, const Ray& cameraRay, float filmX, 
 
 // The body of linearKernel / tileKernel for one pixel, all five programs
 // (acc.cl:314-318, basic.cl:338-342, basic_lighting.cl:309-321, resources gi :408-420).
-// hitRow: the square's stored camera hits (camera_hit), or null.
+// hitRow: the square's stored camera hits (camera_hit), or null; storeRow: where accumulator's walked hit is to be stored, or null.
 template <int PROGRAM, class CFG>
 __device__ inline V3 shade_pixel(const SceneDev& sc, const FrameParams& fp, uint32_t frameCount, int x, int y, Stack<CFG::kDeep>& st,
-                                 Counters& c, uint32_t qslot, uint32_t qpixel, uint32_t qframe, bool& queued, const uint4* hitRow) {
+                                 Counters& c, uint32_t qslot, uint32_t qpixel, uint32_t qframe, bool& queued, const uint4* hitRow,
+                                 uint4* storeRow = nullptr) {
   float fx, fy;
   const Ray ray = camera_ray<CFG::kDevLibm>(fp, x, y, fx, fy);
   V3 color;
@@ -1703,7 +1714,7 @@ __device__ inline V3 shade_pixel(const SceneDev& sc, const FrameParams& fp, uint
     color = user_shade<CFG>(sc, ray, fx, fy, frameCount, st, c);
 #endif
   } else if (PROGRAM == kAccumulator || PROGRAM == kAccumulatorQueue) {
-    const Hit pl = camera_hit<PROGRAM, CFG>(sc, ray, hitRow, st, c);
+    const Hit pl = camera_hit<PROGRAM, CFG>(sc, ray, hitRow, st, c, storeRow);
     color = shade_lighting<PROGRAM, CFG>(sc, pl, fx, fy, frameCount, st, c, qslot, qpixel, qframe, queued);
   } else if (PROGRAM == kGI) {
     color = shade_gi<CFG>(sc, ray, fx, fy, frameCount, fp.giMaxDepth, st, c);

@@ -63,6 +63,12 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
   constexpr bool queueing = PROGRAM == kAccumulatorQueue;
   const uint32_t qslot = (pos * fp.fusedFrames + frame) * (uint32_t)kBlock + lane;
   bool queued = false;
+  // A head square's item of the call's first frame keeps what its camera walk finds (FrameParams::storeHeadHits): all 64 slots, as
+  // camera_hit_square writes them.  Its other frames' items do not wait for that: they walk as before.
+  uint4* storeRow = nullptr;
+  if constexpr ((PROGRAM == kAccumulator || PROGRAM == kAccumulatorQueue) && !STATS)
+    if (fp.storeHeadHits && hitRow == nullptr && frame == 0u && fp.cameraHits != nullptr) storeRow = fp.cameraHits + (size_t)pos * kBlock;
+  if (storeRow != nullptr && !valid) storeRow[lane] = make_uint4(0u, 0u, 0u, 0u);
   if (valid) {
     Counters pc{};   // this pixel's own counters (diagnostic output), folded into the lane's totals below
     const uint32_t pixel = (k * fp.tileH + ly) * fp.tileW + lx;
@@ -93,9 +99,9 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
       // compiler keeps: one inlined copy of shade_pixel and its walks)
 #pragma unroll 1
       for (uint32_t f = frame; !grouped && f < frame + frames; f++)
-        store(o + (size_t)(f - frame) * fp.frameStride, shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + f, (int)x, (int)y, st, c, qslot, pixel, f, queued, hitRow));
+        store(o + (size_t)(f - frame) * fp.frameStride, shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + f, (int)x, (int)y, st, c, qslot, pixel, f, queued, hitRow, storeRow));
     } else {
-      const V3 color = shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, STATS ? pc : c, qslot, pixel, frame, queued, hitRow);
+      const V3 color = shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, STATS ? pc : c, qslot, pixel, frame, queued, hitRow, storeRow);
       if (STATS && fp.pixelCounters) {
         o[0] = (float)pc.rays; o[1] = (float)pc.shadow; o[2] = (float)pc.nodes; o[3] = (float)pc.tris;
       } else {
@@ -146,7 +152,8 @@ __device__ __forceinline__ void camera_hit_square(const SceneDev& sc, const Fram
 constexpr int waves_per_simd(int program) { return (program == kGI || program == kGI25) ? LT_GI_WAVES : LT_ACC_WAVES; }
 
 // HITS: the camera-hit pass (lt_camera_hits_kernel): every square of the XCDs' shares but their head squares, once, through
-// camera_hit_square, in the order and on the XCD that the render launches give them.
+// camera_hit_square, in the order and on the XCD that the render launches give them.  (The head squares' slots are filled by the
+// first render launch behind the pass: render_square, FrameParams::storeHeadHits.)
 template <int PROGRAM, class CFG, bool HITS = false>
 __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const FrameParams& fp, float* __restrict__ out,
                                                    unsigned long long* __restrict__ stats, uint32_t* __restrict__ queues) {

@@ -392,6 +392,11 @@ class RendererHIP:
     def synchronize(self, stream=0):
         self._check(self._L.lt_hip_synchronize(self._ctx, ctypes.c_void_p(stream)))
 
+    def camera_hit_passes(self):
+        """lt_hip_camera_hit_passes: camera-hit passes this context has launched.  accumulator keeps a call's camera hits, and a call
+        with the same scene, camera, image, tiles and math flavour as the one before it (frame_first may move on) launches none."""
+        return int(self._L.lt_hip_camera_hit_passes(self._ctx))
+
     def scene_structure(self, what):
         """lt_hip_read_scene_structure: 0 own tree (NODE_DTYPE array), 1 leaf order table (n_prims x 8 uint32), 2 the per-lane walks'
         array (bytes), 3 (own height, group-tree height, groups, prepared on the device), 4 the packet walks' records (bytes, 64 per
