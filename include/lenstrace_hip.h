@@ -652,6 +652,19 @@ int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
  * every such call launches one.  Waits for nothing; 0 for a null ctx. */
 uint64_t lt_hip_camera_hit_passes(const lt_hip_context* ctx);
 
+/* Entry cuts: with the camera hits accumulator keeps, per 8x8 square, a list of at most fifteen nodes of its own tree that
+ * the square's shadow rays towards the lights can reach at all, and the two-frame shadow walks of the square start there instead
+ * of at the root -- same pixels.  The first call that reuses a set of kept hits builds the lists, later ones reuse them; a call
+ * that runs its own camera-hit pass builds none (but for the one call that times the shadow walks).  out3[0]: builds on ctx so
+ * far; out3[1], out3[2]: squares with a non-empty list and the entries of those lists, of the cuts ctx holds now.  Waits for the
+ * context's last render.  LT_ENTRY_CUT=0: no cuts are built and every walk starts at the root. */
+int lt_hip_entry_cut_counts(lt_hip_context* ctx, uint64_t* out3);
+
+/* The entry cut's interval test on the host, for tests: n cases of (origin: 3 floats, the light primitives' vertex box before it is
+ * pushed outwards: lo xyz hi xyz, a node's box: lo xyz hi xyz).  out[i]: 0 no half-line from the origin towards a point of the
+ * light box meets the node's box, 1 one may, 2 the lane is one the cut is not built for (non-finite or huge values).  No GPU. */
+int lt_hip_entry_cut_test_host(const float* origins, const float* light_boxes, const float* boxes, uint64_t n, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -336,6 +336,12 @@ struct lt_hip_context {
   uint64_t camhits_slots = 0;
   std::vector<unsigned char> camhits_key;   // what d_camhits holds the hits of, every square's (camera_hits_key); empty: nothing to reuse
   uint64_t camhit_passes = 0;        // camera-hit passes launched so far (lt_hip_camera_hit_passes)
+  // The entry cuts of the stored hits' squares (lt_entry_cut_kernel): 64 bytes per square, kept with the hits under camhits_key.
+  uint32_t* d_cuts = nullptr;
+  uint64_t cuts_squares = 0;
+  bool cuts_valid = false;           // d_cuts holds the cuts of every square of the hits that camhits_key speaks of
+  unsigned long long* d_cut_stats = nullptr;   // [0] squares with a non-empty list, [1] their entries: of the cuts d_cuts holds
+  uint64_t cut_builds = 0;           // launches of lt_entry_cut_kernel so far (lt_hip_entry_cut_counts)
   uint64_t scene_generation = 0;     // goes up whenever a resident scene buffer or an array derived from one is written or given back
   hipEvent_t render_ev = nullptr;    // behind the last launch of the last render call, on render_stream: a render on another stream waits for it
   hipStream_t render_stream = nullptr;
@@ -478,6 +484,8 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_queues) (void)hipFree(ctx->d_queues);
   if (ctx->d_samples) (void)hipFree(ctx->d_samples);
   if (ctx->d_camhits) (void)hipFree(ctx->d_camhits);
+  if (ctx->d_cuts) (void)hipFree(ctx->d_cuts);
+  if (ctx->d_cut_stats) (void)hipFree(ctx->d_cut_stats);
   if (ctx->render_ev) (void)hipEventDestroy(ctx->render_ev);
   if (ctx->d_groupWalks) (void)hipFree(ctx->d_groupWalks);
   if (ctx->d_shadowq) (void)hipFree(ctx->d_shadowq);
@@ -1134,6 +1142,7 @@ struct RenderKnobs {
   bool pinned_readback = !env_off("LT_PINNED_READBACK");   // off: lt_hip_render reads back in one copy (readback_piece)
   bool camera_hits = !env_off("LT_CAMERA_HITS");   // off: every launch walks its camera rays (launch_camera_hits)
   bool camera_hits_keep = !env_off("LT_CAMERA_HITS_KEEP");   // off: a call's camera hits are not kept for the next one (camera_hits_key)
+  bool entry_cut = !env_off("LT_ENTRY_CUT");   // off: every square's entry cut is the empty list (launch_entry_cuts)
   uint32_t shadow_frames = 2;           // LT_SHADOW_FRAMES=1..2: frames per work item whose shadow rays walk together (launch_walk)
   bool debug_shadow_frames = getenv("LT_DEBUG_SHADOW_FRAMES") != nullptr;   // launch_walk prints the frame groups of every render launch
                                                                             // and, where there are groups, how many waves walked them together
@@ -1774,12 +1783,15 @@ static int calibrate_shadow_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& s
 // FrameParams, field by field: camx .. yaw, width, height (camera_ray), tileW .. totalSquares (square_pixel), order, orderHead and
 // persistent (the hand-out), ldsRows (the walk's stack) are in the key; depth, clampOutput, giMaxDepth, pixelCounters and squareMajor do
 // not reach a camera hit and are in it all the same; frameCount, accumulateN, fusedFrames, frameStride, shadowFrames, storeHeadHits and
-// the cameraHits pointer are cleared.
-static_assert(sizeof(FrameParams) == 184 && offsetof(FrameParams, storeHeadHits) + sizeof(uint32_t) == sizeof(FrameParams),
+// the cameraHits and entryCuts pointers are cleared.  (The entry cuts kept with the hits are a function of the hits, of the scene's
+// primitives, lights and own tree -- the scene generation -- and of nothing else.)
+static_assert(sizeof(FrameParams) == 192 && offsetof(FrameParams, entryCuts) + sizeof(const uint32_t*) == sizeof(FrameParams) &&
+                  offsetof(FrameParams, storeHeadHits) + sizeof(uint32_t) == offsetof(FrameParams, entryCuts),
               "FrameParams changed: say in camera_hits_key whether the new field is part of the key or cleared");
 static std::vector<unsigned char> camera_hits_key(const lt_hip_context* ctx, const FrameParams& pass, const lt_hip_render_desc* d, int devlibm) {
   FrameParams f = pass;
   f.frameCount = 0; f.accumulateN = 0; f.fusedFrames = 0; f.frameStride = 0; f.shadowFrames = 0; f.storeHeadHits = 0; f.cameraHits = nullptr;
+  f.entryCuts = nullptr;
   std::vector<unsigned char> key;
   auto put = [&](const void* p, size_t n) { key.insert(key.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
   put(&f, sizeof(f));   // (no padding inside: the assertion above and the fields' natural alignment)
@@ -1808,8 +1820,31 @@ static std::vector<unsigned char> camera_hits_key(const lt_hip_context* ctx, con
 // nor disturb them.  LT_CAMERA_HITS_KEEP=0: nothing is kept, every call runs its pass.
 // Not the counting kernels: their walks are what their ray, node and triangle counts count.  Run after ev0 (render_ms holds it),
 // not counted in kernel_launches (lt_hip_camera_hit_passes counts the passes).  LT_CAMERA_HITS=0: every launch walks its camera rays.
+// The entry cuts of the squares whose camera hits are stored (lt_entry_cut.hpp, lt_entry_cut_kernel): where the two-frame shadow
+// walks of those squares start instead of the root.  Built on the render's stream by the first call that REUSES a set of hits, for
+// every square (`all`), and kept with the hits from then on: later reusing calls launch nothing.  A call that runs its own
+// camera-hit pass builds none -- a caller whose camera moves with every call would pay the build (4.0 ms on the 1 M-triangle wall
+// at 4K: a chain of dependent record fetches per square) for walks that save 2.8 ms in their one call -- unless it is the call that times the shadow walks, which then times the
+// packet walk as it will run: with the cuts of the squares its pass walked (`all` false; not kept).  LT_ENTRY_CUT=0, a scene
+// without an own tree or with one so high that no list fits the walk's stack beside its own entries (entry_cut_limit): no cuts.
+static int launch_entry_cuts(lt_hip_context* ctx, const RenderCall& c, const SceneDev& sc, const FrameParams& fh, bool all) {
+  ctx->cuts_valid = false;
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_cuts, ctx->cuts_squares, c.nblocks, c.nblocks * lt_entry_cut::kListWords * sizeof(uint32_t)));
+  if (!ctx->d_cut_stats) LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_cut_stats, 2 * sizeof(unsigned long long)));
+  LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_cut_stats, 0, 2 * sizeof(unsigned long long), c.s));
+  with_math(c.devlibm, [&](auto m) {
+    hipLaunchKernelGGL((lt_entry_cut_kernel<Config<false, false, decltype(m)::value>>), dim3((uint32_t)c.nblocks), dim3(kBlock), 0, c.s, sc, fh, ctx->d_cuts,
+                       all ? 1u : 0u, (uint32_t)lt_entry_cut::entry_cut_limit(ctx->height2), ctx->d_cut_stats);
+    return 0;
+  });
+  LT_HIP_CHECK(ctx, hipGetLastError());
+  ctx->cuts_valid = all;
+  ctx->cut_builds++;
+  return LT_OK;
+}
+
 static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const SceneDev& sc, FrameParams& fp, uint32_t* queues, uint32_t resident,
-                              std::vector<unsigned char>& pendingKey) {
+                              std::vector<unsigned char>& pendingKey, bool wantCuts, bool timingCall) {
   uint64_t squares = 0;   // those of the pass: every square but the head squares (the kernel's own count, lt_kernel.hpp)
   for (uint32_t xcd = 0; xcd < 8; xcd++) squares += camera_hit_squares(fp, xcd);
   if (squares == 0) {
@@ -1826,10 +1861,18 @@ static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const Sc
               (unsigned long long)c.nblocks, (unsigned long long)ctx->camhit_passes);
     fp.cameraHits = ctx->d_camhits;
     for (uint32_t& h : fp.orderHead) h = 0u;
+    if (wantCuts) {
+      if (!ctx->cuts_valid || ctx->cuts_squares < c.nblocks) {
+        fh.cameraHits = ctx->d_camhits;
+        if (const int rc = launch_entry_cuts(ctx, c, sc, fh, true)) return rc;
+      }
+      fp.entryCuts = ctx->d_cuts;
+    }
     return LT_OK;
   }
   if (c.k.debug_camera_hits) fprintf(stderr, "camera-hit pass: %llu of %llu squares\n", (unsigned long long)squares, (unsigned long long)c.nblocks);
   ctx->camhits_key.clear();   // (from here on the hits are being overwritten, or their buffer replaced)
+  ctx->cuts_valid = false;
   LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_camhits, ctx->camhits_slots, c.nblocks * kBlock, c.nblocks * kBlock * sizeof(uint4)));
   fp.cameraHits = fh.cameraHits = ctx->d_camhits;
   with_math(c.devlibm, [&](auto m) {
@@ -1839,6 +1882,10 @@ static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const Sc
   });
   LT_HIP_CHECK(ctx, hipGetLastError());
   ctx->camhit_passes++;
+  if (wantCuts && timingCall) {
+    if (const int rc = launch_entry_cuts(ctx, c, sc, fh, false)) return rc;
+    fp.entryCuts = ctx->d_cuts;
+  }
   if (c.k.camera_hits_keep) {
     fp.storeHeadHits = 1u;
     pendingKey = camera_hits_key(ctx, fh, c.d, c.devlibm);
@@ -1911,9 +1958,12 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   const uint32_t resident = (uint32_t)ctx->cu_count * 32u;   // every wave slot of the chip, once
   ctx->mean_pairs = 0;
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, s));
+  // entry cuts: for the walks that take them (the two-frame packet walk of shadow walks 1 and 2; a walk yet to be timed is timed with them)
+  const bool wantCuts = k.entry_cut && ctx->d_pairs2 != nullptr && lt_entry_cut::entry_cut_limit(ctx->height2) != 0 && shadowGroup >= 2u &&
+                        (shadowMode < 0 || shadowMode == 1 || shadowMode == 2);
   std::vector<unsigned char> hitsKey;   // (launch_camera_hits: what the hits will belong to once the first launch has stored the head squares')
   if (k.camera_hits && k.persistent && !stats && frames > 1 && nblocks > 0 && d->program == LT_PROGRAM_ACCUMULATOR)
-    if (const int rc = launch_camera_hits(ctx, call, sc, fp, ctx->d_queues + (size_t)frames * 8 * kQueueStride, resident, hitsKey)) return rc;
+    if (const int rc = launch_camera_hits(ctx, call, sc, fp, ctx->d_queues + (size_t)frames * 8 * kQueueStride, resident, hitsKey, wantCuts, shadowMode < 0 && calibrate)) return rc;
   for (uint32_t f = 0, launchIndex = 0; f < frames && nblocks > 0; launchIndex++) {
     const uint32_t nf = fused ? std::min(fu.chunk, frames - f) : 1u;   // frames of this launch
     fp.frameCount = d->frame_count ? d->frame_first + f : camFrame;
@@ -2994,6 +3044,36 @@ extern "C" int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* 
 }
 
 extern "C" uint64_t lt_hip_camera_hit_passes(const lt_hip_context* ctx) { return ctx ? ctx->camhit_passes : 0; }
+
+// lt_entry_cut.hpp's interval test as the host compiles it, case by case: what lt_entry_cut_kernel asks of a lane and a box
+// (light_box_pad, lane_set, may_reach).  out[i]: 0 the box is excluded, 1 it may be reached, 2 lane_set refuses the lane.
+extern "C" int lt_hip_entry_cut_test_host(const float* origins, const float* light_boxes, const float* boxes, uint64_t n, uint8_t* out) {
+  if ((!origins || !light_boxes || !boxes || !out) && n) return LT_ERR_INVALID_ARGUMENT;
+  for (uint64_t i = 0; i < n; i++) {
+    const float *o = origins + 3 * i, *L = light_boxes + 6 * i, *b = boxes + 6 * i;
+    float Llo[3] = {L[0], L[1], L[2]}, Lhi[3] = {L[3], L[4], L[5]};
+    for (int a = 0; a < 3; a++) lt_entry_cut::light_box_pad(Llo[a], Lhi[a]);
+    lt_entry_cut::LaneSet ls;
+    if (!lt_entry_cut::lane_set(o[0], o[1], o[2], Llo, Lhi, ls)) out[i] = 2;
+    else out[i] = lt_entry_cut::may_reach(ls, b[0], b[1], b[2], b[3], b[4], b[5]) ? 1 : 0;
+  }
+  return LT_OK;
+}
+
+extern "C" int lt_hip_entry_cut_counts(lt_hip_context* ctx, uint64_t* out3) {
+  if (!ctx || !out3) return LT_ERR_INVALID_ARGUMENT;
+  out3[0] = ctx->cut_builds;
+  out3[1] = out3[2] = 0;
+  if (ctx->cuts_valid && ctx->d_cut_stats) {
+    LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (ctx->render_ev_recorded) LT_HIP_CHECK(ctx, hipEventSynchronize(ctx->render_ev));
+    unsigned long long h[2];
+    LT_HIP_CHECK(ctx, hipMemcpy(h, ctx->d_cut_stats, sizeof(h), hipMemcpyDeviceToHost));
+    out3[1] = h[0];
+    out3[2] = h[1];
+  }
+  return LT_OK;
+}
 
 extern "C" int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out) {
   if (!ctx || !out) return LT_ERR_INVALID_ARGUMENT;

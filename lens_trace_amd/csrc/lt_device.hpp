@@ -997,7 +997,8 @@ __device__ __forceinline__ bool leaf2_frame(V4 v0v1, V4 v0v2, V4 tvec, V4 d, flo
   return ok && (tt < tmax);
 }
 template <int PROGRAM, int NEG>
-__device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave) {
+__device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave,
+                                        const uint32_t* cut) {
   using u64 = unsigned long long;
   const __attribute__((address_space(4))) char* const pairs = (const __attribute__((address_space(4))) char*)(unsigned long long)sc.ownPairs;
   const int lane = (int)__lane_id();
@@ -1013,6 +1014,12 @@ __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2],
   const float eps = walk2_eps<PROGRAM>();
   uint32_t cur = 0u;
   int sp = 0;
+  // the square's entry cut (lt_entry_cut.hpp), as LT_ASM_WALK2 takes it: the stack starts as the list, the walk at its top
+  const uint32_t cutCount = cut != nullptr ? (uint32_t)__builtin_amdgcn_readfirstlane((int)cut[0]) : 0u;
+  if (cutCount != 0u) {
+    for (uint32_t i = 0; i < cutCount; i++) ldsWave[sp++] = (int)cut[1u + i];
+    cur = (uint32_t)__builtin_amdgcn_readfirstlane(ldsWave[--sp]);
+  }
   for (;;) {
     const F16v r = *(ConstF16)(pairs + (cur << 6));
     if ((int)cur >= 0) {
@@ -1045,18 +1052,19 @@ __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2],
 }
 
 template <int PROGRAM, int NEG>
-__device__ __forceinline__ void packet_walk2(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave) {
+__device__ __forceinline__ void packet_walk2(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave,
+                                             const uint32_t* cut) {
 #ifndef LT_NO_ASM_WALKS
   const float eps = walk2_eps<PROGRAM>();
   const uint32_t ldsrow = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) int*)ldsWave);
   unsigned long long open0 = __builtin_amdgcn_ballot_w64(true), open1 = open0;
   packet_anyhit_walk2<NEG>((const void*)sc.ownPairs, ray[0].o.x, ray[0].o.y, ray[0].o.z, inv[0][0], inv[0][1], inv[0][2], ray[0].d.x, ray[0].d.y,
                            ray[0].d.z, pl[0].t, inv[1][0], inv[1][1], inv[1][2], ray[1].d.x, ray[1].d.y, ray[1].d.z, pl[1].t, ign, eps,
-                           sc.fastRcp, open0, open1, ldsrow);
+                           sc.fastRcp, open0, open1, ldsrow, (const void*)cut);
   pl[0].hitType = ((open0 >> __lane_id()) & 1ull) != 0ull ? pl[0].hitType : 1;
   pl[1].hitType = ((open1 >> __lane_id()) & 1ull) != 0ull ? pl[1].hitType : 1;
 #else
-  packet_walk2_cpp<PROGRAM, NEG>(sc, ray, inv, ign, pl, ldsWave);
+  packet_walk2_cpp<PROGRAM, NEG>(sc, ray, inv, ign, pl, ldsWave, cut);
 #endif
 }
 
@@ -1166,8 +1174,10 @@ __device__ inline void traverse(const SceneDev& sc, const Ray& ray, bool useIgno
 // along at most one axis (one octant, or a one-mixed-axis form: what a receiver within an area light's extent along one axis
 // sees): true.  Otherwise false, and nothing is walked: the caller renders each frame as it does alone (render_square), so that
 // the kernel holds one copy of traverse and its walks, not two.
+// cut: the entry cut of the square whose stored camera hits these rays leave (lt_entry_cut.hpp; wave-uniform), or null.
 template <int PROGRAM, class CFG>
-__device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2], int ignore, Hit (&pl)[2], Stack<CFG::kDeep>& st, Counters& c) {
+__device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2], int ignore, Hit (&pl)[2], Stack<CFG::kDeep>& st, Counters& c,
+                                        const uint32_t* cut) {
   bool ok = false;
   if constexpr (!CFG::kStats && !CFG::kDeep && !CFG::kLdsScene) {
     float inv[2][3];
@@ -1211,26 +1221,26 @@ __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2],
     if (ok) {
       int* const row = st.lds - __lane_id();
       switch (form) {
-        case 0: packet_walk2<PROGRAM, 0>(sc, ray, inv, ignore, pl, row); break;
-        case 1: packet_walk2<PROGRAM, 1>(sc, ray, inv, ignore, pl, row); break;
-        case 2: packet_walk2<PROGRAM, 2>(sc, ray, inv, ignore, pl, row); break;
-        case 3: packet_walk2<PROGRAM, 3>(sc, ray, inv, ignore, pl, row); break;
-        case 4: packet_walk2<PROGRAM, 4>(sc, ray, inv, ignore, pl, row); break;
-        case 5: packet_walk2<PROGRAM, 5>(sc, ray, inv, ignore, pl, row); break;
-        case 6: packet_walk2<PROGRAM, 6>(sc, ray, inv, ignore, pl, row); break;
-        case 7: packet_walk2<PROGRAM, 7>(sc, ray, inv, ignore, pl, row); break;
-        case 8: packet_walk2<PROGRAM, 8>(sc, ray, inv, ignore, pl, row); break;
-        case 9: packet_walk2<PROGRAM, 9>(sc, ray, inv, ignore, pl, row); break;
-        case 10: packet_walk2<PROGRAM, 10>(sc, ray, inv, ignore, pl, row); break;
-        case 11: packet_walk2<PROGRAM, 11>(sc, ray, inv, ignore, pl, row); break;
-        case 12: packet_walk2<PROGRAM, 12>(sc, ray, inv, ignore, pl, row); break;
-        case 13: packet_walk2<PROGRAM, 13>(sc, ray, inv, ignore, pl, row); break;
-        case 14: packet_walk2<PROGRAM, 14>(sc, ray, inv, ignore, pl, row); break;
-        case 15: packet_walk2<PROGRAM, 15>(sc, ray, inv, ignore, pl, row); break;
-        case 16: packet_walk2<PROGRAM, 16>(sc, ray, inv, ignore, pl, row); break;
-        case 17: packet_walk2<PROGRAM, 17>(sc, ray, inv, ignore, pl, row); break;
-        case 18: packet_walk2<PROGRAM, 18>(sc, ray, inv, ignore, pl, row); break;
-        default: packet_walk2<PROGRAM, 19>(sc, ray, inv, ignore, pl, row); break;
+        case 0: packet_walk2<PROGRAM, 0>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 1: packet_walk2<PROGRAM, 1>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 2: packet_walk2<PROGRAM, 2>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 3: packet_walk2<PROGRAM, 3>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 4: packet_walk2<PROGRAM, 4>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 5: packet_walk2<PROGRAM, 5>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 6: packet_walk2<PROGRAM, 6>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 7: packet_walk2<PROGRAM, 7>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 8: packet_walk2<PROGRAM, 8>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 9: packet_walk2<PROGRAM, 9>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 10: packet_walk2<PROGRAM, 10>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 11: packet_walk2<PROGRAM, 11>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 12: packet_walk2<PROGRAM, 12>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 13: packet_walk2<PROGRAM, 13>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 14: packet_walk2<PROGRAM, 14>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 15: packet_walk2<PROGRAM, 15>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 16: packet_walk2<PROGRAM, 16>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 17: packet_walk2<PROGRAM, 17>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 18: packet_walk2<PROGRAM, 18>(sc, ray, inv, ignore, pl, row, cut); break;
+        default: packet_walk2<PROGRAM, 19>(sc, ray, inv, ignore, pl, row, cut); break;
       }
     }
   }
@@ -1265,6 +1275,12 @@ __device__ __forceinline__ const float* light_prim(const SceneDev& sc, float rnd
   const int idx = (int)(rnd * (float)sc.lights->count);
   const uint32_t p = (idx >= 0 && idx < 64) ? sc.lights->primitives[idx] : 0u;
   return prim_ptr(sc, (int)p);
+}
+// ... and whether that index is one of the list's `count` (not its zero tail, which stands for primitive 0)
+__device__ __forceinline__ bool light_index_listed(const SceneDev& sc, float rnd) {
+  const uint32_t n = sc.lights->count;
+  const int idx = (int)(rnd * (float)n);
+  return idx >= 0 && (uint32_t)idx < n && idx < 64;
 }
 
 // Light sample + shadow ray: acc.cl:239-279, basic_lighting.cl:234-274, gi.cl:267-297 and :323-349.
@@ -1456,7 +1472,7 @@ __device__ inline V3 shade_lighting(const SceneDev& sc, const Hit& pl, float fx,
 // direct_light, and their fences.  False where the two rays could not walk together: `out` is then not the colours.
 template <class CFG>
 __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float fx, float fy, uint32_t s, Stack<CFG::kDeep>& st, Counters& c,
-                                       V3 (&out)[2]) {
+                                       V3 (&out)[2], const uint32_t* cut) {
   out[0] = out[1] = V3{0.0f, 0.0f, 0.0f};
   if (is_light(sc.lights, pl.prim)) {
     out[0] = out[1] = V3{1.0f, 1.0f, 1.0f};
@@ -1480,9 +1496,11 @@ __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float 
     for (int i = 0; i < 4; i++) rnd[i] = random_<CFG::kDevLibm>(fx, fy, (float)(s + (uint32_t)i));
   }
   V4 lightPosition[2];
+  bool listed = true;   // both samples are points of the light list's primitives: what the square's entry cut was made for
 #pragma unroll
   for (int j = 0; j < 2; j++) {
     const float* lp = light_prim(sc, rnd[j]);
+    if (cut != nullptr) listed = listed && light_index_listed(sc, rnd[j]);
     float uvx = rnd[j + 1], uvy = rnd[j + 2];
     if (uvx + uvy > 1.0f) {
       uvx = 1.0f - uvx;
@@ -1515,7 +1533,8 @@ __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float 
     ray[j] = Ray{position, toLight};
   }
   asm volatile("" : "+v"(ndotl[0]), "+v"(ndotl[1]));
-  if (!traverse_shadow2<kAccumulator, CFG>(sc, ray, pl.prim, spl, st, c)) return false;
+  if (cut != nullptr && __builtin_amdgcn_ballot_w64(!listed) != 0ull) cut = nullptr;
+  if (!traverse_shadow2<kAccumulator, CFG>(sc, ray, pl.prim, spl, st, c, cut)) return false;
   asm volatile("" ::: "memory");
   const Material* m = sc.mats + prim_material(prim_ptr(sc, pl.prim));
 #pragma unroll
@@ -1650,6 +1669,10 @@ struct FrameParams {
   // rays -- a head square's -- stores what it found in its 64 slots of cameraHits, as the pass would have: a later call with the same
   // camera then finds every square's hits there (lt_capi.hip: CameraHitsKey).
   uint32_t storeHeadHits;
+  // The entry cuts of the squares whose hits are stored (lt_entry_cut_kernel, lt_entry_cut.hpp): 16 words at entryCuts[p * 16] for
+  // the square at hand-out position p -- a count, then that many references into the pair records, where the two-frame shadow walk
+  // of the square's items starts instead of the root; count 0: at the root.  Null: no cuts (LT_ENTRY_CUT=0, nothing stored).
+  const uint32_t* entryCuts;
 };
 
 // Camera ray of pixel (x,y): acc.cl:304-312.
@@ -1673,11 +1696,11 @@ __device__ __forceinline__ Ray camera_ray(const FrameParams& fp, int x, int y, f
 // or false where the frames' shadow rays could not walk together (shade_lighting2)
 template <class CFG>
 __device__ inline bool shade_pixel2(const SceneDev& sc, const FrameParams& fp, uint32_t frameCount, int x, int y, Stack<CFG::kDeep>& st,
-                                    Counters& c, const uint4* hitRow, V3 (&color)[2]) {
+                                    Counters& c, const uint4* hitRow, V3 (&color)[2], const uint32_t* cut) {
   float fx, fy;
   const Ray ray = camera_ray<CFG::kDevLibm>(fp, x, y, fx, fy);
   const Hit pl = camera_hit<kAccumulator, CFG>(sc, ray, hitRow, st, c);
-  if (!shade_lighting2<CFG>(sc, pl, fx, fy, frameCount, st, c, color)) return false;
+  if (!shade_lighting2<CFG>(sc, pl, fx, fy, frameCount, st, c, color, cut)) return false;
   if (fp.clampOutput)
 #pragma unroll
     for (int j = 0; j < 2; j++)

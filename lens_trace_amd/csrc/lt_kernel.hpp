@@ -4,6 +4,7 @@
 // src/opencl/renderer_opencl.cpp:35-54; here the user supplies the shade step in HIP and gets the built-in traversal).
 #pragma once
 #include "lt_device.hpp"
+#include "lt_entry_cut.hpp"
 
 using namespace lt;
 
@@ -45,11 +46,12 @@ __device__ __forceinline__ bool square_pixel(const FrameParams& fp, uint32_t b, 
 // One 8x8 pixel square (logical index b, already XCD-ordered) by one wavefront.
 // (pos: the square's position in the hand-out order -- what a queued shadow ray's slot is made of, SceneDev::shadowPackets == 3;
 // hitRow: the square's stored camera hits, FrameParams::cameraHits, or null; frames: 2 for a work item of two frames, frame and
-// frame + 1, of accumulator over stored hits -- FrameParams::shadowFrames -- else 1)
+// frame + 1, of accumulator over stored hits -- FrameParams::shadowFrames -- else 1; cut: the square's entry cut, FrameParams::entryCuts,
+// or null)
 template <int PROGRAM, class CFG>
 __device__ __forceinline__ void render_square(const SceneDev& sc, const FrameParams& fp, float* __restrict__ out, uint32_t b,
                                               uint32_t frame, uint32_t frames, Stack<CFG::kDeep>& st, Counters& c, uint32_t pos,
-                                              const uint4* hitRow) {
+                                              const uint4* hitRow, const uint32_t* cut) {
   constexpr bool STATS = CFG::kStats;
   const uint32_t k = b / fp.blocksPerTile, sb = b % fp.blocksPerTile;
   const uint32_t sbx = sb % fp.blocksPerTileX, sby = sb / fp.blocksPerTileX;
@@ -87,7 +89,7 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
     if constexpr (PROGRAM == kAccumulator && CFG::kGroups && !STATS) {
       if (frames > 1u) {
         V3 color[2];
-        grouped = shade_pixel2<CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, c, hitRow, color);
+        grouped = shade_pixel2<CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, c, hitRow, color, cut);
         if (grouped) {
           store(o, color[0]);
           store(o + fp.frameStride, color[1]);
@@ -221,7 +223,8 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
       if (fp.order) b = (uint32_t)__builtin_amdgcn_readfirstlane((int)fp.order[b]);
     }
     if (HITS) camera_hit_square<CFG>(sc, fp, b, pos, st, c);
-    else render_square<PROGRAM, CFG>(sc, fp, out, b, frame, frames, st, c, pos, stored ? fp.cameraHits + (size_t)pos * kBlock : nullptr);
+    else render_square<PROGRAM, CFG>(sc, fp, out, b, frame, frames, st, c, pos, stored ? fp.cameraHits + (size_t)pos * kBlock : nullptr,
+                                     stored && fp.entryCuts != nullptr ? fp.entryCuts + (size_t)pos * lt_entry_cut::kListWords : nullptr);
   }
   if (STATS) {
     atomicAdd(&stats[0], (unsigned long long)c.rays);
@@ -247,6 +250,104 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(PROGRAM)) void lt_render_ker
 template <class CFG>
 __global__ __launch_bounds__(kBlock, LT_ACC_WAVES) void lt_camera_hits_kernel(SceneDev sc, FrameParams fp, uint32_t* __restrict__ queues) {
   render_kernel_body<kAccumulator, CFG, true>(sc, fp, nullptr, nullptr, queues);
+}
+
+// The entry cuts of stored camera hits (lt_entry_cut.hpp; FrameParams::entryCuts): one wave per square of the hand-out order,
+// position blockIdx.x -- every square (all != 0: the hits are whole, a call that reuses them) or all but the head squares of fp's
+// hand-out order (all == 0: behind a call's own camera-hit pass, whose render launches walk the head squares themselves).  A lane casts shadow rays iff its stored hit is a surface that is
+// no light (shade_lighting2); the square's list starts as the root and the shallowest interior entry is replaced by those of its
+// two children that some casting lane may reach (may_reach), until a replacement would make it longer than `limit` (<= kCut).  The empty list
+// -- start at the root -- where the argument does not hold or nothing is gained: no light, a casting lane that lane_set refuses,
+// no casting lane, a list that is the root alone or empty.  stats: [0] squares with a non-empty list, [1] their entries.
+template <class CFG>
+__global__ __launch_bounds__(kBlock) void lt_entry_cut_kernel(SceneDev sc, FrameParams fp, uint32_t* __restrict__ cuts, uint32_t all,
+                                                             uint32_t limit, unsigned long long* __restrict__ stats) {
+  using namespace lt_entry_cut;
+  const uint32_t pos = blockIdx.x, lane = threadIdx.x;
+  if (pos >= fp.totalSquares) return;
+  bool head = false;
+  for (uint32_t xcd = 0; xcd < 8u; xcd++) {
+    const uint32_t start = xcd_share_start(fp.totalSquares, xcd);
+    if (pos >= start && pos - start < xcd_share_size(fp.totalSquares, xcd)) head = fp.order != nullptr && pos - start < fp.orderHead[xcd];
+  }
+  if (head && all == 0u) return;
+  __shared__ uint32_t refs[kCut + 2], depth[kCut + 2];
+  // the light primitives' vertex box, pushed outwards
+  const uint32_t nLights = sc.lights->count;
+  float Llo[3], Lhi[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) { Llo[a] = __builtin_inff(); Lhi[a] = -__builtin_inff(); }
+  if (lane < nLights && lane < 64u) {
+    const float* lp = prim_ptr(sc, (int)sc.lights->primitives[lane]);
+#pragma unroll
+    for (int v = 0; v < 3; v++)
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        Llo[a] = __builtin_fminf(Llo[a], lp[3 * v + a]);
+        Lhi[a] = __builtin_fmaxf(Lhi[a], lp[3 * v + a]);
+      }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    for (int m = 32; m >= 1; m >>= 1) {
+      Llo[a] = __builtin_fminf(Llo[a], __shfl_xor(Llo[a], m));
+      Lhi[a] = __builtin_fmaxf(Lhi[a], __shfl_xor(Lhi[a], m));
+    }
+    light_box_pad(Llo[a], Lhi[a]);
+  }
+  // this lane's origin: shade_lighting2's `position`, the same operations on the same stored hit
+  const uint32_t b = fp.order ? fp.order[pos] : pos;
+  uint32_t x, y, pix;
+  bool casts = false;
+  LaneSet ls{};
+  bool covered = true;
+  if (square_pixel(fp, b, x, y, pix)) {
+    const uint4 h = fp.cameraHits[(size_t)pos * kBlock + lane];
+    if ((int)h.y == 1 && !is_light(sc.lights, (int)h.x)) {
+      casts = true;
+      const float* pr = prim_ptr(sc, (int)h.x);
+      const V3 p3 = bary3<CFG::kDevLibm>(pr + 0, pr + 3, pr + 6, barycentrics(__uint_as_float(h.z), __uint_as_float(h.w)));
+      covered = lane_set(p3.x, p3.y, p3.z, Llo, Lhi, ls);
+    }
+  }
+  uint32_t n = 0u;
+  const bool build = nLights != 0u && nLights <= 64u && sc.ownPairs != nullptr && __builtin_amdgcn_ballot_w64(casts) != 0ull &&
+                     __builtin_amdgcn_ballot_w64(casts && !covered) == 0ull;
+  if (build) {
+    if (lane == 0u) { refs[0] = 0u; depth[0] = 0u; }
+    n = 1u;
+    __syncthreads();
+    const __attribute__((address_space(4))) char* const pairs = (const __attribute__((address_space(4))) char*)(unsigned long long)sc.ownPairs;
+    for (;;) {
+      uint32_t pick = n, best = 0xffffffffu;   // the shallowest interior entry, the first of several
+      for (uint32_t i = 0; i < n; i++)
+        if ((int)refs[i] >= 0 && depth[i] < best) { best = depth[i]; pick = i; }
+      if (pick == n) break;
+      const F16v r = *(ConstF16)(pairs + ((size_t)refs[pick] << 6));
+      const bool inL = __builtin_amdgcn_ballot_w64(casts && may_reach(ls, r.s0, r.s1, r.s2, r.s3, r.s4, r.s5)) != 0ull;
+      const bool inR = __builtin_amdgcn_ballot_w64(casts && may_reach(ls, r.s8, r.s9, r.sa, r.sb, r.sc, r.sd)) != 0ull;
+      const uint32_t kids = (inL ? 1u : 0u) + (inR ? 1u : 0u);
+      if (n - 1u + kids > limit || n - 1u + kids > (uint32_t)kCut) break;
+      __syncthreads();
+      if (lane == 0u) {
+        const uint32_t d = depth[pick] + 1u;
+        // (the picked entry's place goes to the last entry, the children to the end: the walk takes a list in any order)
+        refs[pick] = refs[n - 1u]; depth[pick] = depth[n - 1u];
+        uint32_t m = n - 1u;
+        if (inL) { refs[m] = __float_as_uint(r.s6); depth[m] = d; m++; }
+        if (inR) { refs[m] = __float_as_uint(r.se); depth[m] = d; m++; }
+      }
+      n = n - 1u + kids;
+      __syncthreads();
+      if (n == 0u) break;
+    }
+    if (n == 1u && refs[0] == 0u) n = 0u;   // the root alone
+  }
+  if (lane < (uint32_t)kListWords) cuts[(size_t)pos * kListWords + lane] = lane == 0u ? n : lane <= n ? refs[lane - 1u] : 0u;
+  if (lane == 0u && n != 0u && stats != nullptr) {
+    atomicAdd(&stats[0], 1ull);
+    atomicAdd(&stats[1], (unsigned long long)n);
+  }
 }
 
 // =====================================================================================================================

@@ -25,6 +25,8 @@
 //     register's 64 lanes are parked in the wave's LDS row around a walk that runs with lanes switched off: LT_ASM_WALK).  Pushes
 //     are branch-free: write the child at the top, then add "some lane hit it" (SCC of s_cmp_lg_u64) to the pointer.  Depth:
 //     at most two waiting entries per level plus four at the frontier, 2 * height + 2 <= 62 (the build caps the height at 30);
+//     the two-frame walk may start with a square's entry cut on the stack, at most kCut entries that wait below whichever subtree is
+//     being walked (lt_entry_cut.hpp: entry_cut_limit keeps 2 * height + 2 + entries <= 64);
 //   * two interior nodes per iteration when the stack holds two: their records are fetched together, halving the number of
 //     dependent memory round trips, which is what this walk waits for (on the 1 M-triangle scene one record fetch in three
 //     hits the scalar cache and two in three of the rest the XCD's L2);
@@ -677,7 +679,20 @@ typedef unsigned long long lt_u64;
   ".Lsaved%=:\n"                                                                                                                \
   "s_mov_b32 m0, 0\n"                                                                                                           \
   "s_mov_b32 " LT_R_CUR ", 0\n"                                                                                                 \
-  "s_branch .Lnode%=\n"                                                                                                         \
+  /* The square's entry cut (lt_entry_cut.hpp), or null: [count][references, in the stack's own encoding].  The stack register is  \
+     the walk's from here on (parked above, or every lane is this path's), so it serves as its own address: lane i of the first    \
+     fifteen takes entry i, M0 the count, and the walk enters at the pop; count 0: at the root, as without a list. */             \
+  "s_cmp_eq_u64 %[cut], 0\n"                                                                                                    \
+  "s_cbranch_scc1 .Lnode%=\n"                                                                                                   \
+  "s_load_dword " LT_R_LEAF ", %[cut], 0x0\n"                                                                                   \
+  "s_mov_b64 exec, 0x7fff\n"                                                                                                    \
+  "v_mbcnt_lo_u32_b32 %[stk], -1, 0\n"                                                                                          \
+  "v_lshlrev_b32_e32 %[stk], 2, %[stk]\n"                                                                                       \
+  "global_load_dword %[stk], %[stk], %[cut] offset:4\n"                                                                         \
+  "s_waitcnt vmcnt(0) lgkmcnt(0)\n"                                                                                             \
+  "s_cmp_eq_u32 " LT_R_LEAF ", 0\n"                                                                                             \
+  "s_cbranch_scc1 .Lnode%=\n"                                                                                                   \
+  "s_mov_b32 m0, " LT_R_LEAF "\n"                                                                                               \
   ".Lpop%=:\n"                                                                                                                  \
   "s_cmp_eq_u32 m0, 0\n"                                                                                                        \
   "s_cbranch_scc1 .Ldone%=\n"                                                                                                   \
@@ -697,7 +712,7 @@ typedef unsigned long long lt_u64;
   "s_lshl_b32 " LT_R_TMPHI ", " LT_R_CUR2 ", 6\n"                                                                               \
   "s_load_dwordx16 " LT_R_REC1 ", %[pairs], " LT_R_TMPHI "\n"                                                                   \
   "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
-  LT_ASM_TESTS2(NF, 0, 1, "a")                                                                                                  \
+  LT_ASM_TESTS2(NF, 0, 1, "a")                                                                                            \
   LT_ASM_PUSH(LT_R_REF0L, LT_R_HML)                                                                                             \
   LT_ASM_PUSH(LT_R_REF0R, LT_R_HMR)                                                                                             \
   LT_ASM_TESTS2(NF, 2, 3, "b")                                                                                                  \
@@ -781,12 +796,13 @@ __device__ __forceinline__ lt_u64 packet_anyhit_walk(const void* pairs, float ox
 // The any-hit walk of two frames' rays from one origin (LT_ASM_WALK2), one octant NEG = 0 .. 7 for both, or one mixed axis and
 // one sign along each of the other two for both (NEG = 8 .. 19): on return open0 / open1 hold the lanes whose ray of that frame
 // found no occluder.  The second frame's ray: inverse direction i?1, direction d?1, tmax1.  (No direction `w`: the leaf of this
-// walk has no use for it -- see the argument in front of LT_ASM_TESTS2 -- and eps must be positive.)
+// walk has no use for it -- see the argument in front of LT_ASM_TESTS2 -- and eps must be positive.)  cut: the square's entry
+// cut, where the walk starts instead of the root (lt_entry_cut.hpp: the same accepts), or null.
 template <int NEG>
 __device__ __forceinline__ void packet_anyhit_walk2(const void* pairs, float ox, float oy, float oz, float ix, float iy, float iz, float dx,
                                                     float dy, float dz, float tmax, float ix1, float iy1, float iz1, float dx1, float dy1,
                                                     float dz1, float tmax1, int ign, float eps, uint32_t fast, lt_u64& open0, lt_u64& open1,
-                                                    uint32_t ldsrow) {
+                                                    uint32_t ldsrow, const void* cut) {
   const PacketRay pr = packet_ray(ox, oy, oz, ix, iy, iz), pr1 = packet_ray(ox, oy, oz, ix1, iy1, iz1);
   int stk = 0;
   float t0, t1, t2, t3, t4, t5, t6, t7, tvx, tvy, tvz;
@@ -796,7 +812,7 @@ __device__ __forceinline__ void packet_anyhit_walk2(const void* pairs, float ox,
                  [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6), [t7] "=&v"(t7), [tvx] "=&v"(tvx), [tvy] "=&v"(tvy),     \
                  [tvz] "=&v"(tvz)                                                                                                        \
                : [pairs] "s"(pairs), [ox] "v"(ox), [oy] "v"(oy), [oz] "v"(oz), [ign] "v"(ign), [eps] "s"(eps), [fast] "s"(fast),          \
-                 [ldsrow] "s"(ldsrow),                                                                                                   \
+                 [ldsrow] "s"(ldsrow), [cut] "s"(cut),                                                                                                 \
                  [ix] "v"(ix), [iy] "v"(iy), [iz] "v"(iz), [px] "v"(pr.px), [py] "v"(pr.py), [pz] "v"(pr.pz), [mg] "v"(pr.mg),             \
                  [dx] "v"(dx), [dy] "v"(dy), [dz] "v"(dz), [tmax] "v"(tmax),                                                              \
                  [ix_1] "v"(ix1), [iy_1] "v"(iy1), [iz_1] "v"(iz1), [px_1] "v"(pr1.px), [py_1] "v"(pr1.py), [pz_1] "v"(pr1.pz),           \

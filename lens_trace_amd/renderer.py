@@ -397,6 +397,14 @@ class RendererHIP:
         with the same scene, camera, image, tiles and math flavour as the one before it (frame_first may move on) launches none."""
         return int(self._L.lt_hip_camera_hit_passes(self._ctx))
 
+    def entry_cut_counts(self):
+        """lt_hip_entry_cut_counts: (builds of entry cuts so far, squares whose list is not empty, entries of those lists) -- the
+        last two of the cuts the context holds now.  The cuts are kept with the camera hits: the first call that reuses a set of
+        hits builds them, later ones build none.  Waits for the context's last render.  LT_ENTRY_CUT=0: (0, 0, 0)."""
+        out = (ctypes.c_uint64 * 3)()
+        self._check(self._L.lt_hip_entry_cut_counts(self._ctx, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def scene_structure(self, what):
         """lt_hip_read_scene_structure: 0 own tree (NODE_DTYPE array), 1 leaf order table (n_prims x 8 uint32), 2 the per-lane walks'
         array (bytes), 3 (own height, group-tree height, groups, prepared on the device), 4 the packet walks' records (bytes, 64 per
