@@ -665,6 +665,21 @@ int lt_hip_entry_cut_counts(lt_hip_context* ctx, uint64_t* out3);
  * light box meets the node's box, 1 one may, 2 the lane is one the cut is not built for (non-finite or huge values).  No GPU. */
 int lt_hip_entry_cut_test_host(const float* origins, const float* light_boxes, const float* boxes, uint64_t n, uint8_t* out);
 
+/* The leaf pass of the entry cuts: after the node lists, the build tests the triangles of the leaves a square's rays can
+ * reach against the shaft of lines from its stored camera hits towards the light box.  Where it finishes within its budget of
+ * records and at most a list's worth of leaves survive, those leaves replace the square's list -- or, where none survives, the
+ * square is marked clear and its two-frame shadow walks are not run at all.  Same pixels.  out3[0]: squares marked clear, out3[1]:
+ * squares whose list is leaves, out3[2]: the entries of those lists, of the cuts ctx holds now (lt_hip_entry_cut_counts keeps
+ * describing the node lists the pass started from).  Waits for the context's last render.  LT_ENTRY_CUT_LEAVES=0: node lists only,
+ * (0, 0, 0); LT_ENTRY_CUT_LEAVES=N, N >= 2: the budget of records per square, for measurements (default 512). */
+int lt_hip_entry_cut_leaf_counts(lt_hip_context* ctx, uint64_t* out3);
+
+/* The leaf pass's triangle test on the host, for tests: n cases of (origin: 3 floats, the light primitives' vertex box before it is
+ * pushed outwards: lo xyz hi xyz, a traversal triangle as the walks' leaf records hold it: v0, v1 - v0, v2 - v0).  out[i]: 0 no
+ * line through the origin towards a point of the light box passes the float triangle test in any math flavour, 1 one may, 2 the
+ * lane is one the cut is not built for.  No GPU. */
+int lt_hip_entry_cut_triangle_test_host(const float* origins, const float* light_boxes, const float* triangles, uint64_t n, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

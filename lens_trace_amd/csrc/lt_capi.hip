@@ -340,8 +340,10 @@ struct lt_hip_context {
   uint32_t* d_cuts = nullptr;
   uint64_t cuts_squares = 0;
   bool cuts_valid = false;           // d_cuts holds the cuts of every square of the hits that camhits_key speaks of
-  unsigned long long* d_cut_stats = nullptr;   // [0] squares with a non-empty list, [1] their entries: of the cuts d_cuts holds
-  uint64_t cut_builds = 0;           // launches of lt_entry_cut_kernel so far (lt_hip_entry_cut_counts)
+  unsigned long long* d_cut_stats = nullptr;   // [0] squares with a non-empty list, [1] their entries: of the cuts d_cuts holds;
+                                               // [2] squares marked clear, [3] squares with a list of leaves, [4] those lists' entries
+  uint32_t cuts_leaves = 0;          // RenderKnobs::entry_cut_leaves of the build that made them (another value: built again)
+  uint64_t cut_builds = 0;          // launches of lt_entry_cut_kernel so far (lt_hip_entry_cut_counts)
   uint64_t scene_generation = 0;     // goes up whenever a resident scene buffer or an array derived from one is written or given back
   hipEvent_t render_ev = nullptr;    // behind the last launch of the last render call, on render_stream: a render on another stream waits for it
   hipStream_t render_stream = nullptr;
@@ -1143,6 +1145,8 @@ struct RenderKnobs {
   bool camera_hits = !env_off("LT_CAMERA_HITS");   // off: every launch walks its camera rays (launch_camera_hits)
   bool camera_hits_keep = !env_off("LT_CAMERA_HITS_KEEP");   // off: a call's camera hits are not kept for the next one (camera_hits_key)
   bool entry_cut = !env_off("LT_ENTRY_CUT");   // off: every square's entry cut is the empty list (launch_entry_cuts)
+  uint32_t entry_cut_leaves = 512;      // LT_ENTRY_CUT_LEAVES=0: node cuts only, no leaf pass (lt_entry_cut_kernel); =N >= 2: the records its
+                                        // leaf pass may visit per square, for measurements (1, or unset: 512)
   uint32_t shadow_frames = 2;           // LT_SHADOW_FRAMES=1..2: frames per work item whose shadow rays walk together (launch_walk)
   bool debug_shadow_frames = getenv("LT_DEBUG_SHADOW_FRAMES") != nullptr;   // launch_walk prints the frame groups of every render launch
                                                                             // and, where there are groups, how many waves walked them together
@@ -1153,6 +1157,10 @@ struct RenderKnobs {
     if (const char* e = getenv("LT_TRACE_REFILL")) trace_refill = (uint32_t)std::max(1, std::min(64, atoi(e)));
     if (const char* e = getenv("LT_FUSED_BYTES")) fused_bytes = strtoull(e, nullptr, 10);
     if (const char* e = getenv("LT_DEBUG_LDS_ROWS")) debug_lds_rows = (uint32_t)std::max(1, std::min(160, atoi(e)));
+    if (const char* e = getenv("LT_ENTRY_CUT_LEAVES")) {
+      const int v = atoi(e);
+      entry_cut_leaves = v <= 0 ? 0u : v == 1 ? 512u : (uint32_t)std::min(v, 1 << 20);
+    }
     if (const char* e = getenv("LT_SHADOW_FRAMES")) shadow_frames = (uint32_t)std::max(1, std::min(2, atoi(e)));
   }
 };
@@ -1827,18 +1835,25 @@ static std::vector<unsigned char> camera_hits_key(const lt_hip_context* ctx, con
 // at 4K: a chain of dependent record fetches per square) for walks that save 2.8 ms in their one call -- unless it is the call that times the shadow walks, which then times the
 // packet walk as it will run: with the cuts of the squares its pass walked (`all` false; not kept).  LT_ENTRY_CUT=0, a scene
 // without an own tree or with one so high that no list fits the walk's stack beside its own entries (entry_cut_limit): no cuts.
+// The same launch then runs the leaf pass (lt_entry_cut_kernel; lt_entry_cut.hpp: may_accept) with RenderKnobs::entry_cut_leaves
+// records per square: squares marked clear, squares whose list becomes a few leaves (lt_hip_entry_cut_leaf_counts); 0: none.
+// Not in the timing call (`all` false): there the packet walk is timed from the node lists, as it was before there was a leaf pass.
+// On bench.py's mixed scene the timed packets and the timed queued walk are within 0.1 - 0.3 ms of each other as it is (27.2 - 27.5
+// against 26.4 - 27.3 ms: the queued walk's timed launch includes the first allocation of its queue), while in the calls that reuse
+// their hits the queue wins clearly (23.8 against 26.2 ms per step): a faster timed packet launch would tip that toss the wrong way.
 static int launch_entry_cuts(lt_hip_context* ctx, const RenderCall& c, const SceneDev& sc, const FrameParams& fh, bool all) {
   ctx->cuts_valid = false;
   LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_cuts, ctx->cuts_squares, c.nblocks, c.nblocks * lt_entry_cut::kListWords * sizeof(uint32_t)));
-  if (!ctx->d_cut_stats) LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_cut_stats, 2 * sizeof(unsigned long long)));
-  LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_cut_stats, 0, 2 * sizeof(unsigned long long), c.s));
+  if (!ctx->d_cut_stats) LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_cut_stats, 5 * sizeof(unsigned long long)));
+  LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_cut_stats, 0, 5 * sizeof(unsigned long long), c.s));
   with_math(c.devlibm, [&](auto m) {
     hipLaunchKernelGGL((lt_entry_cut_kernel<Config<false, false, decltype(m)::value>>), dim3((uint32_t)c.nblocks), dim3(kBlock), 0, c.s, sc, fh, ctx->d_cuts,
-                       all ? 1u : 0u, (uint32_t)lt_entry_cut::entry_cut_limit(ctx->height2), ctx->d_cut_stats);
+                       all ? 1u : 0u, (uint32_t)lt_entry_cut::entry_cut_limit(ctx->height2), ctx->d_cut_stats, all ? c.k.entry_cut_leaves : 0u);
     return 0;
   });
   LT_HIP_CHECK(ctx, hipGetLastError());
   ctx->cuts_valid = all;
+  ctx->cuts_leaves = c.k.entry_cut_leaves;
   ctx->cut_builds++;
   return LT_OK;
 }
@@ -1862,7 +1877,7 @@ static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const Sc
     fp.cameraHits = ctx->d_camhits;
     for (uint32_t& h : fp.orderHead) h = 0u;
     if (wantCuts) {
-      if (!ctx->cuts_valid || ctx->cuts_squares < c.nblocks) {
+      if (!ctx->cuts_valid || ctx->cuts_squares < c.nblocks || ctx->cuts_leaves != c.k.entry_cut_leaves) {
         fh.cameraHits = ctx->d_camhits;
         if (const int rc = launch_entry_cuts(ctx, c, sc, fh, true)) return rc;
       }
@@ -3056,6 +3071,36 @@ extern "C" int lt_hip_entry_cut_test_host(const float* origins, const float* lig
     lt_entry_cut::LaneSet ls;
     if (!lt_entry_cut::lane_set(o[0], o[1], o[2], Llo, Lhi, ls)) out[i] = 2;
     else out[i] = lt_entry_cut::may_reach(ls, b[0], b[1], b[2], b[3], b[4], b[5]) ? 1 : 0;
+  }
+  return LT_OK;
+}
+
+// lt_entry_cut.hpp's triangle test as the host compiles it: what the leaf pass of lt_entry_cut_kernel asks of a lane and a leaf's
+// traversal triangle (A, v0v1, v0v2: nine floats).  out[i]: 0 the triangle is excluded, 1 it is kept, 2 lane_set refuses the lane.
+extern "C" int lt_hip_entry_cut_triangle_test_host(const float* origins, const float* light_boxes, const float* triangles, uint64_t n, uint8_t* out) {
+  if ((!origins || !light_boxes || !triangles || !out) && n) return LT_ERR_INVALID_ARGUMENT;
+  for (uint64_t i = 0; i < n; i++) {
+    const float *o = origins + 3 * i, *L = light_boxes + 6 * i, *t = triangles + 9 * i;
+    float Llo[3] = {L[0], L[1], L[2]}, Lhi[3] = {L[3], L[4], L[5]};
+    for (int a = 0; a < 3; a++) lt_entry_cut::light_box_pad(Llo[a], Lhi[a]);
+    lt_entry_cut::LaneSet ls;
+    if (!lt_entry_cut::lane_set(o[0], o[1], o[2], Llo, Lhi, ls)) out[i] = 2;
+    else out[i] = lt_entry_cut::may_accept(ls, t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8]) ? 1 : 0;
+  }
+  return LT_OK;
+}
+
+extern "C" int lt_hip_entry_cut_leaf_counts(lt_hip_context* ctx, uint64_t* out3) {
+  if (!ctx || !out3) return LT_ERR_INVALID_ARGUMENT;
+  out3[0] = out3[1] = out3[2] = 0;
+  if (ctx->cuts_valid && ctx->d_cut_stats) {
+    LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (ctx->render_ev_recorded) LT_HIP_CHECK(ctx, hipEventSynchronize(ctx->render_ev));
+    unsigned long long h[5];
+    LT_HIP_CHECK(ctx, hipMemcpy(h, ctx->d_cut_stats, sizeof(h), hipMemcpyDeviceToHost));
+    out3[0] = h[2];
+    out3[1] = h[3];
+    out3[2] = h[4];
   }
   return LT_OK;
 }

@@ -1175,6 +1175,7 @@ __device__ inline void traverse(const SceneDev& sc, const Ray& ray, bool useIgno
 // sees): true.  Otherwise false, and nothing is walked: the caller renders each frame as it does alone (render_square), so that
 // the kernel holds one copy of traverse and its walks, not two.
 // cut: the entry cut of the square whose stored camera hits these rays leave (lt_entry_cut.hpp; wave-uniform), or null.
+constexpr uint32_t kEntryCutClear = 0xffffffffu;   // lt_entry_cut::kClearMark (lt_kernel.hpp holds the two together)
 template <int PROGRAM, class CFG>
 __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2], int ignore, Hit (&pl)[2], Stack<CFG::kDeep>& st, Counters& c,
                                         const uint32_t* cut) {
@@ -1218,6 +1219,9 @@ __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2],
       atomicAdd(&sc.groupWalks[ok ? 0 : 1], 1ull);
       if (ok && form >= 8u) atomicAdd(&sc.groupWalks[form - 6u], 1ull);
     }
+    // A square marked clear (lt_entry_cut.hpp: kClearMark, one scalar load): no leaf can occlude a ray of it, both hits stay
+    // unoccluded without a walk.  Decided here and nowhere earlier: together or apart, and the count above, are what they were.
+    if (ok && cut != nullptr && *(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)cut == kEntryCutClear) return true;
     if (ok) {
       int* const row = st.lds - __lane_id();
       switch (form) {
@@ -1671,7 +1675,8 @@ struct FrameParams {
   uint32_t storeHeadHits;
   // The entry cuts of the squares whose hits are stored (lt_entry_cut_kernel, lt_entry_cut.hpp): 16 words at entryCuts[p * 16] for
   // the square at hand-out position p -- a count, then that many references into the pair records, where the two-frame shadow walk
-  // of the square's items starts instead of the root; count 0: at the root.  Null: no cuts (LT_ENTRY_CUT=0, nothing stored).
+  // of the square's items starts instead of the root; count 0: at the root; kEntryCutClear in place of the count: no leaf can occlude
+  // a ray of the square, no walk (traverse_shadow2).  Null: no cuts (LT_ENTRY_CUT=0, nothing stored).
   const uint32_t* entryCuts;
 };
 

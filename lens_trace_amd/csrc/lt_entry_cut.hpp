@@ -82,6 +82,10 @@ namespace lt_entry_cut {
 constexpr int kCut = LT_ENTRY_CUT_K;   // entries of a list at most; a list's 64 bytes hold a count and up to 15 references
 static_assert(kCut >= 2 && kCut <= 15, "a list is one count and at most 15 references");
 constexpr int kListWords = 16;
+// Word 0 of a list is its count, 0 .. kCut, or kClearMark: no leaf of the tree can occlude a shadow ray of the square (the leaf pass
+// of lt_entry_cut_kernel; may_accept below), so its two-frame walks are not run at all (traverse_shadow2 -- the mark never reaches
+// a walk, which would take it for a count).
+constexpr unsigned kClearMark = 0xffffffffu;
 
 constexpr float kRel = 0x1p-16f;       // R
 constexpr float kAbs = 0x1p-100f;
@@ -147,6 +151,143 @@ LT_EC_HD inline bool may_reach(const LaneSet& ls, float lox, float loy, float lo
     if (upper < tHi) tHi = upper;
   }
   return !(tLo > tHi);
+}
+
+// ---- The triangle test (may_accept): which LEAVES the lane's rays can be occluded by.  A leaf's own box contains or touches the
+// origins of a square that lies on its neighbours, so no box test removes it; the triangle itself does.
+//
+// The walk's leaf (LT_ASM_TRI2_*, leaf2_frame; the reference's intersect_triangle_data) of the traversal triangle (A, e1 = v0v1,
+// e2 = v0v2) and a ray (o, d), T = fl(o - A) -- ONE subtraction per axis, the same in every flavour, and the T of this file:
+//     det^ = e1 . (d x e2),  U^ = T . (d x e2),  V^ = d . (T x e1),  inv^ = 1 / det^  (a division, or the as-shipped rcp),
+//     u^ = fl(U^ inv^),  v^ = fl(V^ inv^);  accepted only if  !(|det^| < 1e-4), !(u^ < 0), !(u^ > 1), !(v^ < 0), !(fl(u^ + v^) > 1),
+// then t^ = fl(N^ inv^) < tmax, N^ = e2 . (T x e1), and the leaf's own slab test.  There is NO test of t^ > 0: a triangle behind the
+// origin occludes.  So the ray counts as the whole LINE through o along d up to tmax, and nothing below looks at the slab or at
+// the 1e-4 gate: leaving a test out only keeps more.  tmax is shade_lighting2's: fl((double)dist^ - 0.01), dist^ = distance4(o, l)
+// within 8u of |l - o| in every flavour (a difference, three squares, two sums: 5u under the root, which halves it; the root 2u).
+// Without it no square were ever clear: the shaft ends on the light's own triangles.  As functions of the direction the three
+// numerators are LINEAR and N does not depend on it:  for any real vector w
+//     D(w) = w . cD,  U(w) = w . cU,  V(w) = w . cV,  N = e2 . cV,   cD = e2 x e1,  cU = e2 x T,  cV = T x e1   (scalar triple products),
+// and a linear function over the box W = [wl, wh] of lane_set takes its extremes at corners: min f = sum_a min(c_a wl_a, c_a wh_a).
+//
+// What is rounded, u = 2^-24.  Write S_f(w) = sum over the six products x_i y_j w_k of f of their magnitudes (S_D: e2, e1; S_U: e2,
+// T; S_V: T, e1; S_N: the products of N, no w), S_f = its largest value over W = sum_a M_a P_a with M_a = max(|wl_a|, |wh_a|) and P the cross product of the
+// magnitudes with a plus.
+//   (a) The walk.  Every product of det^, U^, V^ passes at most five roundings whatever the flavour -- the product inside the cross
+//       product, its difference, the product with the third vector, two additions; a contracted form (fma) has fewer, the order of
+//       the additions does not matter to the bound, dot4's `w` terms are exact zeros -- so |f^ - f(d)| <= 5.01 u S_f(d), plus at most
+//       sixteen flushed or subnormal results of 2^-126 each times a factor, below 2^-121 (1 + |T|_1 + |e1|_1 + |e2|_1).
+//       inv^ = (1 + e) / det^ with |e| <= 4u in either flavour, and the product with it rounds once more: u^ det^ = U^ (1 + e'),
+//       |e'| <= 5.01 u (and 2^-126 |det^| where it underflows), v^ likewise.
+//   (b) This file (-ffp-contract=off: one rounding per operation).  A component of cD, cU, cV: two products and a difference, off by
+//       at most 2.01 u P_a; the combined vectors cU - cD and cU + cV - cD: one and two more roundings of at most the sum of the
+//       magnitudes; the range sum: a product and two additions, 3.01 u sum_a |c_a| M_a.  In all below 8 u (S_U + S_V + S_D) for every
+//       range used, plus underflows of 2^-126 each, at most 2^-122 (1 + M_1).
+//   (c) The direction.  As in the proof above d_a = q w''_a for ONE real q > 0, w''_a = (l_a - o_a)(1 + e1)(1 + e2), which differs from
+//       w_a = l_a - o_a by at most 2.01 u |w_a| towards or away from 0, and wl / wh keep (R - 3u)(|L_a| + |o_a|) >= 2.01 u |w_a| of
+//       their margin after their own roundings: w'' lies in W.  |d| is within 4u of 1, so q >= 0.99 / M_1.
+// With G = 64 u = 2^-18 and Z = 2^-100 (1 + M_1 (1 + |cD|_1 bound P_D,1 + |T|_1 + |e1|_1 + |e2|_1)) every test below compares a range
+// bound with a margin  m_f = G S_f + Z  (S over the functions the range is made of).  G is (a) + (b) + the slack of the `> 1` tests
+// with room to spare (the largest sums: for u + v 11.1 u + 8 u, for t 30.5 u + 16 u); Z times q >= 0.99 Z / M_1 outweighs every absolute term of (a), and
+// Z every one of (b).
+//
+// CLAIM.  Let the lane be one that lane_set accepts and its ray (o, d) one that traverse_shadow2 sends through a packet walk, as in
+// the claim above.  If the ray passes the float triangle test of the traversal triangle (A, e1, e2) in any flavour, t^ < tmax included, may_accept is true.
+//
+// PROOF.  Suppose may_accept is false.  Then its values are finite and below 2^40 and one sign s holds for D: the computed range of
+// D lies beyond m_D on one side, so by (b) s D(w) > (G - 8u) S_D + Z' for every w in W, in particular for w'' (c), and
+// s D(d) = q s D(w'') > q (56 u S_D(w'') + Z') >= 5.01 u S_D(d) + (the absolute term of (a)): det^ is not zero and has the sign s.
+// Say s = + (else negate cD, cU, cV: the code does, and every statement below mirrors).  One of five holds:
+//   * U < -m_U over W.  Then U^ <= U(d) + 5.01 u S_U(d) + abs < -q (56 u S_U + Z') + ... < 0, and by the absolute part of Z
+//     |U^| > 2^-101 q (1 + P_D,1) M_1 >= 2^-102 |det^|, so U^ inv^, a negative number of magnitude above 2^-103, does not round to -0:
+//     u^ < 0 and the ray is rejected.   * V < -m_V: the same for v^.
+//   * U - D > m over W (m of U and D).  Then U^ (1 - 5.01 u) - det^ >= U(d) - D(d) - 10.1 u (S_U(d) + S_D(d)) - abs > 2u det^ (as
+//     det^ <= 1.01 S_D(d)), so U^ inv^ (1 + e') >= 1 + 2u, a float, and rounding is monotone: u^ >= 1 + 2u > 1, rejected.
+//   * U + V - D > m over W (m of all three).  (u^ + v^) det^ >= U^ + V^ - 5.01 u (|U^| + |V^|) - 2^-125 det^ >= U(d) + V(d) -
+//     10.1 u (S_U(d) + S_V(d)) - abs, and that exceeds (1 + 2u) det^ <= D(d) + 8.1 u S_D(d) by the margin: u^ + v^ >= 1 + 2u as reals,
+//     fl(u^ + v^) >= 1 + 2u > 1 (also when the sum was contracted into an fma: one rounding fewer), rejected.
+//   * N - max D + k min D > m over W (m of N and D), k = min(1, 0.0098 / M_1) <= 0.0099 / |w''|: the plane is met beyond the light
+//     point, or less than 0.01 in front of it.  t^ det^ >= N^ (1 - 5.01 u) >= N - 10.1 u S_N and det^ <= D(d) + 5.01 u S_D(d), so with
+//     1 / q = |w''| / |d| >= (1 - 4u) |w''|:  t^ >= (1 - 4u) |w''| X,  X = (N - 10.1 u S_N) / (D(w'') + 5.01 u S_D(w'')).  And
+//     tmax <= (1 + 9.1 u) |l - o| - 0.0099 <= (1 + 11.2 u) |w''| - 0.0099.  So t^ >= tmax follows from X >= 1 + 15.3 u - k, i.e. from
+//     N - D(w'') >= -k D(w'') + 10.1 u S_N + 20.4 u S_D, and that from the range: D(w'') lies between min D and max D, the computed
+//     ones are off by 8 u S_D each and N by 8 u S_N (b), k <= 1:  46.5 u in all.  t^ < tmax is false, rejected.
+// In every case the ray does not pass.  QED.  Every exclusion needs a compare to be TRUE: a NaN or an infinity (a margin that
+// overflows) excludes nothing, and a D whose range contains 0 -- among them every lane whose light box contains its origin --
+// keeps the triangle.  The caller leaves out the lanes that START on the triangle (the walk ignores that primitive and no other).
+// The cull is per lane and per triangle, for all frames: lt_entry_cut_kernel keeps a leaf that any casting lane may accept.
+constexpr float kTriRel = 0x1p-18f;    // G
+
+LT_EC_HD inline void cross_signed_abs(const float (&x)[3], const float (&y)[3], float (&c)[3], float (&p)[3]) {
+  for (int a = 0; a < 3; a++) {
+    const int b = (a + 1) % 3, d = (a + 2) % 3;
+    c[a] = x[b] * y[d] - x[d] * y[b];
+    p[a] = __builtin_fabsf(x[b]) * __builtin_fabsf(y[d]) + __builtin_fabsf(x[d]) * __builtin_fabsf(y[b]);
+  }
+}
+// The range of w . c over the lane's direction box.
+LT_EC_HD inline void range_over_box(const LaneSet& ls, const float (&c)[3], float& lo, float& hi) {
+  lo = 0.0f; hi = 0.0f;
+  for (int a = 0; a < 3; a++) {
+    const float p = c[a] * ls.wl[a], q = c[a] * ls.wh[a];
+    lo = lo + (p < q ? p : q);
+    hi = hi + (p < q ? q : p);
+  }
+}
+
+// The triangle test: false only if no line through the lane's origin along a direction of its ray set passes the float triangle
+// test of the traversal triangle (A, e1, e2) -- in any math flavour, whatever t.
+LT_EC_HD inline bool may_accept(const LaneSet& ls, float ax, float ay, float az, float e1x, float e1y, float e1z, float e2x, float e2y, float e2z) {
+  const float A[3] = {ax, ay, az}, e1[3] = {e1x, e1y, e1z}, e2[3] = {e2x, e2y, e2z};
+  float T[3], M[3];
+  float norm1 = 1.0f, M1 = 0.0f;
+  bool sane = true;
+  for (int a = 0; a < 3; a++) {
+    T[a] = ls.o[a] - A[a];
+    const float wl = __builtin_fabsf(ls.wl[a]), wh = __builtin_fabsf(ls.wh[a]);
+    M[a] = wl > wh ? wl : wh;
+    M1 = M1 + M[a];
+    sane = sane && __builtin_fabsf(T[a]) < kMaxMagnitude && __builtin_fabsf(e1[a]) < kMaxMagnitude && __builtin_fabsf(e2[a]) < kMaxMagnitude;
+    norm1 = norm1 + ((__builtin_fabsf(T[a]) + __builtin_fabsf(e1[a])) + __builtin_fabsf(e2[a]));
+  }
+  if (!sane) return true;
+  float cD[3], cU[3], cV[3], pD[3], pU[3], pV[3];
+  cross_signed_abs(e2, e1, cD, pD);
+  cross_signed_abs(e2, T, cU, pU);
+  cross_signed_abs(T, e1, cV, pV);
+  float SD = 0.0f, SU = 0.0f, SV = 0.0f, SN = 0.0f, N = 0.0f;
+  for (int a = 0; a < 3; a++) {
+    SD = SD + M[a] * pD[a];
+    SU = SU + M[a] * pU[a];
+    SV = SV + M[a] * pV[a];
+    SN = SN + __builtin_fabsf(e2[a]) * pV[a];
+    N = N + e2[a] * cV[a];
+    norm1 = norm1 + pD[a];
+  }
+  const float Z = (M1 * norm1) * kAbs + kAbs;
+  float lo, hi;
+  range_over_box(ls, cD, lo, hi);
+  const float mD = kTriRel * SD + Z;
+  float s, minD, maxD;
+  if (lo > mD) { s = 1.0f; minD = lo; maxD = hi; }
+  else if (hi < -mD) { s = -1.0f; minD = -hi; maxD = -lo; }
+  else return true;
+  const float k = 0.0098f / M1;
+  if ((s * N - maxD) + (k < 1.0f ? k : 1.0f) * minD > kTriRel * (SN + SD) + Z) return false;   // t >= tmax
+  float cUD[3], cUVD[3];
+  for (int a = 0; a < 3; a++) {   // (times s: exact)
+    cD[a] = s * cD[a]; cU[a] = s * cU[a]; cV[a] = s * cV[a];
+    cUD[a] = cU[a] - cD[a];
+    cUVD[a] = (cU[a] + cV[a]) - cD[a];
+  }
+  range_over_box(ls, cU, lo, hi);
+  if (hi < -(kTriRel * SU + Z)) return false;                    // u < 0
+  range_over_box(ls, cV, lo, hi);
+  if (hi < -(kTriRel * SV + Z)) return false;                    // v < 0
+  range_over_box(ls, cUD, lo, hi);
+  if (lo > kTriRel * (SU + SD) + Z) return false;                // u > 1
+  range_over_box(ls, cUVD, lo, hi);
+  if (lo > kTriRel * ((SU + SV) + SD) + Z) return false;         // u + v > 1
+  return true;
 }
 
 }  // namespace lt_entry_cut

@@ -258,11 +258,14 @@ __global__ __launch_bounds__(kBlock, LT_ACC_WAVES) void lt_camera_hits_kernel(Sc
 // no light (shade_lighting2); the square's list starts as the root and the shallowest interior entry is replaced by those of its
 // two children that some casting lane may reach (may_reach), until a replacement would make it longer than `limit` (<= kCut).  The empty list
 // -- start at the root -- where the argument does not hold or nothing is gained: no light, a casting lane that lane_set refuses,
-// no casting lane, a list that is the root alone or empty.  stats: [0] squares with a non-empty list, [1] their entries.
+// no casting lane, a list that is the root alone or empty.  stats: [0] squares with a non-empty list, [1] their entries -- of the
+// node cut, whatever the leaf pass below makes of the square; [2] squares the leaf pass marks clear, [3] squares it gives a list of
+// leaves, [4] the entries of those.  leafBudget: the records the leaf pass may visit per square; 0: no leaf pass (LT_ENTRY_CUT_LEAVES=0).
 template <class CFG>
 __global__ __launch_bounds__(kBlock) void lt_entry_cut_kernel(SceneDev sc, FrameParams fp, uint32_t* __restrict__ cuts, uint32_t all,
-                                                             uint32_t limit, unsigned long long* __restrict__ stats) {
+                                                             uint32_t limit, unsigned long long* __restrict__ stats, uint32_t leafBudget) {
   using namespace lt_entry_cut;
+  static_assert(kClearMark == kEntryCutClear && kClearMark > (unsigned)kCut, "traverse_shadow2 looks for the mark that this kernel writes; no count is one");
   const uint32_t pos = blockIdx.x, lane = threadIdx.x;
   if (pos >= fp.totalSquares) return;
   bool head = false;
@@ -299,12 +302,14 @@ __global__ __launch_bounds__(kBlock) void lt_entry_cut_kernel(SceneDev sc, Frame
   const uint32_t b = fp.order ? fp.order[pos] : pos;
   uint32_t x, y, pix;
   bool casts = false;
+  int own = -1;   // the primitive this lane's rays start from
   LaneSet ls{};
   bool covered = true;
   if (square_pixel(fp, b, x, y, pix)) {
     const uint4 h = fp.cameraHits[(size_t)pos * kBlock + lane];
     if ((int)h.y == 1 && !is_light(sc.lights, (int)h.x)) {
       casts = true;
+      own = (int)h.x;
       const float* pr = prim_ptr(sc, (int)h.x);
       const V3 p3 = bary3<CFG::kDevLibm>(pr + 0, pr + 3, pr + 6, barycentrics(__uint_as_float(h.z), __uint_as_float(h.w)));
       covered = lane_set(p3.x, p3.y, p3.z, Llo, Lhi, ls);
@@ -343,11 +348,52 @@ __global__ __launch_bounds__(kBlock) void lt_entry_cut_kernel(SceneDev sc, Frame
     }
     if (n == 1u && refs[0] == 0u) n = 0u;   // the root alone
   }
-  if (lane < (uint32_t)kListWords) cuts[(size_t)pos * kListWords + lane] = lane == 0u ? n : lane <= n ? refs[lane - 1u] : 0u;
   if (lane == 0u && n != 0u && stats != nullptr) {
     atomicAdd(&stats[0], 1ull);
     atomicAdd(&stats[1], (unsigned long long)n);
   }
+  // The leaf pass: depth first from the root, a child where some casting lane may reach its box, a leaf where some casting lane that
+  // does not start on it may reach its own box and may accept its triangle (may_accept).  The stack and the surviving leaves are
+  // wave-uniform and live in one register each, a lane per slot (2 * height + 2 <= 62 slots: entry_cut_limit != 0).  Finished
+  // within leafBudget records and with at most `limit` leaves: those leaves are the square's list -- by the two claims no ray of
+  // the square is accepted anywhere else -- and none at all is the clear mark; else the node cut above stays.
+  uint32_t word0 = n;
+  int listv = lane >= 1u && lane <= n ? (int)refs[lane - 1u] : 0;   // word `lane` of the list
+  if (build && leafBudget != 0u) {
+    const __attribute__((address_space(4))) char* const pairs = (const __attribute__((address_space(4))) char*)(unsigned long long)sc.ownPairs;
+    int stackv = 0, keepv = 0;
+    uint32_t sp = 0u, kept = 0u, visited = 0u, cur = 0u;
+    bool whole = true;
+    for (;;) {
+      if (++visited > leafBudget) { whole = false; break; }
+      const F16v r = *(ConstF16)(pairs + (size_t)(cur << 6));
+      if ((int)cur >= 0) {
+        const bool inL = __builtin_amdgcn_ballot_w64(casts && may_reach(ls, r.s0, r.s1, r.s2, r.s3, r.s4, r.s5)) != 0ull;
+        const bool inR = __builtin_amdgcn_ballot_w64(casts && may_reach(ls, r.s8, r.s9, r.sa, r.sb, r.sc, r.sd)) != 0ull;
+        if (sp + 2u > 64u) { whole = false; break; }
+        if (inR) stackv = lane == sp++ ? __float_as_int(r.se) : stackv;
+        if (inL) stackv = lane == sp++ ? __float_as_int(r.s6) : stackv;
+      } else {
+        const bool may = casts && own != __float_as_int(r.sf) && may_reach(ls, r.s9, r.sa, r.sb, r.sc, r.sd, r.se) &&
+                         may_accept(ls, r.s0, r.s1, r.s2, r.s3, r.s4, r.s5, r.s6, r.s7, r.s8);
+        if (__builtin_amdgcn_ballot_w64(may) != 0ull) {
+          if (kept >= limit || kept >= (uint32_t)kCut) { whole = false; break; }
+          keepv = lane == 1u + kept++ ? (int)cur : keepv;
+        }
+      }
+      if (sp == 0u) break;
+      cur = (uint32_t)__builtin_amdgcn_readlane(stackv, (int)--sp);
+    }
+    if (whole) {
+      word0 = kept == 0u ? kClearMark : kept;
+      listv = lane >= 1u && lane <= kept ? keepv : 0;
+      if (lane == 0u && stats != nullptr) {
+        if (kept == 0u) atomicAdd(&stats[2], 1ull);
+        else { atomicAdd(&stats[3], 1ull); atomicAdd(&stats[4], (unsigned long long)kept); }
+      }
+    }
+  }
+  if (lane < (uint32_t)kListWords) cuts[(size_t)pos * kListWords + lane] = lane == 0u ? word0 : (uint32_t)listv;
 }
 
 // =====================================================================================================================

@@ -405,6 +405,14 @@ class RendererHIP:
         self._check(self._L.lt_hip_entry_cut_counts(self._ctx, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def entry_cut_leaf_counts(self):
+        """lt_hip_entry_cut_leaf_counts: (squares the cuts' leaf pass marked clear -- their two-frame shadow walks are not run --,
+        squares whose list is leaves, entries of those lists), of the cuts the context holds now.  entry_cut_counts keeps
+        describing the node lists.  Waits for the context's last render.  LT_ENTRY_CUT_LEAVES=0: (0, 0, 0)."""
+        out = (ctypes.c_uint64 * 3)()
+        self._check(self._L.lt_hip_entry_cut_leaf_counts(self._ctx, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def scene_structure(self, what):
         """lt_hip_read_scene_structure: 0 own tree (NODE_DTYPE array), 1 leaf order table (n_prims x 8 uint32), 2 the per-lane walks'
         array (bytes), 3 (own height, group-tree height, groups, prepared on the device), 4 the packet walks' records (bytes, 64 per
