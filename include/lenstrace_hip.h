@@ -276,8 +276,8 @@ int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* out, uint64
  * tmin, `t < tmax` with tmax as given (0, negative, inf and NaN included).  The kernel sets origin.w = 1, direction.w = +0.
  * The walk may follow the backend's own hierarchy: results are the same bit for bit (equal t from two triangles: the
  * reference's first leaf wins).  lens_trace_amd/csrc/lt_query.hip.
- * Streams: the ray, point and box queries (lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_nearest_points,
- * lt_hip_nearest_k, lt_hip_overlap_boxes, host and _device forms) share the context's work counters, so calls of these entry
+ * Streams: the ray, point, box and triangle queries (lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface,
+ * lt_hip_nearest_points, lt_hip_nearest_k, lt_hip_overlap_boxes, lt_hip_overlap_tris, host and _device forms) share the context's work counters, so calls of these entry
  * points are ordered among themselves on any streams (each waits for the one enqueued before it). */
 typedef struct lt_hip_ray { float origin[3]; float tmax; float direction[3]; int32_t ignore; } lt_hip_ray;   /* 32 B, ignore -1 = none */
 typedef struct lt_hip_hit { float t; int32_t prim; float u, v; } lt_hip_hit;   /* 16 B; a miss: prim = -1, t = tmax, u = v = 0 */
@@ -642,6 +642,58 @@ int lt_hip_overlap_boxes_device(lt_hip_context* ctx, const lt_hip_overlap_desc* 
  * call writes nothing. */
 int lt_hip_overlap_boxes_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
                               const lt_hip_overlap_desc* desc, const lt_hip_box* boxes, uint64_t n, void* out, uint64_t out_bytes);
+
+/* Triangle-overlap queries: the primitives a query triangle meets, their number, or whether there is any -- the narrow phase of
+ * a collision check (a moving mesh, a swept polygon), cutting planes, portal quads; a needle is a segment query and a point
+ * triangle a point-on-surface query.  With rays, spheres (the nearest queries) and boxes this completes the query shapes.
+ *
+ * Record: lt_hip_tri {a[3], pad0, b[3], pad1, c[3], pad2}: the vertices P, Q, R; the pads are ignored.  A query is EMPTY, and
+ * meets nothing, when any of its nine coordinates is not finite.  A degenerate triangle is valid.
+ * Candidates: the leaves of the caller's LinearBVHNode array, each with its one primitive, exactly as the box queries take them.
+ * A candidate touches the query iff both hold:
+ *   boxes_meet     the query's box meets the leaf's own box as the caller gave it (lt_hip_overlap_boxes' boxes_meet), with
+ *                  qbox.lo[k] = min3(P[k], Q[k], R[k]), qbox.hi[k] = max3(P[k], Q[k], R[k]) by that call's compare chains.
+ *   tri_meets_tri  none of 17 axes separates the traversal triangle as the scene stores it, A, e1 = fl(B - A), e2 = fl(C - A),
+ *                  from the query.  Every operation is one IEEE float32 operation rounded once, in the order given; nothing is
+ *                  contracted, subnormals are kept.  A compare with a NaN is false, which reads "not separated".  Everything is
+ *                  seen from P:
+ *     terms          g1 = Q - P, g2 = R - P, d = A - P; the scene's vertices s0 = d, s1 = d + e1, s2 = d + e2; the query's +0,
+ *                    g1, g2.  Edges f0 = e1, f1 = e2 - e1, f2 = -e2 and h0 = g1, h1 = g2 - g1, h2 = -g2.
+ *                    cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x); dot = (x x' + y y') + z z'.
+ *     axes (17)      in this order: n = cross(e1, e2); m = cross(g1, g2); the nine cross(f_i, h_j), i-major; cross(n, f_i),
+ *                    i = 0..2; cross(m, h_j), j = 0..2.  The last six lie in the two planes and decide coplanar pairs.
+ *     per axis a     ps = (dot(a, s0), dot(a, s1), dot(a, s2)), pq = (+0, dot(a, g1), dot(a, g2)); the axis separates iff
+ *                    (min3(ps) > max3(pq) or max3(ps) < min3(pq)) and the five dot products are all finite.  A zero axis
+ *                    separates nothing; an axis whose arithmetic overflowed to inf or NaN separates nothing (that is what the
+ *                    finiteness clause is for: the compare chains keep their first operand against a NaN); one that underflowed
+ *                    to zero separates nothing.
+ *                  At the magnitude limits (coordinates near 2^40 or 2^-40) the in-plane axes, products of four lengths, degrade
+ *                  first -- they overflow or underflow and drop out -- and the answer stays conservative: more touches, never
+ *                  fewer than the axes that survive allow.
+ *                  A query whose first vertex P equals a vertex of a primitive bit for bit touches that primitive whenever
+ *                  boxes_meet holds: P = A gives s0 = 0; P = B gives s1 = fl(fl(A - B) + fl(B - A)) = 0 exactly, likewise P = C;
+ *                  so both projection sets contain 0 on every axis.
+ *                  (lens_trace_amd/csrc/lt_tritri.hpp is the expression sequence; tests/overlap_tris.py restates it in numpy.)
+ * The sequence of a query: every touching candidate once, by ascending primitive offset, then ascending node index.  Kinds,
+ * descriptor and output words are lt_hip_overlap_boxes': LT_OVERLAP_FIRST_K (max_k int32 offsets per query, -1 in unused slots),
+ * LT_OVERLAP_COUNT, LT_OVERLAP_ANY (one uint32 per query).
+ *
+ * flags: 0.  Host memory, synchronous.  Errors and their order are lt_hip_overlap_boxes': LT_ERR_INVALID_ARGUMENT for a null ctx /
+ * desc, struct_size too small, flags != 0, an unknown kind, max_k outside its range for the kind, n >= 2^32, a null pointer with
+ * n > 0 (and, device entry point, pointers that are not 16-byte aligned); LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when
+ * out_bytes < 4 max_k n (FIRST_K) or 4 n (COUNT, ANY).  A failed call writes nothing to out; n == 0 launches nothing.
+ * lt_hip_get_stats then reports rays = n, kernel_launches = 1 and kernel_ms.  (lens_trace_amd/csrc/lt_tritri.hip) */
+typedef struct lt_hip_tri { float a[3]; uint32_t pad0; float b[3]; uint32_t pad1; float c[3]; uint32_t pad2; } lt_hip_tri;   /* 48 B */
+
+int lt_hip_overlap_tris(lt_hip_context* ctx, const lt_hip_overlap_desc* desc, const lt_hip_tri* tris, uint64_t n,
+                        void* out, uint64_t out_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_overlap_tris_device(lt_hip_context* ctx, const lt_hip_overlap_desc* desc, const lt_hip_tri* tris, uint64_t n,
+                               void* out, uint64_t out_bytes, void* hip_stream);
+/* The same answers on the host, without a context or a GPU, from the caller's buffers, as lt_hip_overlap_boxes_host takes them: a
+ * scan of the caller's leaves in node order.  Errors as lt_hip_overlap_boxes_host's; a failed call writes nothing. */
+int lt_hip_overlap_tris_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                             const lt_hip_overlap_desc* desc, const lt_hip_tri* tris, uint64_t n, void* out, uint64_t out_bytes);
 
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);

@@ -41,6 +41,7 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_nearest_points", "lt_hip_nearest_points_device", "lt_hip_nearest_points_host",
            "lt_hip_nearest_k", "lt_hip_nearest_k_device", "lt_hip_nearest_k_host",
            "lt_hip_overlap_boxes", "lt_hip_overlap_boxes_device", "lt_hip_overlap_boxes_host",
+           "lt_hip_overlap_tris", "lt_hip_overlap_tris_device", "lt_hip_overlap_tris_host",
            "lt_hip_entry_cut_counts", "lt_hip_entry_cut_test_host",
            "lt_hip_entry_cut_leaf_counts", "lt_hip_entry_cut_triangle_test_host"]
 # (lt_hip_camera_hit_passes returns a uint64_t count, not a status: bound in load() beside these)
@@ -130,6 +131,11 @@ class Box(ctypes.Structure):   # lt_hip_box
     _fields_ = [("lo", ctypes.c_float * 3), ("pad0", ctypes.c_uint32), ("hi", ctypes.c_float * 3), ("pad1", ctypes.c_uint32)]
 
 
+class Tri(ctypes.Structure):   # lt_hip_tri
+    _fields_ = [("a", ctypes.c_float * 3), ("pad0", ctypes.c_uint32), ("b", ctypes.c_float * 3), ("pad1", ctypes.c_uint32),
+                ("c", ctypes.c_float * 3), ("pad2", ctypes.c_uint32)]
+
+
 class OverlapDesc(ctypes.Structure):   # lt_hip_overlap_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("kind", ctypes.c_int32), ("max_k", ctypes.c_uint32)]
 
@@ -177,6 +183,14 @@ def _np_box_dtype():
 
 
 BOX_DTYPE = _np_box_dtype()   # numpy view of lt_hip_box (32 bytes)
+
+
+def _np_tri_dtype():
+    import numpy as np
+    return np.dtype([("a", "<f4", (3,)), ("pad0", "<u4"), ("b", "<f4", (3,)), ("pad1", "<u4"), ("c", "<f4", (3,)), ("pad2", "<u4")])
+
+
+TRI_DTYPE = _np_tri_dtype()   # numpy view of lt_hip_tri (48 bytes)
 
 
 class LensTraceError(RuntimeError):
@@ -252,6 +266,10 @@ def load():
         L.lt_hip_overlap_boxes.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
         L.lt_hip_overlap_boxes_device.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64, vp]
         L.lt_hip_overlap_boxes_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
+    if hasattr(L, "lt_hip_overlap_tris"):
+        L.lt_hip_overlap_tris.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
+        L.lt_hip_overlap_tris_device.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64, vp]
+        L.lt_hip_overlap_tris_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
     if hasattr(L, "lt_hip_camera_hit_passes"):
         L.lt_hip_camera_hit_passes.argtypes = [vp]
         L.lt_hip_camera_hit_passes.restype = u64

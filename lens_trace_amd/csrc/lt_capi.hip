@@ -7,6 +7,7 @@
 #include "lt_query.hpp"
 #include "lt_nearest.hpp"
 #include "lt_overlap.hpp"
+#include "lt_tritri.hpp"
 #include "lt_shade.hpp"
 #include "lt_paths.hpp"
 
@@ -2224,10 +2225,10 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
 }
 
 // ---------------------------------------------------------------------------------- ray queries
-// Nine families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
+// Ten families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
 // lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at (lt_query.hip), lt_hip_shade_rays (lt_shade.hip),
 // lt_hip_shade_paths (lt_paths.hip), lt_hip_nearest_points and lt_hip_nearest_k (lt_nearest.hip), lt_hip_overlap_boxes
-// (lt_overlap.hip).  Every argument error is found before anything is enqueued, so that a failed call writes nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
+// (lt_overlap.hip), lt_hip_overlap_tris (lt_tritri.hip).  Every argument error is found before anything is enqueued, so that a failed call writes nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
 // check_ray_buffers), the course of an entry point with the host form's staging (run_ray_call) and the events and statistics
 // around the launches (begin_ray_launches, end_ray_launches).  A family has its check (the rules about its descriptor, at their
 // place in the order), its launches (enqueue_*) and two one-line entry points.
@@ -2241,6 +2242,7 @@ static_assert(sizeof(lt_hip_nearest_k_desc) == 16 && LT_NEAREST_MAX_K == lt_near
 static_assert(sizeof(lt_hip_box) == 32 && sizeof(lt_hip_overlap_desc) == 16 && LT_OVERLAP_MAX_K == lt_overlap::kMaxK &&
                   LT_OVERLAP_FIRST_K == lt_overlap::kFirstK && LT_OVERLAP_COUNT == lt_overlap::kCount && LT_OVERLAP_ANY == lt_overlap::kAny,
               "box-overlap records (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_tri) == 48, "triangle-overlap records (include/lenstrace_hip.h)");
 
 // What every family's check leaves for its launches: the math flavour (SceneDev: 0 portable, 1 strict, 2 as shipped) and the bytes
 // of one result.
@@ -2259,6 +2261,7 @@ constexpr RayWording kPathsWording{"lt_hip_shade_paths", "rays", "call", "rays"}
 constexpr RayWording kNearestWording{"lt_hip_nearest_points", "points", "call", "points"};
 constexpr RayWording kNearestKWording{"lt_hip_nearest_k", "points", "call", "points"};
 constexpr RayWording kOverlapWording{"lt_hip_overlap_boxes", "boxes", "call", "boxes"};
+constexpr RayWording kOverlapTrisWording{"lt_hip_overlap_tris", "triangles", "call", "tris"};
 
 // The flags of a call: the two math flags and, `coherent`, LT_TRACE_FLAG_COHERENT; `who`: the family's "... take(s)".
 static int check_ray_flags(lt_hip_context* ctx, uint32_t flags, bool coherent, const char* who, RayCall& call) {
@@ -2760,6 +2763,89 @@ extern "C" int lt_hip_overlap_boxes_host(const void* nodes, uint64_t node_bytes,
         const float* p = pr + 19 * (size_t)nd[i].off;
         const float e1[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
         if (!lt_overlap::tri_meets_box(lo, hi, p, e1, e2)) continue;
+        count++;
+        if (maxK) list.offer(nd[i].off);
+        else if (desc->kind == LT_OVERLAP_ANY) break;
+      }
+    }
+    if (maxK) for (uint32_t e = 0; e < maxK; e++) ((int32_t*)out)[j * maxK + e] = list.at(e);
+    else ((uint32_t*)out)[j] = desc->kind == LT_OVERLAP_ANY ? (count != 0 ? 1u : 0u) : count;
+  }
+  return LT_OK;
+}
+
+// lt_hip_overlap_tris*: the primitives each query triangle meets (lt_overlap_tris_kernel).  The descriptor, its rules and their
+// order are lt_hip_overlap_boxes', word for word; the records are 48 bytes, so sizes are (size_t)idx * 48.
+static int check_overlap_tris(lt_hip_context* ctx, const lt_hip_overlap_desc* d, const lt_hip_tri* tris, uint64_t n, const void* out, uint64_t out_bytes,
+                              bool device, OverlapCall& call) {
+  if (const char* why = overlap_desc_error(d)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, why);
+  call.devlibm = 2;
+  call.kind = (uint32_t)d->kind;
+  call.maxK = d->max_k;
+  call.outRecord = d->kind == LT_OVERLAP_FIRST_K ? (uint64_t)d->max_k * sizeof(int32_t) : sizeof(uint32_t);
+  return check_ray_buffers(ctx, kOverlapTrisWording, tris, n, out, out_bytes, device, call);
+}
+
+static int enqueue_overlap_tris(lt_hip_context* ctx, const OverlapCall& call, const void* tris, uint64_t n, void* out, hipStream_t s) {
+  const RenderKnobs k;
+  LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_query_ctl));
+  lt_overlap::Params qp{};
+  qp.boxes = (const float4*)tris;   // three float4 per record
+  qp.out = (uint32_t*)out;
+  qp.n = (uint32_t)n;
+  qp.kind = call.kind;
+  qp.maxK = call.maxK;
+  qp.next = ctx->d_query_ctl;
+  qp.refill = k.trace_refill;
+  const SceneDev sc = scene_dev(ctx, k, call.devlibm);
+  if (const int rc = begin_ray_launches(ctx, &ctx->query_ev, s)) return rc;
+  LT_HIP_CHECK(ctx, lt_tritri::launch(sc, qp, (uint32_t)ctx->cu_count, s));
+  return end_ray_launches(ctx, ctx->query_ev, s, 1, n, 0);
+}
+
+extern "C" int lt_hip_overlap_tris(lt_hip_context* ctx, const lt_hip_overlap_desc* desc, const lt_hip_tri* tris, uint64_t n, void* out,
+                                   uint64_t out_bytes) {
+  return run_ray_call(ctx, desc, tris, n, out, out_bytes, false, nullptr, check_overlap_tris, enqueue_overlap_tris);
+}
+
+extern "C" int lt_hip_overlap_tris_device(lt_hip_context* ctx, const lt_hip_overlap_desc* desc, const lt_hip_tri* tris, uint64_t n, void* out,
+                                          uint64_t out_bytes, void* hip_stream) {
+  return run_ray_call(ctx, desc, tris, n, out, out_bytes, true, hip_stream, check_overlap_tris, enqueue_overlap_tris);
+}
+
+// The same answers without a context or a GPU: lt_hip_overlap_boxes_host's scan of the caller's leaves in node order over
+// lt_tritri.hpp's query_box and tri_meets_tri and lt_overlap.hpp's boxes_meet and KList.
+extern "C" int lt_hip_overlap_tris_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const lt_hip_overlap_desc* desc,
+                                        const lt_hip_tri* tris, uint64_t n, void* out, uint64_t out_bytes) {
+  if (overlap_desc_error(desc)) return LT_ERR_INVALID_ARGUMENT;
+  if (!nodes || !prims || node_bytes == 0 || node_bytes % 32 || node_bytes > 0xffffffffull * 32 || prim_bytes % 76) return LT_ERR_INVALID_ARGUMENT;
+  if (n > 0xffffffffull || (n > 0 && (!tris || !out))) return LT_ERR_INVALID_ARGUMENT;
+  const lt_retree::Node* nd = (const lt_retree::Node*)nodes;
+  const uint64_t n_nodes = node_bytes / 32, n_prims = prim_bytes / 76;
+  for (uint64_t i = 0; i < n_nodes; i++)
+    if (nd[i].cnt != 0 && (nd[i].off < 0 || (uint64_t)nd[i].off >= n_prims)) return LT_ERR_BAD_SCENE;
+  const uint32_t maxK = desc->max_k;
+  if (out_bytes < n * (maxK ? (uint64_t)maxK * sizeof(int32_t) : sizeof(uint32_t))) return LT_ERR_BUFFER_TOO_SMALL;
+  const float* pr = (const float*)prims;
+  using lt_tritri::Vec;
+  for (uint64_t j = 0; j < n; j++) {
+    const Vec P{tris[j].a[0], tris[j].a[1], tris[j].a[2]}, Q{tris[j].b[0], tris[j].b[1], tris[j].b[2]}, R{tris[j].c[0], tris[j].c[1], tris[j].c[2]};
+    int entries[LT_OVERLAP_MAX_K];
+    lt_overlap::KList<1> list{entries, maxK};
+    list.reset();
+    uint32_t count = 0;
+    if (!lt_tritri::empty_tri(P, Q, R)) {
+      float lo[3], hi[3];
+      lt_tritri::query_box(P, Q, R, lo, hi);
+      lt_tritri::Table table;
+      lt_tritri::put_query(table, P, Q, R);
+      for (uint64_t i = 0; i < n_nodes; i++) {
+        if (nd[i].cnt == 0) continue;
+        if (!lt_overlap::boxes_meet(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], nd[i].lo[0], nd[i].lo[1], nd[i].lo[2], nd[i].hi[0], nd[i].hi[1], nd[i].hi[2]))
+          continue;
+        const float* p = pr + 19 * (size_t)nd[i].off;
+        const Vec A{p[0], p[1], p[2]}, e1{p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2{p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+        if (!lt_tritri::tri_meets_tri(table, A, e1, e2)) continue;
         count++;
         if (maxK) list.offer(nd[i].off);
         else if (desc->kind == LT_OVERLAP_ANY) break;

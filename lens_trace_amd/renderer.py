@@ -283,6 +283,50 @@ def overlap_boxes_host(scene: Scene, boxes, k=None, count=False, any=False):
     return out
 
 
+TRI_DTYPE = C.TRI_DTYPE
+
+
+def make_tris(a, b, c):
+    """Packs query triangles for RendererHIP.overlap_tris: (n, 3) vertices a, b, c into an (n, 12) float32 array of lt_hip_tri
+    records (a, pad, b, pad, c, pad; the pads are zero and ignored)."""
+    a = np.asarray(a, dtype=np.float32)
+    b = np.asarray(b, dtype=np.float32)
+    c = np.asarray(c, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 3 or b.shape != a.shape or c.shape != a.shape:
+        raise ValueError("a, b and c must all have shape (n, 3)")
+    out = np.zeros((a.shape[0], 12), dtype=np.float32)
+    out[:, 0:3] = a
+    out[:, 4:7] = b
+    out[:, 8:11] = c
+    return out
+
+
+def tri_records(tris):
+    """A numpy batch of query triangles as a contiguous (n, 12) float32 array of lt_hip_tri records: a 1-D TRI_DTYPE array or an
+    (n, 12) float32 array (make_tris)."""
+    if tris.dtype == TRI_DTYPE and tris.ndim == 1:
+        tris = np.ascontiguousarray(tris).view(np.float32).reshape(-1, 12)
+    if tris.dtype != np.float32 or tris.ndim != 2 or tris.shape[1] != 12:
+        raise ValueError("tris must be an (n, 12) float32 array (make_tris) or a TRI_DTYPE array")
+    return np.ascontiguousarray(tris)
+
+
+def overlap_tris_host(scene: Scene, tris, k=None, count=False, any=False):
+    """lt_hip_overlap_tris_host: RendererHIP.overlap_tris' answers computed on the host from the scene's own buffers, leaf by
+    leaf -- no context, no GPU.  tris as overlap_tris takes numpy batches; returns an (n, k) int32 array or, count / any, (n,)
+    uint32."""
+    d = _overlap_desc(k, count, any)
+    tr = tri_records(np.asarray(tris))
+    nodes, prims = np.ascontiguousarray(scene.nodes), np.ascontiguousarray(scene.prims)
+    out = np.zeros((tr.shape[0], d.max_k), dtype=np.int32) if d.max_k else np.zeros(tr.shape[0], dtype=np.uint32)
+    vp = ctypes.c_void_p
+    rc = C.load().lt_hip_overlap_tris_host(nodes.ctypes.data_as(vp), nodes.nbytes, prims.ctypes.data_as(vp), prims.nbytes, ctypes.byref(d),
+                                           tr.ctypes.data_as(vp), tr.shape[0], out.ctypes.data_as(vp), out.nbytes)
+    if rc:
+        raise C.LensTraceError(rc, "lt_hip_overlap_tris_host failed")
+    return out
+
+
 _QUERY_RAYS = (RAY_DTYPE, ("make_rays", "RAY_DTYPE"))
 _SHADE_RAYS = (SHADE_RAY_DTYPE, ("make_shade_rays", "SHADE_RAY_DTYPE"))
 
@@ -589,6 +633,23 @@ class RendererHIP:
             out = np.zeros((bx.shape[0], d.max_k), dtype=np.int32) if d.max_k else np.zeros(bx.shape[0], dtype=np.uint32)
             return self._host_call("overlap_boxes", d, bx, out)
         return self._device_call("overlap_boxes", d, boxes, "boxes", "n", 8, ("int32", (d.max_k,) if d.max_k else ()), stream)
+
+    # -- triangle-overlap queries ----------------------------------------------------------------------
+    def overlap_tris(self, tris, k=None, count=False, any=False, stream=None):
+        """The primitives each query triangle meets (lt_hip_overlap_tris; include/lenstrace_hip.h defines "touches": the leaf's
+        box meets the triangle's box and none of 17 axes separates the two triangles): the `k` (1..C.OVERLAP_MAX_K, default 4)
+        lowest primitive offsets in ascending order, -1 in unused slots; with count=True how many there are; with any=True 1 or 0.
+        A triangle with a coordinate that is not finite meets nothing; a needle or a point is a valid query.
+        tris: an (n, 12) float32 array of lt_hip_tri records (make_tris) or a TRI_DTYPE array -- then the host entry point runs
+        and numpy comes back: (n, k) int32 or (n,) uint32; or a contiguous (n, 12) float32 torch tensor on this context's GPU --
+        then the call is enqueued on `stream` (default: the current torch stream) and torch comes back: (n, k) int32 or (n,)
+        int32."""
+        d = _overlap_desc(k, count, any)
+        if isinstance(tris, np.ndarray):
+            tr = tri_records(tris)
+            out = np.zeros((tr.shape[0], d.max_k), dtype=np.int32) if d.max_k else np.zeros(tr.shape[0], dtype=np.uint32)
+            return self._host_call("overlap_tris", d, tr, out)
+        return self._device_call("overlap_tris", d, tris, "tris", "n", 12, ("int32", (d.max_k,) if d.max_k else ()), stream)
 
     # -- shaded rays ------------------------------------------------------------------------------------
     def shade_rays(self, rays, program="accumulator", frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR, portable_math=False,
