@@ -277,7 +277,8 @@ int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* out, uint64
  * The walk may follow the backend's own hierarchy: results are the same bit for bit (equal t from two triangles: the
  * reference's first leaf wins).  lens_trace_amd/csrc/lt_query.hip.
  * Streams: the ray, point, box and triangle queries (lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface,
- * lt_hip_nearest_points, lt_hip_nearest_k, lt_hip_overlap_boxes, lt_hip_overlap_tris, host and _device forms) share the context's work counters, so calls of these entry
+ * lt_hip_nearest_points, lt_hip_nearest_k, lt_hip_overlap_boxes, lt_hip_overlap_tris, lt_hip_overlap_boxes_list,
+ * lt_hip_overlap_tris_list, host and _device forms) share the context's work counters, so calls of these entry
  * points are ordered among themselves on any streams (each waits for the one enqueued before it). */
 typedef struct lt_hip_ray { float origin[3]; float tmax; float direction[3]; int32_t ignore; } lt_hip_ray;   /* 32 B, ignore -1 = none */
 typedef struct lt_hip_hit { float t; int32_t prim; float u, v; } lt_hip_hit;   /* 16 B; a miss: prim = -1, t = tmax, u = v = 0 */
@@ -694,6 +695,57 @@ int lt_hip_overlap_tris_device(lt_hip_context* ctx, const lt_hip_overlap_desc* d
  * scan of the caller's leaves in node order.  Errors as lt_hip_overlap_boxes_host's; a failed call writes nothing. */
 int lt_hip_overlap_tris_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
                              const lt_hip_overlap_desc* desc, const lt_hip_tri* tris, uint64_t n, void* out, uint64_t out_bytes);
+
+/* Overlap lists: the WHOLE sequence of every box or query triangle, as CSR -- what a voxeliser, a brick binner or a narrow phase
+ * needs where LT_OVERLAP_FIRST_K stops at eight.  Queries, candidates, "touches" and the sequence are lt_hip_overlap_boxes' and
+ * lt_hip_overlap_tris', word for word.
+ *   offsets   n + 1 uint64: offsets[i] is the sum of the sequence lengths of queries 0 .. i-1 (an exclusive scan: offsets[0] = 0,
+ *             offsets[n] the total).
+ *   items     offsets[n] int32: items[offsets[i] .. offsets[i + 1]) is the sequence of query i -- every touching candidate's
+ *             primitive offset, ascending (then by node index: the words being offsets only, this is the sorted multiset).  An
+ *             empty query has an empty segment.
+ * So the differences of offsets are LT_OVERLAP_COUNT's words and the first eight of a segment LT_OVERLAP_FIRST_K's.
+ * Sizing: items == NULL with items_bytes == 0 writes the offsets only and returns LT_OK.  With items and
+ * items_bytes < 4 offsets[n], NOTHING is written to items, offsets is written in full and valid, and the host-memory forms return
+ * LT_ERR_BUFFER_TOO_SMALL -- the one exception to "a failed call writes nothing".  The device form cannot know and returns LT_OK:
+ * its caller reads offsets[n].
+ * flags: 0, or LT_OVERLAP_LIST_FLAG_FILL_ONLY: offsets is INPUT -- what an earlier call returned for the same scene and records
+ * -- and only items is written, so that a sized-then-filled pair of calls costs two walks of the hierarchy and not three.
+ * Whatever those offsets hold, nothing is written outside items[0 .. items_bytes / 4): query i writes only into
+ * [offsets[i], min(offsets[i + 1], items_bytes / 4)), and a length that would be negative is 0.  With offsets that are not this
+ * batch's own the words are unspecified, but in bounds.
+ * Cost: the count is LT_OVERLAP_COUNT's walk, the fill that walk again; each segment is then sorted by one wavefront, up to 4096
+ * entries in LDS and longer ones in place in device memory -- a segment of a million entries is slow, but correct.
+ * Errors, in lt_hip_overlap_boxes' order: LT_ERR_INVALID_ARGUMENT for a null ctx / desc, struct_size too small, an unknown flag,
+ * n >= 2^32, null records or offsets with n > 0, items == NULL with items_bytes != 0, LT_OVERLAP_LIST_FLAG_FILL_ONLY with
+ * items == NULL (and, device entry point, pointers that are not 16-byte aligned); LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when
+ * offsets_bytes < 8 (n + 1).  Such a call writes nothing.  n == 0 writes offsets[0] = 0 (not with FILL_ONLY) and launches nothing.
+ * lt_hip_get_stats then reports rays = n, kernel_ms and the kernels launched: 4 for the sizing call (walk, three of the scan),
+ * 2 for FILL_ONLY (walk, ordering), 6 for both.  (lens_trace_amd/csrc/lt_overlist.hip) */
+#define LT_OVERLAP_LIST_FLAG_FILL_ONLY 0x1u
+typedef struct lt_hip_overlap_list_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_overlap_list_desc) */
+  uint32_t flags;               /* 0 / LT_OVERLAP_LIST_FLAG_FILL_ONLY */
+} lt_hip_overlap_list_desc;     /* 8 B */
+
+int lt_hip_overlap_boxes_list(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n,
+                              uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_overlap_boxes_list_device(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n,
+                                     uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, void* hip_stream);
+/* The same lists on the host, without a context or a GPU, from the caller's buffers, as lt_hip_overlap_boxes_host takes them: a
+ * scan of the caller's leaves in node order, sorted per query.  Errors as above, with lt_hip_overlap_boxes_host's for the scene
+ * (LT_ERR_BAD_SCENE where the context's entry points have LT_ERR_NO_SCENE). */
+int lt_hip_overlap_boxes_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                                   const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n, uint64_t* offsets,
+                                   uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes);
+int lt_hip_overlap_tris_list(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n,
+                             uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes);
+int lt_hip_overlap_tris_list_device(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n,
+                                    uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, void* hip_stream);
+int lt_hip_overlap_tris_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                                  const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n, uint64_t* offsets,
+                                  uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes);
 
 /* Statistics of the most recent render call or ray query on ctx (waits for it to finish). */
 int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);

@@ -28,6 +28,7 @@ NEAREST_FIRST_K, NEAREST_COUNT = 0, 1   # lt_hip_nearest_k_desc::kind
 NEAREST_MAX_K = 8                    # LT_NEAREST_MAX_K
 OVERLAP_FIRST_K, OVERLAP_COUNT, OVERLAP_ANY = 0, 1, 2   # lt_hip_overlap_desc::kind
 OVERLAP_MAX_K = 8                    # LT_OVERLAP_MAX_K
+OVERLAP_LIST_FLAG_FILL_ONLY = 1      # lt_hip_overlap_list_desc::flags: offsets is input, only items is written
 SURFACE_LIGHT = 1                    # lt_hip_surface::flags: the primitive is in the light list
 
 # every symbol include/lenstrace_hip.h declares
@@ -42,6 +43,8 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_nearest_k", "lt_hip_nearest_k_device", "lt_hip_nearest_k_host",
            "lt_hip_overlap_boxes", "lt_hip_overlap_boxes_device", "lt_hip_overlap_boxes_host",
            "lt_hip_overlap_tris", "lt_hip_overlap_tris_device", "lt_hip_overlap_tris_host",
+           "lt_hip_overlap_boxes_list", "lt_hip_overlap_boxes_list_device", "lt_hip_overlap_boxes_list_host",
+           "lt_hip_overlap_tris_list", "lt_hip_overlap_tris_list_device", "lt_hip_overlap_tris_list_host",
            "lt_hip_entry_cut_counts", "lt_hip_entry_cut_test_host",
            "lt_hip_entry_cut_leaf_counts", "lt_hip_entry_cut_triangle_test_host"]
 # (lt_hip_camera_hit_passes returns a uint64_t count, not a status: bound in load() beside these)
@@ -138,6 +141,10 @@ class Tri(ctypes.Structure):   # lt_hip_tri
 
 class OverlapDesc(ctypes.Structure):   # lt_hip_overlap_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("kind", ctypes.c_int32), ("max_k", ctypes.c_uint32)]
+
+
+class OverlapListDesc(ctypes.Structure):   # lt_hip_overlap_list_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 def _np_dtypes():
@@ -270,6 +277,12 @@ def load():
         L.lt_hip_overlap_tris.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
         L.lt_hip_overlap_tris_device.argtypes = [vp, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64, vp]
         L.lt_hip_overlap_tris_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(OverlapDesc), vp, u64, vp, u64]
+    if hasattr(L, "lt_hip_overlap_boxes_list"):
+        for shape in ("boxes", "tris"):
+            lists = "lt_hip_overlap_%s_list" % shape
+            getattr(L, lists).argtypes = [vp, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64]
+            getattr(L, lists + "_device").argtypes = [vp, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64, vp]
+            getattr(L, lists + "_host").argtypes = [vp, u64, vp, u64, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64]
     if hasattr(L, "lt_hip_camera_hit_passes"):
         L.lt_hip_camera_hit_passes.argtypes = [vp]
         L.lt_hip_camera_hit_passes.restype = u64

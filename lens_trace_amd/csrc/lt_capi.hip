@@ -8,6 +8,7 @@
 #include "lt_nearest.hpp"
 #include "lt_overlap.hpp"
 #include "lt_tritri.hpp"
+#include "lt_overlist.hpp"
 #include "lt_shade.hpp"
 #include "lt_paths.hpp"
 
@@ -372,6 +373,12 @@ struct lt_hip_context {
   void* d_query_out = nullptr;
   uint64_t query_out_bytes = 0;
   hipEvent_t query_ev = nullptr;
+  // overlap lists (lt_overlist.hip): the scan's per-tile sums and, host entry points, the device copy of the items -- the offsets
+  // are staged in d_query_out, which has to outlive the growth of the items between the call's two halves
+  unsigned long long* d_list_partials = nullptr;
+  uint64_t list_partials_words = 0;
+  int32_t* d_list_items = nullptr;
+  uint64_t list_items_words = 0;
   // shaded rays (lt_shade.hip): lt_shade_rays_kernel's own eight work counters and the event behind its last launch, as above
   uint32_t* d_shade_ctl = nullptr;
   hipEvent_t shade_ev = nullptr;
@@ -498,6 +505,8 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_surface_hits) (void)hipFree(ctx->d_surface_hits);
   if (ctx->d_query_out) (void)hipFree(ctx->d_query_out);
   if (ctx->query_ev) (void)hipEventDestroy(ctx->query_ev);
+  if (ctx->d_list_partials) (void)hipFree(ctx->d_list_partials);
+  if (ctx->d_list_items) (void)hipFree(ctx->d_list_items);
   if (ctx->d_shade_ctl) (void)hipFree(ctx->d_shade_ctl);
   if (ctx->shade_ev) (void)hipEventDestroy(ctx->shade_ev);
   if (ctx->d_order) (void)hipFree(ctx->d_order);
@@ -2228,7 +2237,8 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
 // Ten families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
 // lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at (lt_query.hip), lt_hip_shade_rays (lt_shade.hip),
 // lt_hip_shade_paths (lt_paths.hip), lt_hip_nearest_points and lt_hip_nearest_k (lt_nearest.hip), lt_hip_overlap_boxes
-// (lt_overlap.hip), lt_hip_overlap_tris (lt_tritri.hip).  Every argument error is found before anything is enqueued, so that a failed call writes nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
+// (lt_overlap.hip), lt_hip_overlap_tris (lt_tritri.hip).  (The overlap lists, lt_hip_overlap_boxes_list and lt_hip_overlap_tris_list
+// -- lt_overlist.hip --, have two result buffers and a course of their own: run_list_call, behind the triangle queries.)  Every argument error is found before anything is enqueued, so that a failed call writes nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
 // check_ray_buffers), the course of an entry point with the host form's staging (run_ray_call) and the events and statistics
 // around the launches (begin_ray_launches, end_ray_launches).  A family has its check (the rules about its descriptor, at their
 // place in the order), its launches (enqueue_*) and two one-line entry points.
@@ -2734,6 +2744,24 @@ extern "C" int lt_hip_overlap_boxes_device(lt_hip_context* ctx, const lt_hip_ove
   return run_ray_call(ctx, desc, boxes, n, out, out_bytes, true, hip_stream, check_overlap, enqueue_overlap);
 }
 
+// The scan behind the host forms: f(offset) for every leaf of the caller's array that touches the box, in node order, until f
+// returns false.
+template <class F>
+static void for_touching_box(const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_box& box, F&& f) {
+  const float* lo = box.lo;
+  const float* hi = box.hi;
+  if (lt_overlap::empty_box(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2])) return;
+  for (uint64_t i = 0; i < n_nodes; i++) {
+    if (nd[i].cnt == 0) continue;
+    if (!lt_overlap::boxes_meet(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], nd[i].lo[0], nd[i].lo[1], nd[i].lo[2], nd[i].hi[0], nd[i].hi[1], nd[i].hi[2]))
+      continue;
+    const float* p = pr + 19 * (size_t)nd[i].off;
+    const float e1[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+    if (!lt_overlap::tri_meets_box(lo, hi, p, e1, e2)) continue;
+    if (!f(nd[i].off)) return;
+  }
+}
+
 // The same answers without a context or a GPU: lt_hip_nearest_k_host's scan of the caller's leaves in node order over
 // lt_overlap.hpp's boxes_meet, tri_meets_box and KList.
 extern "C" int lt_hip_overlap_boxes_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const lt_hip_overlap_desc* desc,
@@ -2747,27 +2775,16 @@ extern "C" int lt_hip_overlap_boxes_host(const void* nodes, uint64_t node_bytes,
     if (nd[i].cnt != 0 && (nd[i].off < 0 || (uint64_t)nd[i].off >= n_prims)) return LT_ERR_BAD_SCENE;
   const uint32_t maxK = desc->max_k;
   if (out_bytes < n * (maxK ? (uint64_t)maxK * sizeof(int32_t) : sizeof(uint32_t))) return LT_ERR_BUFFER_TOO_SMALL;
-  const float* pr = (const float*)prims;
   for (uint64_t j = 0; j < n; j++) {
-    const float* lo = boxes[j].lo;
-    const float* hi = boxes[j].hi;
     int entries[LT_OVERLAP_MAX_K];
     lt_overlap::KList<1> list{entries, maxK};
     list.reset();
     uint32_t count = 0;
-    if (!lt_overlap::empty_box(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2])) {
-      for (uint64_t i = 0; i < n_nodes; i++) {
-        if (nd[i].cnt == 0) continue;
-        if (!lt_overlap::boxes_meet(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], nd[i].lo[0], nd[i].lo[1], nd[i].lo[2], nd[i].hi[0], nd[i].hi[1], nd[i].hi[2]))
-          continue;
-        const float* p = pr + 19 * (size_t)nd[i].off;
-        const float e1[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
-        if (!lt_overlap::tri_meets_box(lo, hi, p, e1, e2)) continue;
-        count++;
-        if (maxK) list.offer(nd[i].off);
-        else if (desc->kind == LT_OVERLAP_ANY) break;
-      }
-    }
+    for_touching_box(nd, n_nodes, (const float*)prims, boxes[j], [&](int32_t off) {
+      count++;
+      if (maxK) list.offer(off);
+      return maxK != 0 || desc->kind != LT_OVERLAP_ANY;
+    });
     if (maxK) for (uint32_t e = 0; e < maxK; e++) ((int32_t*)out)[j * maxK + e] = list.at(e);
     else ((uint32_t*)out)[j] = desc->kind == LT_OVERLAP_ANY ? (count != 0 ? 1u : 0u) : count;
   }
@@ -2813,6 +2830,27 @@ extern "C" int lt_hip_overlap_tris_device(lt_hip_context* ctx, const lt_hip_over
   return run_ray_call(ctx, desc, tris, n, out, out_bytes, true, hip_stream, check_overlap_tris, enqueue_overlap_tris);
 }
 
+// lt_hip_overlap_tris_host's scan, as for_touching_box: f(offset) for every leaf that touches the query triangle, in node order.
+template <class F>
+static void for_touching_tri(const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_tri& tri, F&& f) {
+  using lt_tritri::Vec;
+  const Vec P{tri.a[0], tri.a[1], tri.a[2]}, Q{tri.b[0], tri.b[1], tri.b[2]}, R{tri.c[0], tri.c[1], tri.c[2]};
+  if (lt_tritri::empty_tri(P, Q, R)) return;
+  float lo[3], hi[3];
+  lt_tritri::query_box(P, Q, R, lo, hi);
+  lt_tritri::Table table;
+  lt_tritri::put_query(table, P, Q, R);
+  for (uint64_t i = 0; i < n_nodes; i++) {
+    if (nd[i].cnt == 0) continue;
+    if (!lt_overlap::boxes_meet(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], nd[i].lo[0], nd[i].lo[1], nd[i].lo[2], nd[i].hi[0], nd[i].hi[1], nd[i].hi[2]))
+      continue;
+    const float* p = pr + 19 * (size_t)nd[i].off;
+    const Vec A{p[0], p[1], p[2]}, e1{p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2{p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+    if (!lt_tritri::tri_meets_tri(table, A, e1, e2)) continue;
+    if (!f(nd[i].off)) return;
+  }
+}
+
 // The same answers without a context or a GPU: lt_hip_overlap_boxes_host's scan of the caller's leaves in node order over
 // lt_tritri.hpp's query_box and tri_meets_tri and lt_overlap.hpp's boxes_meet and KList.
 extern "C" int lt_hip_overlap_tris_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const lt_hip_overlap_desc* desc,
@@ -2826,35 +2864,228 @@ extern "C" int lt_hip_overlap_tris_host(const void* nodes, uint64_t node_bytes, 
     if (nd[i].cnt != 0 && (nd[i].off < 0 || (uint64_t)nd[i].off >= n_prims)) return LT_ERR_BAD_SCENE;
   const uint32_t maxK = desc->max_k;
   if (out_bytes < n * (maxK ? (uint64_t)maxK * sizeof(int32_t) : sizeof(uint32_t))) return LT_ERR_BUFFER_TOO_SMALL;
-  const float* pr = (const float*)prims;
-  using lt_tritri::Vec;
   for (uint64_t j = 0; j < n; j++) {
-    const Vec P{tris[j].a[0], tris[j].a[1], tris[j].a[2]}, Q{tris[j].b[0], tris[j].b[1], tris[j].b[2]}, R{tris[j].c[0], tris[j].c[1], tris[j].c[2]};
     int entries[LT_OVERLAP_MAX_K];
     lt_overlap::KList<1> list{entries, maxK};
     list.reset();
     uint32_t count = 0;
-    if (!lt_tritri::empty_tri(P, Q, R)) {
-      float lo[3], hi[3];
-      lt_tritri::query_box(P, Q, R, lo, hi);
-      lt_tritri::Table table;
-      lt_tritri::put_query(table, P, Q, R);
-      for (uint64_t i = 0; i < n_nodes; i++) {
-        if (nd[i].cnt == 0) continue;
-        if (!lt_overlap::boxes_meet(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], nd[i].lo[0], nd[i].lo[1], nd[i].lo[2], nd[i].hi[0], nd[i].hi[1], nd[i].hi[2]))
-          continue;
-        const float* p = pr + 19 * (size_t)nd[i].off;
-        const Vec A{p[0], p[1], p[2]}, e1{p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2{p[6] - p[0], p[7] - p[1], p[8] - p[2]};
-        if (!lt_tritri::tri_meets_tri(table, A, e1, e2)) continue;
-        count++;
-        if (maxK) list.offer(nd[i].off);
-        else if (desc->kind == LT_OVERLAP_ANY) break;
-      }
-    }
+    for_touching_tri(nd, n_nodes, (const float*)prims, tris[j], [&](int32_t off) {
+      count++;
+      if (maxK) list.offer(off);
+      return maxK != 0 || desc->kind != LT_OVERLAP_ANY;
+    });
     if (maxK) for (uint32_t e = 0; e < maxK; e++) ((int32_t*)out)[j * maxK + e] = list.at(e);
     else ((uint32_t*)out)[j] = desc->kind == LT_OVERLAP_ANY ? (count != 0 ? 1u : 0u) : count;
   }
   return LT_OK;
+}
+
+// ---------------------------------------------------------------------------------- overlap lists
+// lt_hip_overlap_boxes_list* and lt_hip_overlap_tris_list*: the whole sequence of every query as CSR (lt_overlist.hpp) -- the
+// family's walk with kCountWide into offsets, the scan, the walk again with kList into items, the ordering.  A sibling of
+// run_ray_call: the results are two buffers and the second one's size is known only after the scan, so the host form runs in
+// two halves with a look at offsets[n] between them.  The work counters are the ray queries' (ctx->query_ev).
+static_assert(sizeof(lt_hip_overlap_list_desc) == 8, "overlap-list descriptor (include/lenstrace_hip.h)");
+
+using ListWalk = hipError_t (*)(const SceneDev&, const lt_overlap::Params&, uint32_t, hipStream_t);
+
+static const char* overlap_list_desc_error(const lt_hip_overlap_list_desc* d) {
+  if (!d) return "overlap lists: desc is NULL";
+  if (d->struct_size < sizeof(lt_hip_overlap_list_desc)) return "bad lt_hip_overlap_list_desc (struct_size)";
+  if (d->flags & ~LT_OVERLAP_LIST_FLAG_FILL_ONLY) return "overlap lists take LT_OVERLAP_LIST_FLAG_FILL_ONLY only";
+  return nullptr;
+}
+
+// The rules about the records and the two buffers that the context's entry points and the host forms share, in their order.
+static const char* overlap_list_buffers_error(const lt_hip_overlap_list_desc* d, const void* in, uint64_t n, const void* offsets, const void* items,
+                                              uint64_t items_bytes) {
+  if (n > 0xffffffffull) return "at most 2^32 - 1 queries per call";
+  if (n > 0 && (!in || !offsets)) return "the records or offsets are NULL";
+  if (!items && items_bytes != 0) return "items is NULL and items_bytes is not 0";
+  if ((d->flags & LT_OVERLAP_LIST_FLAG_FILL_ONLY) && !items) return "LT_OVERLAP_LIST_FLAG_FILL_ONLY takes items";
+  return nullptr;
+}
+
+// One half of a call, or both, on `s`, over device memory: `sized` runs the count and the scan, `fill` the fill and the ordering
+// over `capacity` words of items (`oneShot`: behind this stream's own scan, and nothing is written when its total is larger).
+static int enqueue_overlap_list(lt_hip_context* ctx, ListWalk walk, const void* records, uint64_t n, uint64_t* offsets, int32_t* items,
+                                uint64_t capacity, bool sized, bool fill, bool oneShot, hipStream_t s) {
+  const RenderKnobs k;
+  LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_query_ctl));
+  if (sized) {
+    const uint64_t words = lt_overlist::scan_partials(n);
+    LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_list_partials, ctx->list_partials_words, words, words * sizeof(uint64_t)));
+  }
+  lt_overlap::Params qp{};
+  qp.boxes = (const float4*)records;
+  qp.n = (uint32_t)n;
+  qp.next = ctx->d_query_ctl;
+  qp.refill = k.trace_refill;
+  const SceneDev sc = scene_dev(ctx, k, 2);
+  if (const int rc = begin_ray_launches(ctx, &ctx->query_ev, s)) return rc;
+  uint32_t launches = 0;
+  if (sized) {
+    qp.kind = lt_overlap::kCountWide;
+    qp.out = (uint32_t*)offsets;
+    LT_HIP_CHECK(ctx, walk(sc, qp, (uint32_t)ctx->cu_count, s));
+    LT_HIP_CHECK(ctx, lt_overlist::scan((unsigned long long*)offsets, (uint32_t)n, ctx->d_list_partials, s));
+    launches += 1 + lt_overlist::kScanLaunches;
+  }
+  if (fill) {
+    qp.kind = lt_overlap::kList;
+    qp.out = nullptr;
+    qp.offsets = (const unsigned long long*)offsets;
+    qp.items = items;
+    qp.capacity = capacity;
+    qp.oneShot = oneShot ? 1u : 0u;
+    LT_HIP_CHECK(ctx, walk(sc, qp, (uint32_t)ctx->cu_count, s));
+    LT_HIP_CHECK(ctx, lt_overlist::order(qp.offsets, qp.n, items, capacity, oneShot, (uint32_t)ctx->cu_count, s));
+    launches += 1 + lt_overlist::kOrderLaunches;
+  }
+  return end_ray_launches(ctx, ctx->query_ev, s, launches, n, 0);
+}
+
+template <class Record>
+static int run_list_call(lt_hip_context* ctx, const RayWording& w, ListWalk walk, const lt_hip_overlap_list_desc* desc, const Record* in, uint64_t n,
+                         uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, bool device, void* hip_stream) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  if (const char* why = overlap_list_desc_error(desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, why);
+  if (const char* why = overlap_list_buffers_error(desc, in, n, offsets, items, items_bytes))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(w.call) + "_list: " + why);
+  if (device && n > 0 && (((uintptr_t)in | (uintptr_t)offsets | (uintptr_t)items) & 15u))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("device ") + w.in + ", offsets and items must be 16-byte aligned");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, std::string(w.call) + "_list before lt_hip_set_scene");
+  if (offsets_bytes < (n + 1) * sizeof(uint64_t)) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "offsets is smaller than n + 1 words");
+  const bool fillOnly = (desc->flags & LT_OVERLAP_LIST_FLAG_FILL_ONLY) != 0;
+  const uint64_t capacity = items_bytes / sizeof(int32_t);
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (n == 0) {
+    if (fillOnly || !offsets) return LT_OK;
+    if (device) LT_HIP_CHECK(ctx, hipMemsetAsync(offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
+    else offsets[0] = 0;
+    return LT_OK;
+  }
+  if (device) return enqueue_overlap_list(ctx, walk, in, n, offsets, items, capacity, !fillOnly, items != nullptr, !fillOnly, (hipStream_t)hip_stream);
+  // The host form: the records and the offsets in the two staging buffers of the ray families, the items in a buffer of their own
+  // -- growing a buffer frees what it held, and the offsets have to outlive the growth of the items.
+  const uint64_t inBytes = n * sizeof(Record), offBytes = (n + 1) * sizeof(uint64_t);
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_rays, ctx->query_rays_bytes, inBytes, inBytes));
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_query_out, ctx->query_out_bytes, offBytes, offBytes));
+  uint64_t* const dOffsets = (uint64_t*)ctx->d_query_out;
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_query_rays, in, inBytes, hipMemcpyHostToDevice, ctx->stream));
+  uint64_t total = 0;
+  float sizedMs = 0.0f;
+  uint32_t sizedLaunches = 0;
+  if (fillOnly) {
+    LT_HIP_CHECK(ctx, hipMemcpyAsync(dOffsets, offsets, offBytes, hipMemcpyHostToDevice, ctx->stream));
+    total = offsets[n] < capacity ? offsets[n] : capacity;   // the words that can be written at all
+  } else {
+    if (const int rc = enqueue_overlap_list(ctx, walk, ctx->d_query_rays, n, dOffsets, nullptr, 0, true, false, false, ctx->stream)) return rc;
+    LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_pending(ctx)) return rc;
+    sizedMs = ctx->last.kernel_ms;
+    sizedLaunches = ctx->last.kernel_launches;
+    LT_HIP_CHECK(ctx, hipMemcpy(offsets, dOffsets, offBytes, hipMemcpyDeviceToHost));
+    total = offsets[n];
+    if (!items) return LT_OK;
+    if (capacity < total) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "items is smaller than offsets[n] words (offsets is written)");
+  }
+  if (total == 0) return LT_OK;
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_list_items, ctx->list_items_words, total, total * sizeof(int32_t)));
+  if (const int rc = enqueue_overlap_list(ctx, walk, ctx->d_query_rays, n, dOffsets, ctx->d_list_items, total, false, true, false, ctx->stream)) return rc;
+  LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (const int rc = finish_pending(ctx)) return rc;
+  ctx->last.kernel_ms += sizedMs;
+  ctx->last.kernel_launches += sizedLaunches;
+  LT_HIP_CHECK(ctx, hipMemcpy(items, ctx->d_list_items, total * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+extern "C" int lt_hip_overlap_boxes_list(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n,
+                                         uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes) {
+  return run_list_call(ctx, kOverlapWording, lt_overlap::launch, desc, boxes, n, offsets, offsets_bytes, items, items_bytes, false, nullptr);
+}
+
+extern "C" int lt_hip_overlap_boxes_list_device(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n,
+                                                uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, void* hip_stream) {
+  return run_list_call(ctx, kOverlapWording, lt_overlap::launch, desc, boxes, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream);
+}
+
+extern "C" int lt_hip_overlap_tris_list(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n,
+                                        uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes) {
+  return run_list_call(ctx, kOverlapTrisWording, lt_tritri::launch, desc, tris, n, offsets, offsets_bytes, items, items_bytes, false, nullptr);
+}
+
+extern "C" int lt_hip_overlap_tris_list_device(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n,
+                                               uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, void* hip_stream) {
+  return run_list_call(ctx, kOverlapTrisWording, lt_tritri::launch, desc, tris, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream);
+}
+
+// The same lists without a context or a GPU: the host forms' scan of the caller's leaves in node order (`each`: for_touching_box or
+// for_touching_tri), then std::sort per query.  LT_ERR_BAD_SCENE stands where the context's entry points have LT_ERR_NO_SCENE.
+template <class Record, class Each>
+static int overlap_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const lt_hip_overlap_list_desc* desc,
+                             const Record* in, uint64_t n, uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, Each each) {
+  if (overlap_list_desc_error(desc)) return LT_ERR_INVALID_ARGUMENT;
+  if (!nodes || !prims || node_bytes == 0 || node_bytes % 32 || node_bytes > 0xffffffffull * 32 || prim_bytes % 76) return LT_ERR_INVALID_ARGUMENT;
+  if (overlap_list_buffers_error(desc, in, n, offsets, items, items_bytes)) return LT_ERR_INVALID_ARGUMENT;
+  const lt_retree::Node* nd = (const lt_retree::Node*)nodes;
+  const uint64_t n_nodes = node_bytes / 32, n_prims = prim_bytes / 76;
+  for (uint64_t i = 0; i < n_nodes; i++)
+    if (nd[i].cnt != 0 && (nd[i].off < 0 || (uint64_t)nd[i].off >= n_prims)) return LT_ERR_BAD_SCENE;
+  if (offsets_bytes < (n + 1) * sizeof(uint64_t)) return LT_ERR_BUFFER_TOO_SMALL;
+  const bool fillOnly = (desc->flags & LT_OVERLAP_LIST_FLAG_FILL_ONLY) != 0;
+  const uint64_t capacity = items_bytes / sizeof(int32_t);
+  std::vector<int32_t> seq, all;
+  const auto sequence = [&](uint64_t j) {
+    seq.clear();
+    each(nd, n_nodes, (const float*)prims, in[j], [&](int32_t off) { seq.push_back(off); return true; });
+    std::sort(seq.begin(), seq.end());
+  };
+  if (fillOnly) {   // query j's words go to [offsets[j], min(offsets[j + 1], capacity)), whatever the offsets hold
+    for (uint64_t j = 0; j < n; j++) {
+      const uint64_t begin = offsets[j], end = offsets[j + 1] < capacity ? offsets[j + 1] : capacity;
+      if (end <= begin) continue;
+      sequence(j);
+      const uint64_t room = end - begin;
+      std::copy(seq.begin(), seq.begin() + (size_t)(room < seq.size() ? room : seq.size()), items + begin);
+    }
+    return LT_OK;
+  }
+  if (n == 0) {
+    if (offsets) offsets[0] = 0;
+    return LT_OK;
+  }
+  uint64_t total = 0;
+  for (uint64_t j = 0; j < n; j++) {
+    sequence(j);
+    offsets[j] = total;
+    total += seq.size();
+    if (items && total <= capacity) all.insert(all.end(), seq.begin(), seq.end());
+  }
+  offsets[n] = total;
+  if (!items) return LT_OK;
+  if (capacity < total) return LT_ERR_BUFFER_TOO_SMALL;
+  std::copy(all.begin(), all.end(), items);
+  return LT_OK;
+}
+
+extern "C" int lt_hip_overlap_boxes_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                                              const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n, uint64_t* offsets,
+                                              uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes) {
+  return overlap_list_host(nodes, node_bytes, prims, prim_bytes, desc, boxes, n, offsets, offsets_bytes, items, items_bytes,
+                           [](const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_box& q, auto&& f) {
+                             for_touching_box(nd, n_nodes, pr, q, f);
+                           });
+}
+
+extern "C" int lt_hip_overlap_tris_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                                             const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n, uint64_t* offsets,
+                                             uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes) {
+  return overlap_list_host(nodes, node_bytes, prims, prim_bytes, desc, tris, n, offsets, offsets_bytes, items, items_bytes,
+                           [](const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_tri& q, auto&& f) {
+                             for_touching_tri(nd, n_nodes, pr, q, f);
+                           });
 }
 
 // lt_hip_shade_rays*: the colour a program's `shade` returns for caller-supplied rays (lt_shade.hip).

@@ -2,7 +2,8 @@
 // lt_hip_overlap_boxes_device.  For each box: the candidates (a leaf of the caller's tree with its one primitive) that touch it --
 // the leaf's own box meets the box and the traversal triangle passes the 13-axis test, both as lt_overlap.hpp defines them -- as
 // the first K primitive offsets in ascending order, as their number, or as "any".  The answer is a function of the scene and
-// the box alone and the walk only has to find it.
+// the box alone and the walk only has to find it.  The overlap lists (lt_overlist.hpp) run the same kernels with two more sinks:
+// the number as uint64 (kCountWide) and every offset into the box's segment of a CSR array (kList).
 //
 // The walk is depth-first over the per-lane walks' records (SceneDev::wide): a group's four child slots are put back on the grid
 // (slot_box) and the ones that meet the box go on the lane's stack, links only.  A leaf record holds the triangle, the leaf's own
@@ -23,37 +24,8 @@ constexpr int kOvStage = 7;         // rows of staged boxes (lo.xyz, hi.xyz, ind
 struct Grid { float O[3], S[3]; };   // the 16-bit grid of the group slots (wide[-2], wide[-1])
 struct Box { float lo[3], hi[3]; };
 
-// What takes a box's touching candidates.  kCount and kAny count in a register (kAny's walk ends at the first).  kFirstK keeps the
-// K smallest offsets in the lane's column of LDS rows and the list's last entry in a register: once the list is full, an offset
-// that is not below that entry never touches LDS.
-template <int KIND>
-struct Sink {
-  lt_overlap::KList<kBlock> list;
-  int32_t last;    // kFirstK: the list's last entry (-1: not full)
-  uint32_t n;
-  __device__ __forceinline__ void reset() {
-    n = 0u;
-    if (KIND == lt_overlap::kFirstK) { list.reset(); last = -1; }
-  }
-  __device__ __forceinline__ void touch(int32_t p) {
-    n++;
-    if (KIND == lt_overlap::kFirstK) {
-      if (last >= 0 && p >= last) return;
-      list.offer(p);
-      last = list.at(list.k - 1u);
-    }
-  }
-};
-
-template <int KIND>
-__device__ __forceinline__ void put_overlap(const lt_overlap::Params& qp, uint32_t idx, const Sink<KIND>& sink) {
-  if (KIND == lt_overlap::kFirstK) {
-    int32_t* out = (int32_t*)qp.out + (size_t)idx * qp.maxK;
-    for (uint32_t j = 0; j < sink.list.k; j++) out[j] = sink.list.at(j);
-  } else {
-    qp.out[idx] = KIND == lt_overlap::kAny ? (sink.n != 0u ? 1u : 0u) : sink.n;
-  }
-}
+using lt_overlap::Sink;          // what takes a box's touching candidates (lt_overlap.hpp)
+using lt_overlap::put_overlap;
 
 // Whether the candidate of a leaf -- its own box, its traversal triangle -- touches q.
 __device__ __forceinline__ bool leaf_touches(const Box& q, float ax, float ay, float az, float e1x, float e1y, float e1z, float e2x, float e2y, float e2z,
@@ -133,6 +105,7 @@ template <int KIND>
 __global__ __launch_bounds__(kBlock, 8) void lt_overlap_kernel(SceneDev sc, lt_overlap::Params qp) {
   using u64 = unsigned long long;
   extern __shared__ int lds_stack[];   // [kOvEntries stack rows][kOvStage rows of staged boxes][maxK list rows], 64 lanes each
+  if (lt_overlap::list_overflows<KIND>(qp)) return;
   int* const col = lds_stack + threadIdx.x;
   int* const stage = lds_stack + kOvEntries * kBlock;
   const uint32_t total = qp.n;
@@ -185,7 +158,7 @@ __global__ __launch_bounds__(kBlock, 8) void lt_overlap_kernel(SceneDev sc, lt_o
         idx = (uint32_t)stage[6 * kBlock + s];
         q.lo[0] = __int_as_float(stage[0 * kBlock + s]); q.lo[1] = __int_as_float(stage[1 * kBlock + s]); q.lo[2] = __int_as_float(stage[2 * kBlock + s]);
         q.hi[0] = __int_as_float(stage[3 * kBlock + s]); q.hi[1] = __int_as_float(stage[4 * kBlock + s]); q.hi[2] = __int_as_float(stage[5 * kBlock + s]);
-        sink.reset();
+        sink.reset(qp, idx);
         if (lt_overlap::empty_box(q.lo[0], q.lo[1], q.lo[2], q.hi[0], q.hi[1], q.hi[2])) {
           put_overlap(qp, idx, sink);
         } else {
@@ -216,11 +189,12 @@ __global__ __launch_bounds__(kBlock, 8) void lt_overlap_kernel(SceneDev sc, lt_o
 template <int KIND>
 __global__ __launch_bounds__(kBlock, 8) void lt_overlap_scan_kernel(SceneDev sc, lt_overlap::Params qp) {
   extern __shared__ int lds_stack[];   // [maxK list rows], 64 lanes each
+  if (lt_overlap::list_overflows<KIND>(qp)) return;
   Sink<KIND> sink{{lds_stack + threadIdx.x, KIND == lt_overlap::kFirstK ? qp.maxK : 0u}, -1, 0u};
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < qp.n; i += (uint64_t)gridDim.x * kBlock) {
     const float4 a = qp.boxes[2 * (size_t)i], b = qp.boxes[2 * (size_t)i + 1];
     const Box q{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
-    sink.reset();
+    sink.reset(qp, (uint32_t)i);
     if (!lt_overlap::empty_box(q.lo[0], q.lo[1], q.lo[2], q.hi[0], q.hi[1], q.hi[2])) overlap_scan(sc, q, sink);
     put_overlap(qp, (uint32_t)i, sink);
   }
@@ -230,7 +204,7 @@ namespace lt_overlap {
 
 hipError_t launch(const SceneDev& sc, const Params& p, uint32_t cuCount, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  if (p.kind > (uint32_t)kAny || p.maxK > kMaxK || (p.kind == (uint32_t)kFirstK) != (p.maxK != 0u)) return hipErrorInvalidValue;
+  if (p.kind > (uint32_t)kCountWide || p.maxK > kMaxK || (p.kind == (uint32_t)kFirstK) != (p.maxK != 0u)) return hipErrorInvalidValue;
   const hipError_t e = hipMemsetAsync(p.next, 0, 8 * kQueueStride * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   const uint32_t chunks = (uint32_t)(((uint64_t)p.n + kBlock - 1) / kBlock);
@@ -245,11 +219,15 @@ hipError_t launch(const SceneDev& sc, const Params& p, uint32_t cuCount, hipStre
     const uint32_t list = p.maxK * kBlock * (uint32_t)sizeof(int);
     if (p.kind == (uint32_t)kFirstK) hipLaunchKernelGGL((lt_overlap_scan_kernel<kFirstK>), all, dim3(kBlock), list, s, sc, p);
     else if (p.kind == (uint32_t)kCount) hipLaunchKernelGGL((lt_overlap_scan_kernel<kCount>), all, dim3(kBlock), list, s, sc, p);
+    else if (p.kind == (uint32_t)kList) hipLaunchKernelGGL((lt_overlap_scan_kernel<kList>), all, dim3(kBlock), list, s, sc, p);
+    else if (p.kind == (uint32_t)kCountWide) hipLaunchKernelGGL((lt_overlap_scan_kernel<kCountWide>), all, dim3(kBlock), list, s, sc, p);
     else hipLaunchKernelGGL((lt_overlap_scan_kernel<kAny>), all, dim3(kBlock), list, s, sc, p);
     return hipGetLastError();
   }
   if (p.kind == (uint32_t)kFirstK) hipLaunchKernelGGL((lt_overlap_kernel<kFirstK>), grid, dim3(kBlock), bytes, s, sc, p);
   else if (p.kind == (uint32_t)kCount) hipLaunchKernelGGL((lt_overlap_kernel<kCount>), grid, dim3(kBlock), bytes, s, sc, p);
+  else if (p.kind == (uint32_t)kList) hipLaunchKernelGGL((lt_overlap_kernel<kList>), grid, dim3(kBlock), bytes, s, sc, p);
+  else if (p.kind == (uint32_t)kCountWide) hipLaunchKernelGGL((lt_overlap_kernel<kCountWide>), grid, dim3(kBlock), bytes, s, sc, p);
   else hipLaunchKernelGGL((lt_overlap_kernel<kAny>), grid, dim3(kBlock), bytes, s, sc, p);
   return hipGetLastError();
 }

@@ -165,10 +165,13 @@ struct KList {
 
 namespace lt_overlap {
 
-enum Kind { kFirstK = 0, kCount = 1, kAny = 2 };   // LT_OVERLAP_FIRST_K, LT_OVERLAP_COUNT, LT_OVERLAP_ANY
+// LT_OVERLAP_FIRST_K, LT_OVERLAP_COUNT, LT_OVERLAP_ANY, and the two kinds of the overlap lists (lt_overlist.hpp), which no
+// descriptor names: kList, the whole sequence into the query's segment of `items`; kCountWide, kCount as one uint64 per query.
+enum Kind { kFirstK = 0, kCount = 1, kAny = 2, kList = 3, kCountWide = 4 };
 
 // The caller's records as the kernel reads them: 32 bytes per box (lo.xyz, pad, hi.xyz, pad) -- lt_hip_box -- and per box maxK
-// int32 offsets (kFirstK) or one uint32 (kCount, kAny).
+// int32 offsets (kFirstK), one uint32 (kCount, kAny) or one uint64 (kCountWide).  kList writes nothing to `out`: query i's
+// touching offsets go, in walk order, to items[offsets[i] .. min(offsets[i + 1], capacity)) and whatever is beyond that is dropped.
 struct Params {
   const float4* boxes;
   uint32_t* out;
@@ -177,7 +180,66 @@ struct Params {
   uint32_t maxK;      // kFirstK: 1 .. kMaxK; else 0
   uint32_t* next;     // the work counters: eight, kQueueStride dwords apart, zeroed by launch() on the call's stream
   uint32_t refill;    // idle lanes that make a wave take new boxes
+  uint32_t oneShot;   // kList: the offsets are this stream's own scan -- when offsets[n] > capacity the launch writes nothing
+  const unsigned long long* offsets;   // kList: n + 1 words
+  int32_t* items;                      // kList: `capacity` words
+  unsigned long long capacity;
 };
+
+// What takes a query's touching candidates, for the box and the triangle kernels alike.  kCount, kCountWide and kAny count in a
+// register (kAny's walk ends at the first).  kFirstK keeps the K smallest offsets in the lane's column of LDS rows and the list's
+// last entry in a register: once the list is full, an offset that is not below that entry never touches LDS.  kList stores each
+// offset behind the last in the query's segment while words are left of it: a pointer and the words left, no LDS rows.
+template <int KIND>
+struct Sink {
+  KList<lt::kBlock> list;
+  int32_t last;    // kFirstK: the list's last entry (-1: not full)
+  uint32_t n;      // kList: the words left of the segment
+  int32_t* at;     // kList: where the next offset goes
+  // The lane takes query idx.  kList: the clamped bounds -- a length that would be negative is 0, so with any offsets at all no
+  // store falls outside items[0 .. capacity).
+  __device__ __forceinline__ void reset(const Params& qp, uint32_t idx) {
+    n = 0u;
+    if (KIND == kFirstK) { list.reset(); last = -1; }
+    if (KIND == kList) {
+      const unsigned long long begin = qp.offsets[idx], to = qp.offsets[(size_t)idx + 1];
+      const unsigned long long end = to < qp.capacity ? to : qp.capacity;
+      const unsigned long long room = end > begin ? end - begin : 0ull;
+      n = room > 0xffffffffull ? 0xffffffffu : (uint32_t)room;
+      at = qp.items + begin;   // (never dereferenced when n == 0)
+    }
+  }
+  __device__ __forceinline__ void touch(int32_t p) {
+    if (KIND == kList) {
+      if (n != 0u) { *at++ = p; n--; }
+      return;
+    }
+    n++;
+    if (KIND == kFirstK) {
+      if (last >= 0 && p >= last) return;
+      list.offer(p);
+      last = list.at(list.k - 1u);
+    }
+  }
+};
+
+template <int KIND>
+__device__ __forceinline__ void put_overlap(const Params& qp, uint32_t idx, const Sink<KIND>& sink) {
+  if (KIND == kFirstK) {
+    int32_t* out = (int32_t*)qp.out + (size_t)idx * qp.maxK;
+    for (uint32_t j = 0; j < sink.list.k; j++) out[j] = sink.list.at(j);
+  } else if (KIND == kCountWide) {
+    ((unsigned long long*)qp.out)[idx] = sink.n;
+  } else if (KIND != kList) {
+    qp.out[idx] = KIND == kAny ? (sink.n != 0u ? 1u : 0u) : sink.n;
+  }
+}
+
+// kList in its one-shot form: whether the launch has to write nothing (every lane reads the same word).
+template <int KIND>
+__device__ __forceinline__ bool list_overflows(const Params& qp) {
+  return KIND == kList && qp.oneShot != 0u && qp.offsets[qp.n] > qp.capacity;
+}
 
 // Enqueues lt_overlap_kernel<kind> on `s`.  Returns the first HIP error.
 hipError_t launch(const lt::SceneDev& sc, const Params& p, uint32_t cuCount, hipStream_t s);

@@ -2,7 +2,8 @@
 // lt_hip_overlap_tris_device.  For each query triangle: the candidates (a leaf of the caller's tree with its one primitive) that
 // touch it -- the leaf's own box meets the query's box and none of the 17 axes of lt_tritri.hpp separates the two triangles --
 // as the first K primitive offsets in ascending order, as their number, or as "any".  The answer is a function of the scene and
-// the query alone and the walk only has to find it.
+// the query alone and the walk only has to find it.  The overlap lists (lt_overlist.hpp) run the same kernels with the sinks
+// kCountWide and kList of lt_overlap.hpp.
 //
 // The walk is lt_overlap_kernel's (lt_overlap.hip): depth-first over the per-lane walks' records, a group's four child slots put
 // back on the grid (slot_box) and tested against the query's box with boxes_meet, links only on the stack.  Nothing is dropped
@@ -46,36 +47,8 @@ struct Query {
   }
 };
 
-// lt_overlap.hip's sink: kCount and kAny count in a register, kFirstK keeps the K smallest offsets in the lane's column of LDS rows
-// and the list's last entry in a register.
-template <int KIND>
-struct Sink {
-  lt_overlap::KList<kBlock> list;
-  int32_t last;    // kFirstK: the list's last entry (-1: not full)
-  uint32_t n;
-  __device__ __forceinline__ void reset() {
-    n = 0u;
-    if (KIND == lt_overlap::kFirstK) { list.reset(); last = -1; }
-  }
-  __device__ __forceinline__ void touch(int32_t p) {
-    n++;
-    if (KIND == lt_overlap::kFirstK) {
-      if (last >= 0 && p >= last) return;
-      list.offer(p);
-      last = list.at(list.k - 1u);
-    }
-  }
-};
-
-template <int KIND>
-__device__ __forceinline__ void put_overlap(const lt_overlap::Params& qp, uint32_t idx, const Sink<KIND>& sink) {
-  if (KIND == lt_overlap::kFirstK) {
-    int32_t* out = (int32_t*)qp.out + (size_t)idx * qp.maxK;
-    for (uint32_t j = 0; j < sink.list.k; j++) out[j] = sink.list.at(j);
-  } else {
-    qp.out[idx] = KIND == lt_overlap::kAny ? (sink.n != 0u ? 1u : 0u) : sink.n;
-  }
-}
+using lt_overlap::Sink;          // what takes a query's touching candidates (lt_overlap.hpp)
+using lt_overlap::put_overlap;
 
 __device__ __forceinline__ bool meets_query_box(const Query& q, float blx, float bly, float blz, float bhx, float bhy, float bhz) {
   return lt_overlap::boxes_meet(q.lo[0], q.lo[1], q.lo[2], q.hi[0], q.hi[1], q.hi[2], blx, bly, blz, bhx, bhy, bhz);
@@ -155,6 +128,7 @@ template <int KIND>
 __global__ __launch_bounds__(kBlock, 8) void lt_overlap_tris_kernel(SceneDev sc, lt_overlap::Params qp) {
   using u64 = unsigned long long;
   extern __shared__ int lds_stack[];   // [kTtEntries stack rows][kTtQuery rows of the test's operands][maxK list rows], 64 lanes each
+  if (lt_overlap::list_overflows<KIND>(qp)) return;
   int* const col = lds_stack + threadIdx.x;
   const uint32_t total = qp.n;
   const uint32_t lane = threadIdx.x;
@@ -196,7 +170,7 @@ __global__ __launch_bounds__(kBlock, 8) void lt_overlap_tris_kernel(SceneDev sc,
       const uint32_t mine = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));   // idle lanes below this one
       if (!active && mine < take) {
         idx = stageBase + stageTaken + mine;
-        sink.reset();
+        sink.reset(qp, idx);
         if (!q.take(qp.boxes + 3 * (size_t)idx)) {
           put_overlap(qp, idx, sink);
         } else {
@@ -226,10 +200,11 @@ __global__ __launch_bounds__(kBlock, 8) void lt_overlap_tris_kernel(SceneDev sc,
 template <int KIND>
 __global__ __launch_bounds__(kBlock, 8) void lt_overlap_tris_scan_kernel(SceneDev sc, lt_overlap::Params qp) {
   extern __shared__ int lds_stack[];   // [kTtQuery rows of the test's operands][maxK list rows], 64 lanes each
+  if (lt_overlap::list_overflows<KIND>(qp)) return;
   Query q{{}, {}, lds_stack + threadIdx.x};
   Sink<KIND> sink{{lds_stack + kTtQuery * kBlock + threadIdx.x, KIND == lt_overlap::kFirstK ? qp.maxK : 0u}, -1, 0u};
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < qp.n; i += (uint64_t)gridDim.x * kBlock) {
-    sink.reset();
+    sink.reset(qp, (uint32_t)i);
     if (q.take(qp.boxes + 3 * (size_t)i)) tris_scan(sc, q, sink);
     put_overlap(qp, (uint32_t)i, sink);
   }
@@ -239,11 +214,13 @@ namespace lt_tritri {
 
 using lt_overlap::kAny;
 using lt_overlap::kCount;
+using lt_overlap::kCountWide;
 using lt_overlap::kFirstK;
+using lt_overlap::kList;
 
 hipError_t launch(const SceneDev& sc, const lt_overlap::Params& p, uint32_t cuCount, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  if (p.kind > (uint32_t)kAny || p.maxK > lt_overlap::kMaxK || (p.kind == (uint32_t)kFirstK) != (p.maxK != 0u)) return hipErrorInvalidValue;
+  if (p.kind > (uint32_t)kCountWide || p.maxK > lt_overlap::kMaxK || (p.kind == (uint32_t)kFirstK) != (p.maxK != 0u)) return hipErrorInvalidValue;
   const hipError_t e = hipMemsetAsync(p.next, 0, 8 * kQueueStride * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   const uint32_t chunks = (uint32_t)(((uint64_t)p.n + kBlock - 1) / kBlock);
@@ -258,11 +235,15 @@ hipError_t launch(const SceneDev& sc, const lt_overlap::Params& p, uint32_t cuCo
     const uint32_t list = ((uint32_t)kTtQuery + p.maxK) * kBlock * (uint32_t)sizeof(int);
     if (p.kind == (uint32_t)kFirstK) hipLaunchKernelGGL((lt_overlap_tris_scan_kernel<kFirstK>), all, dim3(kBlock), list, s, sc, p);
     else if (p.kind == (uint32_t)kCount) hipLaunchKernelGGL((lt_overlap_tris_scan_kernel<kCount>), all, dim3(kBlock), list, s, sc, p);
+    else if (p.kind == (uint32_t)kList) hipLaunchKernelGGL((lt_overlap_tris_scan_kernel<kList>), all, dim3(kBlock), list, s, sc, p);
+    else if (p.kind == (uint32_t)kCountWide) hipLaunchKernelGGL((lt_overlap_tris_scan_kernel<kCountWide>), all, dim3(kBlock), list, s, sc, p);
     else hipLaunchKernelGGL((lt_overlap_tris_scan_kernel<kAny>), all, dim3(kBlock), list, s, sc, p);
     return hipGetLastError();
   }
   if (p.kind == (uint32_t)kFirstK) hipLaunchKernelGGL((lt_overlap_tris_kernel<kFirstK>), grid, dim3(kBlock), bytes, s, sc, p);
   else if (p.kind == (uint32_t)kCount) hipLaunchKernelGGL((lt_overlap_tris_kernel<kCount>), grid, dim3(kBlock), bytes, s, sc, p);
+  else if (p.kind == (uint32_t)kList) hipLaunchKernelGGL((lt_overlap_tris_kernel<kList>), grid, dim3(kBlock), bytes, s, sc, p);
+  else if (p.kind == (uint32_t)kCountWide) hipLaunchKernelGGL((lt_overlap_tris_kernel<kCountWide>), grid, dim3(kBlock), bytes, s, sc, p);
   else hipLaunchKernelGGL((lt_overlap_tris_kernel<kAny>), grid, dim3(kBlock), bytes, s, sc, p);
   return hipGetLastError();
 }

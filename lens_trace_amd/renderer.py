@@ -327,6 +327,37 @@ def overlap_tris_host(scene: Scene, tris, k=None, count=False, any=False):
     return out
 
 
+def _overlap_list_host(name, scene, rec):
+    """lt_hip_<name>_list_host over a contiguous numpy array of records: the sizing call, then the fill."""
+    nodes, prims = np.ascontiguousarray(scene.nodes), np.ascontiguousarray(scene.prims)
+    vp = ctypes.c_void_p
+    f = getattr(C.load(), "lt_hip_%s_list_host" % name)
+    size = ctypes.sizeof(C.OverlapListDesc)
+    offsets = np.zeros(rec.shape[0] + 1, dtype=np.uint64)
+    items = np.zeros(0, dtype=np.int32)
+    for flags in (0, C.OVERLAP_LIST_FLAG_FILL_ONLY):
+        d = C.OverlapListDesc(size, flags)
+        rc = f(nodes.ctypes.data_as(vp), nodes.nbytes, prims.ctypes.data_as(vp), prims.nbytes, ctypes.byref(d), rec.ctypes.data_as(vp), rec.shape[0],
+               offsets.ctypes.data_as(vp), offsets.nbytes, items.ctypes.data_as(vp) if flags else None, items.nbytes)
+        if rc:
+            raise C.LensTraceError(rc, "lt_hip_%s_list_host failed" % name)
+        if not flags:
+            items = np.zeros(int(offsets[-1]), dtype=np.int32)
+    return offsets, items
+
+
+def overlap_boxes_list_host(scene: Scene, boxes):
+    """lt_hip_overlap_boxes_list_host: RendererHIP.overlap_boxes_list's (offsets, items) computed on the host from the scene's own
+    buffers, leaf by leaf -- no context, no GPU."""
+    return _overlap_list_host("overlap_boxes", scene, box_records(np.asarray(boxes)))
+
+
+def overlap_tris_list_host(scene: Scene, tris):
+    """lt_hip_overlap_tris_list_host: RendererHIP.overlap_tris_list's (offsets, items) computed on the host, as
+    overlap_boxes_list_host."""
+    return _overlap_list_host("overlap_tris", scene, tri_records(np.asarray(tris)))
+
+
 _QUERY_RAYS = (RAY_DTYPE, ("make_rays", "RAY_DTYPE"))
 _SHADE_RAYS = (SHADE_RAY_DTYPE, ("make_shade_rays", "SHADE_RAY_DTYPE"))
 
@@ -650,6 +681,61 @@ class RendererHIP:
             out = np.zeros((tr.shape[0], d.max_k), dtype=np.int32) if d.max_k else np.zeros(tr.shape[0], dtype=np.uint32)
             return self._host_call("overlap_tris", d, tr, out)
         return self._device_call("overlap_tris", d, tris, "tris", "n", 12, ("int32", (d.max_k,) if d.max_k else ()), stream)
+
+    # -- overlap lists ----------------------------------------------------------------------------------
+    def _overlap_list(self, name, records, numpy_records, what, width, stream):
+        """lt_hip_<name>_list: numpy in, the host entry point sized and then filled; a torch tensor in, the device entry point --
+        the sizing call, one .item() for the total, the items allocated, the LT_OVERLAP_LIST_FLAG_FILL_ONLY call."""
+        vp = ctypes.c_void_p
+        size = ctypes.sizeof(C.OverlapListDesc)
+        sizing, fill = C.OverlapListDesc(size, 0), C.OverlapListDesc(size, C.OVERLAP_LIST_FLAG_FILL_ONLY)
+        if isinstance(records, np.ndarray):
+            rec = numpy_records(records)
+            f = getattr(self._L, "lt_hip_%s_list" % name)
+            offsets = np.zeros(rec.shape[0] + 1, dtype=np.uint64)
+            self._check(f(self._ctx, ctypes.byref(sizing), rec.ctypes.data_as(vp), rec.shape[0], offsets.ctypes.data_as(vp), offsets.nbytes, None, 0))
+            items = np.zeros(int(offsets[-1]), dtype=np.int32)
+            if len(items):
+                self._check(f(self._ctx, ctypes.byref(fill), rec.ctypes.data_as(vp), rec.shape[0], offsets.ctypes.data_as(vp), offsets.nbytes,
+                              items.ctypes.data_as(vp), items.nbytes))
+            return offsets, items
+        import torch
+        if not isinstance(records, torch.Tensor):
+            raise TypeError("%s must be a numpy array or a torch tensor" % what)
+        if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != width or not records.is_contiguous():
+            raise ValueError("%s must be a contiguous (n, %d) float32 tensor" % (what, width))
+        dev = torch.device("cuda", self.device)
+        if records.device != dev:
+            raise ValueError("%s must be on %s, the context's device" % (what, dev))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        if not hasattr(stream, "cuda_stream"):
+            stream = torch.cuda.ExternalStream(int(stream), device=dev)
+        handle = stream.cuda_stream
+        f = getattr(self._L, "lt_hip_%s_list_device" % name)
+        n = records.shape[0]
+        with torch.cuda.stream(stream):     # (the total is read on the stream the sizing call runs on)
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)     # (uint64 words: torch has no arithmetic on them)
+            self._check(f(self._ctx, ctypes.byref(sizing), vp(records.data_ptr()), n, vp(offsets.data_ptr()), 8 * (n + 1), None, 0, vp(handle)))
+            total = int(offsets[-1].item())
+            items = torch.empty(total, dtype=torch.int32, device=dev)
+            if total:
+                self._check(f(self._ctx, ctypes.byref(fill), vp(records.data_ptr()), n, vp(offsets.data_ptr()), 8 * (n + 1),
+                              vp(items.data_ptr()), 4 * total, vp(handle)))
+        return offsets, items
+
+    def overlap_boxes_list(self, boxes, stream=None):
+        """Every primitive each box touches, as CSR (lt_hip_overlap_boxes_list): (offsets, items) with items[offsets[i] :
+        offsets[i + 1]] the whole sequence of box i -- overlap_boxes' offsets, ascending, without the limit of eight.  boxes as
+        overlap_boxes takes them: numpy in gives numpy, offsets uint64 (n + 1,) and items int32 (total,); a torch tensor on this
+        context's GPU gives tensors, offsets as int64, after the sizing call, one read of the total and the fill call on `stream`
+        (default: the current torch stream)."""
+        return self._overlap_list("overlap_boxes", boxes, box_records, "boxes", 8, stream)
+
+    def overlap_tris_list(self, tris, stream=None):
+        """Every primitive each query triangle meets, as CSR (lt_hip_overlap_tris_list): overlap_boxes_list's (offsets, items)
+        for tris as overlap_tris takes them."""
+        return self._overlap_list("overlap_tris", tris, tri_records, "tris", 12, stream)
 
     # -- shaded rays ------------------------------------------------------------------------------------
     def shade_rays(self, rays, program="accumulator", frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR, portable_math=False,
