@@ -277,8 +277,8 @@ int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* out, uint64
  * The walk may follow the backend's own hierarchy: results are the same bit for bit (equal t from two triangles: the
  * reference's first leaf wins).  lens_trace_amd/csrc/lt_query.hip.
  * Streams: the ray, point, box and triangle queries (lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface,
- * lt_hip_nearest_points, lt_hip_nearest_k, lt_hip_overlap_boxes, lt_hip_overlap_tris, lt_hip_overlap_boxes_list,
- * lt_hip_overlap_tris_list, host and _device forms) share the context's work counters, so calls of these entry
+ * lt_hip_nearest_points, lt_hip_nearest_k, lt_hip_nearest_list, lt_hip_overlap_boxes, lt_hip_overlap_tris,
+ * lt_hip_overlap_boxes_list, lt_hip_overlap_tris_list, host and _device forms) share the context's work counters, so calls of these entry
  * points are ordered among themselves on any streams (each waits for the one enqueued before it). */
 typedef struct lt_hip_ray { float origin[3]; float tmax; float direction[3]; int32_t ignore; } lt_hip_ray;   /* 32 B, ignore -1 = none */
 typedef struct lt_hip_hit { float t; int32_t prim; float u, v; } lt_hip_hit;   /* 16 B; a miss: prim = -1, t = tmax, u = v = 0 */
@@ -576,6 +576,48 @@ int lt_hip_nearest_k_device(lt_hip_context* ctx, const lt_hip_nearest_k_desc* de
  * LT_ERR_BAD_SCENE (a leaf whose offset lies outside prims), LT_ERR_BUFFER_TOO_SMALL; a failed call writes nothing. */
 int lt_hip_nearest_k_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
                           const lt_hip_nearest_k_desc* desc, const lt_hip_point* points, uint64_t n, void* out, uint64_t out_bytes);
+
+/* Radius lists: the WHOLE candidate sequence of every point, as CSR -- every primitive within the point's radius where
+ * LT_NEAREST_FIRST_K stops at eight: the whole contact set of a clearance check, every surface within a tolerance for
+ * registration, the neighbours an irradiance or sample cache gathers over, proximity-based occlusion.  Candidates, d2, (u, v),
+ * acceptance (d2 < max_d2 by the float `<`), the empty sequence of a point that takes no walk, and the order are
+ * lt_hip_nearest_k's, word for word: d2 ascending, then primitive offset, then node index.
+ *   offsets   n + 1 uint64: offsets[i] is the sum of the sequence lengths of points 0 .. i-1 (an exclusive scan: offsets[0] = 0,
+ *             offsets[n] the total).
+ *   items     offsets[n] lt_hip_hit records of 16 bytes, {t = d2, prim, u, v}: items[offsets[i] .. offsets[i + 1]) is the whole
+ *             sequence of point i.  Every record feeds lt_hip_surface_at as it is.  (Two records of one point with equal d2 and
+ *             equal offset come from the same arithmetic on the same operands and are bit-identical, so the multiset sorted by
+ *             (d2, offset) is the sequence: the third key, the node index, orders records that cannot be told apart.  Accepted
+ *             d2 are never NaN.)
+ * So the differences of offsets are LT_NEAREST_COUNT's words and the first eight records of a segment LT_NEAREST_FIRST_K's real
+ * records, bit for bit.
+ * Sizing, items that are too small, LT_NEAREST_LIST_FLAG_FILL_ONLY, the errors and their order, n == 0 and the statistics are
+ * lt_hip_overlap_boxes_list's (below) with 4 bytes per item replaced by 16: items == NULL with items_bytes == 0 writes the offsets
+ * only; with items_bytes < 16 offsets[n] nothing is written to items, offsets is written in full, the host-memory form returns
+ * LT_ERR_BUFFER_TOO_SMALL and the device form LT_OK; with FILL_ONLY offsets is input and, whatever it holds, point i writes only
+ * into items[offsets[i] .. min(offsets[i + 1], items_bytes / 16)), a length that would be negative being 0; the device entry
+ * point takes pointers that are 16-byte aligned; lt_hip_get_stats reports rays = n and 4 / 2 / 6 kernels launched.
+ * Cost: the count is LT_NEAREST_COUNT's walk, the fill that walk again; each segment is then sorted by one wavefront, up to 1024
+ * records in LDS and longer ones in place in device memory.  max_d2 = inf accepts every finite d2, which makes the call a visit
+ * of every leaf for every point and a segment of every leaf: give a finite radius.
+ * (lens_trace_amd/csrc/lt_nearest.hip, lt_overlist.hip) */
+#define LT_NEAREST_LIST_FLAG_FILL_ONLY 0x1u
+typedef struct lt_hip_nearest_list_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_nearest_list_desc) */
+  uint32_t flags;               /* 0 / LT_NEAREST_LIST_FLAG_FILL_ONLY */
+} lt_hip_nearest_list_desc;     /* 8 B */
+
+int lt_hip_nearest_list(lt_hip_context* ctx, const lt_hip_nearest_list_desc* desc, const lt_hip_point* points, uint64_t n,
+                        uint64_t* offsets, uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_nearest_list_device(lt_hip_context* ctx, const lt_hip_nearest_list_desc* desc, const lt_hip_point* points, uint64_t n,
+                               uint64_t* offsets, uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes, void* hip_stream);
+/* The same lists on the host, without a context or a GPU, from the caller's buffers, as lt_hip_nearest_k_host takes them: a scan
+ * of the caller's leaves in node order, then a stable sort of each segment by (d2, offset).  Errors as above, with
+ * lt_hip_nearest_k_host's for the scene (LT_ERR_BAD_SCENE where the context's entry points have LT_ERR_NO_SCENE). */
+int lt_hip_nearest_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                             const lt_hip_nearest_list_desc* desc, const lt_hip_point* points, uint64_t n, uint64_t* offsets,
+                             uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes);
 
 /* Box-overlap queries: the primitives an axis-aligned box touches, their number, or whether there is any -- for voxelisers and
  * occupancy grids, the broad phase of a collision check against a volume, region selection, binning a scene into bricks.

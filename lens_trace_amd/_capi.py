@@ -29,6 +29,7 @@ NEAREST_MAX_K = 8                    # LT_NEAREST_MAX_K
 OVERLAP_FIRST_K, OVERLAP_COUNT, OVERLAP_ANY = 0, 1, 2   # lt_hip_overlap_desc::kind
 OVERLAP_MAX_K = 8                    # LT_OVERLAP_MAX_K
 OVERLAP_LIST_FLAG_FILL_ONLY = 1      # lt_hip_overlap_list_desc::flags: offsets is input, only items is written
+NEAREST_LIST_FLAG_FILL_ONLY = 1      # lt_hip_nearest_list_desc::flags: the same
 SURFACE_LIGHT = 1                    # lt_hip_surface::flags: the primitive is in the light list
 
 # every symbol include/lenstrace_hip.h declares
@@ -41,6 +42,7 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_trace_surface", "lt_hip_trace_surface_device", "lt_hip_surface_at", "lt_hip_surface_at_device",
            "lt_hip_nearest_points", "lt_hip_nearest_points_device", "lt_hip_nearest_points_host",
            "lt_hip_nearest_k", "lt_hip_nearest_k_device", "lt_hip_nearest_k_host",
+           "lt_hip_nearest_list", "lt_hip_nearest_list_device", "lt_hip_nearest_list_host",
            "lt_hip_overlap_boxes", "lt_hip_overlap_boxes_device", "lt_hip_overlap_boxes_host",
            "lt_hip_overlap_tris", "lt_hip_overlap_tris_device", "lt_hip_overlap_tris_host",
            "lt_hip_overlap_boxes_list", "lt_hip_overlap_boxes_list_device", "lt_hip_overlap_boxes_list_host",
@@ -144,6 +146,10 @@ class OverlapDesc(ctypes.Structure):   # lt_hip_overlap_desc
 
 
 class OverlapListDesc(ctypes.Structure):   # lt_hip_overlap_list_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class NearestListDesc(ctypes.Structure):   # lt_hip_nearest_list_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
@@ -283,6 +289,10 @@ def load():
             getattr(L, lists).argtypes = [vp, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64]
             getattr(L, lists + "_device").argtypes = [vp, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64, vp]
             getattr(L, lists + "_host").argtypes = [vp, u64, vp, u64, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64]
+    if hasattr(L, "lt_hip_nearest_list"):
+        L.lt_hip_nearest_list.argtypes = [vp, ctypes.POINTER(NearestListDesc), vp, u64, vp, u64, vp, u64]
+        L.lt_hip_nearest_list_device.argtypes = [vp, ctypes.POINTER(NearestListDesc), vp, u64, vp, u64, vp, u64, vp]
+        L.lt_hip_nearest_list_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(NearestListDesc), vp, u64, vp, u64, vp, u64]
     if hasattr(L, "lt_hip_camera_hit_passes"):
         L.lt_hip_camera_hit_passes.argtypes = [vp]
         L.lt_hip_camera_hit_passes.restype = u64

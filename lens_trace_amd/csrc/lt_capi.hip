@@ -377,8 +377,8 @@ struct lt_hip_context {
   // are staged in d_query_out, which has to outlive the growth of the items between the call's two halves
   unsigned long long* d_list_partials = nullptr;
   uint64_t list_partials_words = 0;
-  int32_t* d_list_items = nullptr;
-  uint64_t list_items_words = 0;
+  void* d_list_items = nullptr;
+  uint64_t list_items_bytes = 0;
   // shaded rays (lt_shade.hip): lt_shade_rays_kernel's own eight work counters and the event behind its last launch, as above
   uint32_t* d_shade_ctl = nullptr;
   hipEvent_t shade_ev = nullptr;
@@ -2237,8 +2237,8 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
 // Ten families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
 // lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at (lt_query.hip), lt_hip_shade_rays (lt_shade.hip),
 // lt_hip_shade_paths (lt_paths.hip), lt_hip_nearest_points and lt_hip_nearest_k (lt_nearest.hip), lt_hip_overlap_boxes
-// (lt_overlap.hip), lt_hip_overlap_tris (lt_tritri.hip).  (The overlap lists, lt_hip_overlap_boxes_list and lt_hip_overlap_tris_list
-// -- lt_overlist.hip --, have two result buffers and a course of their own: run_list_call, behind the triangle queries.)  Every argument error is found before anything is enqueued, so that a failed call writes nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
+// (lt_overlap.hip), lt_hip_overlap_tris (lt_tritri.hip).  (The lists, lt_hip_overlap_boxes_list, lt_hip_overlap_tris_list and
+// lt_hip_nearest_list -- lt_overlist.hip --, have two result buffers and a course of their own: run_list_call, behind the triangle queries.)  Every argument error is found before anything is enqueued, so that a failed call writes nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
 // check_ray_buffers), the course of an entry point with the host form's staging (run_ray_call) and the events and statistics
 // around the launches (begin_ray_launches, end_ray_launches).  A family has its check (the rules about its descriptor, at their
 // place in the order), its launches (enqueue_*) and two one-line entry points.
@@ -2248,7 +2248,9 @@ static_assert(sizeof(lt_hip_surface) == 48 && sizeof(lt_hip_surface_desc) == 8, 
 static_assert(sizeof(lt_hip_shade_ray) == 32 && sizeof(lt_hip_shade) == 16 && sizeof(lt_hip_shade_desc) == 24, "shaded-ray records (include/lenstrace_hip.h)");
 static_assert(sizeof(lt_hip_paths_desc) == 32, "path-shading descriptor (include/lenstrace_hip.h)");
 static_assert(sizeof(lt_hip_point) == 16 && sizeof(lt_hip_nearest_desc) == 8, "nearest-point records (include/lenstrace_hip.h)");
-static_assert(sizeof(lt_hip_nearest_k_desc) == 16 && LT_NEAREST_MAX_K == lt_nearest::kMaxK, "k-nearest records (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_nearest_k_desc) == 16 && LT_NEAREST_MAX_K == lt_nearest::kMaxK && LT_NEAREST_FIRST_K == lt_nearest::kFirstK &&
+                  LT_NEAREST_COUNT == lt_nearest::kCount,
+              "k-nearest records (include/lenstrace_hip.h)");
 static_assert(sizeof(lt_hip_box) == 32 && sizeof(lt_hip_overlap_desc) == 16 && LT_OVERLAP_MAX_K == lt_overlap::kMaxK &&
                   LT_OVERLAP_FIRST_K == lt_overlap::kFirstK && LT_OVERLAP_COUNT == lt_overlap::kCount && LT_OVERLAP_ANY == lt_overlap::kAny,
               "box-overlap records (include/lenstrace_hip.h)");
@@ -2623,6 +2625,7 @@ static int enqueue_nearest_k(lt_hip_context* ctx, const NearestKCall& call, cons
   qp.counts = call.maxK ? nullptr : (uint32_t*)out;
   qp.n = (uint32_t)n;
   qp.maxK = call.maxK;
+  qp.kind = call.maxK ? lt_nearest::kFirstK : lt_nearest::kCount;
   qp.next = ctx->d_query_ctl;
   qp.refill = k.trace_refill;
   const SceneDev sc = scene_dev(ctx, k, call.devlibm);
@@ -2880,84 +2883,152 @@ extern "C" int lt_hip_overlap_tris_host(const void* nodes, uint64_t node_bytes, 
   return LT_OK;
 }
 
-// ---------------------------------------------------------------------------------- overlap lists
-// lt_hip_overlap_boxes_list* and lt_hip_overlap_tris_list*: the whole sequence of every query as CSR (lt_overlist.hpp) -- the
-// family's walk with kCountWide into offsets, the scan, the walk again with kList into items, the ordering.  A sibling of
-// run_ray_call: the results are two buffers and the second one's size is known only after the scan, so the host form runs in
-// two halves with a look at offsets[n] between them.  The work counters are the ray queries' (ctx->query_ev).
+// ---------------------------------------------------------------------------------- lists
+// lt_hip_overlap_boxes_list*, lt_hip_overlap_tris_list* and lt_hip_nearest_list*: the whole sequence of every query as CSR
+// (lt_overlist.hpp) -- the family's walk with its kCountWide into offsets, the scan, the walk again with its kList into items, the
+// ordering.  A sibling of run_ray_call: the results are two buffers and the second one's size is known only after the scan, so
+// the host form runs in two halves with a look at offsets[n] between them.  The work counters are the ray queries'
+// (ctx->query_ev).  What the three families share is written once -- the descriptor's and the buffers' rules, the course, the
+// staging; a family is a ListFamily: its nouns, the bytes of an item and its two walks.
 static_assert(sizeof(lt_hip_overlap_list_desc) == 8, "overlap-list descriptor (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_nearest_list_desc) == 8 && LT_NEAREST_LIST_FLAG_FILL_ONLY == LT_OVERLAP_LIST_FLAG_FILL_ONLY,
+              "radius-list descriptor (include/lenstrace_hip.h)");
+constexpr uint32_t kListFillOnly = LT_OVERLAP_LIST_FLAG_FILL_ONLY;
 
-using ListWalk = hipError_t (*)(const SceneDev&, const lt_overlap::Params&, uint32_t, hipStream_t);
+// One walk of a list call over device memory: the count into `offsets` (fill == false), or the fill of `items` and its ordering.
+struct ListPass {
+  const void* records;
+  uint32_t n;
+  uint32_t* next;
+  uint32_t refill;
+  bool fill, oneShot;
+  unsigned long long* offsets;
+  void* items;
+  unsigned long long capacity;   // items
+};
+using ListWalk = hipError_t (*)(const SceneDev&, const ListPass&, uint32_t, hipStream_t);
 
-static const char* overlap_list_desc_error(const lt_hip_overlap_list_desc* d) {
-  if (!d) return "overlap lists: desc is NULL";
-  if (d->struct_size < sizeof(lt_hip_overlap_list_desc)) return "bad lt_hip_overlap_list_desc (struct_size)";
-  if (d->flags & ~LT_OVERLAP_LIST_FLAG_FILL_ONLY) return "overlap lists take LT_OVERLAP_LIST_FLAG_FILL_ONLY only";
-  return nullptr;
+struct ListFamily {
+  const char *lists, *desc, *fillOnly;   // the nouns of the error texts: "overlap lists", the descriptor's and the flag's name
+  const char* call;                      // the entry point
+  const char* in;                        // the input pointer
+  const char* items;                     // what items holds: "words", "records"
+  uint64_t itemBytes;
+  ListWalk walk;
+};
+
+using OverlapLaunch = hipError_t (*)(const SceneDev&, const lt_overlap::Params&, uint32_t, hipStream_t);
+template <OverlapLaunch LAUNCH>
+static hipError_t overlap_list_walk(const SceneDev& sc, const ListPass& p, uint32_t cuCount, hipStream_t s) {
+  lt_overlap::Params qp{};
+  qp.boxes = (const float4*)p.records;
+  qp.n = p.n;
+  qp.next = p.next;
+  qp.refill = p.refill;
+  if (!p.fill) {
+    qp.kind = lt_overlap::kCountWide;
+    qp.out = (uint32_t*)p.offsets;
+    return LAUNCH(sc, qp, cuCount, s);
+  }
+  qp.kind = lt_overlap::kList;
+  qp.offsets = p.offsets;
+  qp.items = (int32_t*)p.items;
+  qp.capacity = p.capacity;
+  qp.oneShot = p.oneShot ? 1u : 0u;
+  const hipError_t e = LAUNCH(sc, qp, cuCount, s);
+  return e != hipSuccess ? e : lt_overlist::order(p.offsets, p.n, qp.items, p.capacity, p.oneShot, cuCount, s);
+}
+
+static hipError_t nearest_list_walk(const SceneDev& sc, const ListPass& p, uint32_t cuCount, hipStream_t s) {
+  lt_nearest::KParams qp{};
+  qp.points = (const float4*)p.records;
+  qp.n = p.n;
+  qp.next = p.next;
+  qp.refill = p.refill;
+  qp.offsets = p.offsets;
+  if (!p.fill) {
+    qp.kind = lt_nearest::kCountWide;
+    return lt_nearest::launch_k(sc, qp, cuCount, s);
+  }
+  qp.kind = lt_nearest::kList;
+  qp.items = (uint4*)p.items;
+  qp.capacity = p.capacity;
+  qp.oneShot = p.oneShot ? 1u : 0u;
+  const hipError_t e = lt_nearest::launch_k(sc, qp, cuCount, s);
+  return e != hipSuccess ? e : lt_overlist::order_hits(p.offsets, p.n, qp.items, p.capacity, p.oneShot, cuCount, s);
+}
+
+constexpr ListFamily kOverlapBoxesList{"overlap lists", "lt_hip_overlap_list_desc", "LT_OVERLAP_LIST_FLAG_FILL_ONLY", "lt_hip_overlap_boxes_list",
+                                       "boxes", "words", sizeof(int32_t), overlap_list_walk<lt_overlap::launch>};
+constexpr ListFamily kOverlapTrisList{"overlap lists", "lt_hip_overlap_list_desc", "LT_OVERLAP_LIST_FLAG_FILL_ONLY", "lt_hip_overlap_tris_list",
+                                      "tris", "words", sizeof(int32_t), overlap_list_walk<lt_tritri::launch>};
+constexpr ListFamily kNearestList{"radius lists", "lt_hip_nearest_list_desc", "LT_NEAREST_LIST_FLAG_FILL_ONLY", "lt_hip_nearest_list",
+                                  "points", "records", sizeof(lt_hip_hit), nearest_list_walk};
+
+// The descriptor's rules -- the two descriptors are the same two words --; empty when it passes.
+template <class Desc>
+static std::string list_desc_error(const ListFamily& f, const Desc* d) {
+  if (!d) return std::string(f.lists) + ": desc is NULL";
+  if (d->struct_size < sizeof(Desc)) return std::string("bad ") + f.desc + " (struct_size)";
+  if (d->flags & ~kListFillOnly) return std::string(f.lists) + " take " + f.fillOnly + " only";
+  return std::string();
 }
 
 // The rules about the records and the two buffers that the context's entry points and the host forms share, in their order.
-static const char* overlap_list_buffers_error(const lt_hip_overlap_list_desc* d, const void* in, uint64_t n, const void* offsets, const void* items,
-                                              uint64_t items_bytes) {
+static std::string list_buffers_error(const ListFamily& f, uint32_t flags, const void* in, uint64_t n, const void* offsets, const void* items,
+                                      uint64_t items_bytes) {
   if (n > 0xffffffffull) return "at most 2^32 - 1 queries per call";
   if (n > 0 && (!in || !offsets)) return "the records or offsets are NULL";
   if (!items && items_bytes != 0) return "items is NULL and items_bytes is not 0";
-  if ((d->flags & LT_OVERLAP_LIST_FLAG_FILL_ONLY) && !items) return "LT_OVERLAP_LIST_FLAG_FILL_ONLY takes items";
-  return nullptr;
+  if ((flags & kListFillOnly) && !items) return std::string(f.fillOnly) + " takes items";
+  return std::string();
 }
 
 // One half of a call, or both, on `s`, over device memory: `sized` runs the count and the scan, `fill` the fill and the ordering
-// over `capacity` words of items (`oneShot`: behind this stream's own scan, and nothing is written when its total is larger).
-static int enqueue_overlap_list(lt_hip_context* ctx, ListWalk walk, const void* records, uint64_t n, uint64_t* offsets, int32_t* items,
-                                uint64_t capacity, bool sized, bool fill, bool oneShot, hipStream_t s) {
+// over `capacity` items (`oneShot`: behind this stream's own scan, and nothing is written when its total is larger).
+static int enqueue_list(lt_hip_context* ctx, const ListFamily& f, const void* records, uint64_t n, uint64_t* offsets, void* items,
+                        uint64_t capacity, bool sized, bool fill, bool oneShot, hipStream_t s) {
   const RenderKnobs k;
   LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_query_ctl));
   if (sized) {
     const uint64_t words = lt_overlist::scan_partials(n);
     LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_list_partials, ctx->list_partials_words, words, words * sizeof(uint64_t)));
   }
-  lt_overlap::Params qp{};
-  qp.boxes = (const float4*)records;
-  qp.n = (uint32_t)n;
-  qp.next = ctx->d_query_ctl;
-  qp.refill = k.trace_refill;
+  ListPass p{records, (uint32_t)n, ctx->d_query_ctl, k.trace_refill, false, oneShot, (unsigned long long*)offsets, items, capacity};
   const SceneDev sc = scene_dev(ctx, k, 2);
   if (const int rc = begin_ray_launches(ctx, &ctx->query_ev, s)) return rc;
   uint32_t launches = 0;
   if (sized) {
-    qp.kind = lt_overlap::kCountWide;
-    qp.out = (uint32_t*)offsets;
-    LT_HIP_CHECK(ctx, walk(sc, qp, (uint32_t)ctx->cu_count, s));
-    LT_HIP_CHECK(ctx, lt_overlist::scan((unsigned long long*)offsets, (uint32_t)n, ctx->d_list_partials, s));
+    LT_HIP_CHECK(ctx, f.walk(sc, p, (uint32_t)ctx->cu_count, s));
+    LT_HIP_CHECK(ctx, lt_overlist::scan(p.offsets, p.n, ctx->d_list_partials, s));
     launches += 1 + lt_overlist::kScanLaunches;
   }
   if (fill) {
-    qp.kind = lt_overlap::kList;
-    qp.out = nullptr;
-    qp.offsets = (const unsigned long long*)offsets;
-    qp.items = items;
-    qp.capacity = capacity;
-    qp.oneShot = oneShot ? 1u : 0u;
-    LT_HIP_CHECK(ctx, walk(sc, qp, (uint32_t)ctx->cu_count, s));
-    LT_HIP_CHECK(ctx, lt_overlist::order(qp.offsets, qp.n, items, capacity, oneShot, (uint32_t)ctx->cu_count, s));
+    p.fill = true;
+    LT_HIP_CHECK(ctx, f.walk(sc, p, (uint32_t)ctx->cu_count, s));
     launches += 1 + lt_overlist::kOrderLaunches;
   }
   return end_ray_launches(ctx, ctx->query_ev, s, launches, n, 0);
 }
 
-template <class Record>
-static int run_list_call(lt_hip_context* ctx, const RayWording& w, ListWalk walk, const lt_hip_overlap_list_desc* desc, const Record* in, uint64_t n,
-                         uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, bool device, void* hip_stream) {
+template <class Desc, class Record>
+static int run_list_call(lt_hip_context* ctx, const ListFamily& f, const Desc* desc, const Record* in, uint64_t n, uint64_t* offsets,
+                         uint64_t offsets_bytes, void* items, uint64_t items_bytes, bool device, void* hip_stream) {
   if (!ctx) return LT_ERR_INVALID_ARGUMENT;
-  if (const char* why = overlap_list_desc_error(desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, why);
-  if (const char* why = overlap_list_buffers_error(desc, in, n, offsets, items, items_bytes))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(w.call) + "_list: " + why);
+  {
+    const std::string why = list_desc_error(f, desc);
+    if (!why.empty()) return fail(ctx, LT_ERR_INVALID_ARGUMENT, why);
+  }
+  {
+    const std::string why = list_buffers_error(f, desc->flags, in, n, offsets, items, items_bytes);
+    if (!why.empty()) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(f.call) + ": " + why);
+  }
   if (device && n > 0 && (((uintptr_t)in | (uintptr_t)offsets | (uintptr_t)items) & 15u))
-    return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("device ") + w.in + ", offsets and items must be 16-byte aligned");
-  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, std::string(w.call) + "_list before lt_hip_set_scene");
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("device ") + f.in + ", offsets and items must be 16-byte aligned");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, std::string(f.call) + " before lt_hip_set_scene");
   if (offsets_bytes < (n + 1) * sizeof(uint64_t)) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "offsets is smaller than n + 1 words");
-  const bool fillOnly = (desc->flags & LT_OVERLAP_LIST_FLAG_FILL_ONLY) != 0;
-  const uint64_t capacity = items_bytes / sizeof(int32_t);
+  const bool fillOnly = (desc->flags & kListFillOnly) != 0;
+  const uint64_t capacity = items_bytes / f.itemBytes;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (n == 0) {
     if (fillOnly || !offsets) return LT_OK;
@@ -2965,7 +3036,7 @@ static int run_list_call(lt_hip_context* ctx, const RayWording& w, ListWalk walk
     else offsets[0] = 0;
     return LT_OK;
   }
-  if (device) return enqueue_overlap_list(ctx, walk, in, n, offsets, items, capacity, !fillOnly, items != nullptr, !fillOnly, (hipStream_t)hip_stream);
+  if (device) return enqueue_list(ctx, f, in, n, offsets, items, capacity, !fillOnly, items != nullptr, !fillOnly, (hipStream_t)hip_stream);
   // The host form: the records and the offsets in the two staging buffers of the ray families, the items in a buffer of their own
   // -- growing a buffer frees what it held, and the offsets have to outlive the growth of the items.
   const uint64_t inBytes = n * sizeof(Record), offBytes = (n + 1) * sizeof(uint64_t);
@@ -2978,9 +3049,9 @@ static int run_list_call(lt_hip_context* ctx, const RayWording& w, ListWalk walk
   uint32_t sizedLaunches = 0;
   if (fillOnly) {
     LT_HIP_CHECK(ctx, hipMemcpyAsync(dOffsets, offsets, offBytes, hipMemcpyHostToDevice, ctx->stream));
-    total = offsets[n] < capacity ? offsets[n] : capacity;   // the words that can be written at all
+    total = offsets[n] < capacity ? offsets[n] : capacity;   // the items that can be written at all
   } else {
-    if (const int rc = enqueue_overlap_list(ctx, walk, ctx->d_query_rays, n, dOffsets, nullptr, 0, true, false, false, ctx->stream)) return rc;
+    if (const int rc = enqueue_list(ctx, f, ctx->d_query_rays, n, dOffsets, nullptr, 0, true, false, false, ctx->stream)) return rc;
     LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (const int rc = finish_pending(ctx)) return rc;
     sizedMs = ctx->last.kernel_ms;
@@ -2988,65 +3059,73 @@ static int run_list_call(lt_hip_context* ctx, const RayWording& w, ListWalk walk
     LT_HIP_CHECK(ctx, hipMemcpy(offsets, dOffsets, offBytes, hipMemcpyDeviceToHost));
     total = offsets[n];
     if (!items) return LT_OK;
-    if (capacity < total) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "items is smaller than offsets[n] words (offsets is written)");
+    if (capacity < total) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, std::string("items is smaller than offsets[n] ") + f.items + " (offsets is written)");
   }
   if (total == 0) return LT_OK;
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_list_items, ctx->list_items_words, total, total * sizeof(int32_t)));
-  if (const int rc = enqueue_overlap_list(ctx, walk, ctx->d_query_rays, n, dOffsets, ctx->d_list_items, total, false, true, false, ctx->stream)) return rc;
+  const uint64_t itemBytes = total * f.itemBytes;
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_list_items, ctx->list_items_bytes, itemBytes, itemBytes));
+  if (const int rc = enqueue_list(ctx, f, ctx->d_query_rays, n, dOffsets, ctx->d_list_items, total, false, true, false, ctx->stream)) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   if (const int rc = finish_pending(ctx)) return rc;
   ctx->last.kernel_ms += sizedMs;
   ctx->last.kernel_launches += sizedLaunches;
-  LT_HIP_CHECK(ctx, hipMemcpy(items, ctx->d_list_items, total * sizeof(int32_t), hipMemcpyDeviceToHost));
+  LT_HIP_CHECK(ctx, hipMemcpy(items, ctx->d_list_items, itemBytes, hipMemcpyDeviceToHost));
   return LT_OK;
 }
 
 extern "C" int lt_hip_overlap_boxes_list(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n,
                                          uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes) {
-  return run_list_call(ctx, kOverlapWording, lt_overlap::launch, desc, boxes, n, offsets, offsets_bytes, items, items_bytes, false, nullptr);
+  return run_list_call(ctx, kOverlapBoxesList, desc, boxes, n, offsets, offsets_bytes, items, items_bytes, false, nullptr);
 }
 
 extern "C" int lt_hip_overlap_boxes_list_device(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n,
                                                 uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, void* hip_stream) {
-  return run_list_call(ctx, kOverlapWording, lt_overlap::launch, desc, boxes, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream);
+  return run_list_call(ctx, kOverlapBoxesList, desc, boxes, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream);
 }
 
 extern "C" int lt_hip_overlap_tris_list(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n,
                                         uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes) {
-  return run_list_call(ctx, kOverlapTrisWording, lt_tritri::launch, desc, tris, n, offsets, offsets_bytes, items, items_bytes, false, nullptr);
+  return run_list_call(ctx, kOverlapTrisList, desc, tris, n, offsets, offsets_bytes, items, items_bytes, false, nullptr);
 }
 
 extern "C" int lt_hip_overlap_tris_list_device(lt_hip_context* ctx, const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n,
                                                uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, void* hip_stream) {
-  return run_list_call(ctx, kOverlapTrisWording, lt_tritri::launch, desc, tris, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream);
+  return run_list_call(ctx, kOverlapTrisList, desc, tris, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream);
 }
 
-// The same lists without a context or a GPU: the host forms' scan of the caller's leaves in node order (`each`: for_touching_box or
-// for_touching_tri), then std::sort per query.  LT_ERR_BAD_SCENE stands where the context's entry points have LT_ERR_NO_SCENE.
-template <class Record, class Each>
-static int overlap_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const lt_hip_overlap_list_desc* desc,
-                             const Record* in, uint64_t n, uint64_t* offsets, uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes, Each each) {
-  if (overlap_list_desc_error(desc)) return LT_ERR_INVALID_ARGUMENT;
+extern "C" int lt_hip_nearest_list(lt_hip_context* ctx, const lt_hip_nearest_list_desc* desc, const lt_hip_point* points, uint64_t n,
+                                   uint64_t* offsets, uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes) {
+  return run_list_call(ctx, kNearestList, desc, points, n, offsets, offsets_bytes, items, items_bytes, false, nullptr);
+}
+
+extern "C" int lt_hip_nearest_list_device(lt_hip_context* ctx, const lt_hip_nearest_list_desc* desc, const lt_hip_point* points, uint64_t n,
+                                          uint64_t* offsets, uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes, void* hip_stream) {
+  return run_list_call(ctx, kNearestList, desc, points, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream);
+}
+
+// The same lists without a context or a GPU.  `sequence(nd, n_nodes, prims, record, seq)` fills `seq` with the whole sequence of
+// one query, in order: the host forms' scan of the caller's leaves in node order, then a sort.  LT_ERR_BAD_SCENE stands where the
+// context's entry points have LT_ERR_NO_SCENE.
+template <class Item, class Desc, class Record, class Sequence>
+static int list_host(const ListFamily& f, const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes, const Desc* desc,
+                     const Record* in, uint64_t n, uint64_t* offsets, uint64_t offsets_bytes, Item* items, uint64_t items_bytes, Sequence sequence) {
+  if (!list_desc_error(f, desc).empty()) return LT_ERR_INVALID_ARGUMENT;
   if (!nodes || !prims || node_bytes == 0 || node_bytes % 32 || node_bytes > 0xffffffffull * 32 || prim_bytes % 76) return LT_ERR_INVALID_ARGUMENT;
-  if (overlap_list_buffers_error(desc, in, n, offsets, items, items_bytes)) return LT_ERR_INVALID_ARGUMENT;
+  if (!list_buffers_error(f, desc->flags, in, n, offsets, items, items_bytes).empty()) return LT_ERR_INVALID_ARGUMENT;
   const lt_retree::Node* nd = (const lt_retree::Node*)nodes;
   const uint64_t n_nodes = node_bytes / 32, n_prims = prim_bytes / 76;
   for (uint64_t i = 0; i < n_nodes; i++)
     if (nd[i].cnt != 0 && (nd[i].off < 0 || (uint64_t)nd[i].off >= n_prims)) return LT_ERR_BAD_SCENE;
   if (offsets_bytes < (n + 1) * sizeof(uint64_t)) return LT_ERR_BUFFER_TOO_SMALL;
-  const bool fillOnly = (desc->flags & LT_OVERLAP_LIST_FLAG_FILL_ONLY) != 0;
-  const uint64_t capacity = items_bytes / sizeof(int32_t);
-  std::vector<int32_t> seq, all;
-  const auto sequence = [&](uint64_t j) {
-    seq.clear();
-    each(nd, n_nodes, (const float*)prims, in[j], [&](int32_t off) { seq.push_back(off); return true; });
-    std::sort(seq.begin(), seq.end());
-  };
-  if (fillOnly) {   // query j's words go to [offsets[j], min(offsets[j + 1], capacity)), whatever the offsets hold
+  const bool fillOnly = (desc->flags & kListFillOnly) != 0;
+  const uint64_t capacity = items_bytes / sizeof(Item);
+  std::vector<Item> seq, all;
+  if (fillOnly) {   // query j's items go to [offsets[j], min(offsets[j + 1], capacity)), whatever the offsets hold
     for (uint64_t j = 0; j < n; j++) {
       const uint64_t begin = offsets[j], end = offsets[j + 1] < capacity ? offsets[j + 1] : capacity;
       if (end <= begin) continue;
-      sequence(j);
+      seq.clear();
+      sequence(nd, n_nodes, (const float*)prims, in[j], seq);
       const uint64_t room = end - begin;
       std::copy(seq.begin(), seq.begin() + (size_t)(room < seq.size() ? room : seq.size()), items + begin);
     }
@@ -3058,7 +3137,8 @@ static int overlap_list_host(const void* nodes, uint64_t node_bytes, const void*
   }
   uint64_t total = 0;
   for (uint64_t j = 0; j < n; j++) {
-    sequence(j);
+    seq.clear();
+    sequence(nd, n_nodes, (const float*)prims, in[j], seq);
     offsets[j] = total;
     total += seq.size();
     if (items && total <= capacity) all.insert(all.end(), seq.begin(), seq.end());
@@ -3073,19 +3153,44 @@ static int overlap_list_host(const void* nodes, uint64_t node_bytes, const void*
 extern "C" int lt_hip_overlap_boxes_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
                                               const lt_hip_overlap_list_desc* desc, const lt_hip_box* boxes, uint64_t n, uint64_t* offsets,
                                               uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes) {
-  return overlap_list_host(nodes, node_bytes, prims, prim_bytes, desc, boxes, n, offsets, offsets_bytes, items, items_bytes,
-                           [](const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_box& q, auto&& f) {
-                             for_touching_box(nd, n_nodes, pr, q, f);
-                           });
+  return list_host(kOverlapBoxesList, nodes, node_bytes, prims, prim_bytes, desc, boxes, n, offsets, offsets_bytes, items, items_bytes,
+                   [](const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_box& q, std::vector<int32_t>& seq) {
+                     for_touching_box(nd, n_nodes, pr, q, [&](int32_t off) { seq.push_back(off); return true; });
+                     std::sort(seq.begin(), seq.end());
+                   });
 }
 
 extern "C" int lt_hip_overlap_tris_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
                                              const lt_hip_overlap_list_desc* desc, const lt_hip_tri* tris, uint64_t n, uint64_t* offsets,
                                              uint64_t offsets_bytes, int32_t* items, uint64_t items_bytes) {
-  return overlap_list_host(nodes, node_bytes, prims, prim_bytes, desc, tris, n, offsets, offsets_bytes, items, items_bytes,
-                           [](const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_tri& q, auto&& f) {
-                             for_touching_tri(nd, n_nodes, pr, q, f);
-                           });
+  return list_host(kOverlapTrisList, nodes, node_bytes, prims, prim_bytes, desc, tris, n, offsets, offsets_bytes, items, items_bytes,
+                   [](const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_tri& q, std::vector<int32_t>& seq) {
+                     for_touching_tri(nd, n_nodes, pr, q, [&](int32_t off) { seq.push_back(off); return true; });
+                     std::sort(seq.begin(), seq.end());
+                   });
+}
+
+// lt_hip_nearest_k_host's scan with every accepted candidate kept, then a STABLE sort by lt_nearest::record_before: node order is
+// the third key.
+extern "C" int lt_hip_nearest_list_host(const void* nodes, uint64_t node_bytes, const void* prims, uint64_t prim_bytes,
+                                        const lt_hip_nearest_list_desc* desc, const lt_hip_point* points, uint64_t n, uint64_t* offsets,
+                                        uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes) {
+  static_assert(sizeof(lt_nearest::Record) == sizeof(lt_hip_hit), "a radius list's record is lt_hip_hit");
+  return list_host(kNearestList, nodes, node_bytes, prims, prim_bytes, desc, points, n, offsets, offsets_bytes, (lt_nearest::Record*)items, items_bytes,
+                   [](const lt_retree::Node* nd, uint64_t n_nodes, const float* pr, const lt_hip_point& q, std::vector<lt_nearest::Record>& seq) {
+                     const float px = q.p[0], py = q.p[1], pz = q.p[2];
+                     if (lt_nearest::no_walk(px, py, pz, q.max_d2)) return;
+                     for (uint64_t i = 0; i < n_nodes; i++) {
+                       if (nd[i].cnt == 0) continue;
+                       const float* p = pr + 19 * (size_t)nd[i].off;
+                       const lt_nearest::Tri t = lt_nearest::tri(px, py, pz, p[0], p[1], p[2], p[3] - p[0], p[4] - p[1], p[5] - p[2], p[6] - p[0],
+                                                                 p[7] - p[1], p[8] - p[2]);
+                       const float d2 = lt_nearest::candidate_d2(
+                           t.d2, lt_nearest::box_d2(px, py, pz, nd[i].lo[0], nd[i].lo[1], nd[i].lo[2], nd[i].hi[0], nd[i].hi[1], nd[i].hi[2]));
+                       if (d2 < q.max_d2) seq.push_back(lt_nearest::Record{d2, nd[i].off, t.u, t.v});
+                     }
+                     std::stable_sort(seq.begin(), seq.end(), lt_nearest::record_before);
+                   });
 }
 
 // lt_hip_shade_rays*: the colour a program's `shade` returns for caller-supplied rays (lt_shade.hip).

@@ -12,6 +12,10 @@
 //
 // And the k-nearest queries (lt_hip_nearest_k): lt_nearest_k_kernel, the same loop and step with another sink -- the first K
 // candidates by (d2, offset) in a per-lane list in LDS, or their number -- and "best" read as "K-th best" (DESIGN 5.15).
+//
+// And the count and the fill of the radius lists (lt_hip_nearest_list; the scan and the ordering are lt_overlist.hip's): that
+// kernel with two more sinks, the number as one uint64 and every accepted candidate as a record into the point's segment of a CSR
+// array.
 #include "lt_nearest.hpp"
 
 using namespace lt;
@@ -31,7 +35,8 @@ struct Grid { float O[3], S[3]; };   // the 16-bit grid of the group slots (wide
 
 // One step of the walk for one lane: the record `e` (a group, or a leaf: bit 31) is fetched and dealt with, the next entry that
 // can still hold the answer popped into `e`.  Returns true when the stack is empty.  SINK: what takes the candidates and says
-// which bounds it still reaches -- lt_nearest::Best, or lt_hip_nearest_k's LaneList (the first K) and lt_nearest::KCount.
+// which bounds it still reaches -- lt_nearest::Best, lt_hip_nearest_k's LaneList (the first K) and lt_nearest::KCount, or the
+// radius lists' ListSink.
 template <class SINK>
 __device__ __forceinline__ bool nearest_step(const SceneDev& sc, const Grid& g, uint32_t emptyLink, float px, float py, float pz, SINK& best,
                                              int* col, int* deep, uint32_t& e, int& sp) {
@@ -224,6 +229,46 @@ __device__ __forceinline__ void put_nearest_k(const SceneDev& sc, const lt_neare
   }
 }
 
+// The radius lists' fill: a point's accepted candidates, each stored behind the last in the point's segment while records are
+// left of it, no LDS rows.  u and v arrive with the offer, so nothing is computed again.  The pruning bound never moves: reaches
+// is KCount's.  In registers the sink is KCount's two words, the radius and the records left: u and v stay live across tri() here,
+// which the count lets die, and a pointer on top of them does not fit 64 VGPRs -- so an offer reads the segment's end again (one
+// cached 8-byte load beside a 16-byte store) and stores at end - left.
+struct ListSink {
+  float max_d2;
+  uint32_t left;   // the records left of the segment
+  uint32_t idx;    // the point (the kernel's own register)
+  const lt_nearest::KParams* qp;
+  __device__ __forceinline__ unsigned long long end() const {
+    const unsigned long long to = qp->offsets[(size_t)idx + 1];
+    return to < qp->capacity ? to : qp->capacity;
+  }
+  // The lane takes point i: the clamped bounds -- a length that would be negative is 0, so with any offsets at all no store
+  // falls outside items[0 .. capacity).
+  __device__ __forceinline__ void reset(uint32_t i, float maxD2) {
+    idx = i;
+    const unsigned long long begin = qp->offsets[i], to = end();
+    const unsigned long long room = to > begin ? to - begin : 0ull;
+    max_d2 = maxD2;
+    left = room > 0xffffffffull ? 0xffffffffu : (uint32_t)room;
+  }
+  __device__ __forceinline__ void offer(float d2, float u, float v, int32_t p) {
+    if (d2 < max_d2 && left != 0u) {
+      const unsigned long long to = end();
+      // (left <= to holds while the offsets are what reset() read; were they changed under the launch, the store is dropped)
+      if (left <= to) qp->items[to - left] = make_uint4(__float_as_uint(d2), (uint32_t)p, __float_as_uint(u), __float_as_uint(v));
+      left--;
+    }
+  }
+  __device__ __forceinline__ bool reaches(float bound) const { return bound < max_d2; }
+};
+
+// A point's count: one uint32 (LT_NEAREST_COUNT) or, kCountWide, one uint64 into the list's offsets.
+template <int KIND>
+__device__ __forceinline__ void put_count(const lt_nearest::KParams& qp, uint32_t idx, uint32_t n) {
+  if (KIND == lt_nearest::kCountWide) qp.offsets[idx] = n; else qp.counts[idx] = n;
+}
+
 }  // namespace
 
 // lt_hip_nearest_k: lt_nearest_kernel's claim, stage and refill loop with another sink.  COUNT counts a point's accepted
@@ -232,10 +277,14 @@ __device__ __forceinline__ void put_nearest_k(const SceneDev& sc, const lt_neare
 // lists stay as they are -- and writes out when its walk is done; a subtree is kept while its bound reaches the list's last
 // entry (KList::reaches).  A step pops one stack entry and pushes at most four whatever the sink keeps, so the
 // stack is lt_nearest_kernel's.
-template <bool COUNT>
+// The radius lists (lt_hip_nearest_list) are two more sinks: kCountWide is COUNT stored as one uint64 into offsets[idx]; kList is
+// ListSink above -- no LDS list rows, so its layout and occupancy are the count's -- and points that take no walk write nothing.
+template <int KIND>
 __global__ __launch_bounds__(kBlock, 8) void lt_nearest_k_kernel(SceneDev sc, lt_nearest::KParams qp) {
   using u64 = unsigned long long;
+  constexpr bool COUNT = KIND == lt_nearest::kCount || KIND == lt_nearest::kCountWide, LIST = KIND == lt_nearest::kList;
   extern __shared__ int lds_stack[];   // [2 kNearEntries stack rows][kNearStage rows of staged points][2 maxK list rows], 64 lanes each
+  if (LIST && qp.oneShot != 0u && qp.offsets[qp.n] > qp.capacity) return;   // (every lane reads the same word)
   int* const col = lds_stack + threadIdx.x;
   int* const stage = lds_stack + 2 * kNearEntries * kBlock;
   const uint32_t total = qp.n;
@@ -254,8 +303,9 @@ __global__ __launch_bounds__(kBlock, 8) void lt_nearest_k_kernel(SceneDev sc, lt
   const uint32_t home = __builtin_amdgcn_s_getreg((3u << 11) | 20u) & 7u;   // HW_REG_XCC_ID
   bool drained = false;
   float px = 0.0f, py = 0.0f, pz = 0.0f;
-  LaneList list{{col + (2 * kNearEntries + kNearStage) * kBlock, COUNT ? 0u : qp.maxK}, 0.0f, -1};
+  LaneList list{{col + (2 * kNearEntries + kNearStage) * kBlock, COUNT || LIST ? 0u : qp.maxK}, 0.0f, -1};
   lt_nearest::KCount count{0.0f, 0u};
+  ListSink fill{0.0f, 0u, 0u, &qp};
   uint32_t idx = 0u, e = 0u;
   int sp = 0;
   int deep[2 * kNearDeep];
@@ -294,16 +344,18 @@ __global__ __launch_bounds__(kBlock, 8) void lt_nearest_k_kernel(SceneDev sc, lt
         idx = (uint32_t)stage[4 * kBlock + s];
         px = __int_as_float(stage[0 * kBlock + s]); py = __int_as_float(stage[1 * kBlock + s]); pz = __int_as_float(stage[2 * kBlock + s]);
         const float maxD2 = __int_as_float(stage[3 * kBlock + s]);
-        if (COUNT) count = lt_nearest::KCount{maxD2, 0u}; else list.reset(maxD2);
+        if (COUNT) count = lt_nearest::KCount{maxD2, 0u}; else if (LIST) fill.reset(idx, maxD2); else list.reset(maxD2);
         if (lt_nearest::no_walk(px, py, pz, maxD2)) {
-          if (COUNT) qp.counts[idx] = 0u; else put_nearest_k(sc, list.list, px, py, pz, qp.hits + (size_t)idx * qp.maxK);
+          if (COUNT) put_count<KIND>(qp, idx, 0u); else if (!LIST) put_nearest_k(sc, list.list, px, py, pz, qp.hits + (size_t)idx * qp.maxK);
         } else if (ownTree) {
           e = 0u;   // the root's group
           sp = 0;
           active = true;
         } else if (COUNT) {
           nearest_scan(sc, px, py, pz, count);
-          qp.counts[idx] = count.n;
+          put_count<KIND>(qp, idx, count.n);
+        } else if (LIST) {
+          nearest_scan(sc, px, py, pz, fill);
         } else {
           nearest_scan(sc, px, py, pz, list);
           put_nearest_k(sc, list.list, px, py, pz, qp.hits + (size_t)idx * qp.maxK);
@@ -316,10 +368,11 @@ __global__ __launch_bounds__(kBlock, 8) void lt_nearest_k_kernel(SceneDev sc, lt
       continue;
     }
     if (active) {
-      const bool done = COUNT ? nearest_step(sc, g, emptyLink, px, py, pz, count, col, deep, e, sp)
-                              : nearest_step(sc, g, emptyLink, px, py, pz, list, col, deep, e, sp);
+      const bool done = COUNT  ? nearest_step(sc, g, emptyLink, px, py, pz, count, col, deep, e, sp)
+                        : LIST ? nearest_step(sc, g, emptyLink, px, py, pz, fill, col, deep, e, sp)
+                               : nearest_step(sc, g, emptyLink, px, py, pz, list, col, deep, e, sp);
       if (done) {
-        if (COUNT) qp.counts[idx] = count.n; else put_nearest_k(sc, list.list, px, py, pz, qp.hits + (size_t)idx * qp.maxK);
+        if (COUNT) put_count<KIND>(qp, idx, count.n); else if (!LIST) put_nearest_k(sc, list.list, px, py, pz, qp.hits + (size_t)idx * qp.maxK);
         active = false;
       }
     }
@@ -330,7 +383,7 @@ namespace lt_nearest {
 
 hipError_t launch_k(const SceneDev& sc, const KParams& p, uint32_t cuCount, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  if (p.maxK > kMaxK) return hipErrorInvalidValue;
+  if (p.kind > (uint32_t)kCountWide || p.maxK > kMaxK || (p.kind == (uint32_t)kFirstK) != (p.maxK != 0u)) return hipErrorInvalidValue;
   const hipError_t e = hipMemsetAsync(p.next, 0, 8 * kQueueStride * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   const uint32_t chunks = (uint32_t)(((uint64_t)p.n + kBlock - 1) / kBlock);
@@ -339,8 +392,11 @@ hipError_t launch_k(const SceneDev& sc, const KParams& p, uint32_t cuCount, hipS
   const uint32_t fit = 160u * 1024u / (rows * kBlock * (uint32_t)sizeof(int)), perCu = fit < 32u ? fit : 32u;
   const uint32_t resident = cuCount * perCu;
   const dim3 grid(chunks < resident ? chunks : resident);
-  if (p.maxK == 0u) hipLaunchKernelGGL((lt_nearest_k_kernel<true>), grid, dim3(kBlock), rows * kBlock * (uint32_t)sizeof(int), s, sc, p);
-  else hipLaunchKernelGGL((lt_nearest_k_kernel<false>), grid, dim3(kBlock), rows * kBlock * (uint32_t)sizeof(int), s, sc, p);
+  const uint32_t bytes = rows * kBlock * (uint32_t)sizeof(int);
+  if (p.kind == (uint32_t)kCount) hipLaunchKernelGGL((lt_nearest_k_kernel<kCount>), grid, dim3(kBlock), bytes, s, sc, p);
+  else if (p.kind == (uint32_t)kCountWide) hipLaunchKernelGGL((lt_nearest_k_kernel<kCountWide>), grid, dim3(kBlock), bytes, s, sc, p);
+  else if (p.kind == (uint32_t)kList) hipLaunchKernelGGL((lt_nearest_k_kernel<kList>), grid, dim3(kBlock), bytes, s, sc, p);
+  else hipLaunchKernelGGL((lt_nearest_k_kernel<kFirstK>), grid, dim3(kBlock), bytes, s, sc, p);
   return hipGetLastError();
 }
 

@@ -165,6 +165,12 @@ struct KCount {
   LT_NEAR_HD bool reaches(float bound) const { return bound < max_d2; }
 };
 
+// A record of a radius list (lt_hip_nearest_list): lt_hip_hit's four words.  The ordering of a segment (lt_overlist.hip) and the
+// host form sort by this alone: two records of one point with equal d2 and equal offset come from the same tri() on the same
+// operands and are bit-identical, so the multiset sorted by (d2, offset) IS the sequence; accepted d2 are never NaN.
+struct Record { float d2; int32_t prim; float u, v; };
+LT_NEAR_HD inline bool record_before(const Record& a, const Record& b) { return before(a.d2, a.prim, b.d2, b.prim); }
+
 // A point that needs no walk: a component that is not finite, or a max_d2 nothing is below (0, -0, negative, NaN).
 LT_NEAR_HD inline bool no_walk(float px, float py, float pz, float max_d2) {
   const float inf = __builtin_inff();
@@ -193,16 +199,27 @@ hipError_t launch(const lt::SceneDev& sc, const Params& p, uint32_t cuCount, hip
 
 constexpr uint32_t kMaxK = 8;   // LT_NEAREST_MAX_K
 
-// lt_hip_nearest_k: the first maxK entries of each point's candidate sequence as maxK lt_hip_hit records per point, or -- maxK = 0 --
-// the sequence's length, one uint32 per point.
+// LT_NEAREST_FIRST_K, LT_NEAREST_COUNT, and the two kinds of the radius lists (lt_hip_nearest_list; lt_overlist.hpp), which no
+// descriptor names: kList, the whole sequence into the point's segment of `items`; kCountWide, kCount as one uint64 per point.
+enum Kind { kFirstK = 0, kCount = 1, kList = 2, kCountWide = 3 };
+
+// lt_hip_nearest_k: the first maxK entries of each point's candidate sequence as maxK lt_hip_hit records per point, or -- kCount --
+// the sequence's length, one uint32 per point.  kCountWide writes that length as one uint64 into offsets[i].  kList writes
+// neither `hits` nor `counts`: point i's accepted candidates go, in walk order, to items[offsets[i] .. min(offsets[i + 1], capacity))
+// as {d2, prim, u, v}, and whatever is beyond that is dropped.
 struct KParams {
   const float4* points;
-  uint4* hits;        // [n * maxK], point-major; null when counting
-  uint32_t* counts;   // [n]; null unless counting
+  uint4* hits;        // kFirstK: [n * maxK], point-major
+  uint32_t* counts;   // kCount: [n]
   uint32_t n;
-  uint32_t maxK;      // 0: count
+  uint32_t maxK;      // kFirstK: 1 .. kMaxK; else 0
   uint32_t* next;
   uint32_t refill;
+  uint32_t kind;
+  uint32_t oneShot;   // kList: the offsets are this stream's own scan -- when offsets[n] > capacity the launch writes nothing
+  unsigned long long* offsets;   // kCountWide: written, n words; kList: read, n + 1 words
+  uint4* items;                  // kList: `capacity` records
+  unsigned long long capacity;
 };
 
 // Enqueues lt_nearest_k_kernel on `s`.  Returns the first HIP error.

@@ -1,11 +1,13 @@
 // lt_overlist.hip -- the two steps of an overlap list (lt_overlist.hpp) that are not a walk: the exclusive scan that turns the
 // queries' counts into the segments' bounds, and the ordering of each segment.  The count and the fill are lt_overlap.hip's and
-// lt_tritri.hip's kernels with the sinks kCountWide and kList (lt_overlap.hpp).
+// lt_tritri.hip's kernels with the sinks kCountWide and kList (lt_overlap.hpp).  The radius lists (lt_hip_nearest_list) share both
+// steps: their count and fill are lt_nearest.hip's kernel with its kCountWide and kList, and their segments are 16-byte records.
 //
 // Neither step waits for another workgroup.  The scan is three launches -- per-tile sums, one workgroup over those sums, per-tile
 // scans plus the tile's base -- and the stream orders them.  A segment is sorted by one wave alone.
 #include "lt_overlist.hpp"
 #include "lt_device.hpp"
+#include "lt_nearest.hpp"
 
 using namespace lt;
 
@@ -91,9 +93,21 @@ __global__ __launch_bounds__(kScanLanes) void lt_list_tile_scan_kernel(u64* offs
 
 namespace {
 
-__device__ __forceinline__ void put_smaller_first(int32_t* w, u64 lo, u64 hi) {
-  const int32_t a = w[lo], b = w[hi];
-  if (b < a) { w[lo] = b; w[hi] = a; }
+// The two elements a segment is made of, the order of each and the longest segment of them that is sorted in LDS: an overlap
+// list's int32 offsets by `<`, a radius list's 16-byte records by lt_nearest::record_before on (d2, prim).
+__device__ __forceinline__ bool smaller(int32_t a, int32_t b) { return a < b; }
+__device__ __forceinline__ bool smaller(const uint4& a, const uint4& b) {
+  return lt_nearest::record_before(lt_nearest::Record{__uint_as_float(a.x), (int32_t)a.y, 0.0f, 0.0f},
+                                   lt_nearest::Record{__uint_as_float(b.x), (int32_t)b.y, 0.0f, 0.0f});
+}
+template <class T> struct Span;
+template <> struct Span<int32_t> { static constexpr uint32_t kWords = lt_overlist::kListSortSpan; };
+template <> struct Span<uint4> { static constexpr uint32_t kWords = lt_overlist::kListSortSpanHits; };
+
+template <class T>
+__device__ __forceinline__ void put_smaller_first(T* w, u64 lo, u64 hi) {
+  const T a = w[lo], b = w[hi];
+  if (smaller(b, a)) { w[lo] = b; w[hi] = a; }
 }
 
 // Sorts w[0 .. L) ascending, L >= 2, by the normalised bitonic network over P = the power of two at or above L: every comparator
@@ -104,7 +118,8 @@ __device__ __forceinline__ void put_smaller_first(int32_t* w, u64 lo, u64 hi) {
 // ends in __syncthreads(): the workgroup is this one wave, and the call carries the workgroup-scope release and acquire fences
 // that order one lane's stores before another's loads.  A comparator's lower index grows with its number t, so a lane stops
 // at the first one that starts at or behind L.
-__device__ __forceinline__ void sort_segment(int32_t* w, u64 L) {
+template <class T>
+__device__ __forceinline__ void sort_segment(T* w, u64 L) {
   const u64 lane = threadIdx.x;
   for (uint32_t lk = 1; (1ull << (lk - 1)) < L; lk++) {     // k = 1 << lk
     const u64 half = 1ull << (lk - 1);
@@ -136,9 +151,11 @@ __device__ __forceinline__ u64 lane_word(u64 v, uint32_t lane) {
 }  // namespace
 
 // Order: a wave takes 64 consecutive queries, each lane reads one's clamped bounds (lt_overlap::Sink's), and the wave sorts the
-// segments longer than one word one after another: up to kListSortSpan words in LDS, longer ones where they lie.
-__global__ __launch_bounds__(kBlock) void lt_list_order_kernel(const u64* offsets, uint32_t n, int32_t* items, u64 capacity, uint32_t oneShot) {
-  __shared__ int32_t seg[lt_overlist::kListSortSpan];
+// segments longer than one element one after another: up to Span<T> elements in LDS (16 KB either way), longer ones where they
+// lie.  T: int32_t, an overlap list's offsets, or uint4, a radius list's records.
+template <class T>
+__global__ __launch_bounds__(kBlock) void lt_list_order_kernel(const u64* offsets, uint32_t n, T* items, u64 capacity, uint32_t oneShot) {
+  __shared__ T seg[Span<T>::kWords];
   if (oneShot != 0u && offsets[n] > capacity) return;
   const uint32_t lane = threadIdx.x;
   const uint32_t chunks = (uint32_t)(((u64)n + kBlock - 1) / kBlock);
@@ -156,8 +173,8 @@ __global__ __launch_bounds__(kBlock) void lt_list_order_kernel(const u64* offset
       const uint32_t j = (uint32_t)__builtin_ctzll(todo);
       todo &= todo - 1ull;
       const u64 L = lane_word(length, j);
-      int32_t* const w = items + lane_word(begin, j);
-      if (L <= lt_overlist::kListSortSpan) {
+      T* const w = items + lane_word(begin, j);
+      if (L <= Span<T>::kWords) {
         for (u64 i = lane; i < L; i += kBlock) seg[i] = w[i];
         __syncthreads();
         sort_segment(seg, L);
@@ -180,15 +197,30 @@ hipError_t scan(unsigned long long* offsets, uint32_t n, unsigned long long* par
   return hipGetLastError();
 }
 
-hipError_t order(const unsigned long long* offsets, uint32_t n, int32_t* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
-                 hipStream_t s) {
+namespace {
+
+template <class T>
+hipError_t order_elements(const unsigned long long* offsets, uint32_t n, T* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
+                          hipStream_t s) {
   if (n == 0) return hipSuccess;
   const uint32_t chunks = (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock);
   // 16 KB of LDS per wave: ten waves per CU
   const uint32_t resident = cuCount * 10u;
-  hipLaunchKernelGGL(lt_list_order_kernel, dim3(chunks < resident ? chunks : resident), dim3(kBlock), 0, s, offsets, n, items, capacity,
+  hipLaunchKernelGGL(lt_list_order_kernel<T>, dim3(chunks < resident ? chunks : resident), dim3(kBlock), 0, s, offsets, n, items, capacity,
                      oneShot ? 1u : 0u);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t order(const unsigned long long* offsets, uint32_t n, int32_t* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
+                 hipStream_t s) {
+  return order_elements(offsets, n, items, capacity, oneShot, cuCount, s);
+}
+
+hipError_t order_hits(const unsigned long long* offsets, uint32_t n, uint4* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
+                      hipStream_t s) {
+  return order_elements(offsets, n, items, capacity, oneShot, cuCount, s);
 }
 
 }  // namespace lt_overlist

@@ -7,6 +7,8 @@
 //           and the query alone, whichever hierarchy was walked.  (The words are offsets only, so the sorted multiset is the
 //           sequence: its second key, the node index, orders equal words.)
 // No kernel waits for another workgroup: the scan is three launches, and a segment is sorted by the one wave that took it.
+// The radius lists (lt_hip_nearest_list) are the same four steps with lt_nearest.hip's walk and its kinds of the same names; their
+// items are 16-byte records {d2, prim, u, v}, ordered by (d2, prim).
 #pragma once
 #include <stdint.h>
 
@@ -16,6 +18,8 @@ namespace lt_overlist {
 constexpr uint32_t kListScanTile = 2048;
 // The longest segment that is sorted in LDS: 16 KB per wave.  Longer ones are sorted in place in global memory.
 constexpr uint32_t kListSortSpan = 4096;
+// The same for a radius list's 16-byte records (lt_hip_nearest_list): 16 KB per wave again, ten waves per CU.
+constexpr uint32_t kListSortSpanHits = 1024;
 
 // Partial sums the scan of n queries needs (one uint64 per tile of the n + 1 words).
 inline uint64_t scan_partials(uint64_t n) { return (n + 1 + kListScanTile - 1) / kListScanTile; }
@@ -37,6 +41,11 @@ hipError_t scan(unsigned long long* offsets, uint32_t n, unsigned long long* par
 // offsets are this stream's own scan, and when offsets[n] > capacity nothing is touched.  One launch on `s`.
 hipError_t order(const unsigned long long* offsets, uint32_t n, int32_t* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
                  hipStream_t s);
+
+// The same over 16-byte records {d2, prim, u, v}, ascending by lt_nearest::record_before -- (d2, prim); records that are equal in
+// both are bit-identical, so the order among them is no one's to see.  One launch on `s`.
+hipError_t order_hits(const unsigned long long* offsets, uint32_t n, uint4* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
+                      hipStream_t s);
 
 }  // namespace lt_overlist
 #endif

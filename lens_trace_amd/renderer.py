@@ -327,35 +327,47 @@ def overlap_tris_host(scene: Scene, tris, k=None, count=False, any=False):
     return out
 
 
-def _overlap_list_host(name, scene, rec):
+# The list families: (the descriptor, its FILL_ONLY flag, the numpy dtype of an item, the torch dtype and trailing shape of one).
+_OVERLAP_LIST = (C.OverlapListDesc, C.OVERLAP_LIST_FLAG_FILL_ONLY, np.int32, ("int32", ()))
+_NEAREST_LIST = (C.NearestListDesc, C.NEAREST_LIST_FLAG_FILL_ONLY, HIT_DTYPE, ("float32", (4,)))
+
+
+def _list_host(name, scene, rec, family=_OVERLAP_LIST):
     """lt_hip_<name>_list_host over a contiguous numpy array of records: the sizing call, then the fill."""
+    Desc, fill_only, item, _ = family
     nodes, prims = np.ascontiguousarray(scene.nodes), np.ascontiguousarray(scene.prims)
     vp = ctypes.c_void_p
     f = getattr(C.load(), "lt_hip_%s_list_host" % name)
-    size = ctypes.sizeof(C.OverlapListDesc)
+    size = ctypes.sizeof(Desc)
     offsets = np.zeros(rec.shape[0] + 1, dtype=np.uint64)
-    items = np.zeros(0, dtype=np.int32)
-    for flags in (0, C.OVERLAP_LIST_FLAG_FILL_ONLY):
-        d = C.OverlapListDesc(size, flags)
+    items = np.zeros(0, dtype=item)
+    for flags in (0, fill_only):
+        d = Desc(size, flags)
         rc = f(nodes.ctypes.data_as(vp), nodes.nbytes, prims.ctypes.data_as(vp), prims.nbytes, ctypes.byref(d), rec.ctypes.data_as(vp), rec.shape[0],
                offsets.ctypes.data_as(vp), offsets.nbytes, items.ctypes.data_as(vp) if flags else None, items.nbytes)
         if rc:
             raise C.LensTraceError(rc, "lt_hip_%s_list_host failed" % name)
         if not flags:
-            items = np.zeros(int(offsets[-1]), dtype=np.int32)
+            items = np.zeros(int(offsets[-1]), dtype=item)
     return offsets, items
+
+
+def nearest_list_host(scene: Scene, points, max_d2=np.inf):
+    """lt_hip_nearest_list_host: RendererHIP.nearest_list's (offsets, items) computed on the host from the scene's own buffers, leaf
+    by leaf -- no context, no GPU.  points as nearest_k takes numpy batches."""
+    return _list_host("nearest", scene, point_records(np.asarray(points), max_d2), _NEAREST_LIST)
 
 
 def overlap_boxes_list_host(scene: Scene, boxes):
     """lt_hip_overlap_boxes_list_host: RendererHIP.overlap_boxes_list's (offsets, items) computed on the host from the scene's own
     buffers, leaf by leaf -- no context, no GPU."""
-    return _overlap_list_host("overlap_boxes", scene, box_records(np.asarray(boxes)))
+    return _list_host("overlap_boxes", scene, box_records(np.asarray(boxes)))
 
 
 def overlap_tris_list_host(scene: Scene, tris):
     """lt_hip_overlap_tris_list_host: RendererHIP.overlap_tris_list's (offsets, items) computed on the host, as
     overlap_boxes_list_host."""
-    return _overlap_list_host("overlap_tris", scene, tri_records(np.asarray(tris)))
+    return _list_host("overlap_tris", scene, tri_records(np.asarray(tris)))
 
 
 _QUERY_RAYS = (RAY_DTYPE, ("make_rays", "RAY_DTYPE"))
@@ -648,6 +660,18 @@ class RendererHIP:
         return self._device_call("nearest_k", d, self._point_tensor(points, max_d2, stream), "points", "n", 4,
                                  ("int32", ()) if count else ("float32", (k, 4)), stream)
 
+    def nearest_list(self, points, max_d2=np.inf, stream=None):
+        """Every primitive within each point's radius, as CSR (lt_hip_nearest_list): (offsets, items) with items[offsets[i] :
+        offsets[i + 1]] the whole candidate sequence of point i -- nearest_k's records (t = the squared distance, prim, u, v),
+        nearest first, without the limit of eight; surface_at takes them as they are.  Points and max_d2 as nearest_k takes
+        them: numpy in gives numpy, offsets uint64 (n + 1,) and items HIT_DTYPE (total,); a torch tensor on this context's GPU
+        gives tensors, offsets as int64 and items float32 (total, 4) (column 1: int32 bits), after the sizing call, one read of
+        the total and the fill call on `stream` (default: the current torch stream).  max_d2 = inf lists every leaf for every
+        point: give a finite radius."""
+        if isinstance(points, np.ndarray):
+            return self._list_call("nearest", point_records(points, max_d2), lambda rec: rec, "points", 4, stream, _NEAREST_LIST)
+        return self._list_call("nearest", self._point_tensor(points, max_d2, stream), None, "points", 4, stream, _NEAREST_LIST)
+
     # -- box-overlap queries ---------------------------------------------------------------------------
     def overlap_boxes(self, boxes, k=None, count=False, any=False, stream=None):
         """The primitives each axis-aligned box touches (lt_hip_overlap_boxes; include/lenstrace_hip.h defines "touches": the
@@ -683,18 +707,19 @@ class RendererHIP:
         return self._device_call("overlap_tris", d, tris, "tris", "n", 12, ("int32", (d.max_k,) if d.max_k else ()), stream)
 
     # -- overlap lists ----------------------------------------------------------------------------------
-    def _overlap_list(self, name, records, numpy_records, what, width, stream):
+    def _list_call(self, name, records, numpy_records, what, width, stream, family=_OVERLAP_LIST):
         """lt_hip_<name>_list: numpy in, the host entry point sized and then filled; a torch tensor in, the device entry point --
-        the sizing call, one .item() for the total, the items allocated, the LT_OVERLAP_LIST_FLAG_FILL_ONLY call."""
+        the sizing call, one .item() for the total, the items allocated, the family's FILL_ONLY call."""
         vp = ctypes.c_void_p
-        size = ctypes.sizeof(C.OverlapListDesc)
-        sizing, fill = C.OverlapListDesc(size, 0), C.OverlapListDesc(size, C.OVERLAP_LIST_FLAG_FILL_ONLY)
+        Desc, fill_only, item, (tdtype, tshape) = family
+        size = ctypes.sizeof(Desc)
+        sizing, fill = Desc(size, 0), Desc(size, fill_only)
         if isinstance(records, np.ndarray):
             rec = numpy_records(records)
             f = getattr(self._L, "lt_hip_%s_list" % name)
             offsets = np.zeros(rec.shape[0] + 1, dtype=np.uint64)
             self._check(f(self._ctx, ctypes.byref(sizing), rec.ctypes.data_as(vp), rec.shape[0], offsets.ctypes.data_as(vp), offsets.nbytes, None, 0))
-            items = np.zeros(int(offsets[-1]), dtype=np.int32)
+            items = np.zeros(int(offsets[-1]), dtype=item)
             if len(items):
                 self._check(f(self._ctx, ctypes.byref(fill), rec.ctypes.data_as(vp), rec.shape[0], offsets.ctypes.data_as(vp), offsets.nbytes,
                               items.ctypes.data_as(vp), items.nbytes))
@@ -718,10 +743,10 @@ class RendererHIP:
             offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)     # (uint64 words: torch has no arithmetic on them)
             self._check(f(self._ctx, ctypes.byref(sizing), vp(records.data_ptr()), n, vp(offsets.data_ptr()), 8 * (n + 1), None, 0, vp(handle)))
             total = int(offsets[-1].item())
-            items = torch.empty(total, dtype=torch.int32, device=dev)
+            items = torch.empty((total,) + tshape, dtype=getattr(torch, tdtype), device=dev)
             if total:
                 self._check(f(self._ctx, ctypes.byref(fill), vp(records.data_ptr()), n, vp(offsets.data_ptr()), 8 * (n + 1),
-                              vp(items.data_ptr()), 4 * total, vp(handle)))
+                              vp(items.data_ptr()), items.numel() * items.element_size(), vp(handle)))
         return offsets, items
 
     def overlap_boxes_list(self, boxes, stream=None):
@@ -730,12 +755,12 @@ class RendererHIP:
         overlap_boxes takes them: numpy in gives numpy, offsets uint64 (n + 1,) and items int32 (total,); a torch tensor on this
         context's GPU gives tensors, offsets as int64, after the sizing call, one read of the total and the fill call on `stream`
         (default: the current torch stream)."""
-        return self._overlap_list("overlap_boxes", boxes, box_records, "boxes", 8, stream)
+        return self._list_call("overlap_boxes", boxes, box_records, "boxes", 8, stream)
 
     def overlap_tris_list(self, tris, stream=None):
         """Every primitive each query triangle meets, as CSR (lt_hip_overlap_tris_list): overlap_boxes_list's (offsets, items)
         for tris as overlap_tris takes them."""
-        return self._overlap_list("overlap_tris", tris, tri_records, "tris", 12, stream)
+        return self._list_call("overlap_tris", tris, tri_records, "tris", 12, stream)
 
     # -- shaded rays ------------------------------------------------------------------------------------
     def shade_rays(self, rays, program="accumulator", frame_first=0, frame_count=1, kernel_mode=KERNEL_MODE_LINEAR, portable_math=False,
