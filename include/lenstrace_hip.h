@@ -798,7 +798,7 @@ int lt_hip_get_stats(lt_hip_context* ctx, lt_hip_stats* out);
  * every such call launches one.  Waits for nothing; 0 for a null ctx. */
 uint64_t lt_hip_camera_hit_passes(const lt_hip_context* ctx);
 
-/* Entry cuts: with the camera hits accumulator keeps, per 8x8 square, a list of at most fifteen nodes of its own tree that
+/* Entry cuts: with the camera hits accumulator keeps, per 8x8 square, a list of nodes of its own tree (fifteen to a record) that
  * the square's shadow rays towards the lights can reach at all, and the two-frame shadow walks of the square start there instead
  * of at the root -- same pixels.  The first call that reuses a set of kept hits builds the lists, later ones reuse them; a call
  * that runs its own camera-hit pass builds none (but for the one call that times the shadow walks).  out3[0]: builds on ctx so
@@ -819,6 +819,32 @@ int lt_hip_entry_cut_test_host(const float* origins, const float* light_boxes, c
  * describing the node lists the pass started from).  Waits for the context's last render.  LT_ENTRY_CUT_LEAVES=0: node lists only,
  * (0, 0, 0); LT_ENTRY_CUT_LEAVES=N, N >= 2: the budget of records per square, for measurements (default 512). */
 int lt_hip_entry_cut_leaf_counts(lt_hip_context* ctx, uint64_t* out3);
+
+/* Lists of several records: a square's list may take up to N 64-byte records of at most fifteen entries, which the
+ * square's two-frame shadow walk goes through one after the other with the rays that are still unoccluded -- a list of leaves up to
+ * LT_ENTRY_CUT_CHUNKS=N records, 1 .. 16 (default 16; 1: one record per list, as before there were several), a list of nodes up to
+ * LT_ENTRY_CUT_NODE_CHUNKS=M of them, M <= N (default 2).  Same pixels.  The two calls above keep their meaning: lt_hip_entry_cut_counts counts the node
+ * lists, however long, and lt_hip_entry_cut_leaf_counts the lists of leaves that fit one record.  Where the leaf pass finishes with more
+ * surviving leaves than a list holds, the list is a cut over the tree as the pass saw it, without the subtrees in which no leaf
+ * survived, instead of a node list chosen by box reach alone.  A value of M above N counts as N.  The lists take 64 bytes times N per
+ * 8x8 square of device memory in the context (1 KiB per square at the default N: 133 MB at 4K).
+ * Of the cuts ctx holds now: out23[0] the N they were built with; out23[1], out23[2] the squares whose list is leaves in more than one
+ * record, and the entries of those lists; out23[3], out23[4] the squares whose list is a cut over the pruned tree, and its entries;
+ * out23[5], out23[6] the squares whose list stays a node list of more than one record, and its entries; out23[6 + k], k = 1 .. 16, the
+ * squares whose list, of any kind, takes k records.  Waits for the context's last render. */
+int lt_hip_entry_cut_chunk_counts(lt_hip_context* ctx, uint64_t* out23);
+
+/* The cut over the pruned tree on the host, for tests: a tree of n <= 512 records as the leaf pass writes it down (record 0 the root;
+ * refs[v] negative: a leaf; parents[v], kids[2 v], kids[2 v + 1]: record indices, 0xffff none) and survives[v] != 0 for the leaves that
+ * survive.  out: the references of the cut, at most cap (2 .. 240) of them; *count: their number.  No GPU. */
+int lt_hip_entry_cut_pruned_test_host(const uint32_t* refs, const uint16_t* parents, const uint16_t* kids, const uint8_t* survives, uint32_t n,
+                                      uint32_t cap, uint32_t* out, uint32_t* count);
+
+/* The arithmetic of those records on the host, for tests: n cases of (the own tree's height, the N asked for, a list's entries, a
+ * record's index).  out[4 i ..]: the entries one record holds under that height (0: no lists), the entries a list may have, the
+ * records this list takes, and the count of the record with that index.  No GPU. */
+int lt_hip_entry_cut_chunks_test_host(const int32_t* heights, const uint32_t* chunks, const uint32_t* entries, const uint32_t* which, uint64_t n,
+                                      uint32_t* out);
 
 /* The leaf pass's triangle test on the host, for tests: n cases of (origin: 3 floats, the light primitives' vertex box before it is
  * pushed outwards: lo xyz hi xyz, a traversal triangle as the walks' leaf records hold it: v0, v1 - v0, v2 - v0).  out[i]: 0 no

@@ -338,13 +338,17 @@ struct lt_hip_context {
   uint64_t camhits_slots = 0;
   std::vector<unsigned char> camhits_key;   // what d_camhits holds the hits of, every square's (camera_hits_key); empty: nothing to reuse
   uint64_t camhit_passes = 0;        // camera-hit passes launched so far (lt_hip_camera_hit_passes)
-  // The entry cuts of the stored hits' squares (lt_entry_cut_kernel): 64 bytes per square, kept with the hits under camhits_key.
+  // The entry cuts of the stored hits' squares (lt_entry_cut_kernel): planes of one 64-byte record per square (launch_entry_cuts),
+  // kept with the hits under camhits_key.
   uint32_t* d_cuts = nullptr;
-  uint64_t cuts_squares = 0;
+  uint64_t cuts_squares = 0;         // the records d_cuts has room for: squares times planes
   bool cuts_valid = false;           // d_cuts holds the cuts of every square of the hits that camhits_key speaks of
   unsigned long long* d_cut_stats = nullptr;   // [0] squares with a non-empty list, [1] their entries: of the cuts d_cuts holds;
-                                               // [2] squares marked clear, [3] squares with a list of leaves, [4] those lists' entries
+                                               // [2] squares marked clear, [3] squares with a list of leaves, [4] those lists' entries;
+                                               // from [5] on the lists of several records (lt_entry_cut_kernel: kEntryCutStats in all)
   uint32_t cuts_leaves = 0;          // RenderKnobs::entry_cut_leaves of the build that made them (another value: built again)
+  uint32_t cuts_chunks = 0;          // RenderKnobs::entry_cut_chunks of that build, likewise: the planes of d_cuts that it wrote
+  uint32_t cuts_node_chunks = 0;     // RenderKnobs::entry_cut_node_chunks of that build, likewise
   uint64_t cut_builds = 0;          // launches of lt_entry_cut_kernel so far (lt_hip_entry_cut_counts)
   uint64_t scene_generation = 0;     // goes up whenever a resident scene buffer or an array derived from one is written or given back
   hipEvent_t render_ev = nullptr;    // behind the last launch of the last render call, on render_stream: a render on another stream waits for it
@@ -1157,6 +1161,8 @@ struct RenderKnobs {
   bool entry_cut = !env_off("LT_ENTRY_CUT");   // off: every square's entry cut is the empty list (launch_entry_cuts)
   uint32_t entry_cut_leaves = 512;      // LT_ENTRY_CUT_LEAVES=0: node cuts only, no leaf pass (lt_entry_cut_kernel); =N >= 2: the records its
                                         // leaf pass may visit per square, for measurements (1, or unset: 512)
+  uint32_t entry_cut_chunks = (uint32_t)lt_entry_cut::kDefaultChunks;   // LT_ENTRY_CUT_CHUNKS=1..16: the 64-byte records a square's list may take (lt_entry_cut.hpp: Chunks)
+  uint32_t entry_cut_node_chunks = (uint32_t)lt_entry_cut::kDefaultNodeChunks;   // LT_ENTRY_CUT_NODE_CHUNKS=1..16: the records of a list of nodes at most
   uint32_t shadow_frames = 2;           // LT_SHADOW_FRAMES=1..2: frames per work item whose shadow rays walk together (launch_walk)
   bool debug_shadow_frames = getenv("LT_DEBUG_SHADOW_FRAMES") != nullptr;   // launch_walk prints the frame groups of every render launch
                                                                             // and, where there are groups, how many waves walked them together
@@ -1171,6 +1177,9 @@ struct RenderKnobs {
       const int v = atoi(e);
       entry_cut_leaves = v <= 0 ? 0u : v == 1 ? 512u : (uint32_t)std::min(v, 1 << 20);
     }
+    if (const char* e = getenv("LT_ENTRY_CUT_CHUNKS")) entry_cut_chunks = (uint32_t)std::max(1, std::min(lt_entry_cut::kMaxChunks, atoi(e)));
+    if (const char* e = getenv("LT_ENTRY_CUT_NODE_CHUNKS")) entry_cut_node_chunks = (uint32_t)std::max(1, std::min(lt_entry_cut::kMaxChunks, atoi(e)));
+    entry_cut_node_chunks = std::min(entry_cut_node_chunks, entry_cut_chunks);   // (a list of nodes takes no more records than a list may)
     if (const char* e = getenv("LT_SHADOW_FRAMES")) shadow_frames = (uint32_t)std::max(1, std::min(2, atoi(e)));
   }
 };
@@ -1800,16 +1809,19 @@ static int calibrate_shadow_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& s
 // scene generation; and the allocation the hits live in.
 // FrameParams, field by field: camx .. yaw, width, height (camera_ray), tileW .. totalSquares (square_pixel), order, orderHead and
 // persistent (the hand-out), ldsRows (the walk's stack) are in the key; depth, clampOutput, giMaxDepth, pixelCounters and squareMajor do
-// not reach a camera hit and are in it all the same; frameCount, accumulateN, fusedFrames, frameStride, shadowFrames, storeHeadHits and
-// the cameraHits and entryCuts pointers are cleared.  (The entry cuts kept with the hits are a function of the hits, of the scene's
-// primitives, lights and own tree -- the scene generation -- and of nothing else.)
-static_assert(sizeof(FrameParams) == 192 && offsetof(FrameParams, entryCuts) + sizeof(const uint32_t*) == sizeof(FrameParams) &&
+// not reach a camera hit and are in it all the same; frameCount, accumulateN, fusedFrames, frameStride, shadowFrames, storeHeadHits,
+// the cameraHits and entryCuts pointers and entryCutPlane and entryCutChunks, which say how to read entryCuts, are cleared.  (The
+// entry cuts kept with the hits are a function of the hits, of the scene's primitives, lights and own tree -- the scene generation
+// -- and of the knobs of their build, which launch_camera_hits compares by themselves.)
+static_assert(sizeof(FrameParams) == 200 && offsetof(FrameParams, entryCutChunks) + sizeof(uint32_t) == sizeof(FrameParams) &&
+                  offsetof(FrameParams, entryCuts) + sizeof(const uint32_t*) == offsetof(FrameParams, entryCutPlane) &&
+                  offsetof(FrameParams, entryCutPlane) + sizeof(uint32_t) == offsetof(FrameParams, entryCutChunks) &&
                   offsetof(FrameParams, storeHeadHits) + sizeof(uint32_t) == offsetof(FrameParams, entryCuts),
               "FrameParams changed: say in camera_hits_key whether the new field is part of the key or cleared");
 static std::vector<unsigned char> camera_hits_key(const lt_hip_context* ctx, const FrameParams& pass, const lt_hip_render_desc* d, int devlibm) {
   FrameParams f = pass;
   f.frameCount = 0; f.accumulateN = 0; f.fusedFrames = 0; f.frameStride = 0; f.shadowFrames = 0; f.storeHeadHits = 0; f.cameraHits = nullptr;
-  f.entryCuts = nullptr;
+  f.entryCuts = nullptr; f.entryCutPlane = 0; f.entryCutChunks = 0;
   std::vector<unsigned char> key;
   auto put = [&](const void* p, size_t n) { key.insert(key.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
   put(&f, sizeof(f));   // (no padding inside: the assertion above and the fields' natural alignment)
@@ -1851,19 +1863,31 @@ static std::vector<unsigned char> camera_hits_key(const lt_hip_context* ctx, con
 // On bench.py's mixed scene the timed packets and the timed queued walk are within 0.1 - 0.3 ms of each other as it is (27.2 - 27.5
 // against 26.4 - 27.3 ms: the queued walk's timed launch includes the first allocation of its queue), while in the calls that reuse
 // their hits the queue wins clearly (23.8 against 26.2 ms per step): a faster timed packet launch would tip that toss the wrong way.
+// A list takes up to RenderKnobs::entry_cut_chunks records (LT_ENTRY_CUT_CHUNKS; lt_entry_cut.hpp: Chunks): d_cuts holds that many
+// planes of one record per square, and the launch writes every plane's record of every square it builds.
+static void set_entry_cuts(const lt_hip_context* ctx, FrameParams& fp, uint32_t chunks) {
+  fp.entryCuts = ctx->d_cuts;
+  fp.entryCutPlane = fp.totalSquares * (uint32_t)lt_entry_cut::kListWords;
+  fp.entryCutChunks = chunks;
+}
 static int launch_entry_cuts(lt_hip_context* ctx, const RenderCall& c, const SceneDev& sc, const FrameParams& fh, bool all) {
   ctx->cuts_valid = false;
-  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_cuts, ctx->cuts_squares, c.nblocks, c.nblocks * lt_entry_cut::kListWords * sizeof(uint32_t)));
-  if (!ctx->d_cut_stats) LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_cut_stats, 5 * sizeof(unsigned long long)));
-  LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_cut_stats, 0, 5 * sizeof(unsigned long long), c.s));
+  // (the timing call builds lists of nodes alone: its planes are those a list of nodes may take)
+  const uint32_t chunks = all ? c.k.entry_cut_chunks : c.k.entry_cut_node_chunks;
+  const uint64_t lists = c.nblocks * chunks;   // (cuts_squares counts records: squares times planes)
+  LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_cuts, ctx->cuts_squares, lists, lists * lt_entry_cut::kListWords * sizeof(uint32_t)));
+  if (!ctx->d_cut_stats) LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_cut_stats, kEntryCutStats * sizeof(unsigned long long)));
+  LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_cut_stats, 0, kEntryCutStats * sizeof(unsigned long long), c.s));
   with_math(c.devlibm, [&](auto m) {
     hipLaunchKernelGGL((lt_entry_cut_kernel<Config<false, false, decltype(m)::value>>), dim3((uint32_t)c.nblocks), dim3(kBlock), 0, c.s, sc, fh, ctx->d_cuts,
-                       all ? 1u : 0u, (uint32_t)lt_entry_cut::entry_cut_limit(ctx->height2), ctx->d_cut_stats, all ? c.k.entry_cut_leaves : 0u);
+                       all ? 1u : 0u, (uint32_t)lt_entry_cut::entry_cut_limit(ctx->height2), ctx->d_cut_stats, all ? c.k.entry_cut_leaves : 0u, chunks, c.k.entry_cut_node_chunks);
     return 0;
   });
   LT_HIP_CHECK(ctx, hipGetLastError());
   ctx->cuts_valid = all;
   ctx->cuts_leaves = c.k.entry_cut_leaves;
+  ctx->cuts_chunks = chunks;
+  ctx->cuts_node_chunks = c.k.entry_cut_node_chunks;
   ctx->cut_builds++;
   return LT_OK;
 }
@@ -1887,11 +1911,12 @@ static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const Sc
     fp.cameraHits = ctx->d_camhits;
     for (uint32_t& h : fp.orderHead) h = 0u;
     if (wantCuts) {
-      if (!ctx->cuts_valid || ctx->cuts_squares < c.nblocks || ctx->cuts_leaves != c.k.entry_cut_leaves) {
+      if (!ctx->cuts_valid || ctx->cuts_squares < c.nblocks * c.k.entry_cut_chunks || ctx->cuts_leaves != c.k.entry_cut_leaves ||
+          ctx->cuts_chunks != c.k.entry_cut_chunks || ctx->cuts_node_chunks != c.k.entry_cut_node_chunks) {
         fh.cameraHits = ctx->d_camhits;
         if (const int rc = launch_entry_cuts(ctx, c, sc, fh, true)) return rc;
       }
-      fp.entryCuts = ctx->d_cuts;
+      set_entry_cuts(ctx, fp, ctx->cuts_chunks);
     }
     return LT_OK;
   }
@@ -1909,7 +1934,7 @@ static int launch_camera_hits(lt_hip_context* ctx, const RenderCall& c, const Sc
   ctx->camhit_passes++;
   if (wantCuts && timingCall) {
     if (const int rc = launch_entry_cuts(ctx, c, sc, fh, false)) return rc;
-    fp.entryCuts = ctx->d_cuts;
+    set_entry_cuts(ctx, fp, ctx->cuts_chunks);
   }
   if (c.k.camera_hits_keep) {
     fp.storeHeadHits = 1u;
@@ -3524,6 +3549,56 @@ extern "C" int lt_hip_entry_cut_leaf_counts(lt_hip_context* ctx, uint64_t* out3)
     out3[1] = h[3];
     out3[2] = h[4];
   }
+  return LT_OK;
+}
+
+extern "C" int lt_hip_entry_cut_chunk_counts(lt_hip_context* ctx, uint64_t* out23) {
+  uint64_t* const out21 = out23;
+  if (!ctx || !out23) return LT_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < 7 + lt_entry_cut::kMaxChunks; i++) out23[i] = 0;
+  if (ctx->cuts_valid && ctx->d_cut_stats) {
+    LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (ctx->render_ev_recorded) LT_HIP_CHECK(ctx, hipEventSynchronize(ctx->render_ev));
+    unsigned long long h[kEntryCutStats];
+    LT_HIP_CHECK(ctx, hipMemcpy(h, ctx->d_cut_stats, sizeof(h), hipMemcpyDeviceToHost));
+    out21[0] = ctx->cuts_chunks;
+    out21[1] = h[5]; out21[2] = h[6];
+    out21[3] = h[kEntryCutStatsPruned]; out21[4] = h[kEntryCutStatsPruned + 1];
+    out21[5] = h[7]; out21[6] = h[8];
+    for (int k = 0; k < lt_entry_cut::kMaxChunks; k++) out21[7 + k] = h[kEntryCutStatsChunks + k];
+  }
+  return LT_OK;
+}
+
+// lt_entry_cut.hpp's chunk arithmetic as the host compiles it: for n cases of (tree height, chunks asked for, entries of a list),
+// out[4 * i ..]: entry_cut_limit of the height, the entries a list may have, the chunks this one takes, and the count of chunk
+// `which[i]` of it.
+extern "C" int lt_hip_entry_cut_chunks_test_host(const int32_t* heights, const uint32_t* chunks, const uint32_t* entries, const uint32_t* which,
+                                                 uint64_t n, uint32_t* out) {
+  if ((!heights || !chunks || !entries || !which || !out) && n) return LT_ERR_INVALID_ARGUMENT;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t limit = (uint32_t)lt_entry_cut::entry_cut_limit(heights[i]);
+    out[4 * i + 0] = limit;
+    out[4 * i + 1] = lt_entry_cut::chunk_capacity(limit, chunks[i]);
+    out[4 * i + 2] = lt_entry_cut::chunk_count(entries[i], limit);
+    out[4 * i + 3] = lt_entry_cut::chunk_entries(entries[i], limit, which[i]);
+  }
+  return LT_OK;
+}
+
+// lt_entry_cut.hpp's cut over the pruned tree as the host compiles it, on a recorded tree of n records (refs, parents, kids[2 n] as
+// the leaf pass writes them down; survives[v] != 0: leaf record v survives): marks with pruned_mark in the order of the records,
+// selects with pruned_cut_select.  out: room for cap references; *count: their number.
+extern "C" int lt_hip_entry_cut_pruned_test_host(const uint32_t* refs, const uint16_t* parents, const uint16_t* kids, const uint8_t* survives,
+                                                 uint32_t n, uint32_t cap, uint32_t* out, uint32_t* count) {
+  if (!refs || !parents || !kids || !survives || !out || !count || n == 0 || n > (uint32_t)lt_entry_cut::kPruneRecords || cap < 2 ||
+      cap > (uint32_t)lt_entry_cut::kMaxEntries)
+    return LT_ERR_INVALID_ARGUMENT;
+  std::vector<unsigned char> mark(n, 0), depth(cap + 2);
+  std::vector<unsigned short> entry(cap + 2);
+  for (uint32_t v = 0; v < n; v++)
+    if ((int)refs[v] < 0 && survives[v]) lt_entry_cut::pruned_mark(parents, mark.data(), v);
+  *count = lt_entry_cut::pruned_cut_select(refs, kids, mark.data(), cap, entry.data(), depth.data(), out);
   return LT_OK;
 }
 

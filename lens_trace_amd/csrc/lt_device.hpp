@@ -998,7 +998,7 @@ __device__ __forceinline__ bool leaf2_frame(V4 v0v1, V4 v0v2, V4 tvec, V4 d, flo
 }
 template <int PROGRAM, int NEG>
 __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave,
-                                        const uint32_t* cut) {
+                                        const uint32_t* cut, unsigned long long& open0, unsigned long long& open1) {
   using u64 = unsigned long long;
   const __attribute__((address_space(4))) char* const pairs = (const __attribute__((address_space(4))) char*)(unsigned long long)sc.ownPairs;
   const int lane = (int)__lane_id();
@@ -1008,7 +1008,7 @@ __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2],
   for (int j = 0; j < 2; j++) {
     pr[j].px = ray[j].o.x * inv[j][0]; pr[j].py = ray[j].o.y * inv[j][1]; pr[j].pz = ray[j].o.z * inv[j][2];
     pr[j].mg = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(pr[j].px), __builtin_fabsf(pr[j].py)), __builtin_fabsf(pr[j].pz)) * 0x1p-19f + 0x1p-140f;
-    live[j] = __builtin_amdgcn_ballot_w64(true);
+    live[j] = j == 0 ? open0 : open1;   // (the lanes still looking: every lane, or those an earlier chunk of the list left)
   }
   const bool fast = sc.fastRcp != 0u;
   const float eps = walk2_eps<PROGRAM>();
@@ -1047,25 +1047,39 @@ __device__ inline void packet_walk2_cpp(const SceneDev& sc, const Ray (&ray)[2],
     if (sp == 0) break;
     cur = (uint32_t)__builtin_amdgcn_readfirstlane(ldsWave[--sp]);
   }
-#pragma unroll
-  for (int j = 0; j < 2; j++) pl[j].hitType = ((live[j] >> lane) & 1ull) != 0ull ? pl[j].hitType : 1;
+  open0 = live[0];
+  open1 = live[1];
 }
 
+constexpr uint32_t kEntryCutMaxCount = 15u;   // lt_entry_cut::kCut at most (lt_kernel.hpp holds the two together)
 template <int PROGRAM, int NEG>
 __device__ __forceinline__ void packet_walk2(const SceneDev& sc, const Ray (&ray)[2], const float (&inv)[2][3], int ign, Hit (&pl)[2], int* ldsWave,
-                                             const uint32_t* cut) {
+                                             const uint32_t* cut, uint32_t cutPlane, uint32_t cutChunks) {
 #ifndef LT_NO_ASM_WALKS
   const float eps = walk2_eps<PROGRAM>();
   const uint32_t ldsrow = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) int*)ldsWave);
+#endif
   unsigned long long open0 = __builtin_amdgcn_ballot_w64(true), open1 = open0;
-  packet_anyhit_walk2<NEG>((const void*)sc.ownPairs, ray[0].o.x, ray[0].o.y, ray[0].o.z, inv[0][0], inv[0][1], inv[0][2], ray[0].d.x, ray[0].d.y,
-                           ray[0].d.z, pl[0].t, inv[1][0], inv[1][1], inv[1][2], ray[1].d.x, ray[1].d.y, ray[1].d.z, pl[1].t, ign, eps,
-                           sc.fastRcp, open0, open1, ldsrow, (const void*)cut);
+  // One walk per chunk of the square's list (lt_entry_cut.hpp: Chunks), each from an empty stack with the lanes the chunks before
+  // left open, until no lane is or the list ends: the next plane's count is 0, or there is no further plane.  Without a list, or
+  // with a list of one chunk: one walk.
+#pragma nounroll
+  for (uint32_t chunk = 1u;; chunk++) {
+#ifndef LT_NO_ASM_WALKS
+    packet_anyhit_walk2<NEG>((const void*)sc.ownPairs, ray[0].o.x, ray[0].o.y, ray[0].o.z, inv[0][0], inv[0][1], inv[0][2], ray[0].d.x, ray[0].d.y,
+                             ray[0].d.z, pl[0].t, inv[1][0], inv[1][1], inv[1][2], ray[1].d.x, ray[1].d.y, ray[1].d.z, pl[1].t, ign, eps,
+                             sc.fastRcp, open0, open1, ldsrow, (const void*)cut);
+#else
+    packet_walk2_cpp<PROGRAM, NEG>(sc, ray, inv, ign, pl, ldsWave, cut, open0, open1);
+#endif
+    if (cut == nullptr || chunk >= cutChunks || (open0 | open1) == 0ull) break;
+    cut += cutPlane;
+    // (a count of 0 ends the list -- a walk would take it for "start at the root" --; anything that is no count of a further chunk,
+    // 1 .. 15, ends it too: the walk would run that many pops)
+    if (*(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)cut - 1u >= kEntryCutMaxCount) break;
+  }
   pl[0].hitType = ((open0 >> __lane_id()) & 1ull) != 0ull ? pl[0].hitType : 1;
   pl[1].hitType = ((open1 >> __lane_id()) & 1ull) != 0ull ? pl[1].hitType : 1;
-#else
-  packet_walk2_cpp<PROGRAM, NEG>(sc, ray, inv, ign, pl, ldsWave, cut);
-#endif
 }
 
 // Camera rays: packet traversal when the wave qualifies, the per-lane traversal otherwise.
@@ -1174,11 +1188,12 @@ __device__ inline void traverse(const SceneDev& sc, const Ray& ray, bool useIgno
 // along at most one axis (one octant, or a one-mixed-axis form: what a receiver within an area light's extent along one axis
 // sees): true.  Otherwise false, and nothing is walked: the caller renders each frame as it does alone (render_square), so that
 // the kernel holds one copy of traverse and its walks, not two.
-// cut: the entry cut of the square whose stored camera hits these rays leave (lt_entry_cut.hpp; wave-uniform), or null.
+// cut: the entry cut of the square whose stored camera hits these rays leave (lt_entry_cut.hpp; wave-uniform), or null; cutPlane,
+// cutChunks: where its further chunks are (FrameParams::entryCutPlane, entryCutChunks).
 constexpr uint32_t kEntryCutClear = 0xffffffffu;   // lt_entry_cut::kClearMark (lt_kernel.hpp holds the two together)
 template <int PROGRAM, class CFG>
 __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2], int ignore, Hit (&pl)[2], Stack<CFG::kDeep>& st, Counters& c,
-                                        const uint32_t* cut) {
+                                        const uint32_t* cut, uint32_t cutPlane, uint32_t cutChunks) {
   bool ok = false;
   if constexpr (!CFG::kStats && !CFG::kDeep && !CFG::kLdsScene) {
     float inv[2][3];
@@ -1225,26 +1240,26 @@ __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2],
     if (ok) {
       int* const row = st.lds - __lane_id();
       switch (form) {
-        case 0: packet_walk2<PROGRAM, 0>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 1: packet_walk2<PROGRAM, 1>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 2: packet_walk2<PROGRAM, 2>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 3: packet_walk2<PROGRAM, 3>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 4: packet_walk2<PROGRAM, 4>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 5: packet_walk2<PROGRAM, 5>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 6: packet_walk2<PROGRAM, 6>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 7: packet_walk2<PROGRAM, 7>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 8: packet_walk2<PROGRAM, 8>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 9: packet_walk2<PROGRAM, 9>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 10: packet_walk2<PROGRAM, 10>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 11: packet_walk2<PROGRAM, 11>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 12: packet_walk2<PROGRAM, 12>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 13: packet_walk2<PROGRAM, 13>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 14: packet_walk2<PROGRAM, 14>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 15: packet_walk2<PROGRAM, 15>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 16: packet_walk2<PROGRAM, 16>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 17: packet_walk2<PROGRAM, 17>(sc, ray, inv, ignore, pl, row, cut); break;
-        case 18: packet_walk2<PROGRAM, 18>(sc, ray, inv, ignore, pl, row, cut); break;
-        default: packet_walk2<PROGRAM, 19>(sc, ray, inv, ignore, pl, row, cut); break;
+        case 0: packet_walk2<PROGRAM, 0>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 1: packet_walk2<PROGRAM, 1>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 2: packet_walk2<PROGRAM, 2>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 3: packet_walk2<PROGRAM, 3>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 4: packet_walk2<PROGRAM, 4>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 5: packet_walk2<PROGRAM, 5>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 6: packet_walk2<PROGRAM, 6>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 7: packet_walk2<PROGRAM, 7>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 8: packet_walk2<PROGRAM, 8>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 9: packet_walk2<PROGRAM, 9>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 10: packet_walk2<PROGRAM, 10>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 11: packet_walk2<PROGRAM, 11>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 12: packet_walk2<PROGRAM, 12>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 13: packet_walk2<PROGRAM, 13>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 14: packet_walk2<PROGRAM, 14>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 15: packet_walk2<PROGRAM, 15>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 16: packet_walk2<PROGRAM, 16>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 17: packet_walk2<PROGRAM, 17>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        case 18: packet_walk2<PROGRAM, 18>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
+        default: packet_walk2<PROGRAM, 19>(sc, ray, inv, ignore, pl, row, cut, cutPlane, cutChunks); break;
       }
     }
   }
@@ -1476,7 +1491,7 @@ __device__ inline V3 shade_lighting(const SceneDev& sc, const Hit& pl, float fx,
 // direct_light, and their fences.  False where the two rays could not walk together: `out` is then not the colours.
 template <class CFG>
 __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float fx, float fy, uint32_t s, Stack<CFG::kDeep>& st, Counters& c,
-                                       V3 (&out)[2], const uint32_t* cut) {
+                                       V3 (&out)[2], const uint32_t* cut, uint32_t cutPlane, uint32_t cutChunks) {
   out[0] = out[1] = V3{0.0f, 0.0f, 0.0f};
   if (is_light(sc.lights, pl.prim)) {
     out[0] = out[1] = V3{1.0f, 1.0f, 1.0f};
@@ -1538,7 +1553,7 @@ __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float 
   }
   asm volatile("" : "+v"(ndotl[0]), "+v"(ndotl[1]));
   if (cut != nullptr && __builtin_amdgcn_ballot_w64(!listed) != 0ull) cut = nullptr;
-  if (!traverse_shadow2<kAccumulator, CFG>(sc, ray, pl.prim, spl, st, c, cut)) return false;
+  if (!traverse_shadow2<kAccumulator, CFG>(sc, ray, pl.prim, spl, st, c, cut, cutPlane, cutChunks)) return false;
   asm volatile("" ::: "memory");
   const Material* m = sc.mats + prim_material(prim_ptr(sc, pl.prim));
 #pragma unroll
@@ -1678,6 +1693,11 @@ struct FrameParams {
   // of the square's items starts instead of the root; count 0: at the root; kEntryCutClear in place of the count: no leaf can occlude
   // a ray of the square, no walk (traverse_shadow2).  Null: no cuts (LT_ENTRY_CUT=0, nothing stored).
   const uint32_t* entryCuts;
+  // A list longer than one record goes on in further chunks (lt_entry_cut.hpp: Chunks): chunk c of position p is the 16 words at
+  // entryCuts[c * entryCutPlane + p * 16], c < entryCutChunks, a count and that many references; a count of 0 ends the list.  The
+  // builder's values (LT_ENTRY_CUT_CHUNKS), set with entryCuts: the same for every frame of every call that reads those cuts.
+  uint32_t entryCutPlane;    // words between the planes, totalSquares * 16
+  uint32_t entryCutChunks;   // >= 1 where entryCuts is set
 };
 
 // Camera ray of pixel (x,y): acc.cl:304-312.
@@ -1705,7 +1725,7 @@ __device__ inline bool shade_pixel2(const SceneDev& sc, const FrameParams& fp, u
   float fx, fy;
   const Ray ray = camera_ray<CFG::kDevLibm>(fp, x, y, fx, fy);
   const Hit pl = camera_hit<kAccumulator, CFG>(sc, ray, hitRow, st, c);
-  if (!shade_lighting2<CFG>(sc, pl, fx, fy, frameCount, st, c, color, cut)) return false;
+  if (!shade_lighting2<CFG>(sc, pl, fx, fy, frameCount, st, c, color, cut, fp.entryCutPlane, fp.entryCutChunks)) return false;
   if (fp.clampOutput)
 #pragma unroll
     for (int j = 0; j < 2; j++)

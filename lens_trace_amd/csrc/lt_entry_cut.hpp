@@ -65,6 +65,28 @@
 // What the claim does NOT cover gets the empty list (start at the root): a non-finite or huge origin or light box, no light, a
 // light sample whose index falls on the list's zero tail (index == count: shade_lighting2 looks at its own samples and drops the
 // list for that work item), a stack that could overflow (entry_cut_limit).
+//
+// Chunks.  A square's list may be longer than one record holds: it is then cut into up to `chunks` records of at most
+// entry_cut_limit entries each (chunk_count, chunk_entries), chunk c in plane c of the buffer, and packet_walk2 runs the walk once
+// per chunk (a list of leaves up to `chunks` records, a list of nodes up to the smaller nodeChunks), each time from an empty stack, with the lanes still open after the chunk before (it stops when none is).  The argument
+// above goes through per chunk: every leaf that some ray of the square could be accepted in lies below an entry of exactly one
+// chunk, and the walk of that chunk reaches it from that entry as a walk from the root would -- the tests between the entry and
+// the leaf are the same.  A lane that an earlier chunk closed found an accepted hit there, which a walk from the root finds too (in
+// another order); a lane open to the end was accepted in no leaf below any entry.  The accepts are those of the same leaves under
+// the same tests in another order, and an any-hit caller reads nothing else.  Word 0 of every chunk after the first is a plain
+// count, 0 .. limit, written for every square by every build: 0 ends the list, and a chunk of count 0 is never handed to a walk
+// (nor is a word that is no count, 1 .. kCut: packet_walk2 ends the list there).
+//
+// The cut over the pruned tree.  Where the leaf pass (lt_entry_cut_kernel) finishes -- it has visited every record that some casting
+// lane may reach and tested every leaf among them -- but more leaves survive than a list holds, the square's list is a cut of the
+// tree AS THE PASS SAW IT (pruned_cut_select over the records the pass wrote down): an interior record below which no leaf survived
+// is dropped, a surviving leaf stands for itself, and the cut is deepened shallowest first as the node cut is.  It leans on the
+// claim that justifies the lists of leaves: no ray of the square is accepted in a leaf that did not survive -- a leaf the pass did
+// not visit has an ancestor that no casting lane may reach (the first claim), a leaf it visited and dropped accepts no ray of the
+// square (the second) -- so every leaf in which some ray could be accepted is a surviving leaf, lies below exactly one entry of
+// the cut (pruned_mark marks every record above a survivor, and an entry is replaced by ALL its marked children or not at all), and
+// is reached from that entry by the same tests as from the root.  A pass that does not finish, or one that visits more records
+// than are written down (kPruneRecords), knows no such tree: the square keeps the node cut chosen by box reach.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -100,6 +122,25 @@ LT_EC_HD inline int entry_cut_limit(int ownHeight) {
   const int room = 64 - (2 * ownHeight + 2);
   const int limit = room < kCut ? room : kCut;
   return limit >= 2 ? limit : 0;
+}
+
+// A list of `entries` references in chunks of at most `limit` (entry_cut_limit's, 0: no lists), at most kMaxChunks of them: every
+// chunk but the last is full.
+constexpr int kMaxChunks = 16;
+constexpr int kDefaultChunks = 16;  // LT_ENTRY_CUT_CHUNKS unset (1, 2, 4, 8, 12 and 16 timed on the 1 M-triangle wall)
+// LT_ENTRY_CUT_NODE_CHUNKS unset: a list of NODES takes no more records than this.  A deeper cut by box reach alone is not always
+// a better one -- every entry is a record fetched and two boxes tested by every work item, where a node higher up lets the rays
+// themselves cull both -- DESIGN 5.1: the colonnade gains with 2 and loses with 4 and 8, the wall gains with all.
+constexpr int kDefaultNodeChunks = 2;
+constexpr int kMaxEntries = kMaxChunks * kCut;
+LT_EC_HD inline unsigned chunk_capacity(unsigned limit, unsigned chunks) {   // the entries a square's list may have
+  const unsigned c = chunks < 1u ? 1u : chunks > (unsigned)kMaxChunks ? (unsigned)kMaxChunks : chunks;
+  return limit * c;
+}
+LT_EC_HD inline unsigned chunk_count(unsigned entries, unsigned limit) { return limit == 0u ? 0u : (entries + limit - 1u) / limit; }
+LT_EC_HD inline unsigned chunk_entries(unsigned entries, unsigned limit, unsigned chunk) {   // the count of chunk `chunk`
+  const unsigned first = chunk * limit;
+  return entries <= first ? 0u : entries - first < limit ? entries - first : limit;
 }
 
 // One axis of the light primitives' vertex box, pushed outwards (in place).
@@ -288,6 +329,51 @@ LT_EC_HD inline bool may_accept(const LaneSet& ls, float ax, float ay, float az,
   range_over_box(ls, cUVD, lo, hi);
   if (lo > kTriRel * ((SU + SV) + SD) + Z) return false;         // u + v > 1
   return true;
+}
+
+// ---- The tree as the leaf pass saw it: record v (the v-th it visited, the root first) has the reference ref[v] (negative: a leaf),
+// the record it was reached from, parent[v] (kNoRecord for the root), and the records its two children became, kid[2 v], kid[2 v + 1]
+// (kNoRecord: not reached).  mark[v]: a surviving leaf, or a record above one.
+constexpr int kPruneRecords = 512;
+constexpr unsigned short kNoRecord = 0xffffu;
+
+// Leaf record v survives: marks it and every record above it (stops at the first that is marked already).
+LT_EC_HD inline void pruned_mark(const unsigned short* parent, unsigned char* mark, unsigned v) {
+  while (v != (unsigned)kNoRecord && mark[v] == 0) {
+    mark[v] = 1;
+    v = parent[v];
+  }
+}
+
+// The cut: starts as the root record, and the shallowest interior entry -- the first of several -- is replaced by its marked
+// children, until a replacement would make it longer than cap or every entry is a leaf.  entry / depth: room for cap + 2 each.
+// Writes the references of the cut to out (cap at least 2) and returns their number; 0 when the root is not marked.
+LT_EC_HD inline unsigned pruned_cut_select(const unsigned* ref, const unsigned short* kid, const unsigned char* mark, unsigned cap,
+                                           unsigned short* entry, unsigned char* depth, unsigned* out) {
+  if (mark[0] == 0) return 0u;
+  unsigned n = 1u;
+  entry[0] = 0;
+  depth[0] = 0;
+  for (;;) {
+    unsigned pick = n, best = 0xffffffffu;
+    for (unsigned i = 0; i < n; i++)
+      if ((int)ref[entry[i]] >= 0 && depth[i] < best) { best = depth[i]; pick = i; }
+    if (pick == n) break;
+    const unsigned v = entry[pick];
+    unsigned short kids[2];
+    unsigned k = 0u;
+    for (unsigned s = 0; s < 2u; s++)
+      if (kid[2u * v + s] != kNoRecord && mark[kid[2u * v + s]] != 0) kids[k++] = kid[2u * v + s];
+    if (n - 1u + k > cap) break;
+    const unsigned char d = (unsigned char)(depth[pick] + 1);
+    entry[pick] = entry[n - 1u]; depth[pick] = depth[n - 1u];
+    unsigned m = n - 1u;
+    for (unsigned s = 0; s < k; s++) { entry[m] = kids[s]; depth[m] = d; m++; }
+    n = m;
+    if (n == 0u) break;   // (a marked interior record has a marked child: not reached)
+  }
+  for (unsigned i = 0; i < n; i++) out[i] = ref[entry[i]];
+  return n;
 }
 
 }  // namespace lt_entry_cut

@@ -277,16 +277,25 @@ __global__ __launch_bounds__(kBlock, LT_ACC_WAVES) void lt_camera_hits_kernel(Sc
 // position blockIdx.x -- every square (all != 0: the hits are whole, a call that reuses them) or all but the head squares of fp's
 // hand-out order (all == 0: behind a call's own camera-hit pass, whose render launches walk the head squares themselves).  A lane casts shadow rays iff its stored hit is a surface that is
 // no light (shade_lighting2); the square's list starts as the root and the shallowest interior entry is replaced by those of its
-// two children that some casting lane may reach (may_reach), until a replacement would make it longer than `limit` (<= kCut).  The empty list
+// two children that some casting lane may reach (may_reach), until a replacement would make it longer than `chunks` records of
+// `limit` (<= kCut) entries hold (lt_entry_cut.hpp: Chunks; chunk c at cuts[(c * totalSquares + pos) * 16]).  The empty list
 // -- start at the root -- where the argument does not hold or nothing is gained: no light, a casting lane that lane_set refuses,
 // no casting lane, a list that is the root alone or empty.  stats: [0] squares with a non-empty list, [1] their entries -- of the
 // node cut, whatever the leaf pass below makes of the square; [2] squares the leaf pass marks clear, [3] squares it gives a list of
-// leaves, [4] the entries of those.  leafBudget: the records the leaf pass may visit per square; 0: no leaf pass (LT_ENTRY_CUT_LEAVES=0).
+// leaves that fits one chunk, [4] the entries of those; [5], [6] the same for the lists of leaves that take several chunks; [7], [8]
+// the squares whose list stays a node cut of several chunks, and its entries; [kEntryCutStatsChunks + k - 1] the squares whose
+// list, of any kind, takes k chunks; [kEntryCutStatsPruned], [+ 1] the squares whose list is a cut over the pruned tree, and its entries.  leafBudget: the records the leaf pass may visit per square; 0: no leaf pass
+// (LT_ENTRY_CUT_LEAVES=0).
+constexpr uint32_t kEntryCutStatsChunks = 9u, kEntryCutStatsPruned = kEntryCutStatsChunks + (uint32_t)lt_entry_cut::kMaxChunks,
+                   kEntryCutStats = kEntryCutStatsPruned + 2u;
 template <class CFG>
 __global__ __launch_bounds__(kBlock) void lt_entry_cut_kernel(SceneDev sc, FrameParams fp, uint32_t* __restrict__ cuts, uint32_t all,
-                                                             uint32_t limit, unsigned long long* __restrict__ stats, uint32_t leafBudget) {
+                                                             uint32_t limit, unsigned long long* __restrict__ stats, uint32_t leafBudget, uint32_t chunks,
+                                                             uint32_t nodeChunks) {
   using namespace lt_entry_cut;
   static_assert(kClearMark == kEntryCutClear && kClearMark > (unsigned)kCut, "traverse_shadow2 looks for the mark that this kernel writes; no count is one");
+  static_assert(kMaxEntries + 2 <= 256, "the pick below keeps an entry's index in eight bits");
+  static_assert((unsigned)kCut <= kEntryCutMaxCount, "packet_walk2 takes a further chunk's count for one only up to kEntryCutMaxCount");
   const uint32_t pos = blockIdx.x, lane = threadIdx.x;
   if (pos >= fp.totalSquares) return;
   bool head = false;
@@ -295,7 +304,11 @@ __global__ __launch_bounds__(kBlock) void lt_entry_cut_kernel(SceneDev sc, Frame
     if (pos >= start && pos - start < xcd_share_size(fp.totalSquares, xcd)) head = fp.order != nullptr && pos - start < fp.orderHead[xcd];
   }
   if (head && all == 0u) return;
-  __shared__ uint32_t refs[kCut + 2], depth[kCut + 2];
+  if (limit > (uint32_t)kCut) limit = (uint32_t)kCut;
+  chunks = chunks < 1u ? 1u : chunks > (uint32_t)kMaxChunks ? (uint32_t)kMaxChunks : chunks;
+  const uint32_t cap = chunk_capacity(limit, chunks);   // the entries of a square's list at most: `chunks` records of `limit`
+  const uint32_t nodeCap = chunk_capacity(limit, nodeChunks < chunks ? nodeChunks : chunks);   // ... and of a list of nodes
+  __shared__ uint32_t refs[kMaxEntries + 2], depth[kMaxEntries + 2], leaves[kMaxEntries];
   // the light primitives' vertex box, pushed outwards
   const uint32_t nLights = sc.lights->count;
   float Llo[3], Lhi[3];
@@ -345,15 +358,21 @@ __global__ __launch_bounds__(kBlock) void lt_entry_cut_kernel(SceneDev sc, Frame
     __syncthreads();
     const __attribute__((address_space(4))) char* const pairs = (const __attribute__((address_space(4))) char*)(unsigned long long)sc.ownPairs;
     for (;;) {
-      uint32_t pick = n, best = 0xffffffffu;   // the shallowest interior entry, the first of several
-      for (uint32_t i = 0; i < n; i++)
-        if ((int)refs[i] >= 0 && depth[i] < best) { best = depth[i]; pick = i; }
-      if (pick == n) break;
+      // the shallowest interior entry, the first of several: the least (depth, index), a lane per entry and 64 entries a round
+      uint32_t key = 0xffffffffu;
+      for (uint32_t i = lane; i < n; i += 64u)
+        if ((int)refs[i] >= 0 && (depth[i] << 8 | i) < key) key = depth[i] << 8 | i;
+      for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)key, m);
+        key = other < key ? other : key;
+      }
+      if (key == 0xffffffffu) break;
+      const uint32_t pick = key & 255u;
       const F16v r = *(ConstF16)(pairs + ((size_t)refs[pick] << 6));
       const bool inL = __builtin_amdgcn_ballot_w64(casts && may_reach(ls, r.s0, r.s1, r.s2, r.s3, r.s4, r.s5)) != 0ull;
       const bool inR = __builtin_amdgcn_ballot_w64(casts && may_reach(ls, r.s8, r.s9, r.sa, r.sb, r.sc, r.sd)) != 0ull;
       const uint32_t kids = (inL ? 1u : 0u) + (inR ? 1u : 0u);
-      if (n - 1u + kids > limit || n - 1u + kids > (uint32_t)kCut) break;
+      if (n - 1u + kids > nodeCap) break;
       __syncthreads();
       if (lane == 0u) {
         const uint32_t d = depth[pick] + 1u;
@@ -374,47 +393,85 @@ __global__ __launch_bounds__(kBlock) void lt_entry_cut_kernel(SceneDev sc, Frame
     atomicAdd(&stats[1], (unsigned long long)n);
   }
   // The leaf pass: depth first from the root, a child where some casting lane may reach its box, a leaf where some casting lane that
-  // does not start on it may reach its own box and may accept its triangle (may_accept).  The stack and the surviving leaves are
-  // wave-uniform and live in one register each, a lane per slot (2 * height + 2 <= 62 slots: entry_cut_limit != 0).  Finished
-  // within leafBudget records and with at most `limit` leaves: those leaves are the square's list -- by the two claims no ray of
-  // the square is accepted anywhere else -- and none at all is the clear mark; else the node cut above stays.
-  uint32_t word0 = n;
-  int listv = lane >= 1u && lane <= n ? (int)refs[lane - 1u] : 0;   // word `lane` of the list
+  // does not start on it may reach its own box and may accept its triangle (may_accept).  The stack is wave-uniform and lives in one
+  // register, a lane per slot (2 * height + 2 <= 62 slots: entry_cut_limit != 0); the surviving leaves go to LDS.  Finished within
+  // leafBudget records and with at most `cap` leaves: those leaves are the square's list -- by the two claims no ray of the square
+  // is accepted anywhere else -- and none at all is the clear mark.  Finished with more leaves than that, and within kPruneRecords
+  // records: the pass has written down the tree as it saw it (the first kPruneRecords records it visits: each one's reference, the
+  // record it came from and the records its children became; a second stack register carries where a waiting child came from), and
+  // the list is a cut of that tree without the subtrees in which no leaf survived (lt_entry_cut.hpp: pruned_cut_select; lane 0
+  // runs it).  Else the node cut above stays.
+  __shared__ uint32_t seenRef[kPruneRecords];
+  __shared__ unsigned short seenParent[kPruneRecords], seenKid[2 * kPruneRecords], cutEntry[kMaxEntries + 2];
+  __shared__ unsigned char seenMark[kPruneRecords], cutDepth[kMaxEntries + 2];
+  bool whole = false, pruned = false;
+  uint32_t kept = 0u, prunedEntries = 0u;
   if (build && leafBudget != 0u) {
     const __attribute__((address_space(4))) char* const pairs = (const __attribute__((address_space(4))) char*)(unsigned long long)sc.ownPairs;
-    int stackv = 0, keepv = 0;
-    uint32_t sp = 0u, kept = 0u, visited = 0u, cur = 0u;
-    bool whole = true;
+    int stackv = 0, stackFrom = 0;
+    uint32_t sp = 0u, visited = 0u, cur = 0u, from = 0xffffffffu;   // from: 2 * (the record `cur` was reached from) + which child it is
+    bool finished = true;
     for (;;) {
-      if (++visited > leafBudget) { whole = false; break; }
+      if (++visited > leafBudget) { finished = false; break; }
+      const uint32_t v = visited - 1u;
+      if (v < (uint32_t)kPruneRecords && lane == 0u) {
+        seenRef[v] = cur;
+        seenParent[v] = from == 0xffffffffu ? kNoRecord : (unsigned short)(from >> 1);
+        seenKid[2u * v] = seenKid[2u * v + 1u] = kNoRecord;
+        seenMark[v] = 0;
+        if (from != 0xffffffffu) seenKid[from] = (unsigned short)v;
+      }
       const F16v r = *(ConstF16)(pairs + (size_t)(cur << 6));
       if ((int)cur >= 0) {
         const bool inL = __builtin_amdgcn_ballot_w64(casts && may_reach(ls, r.s0, r.s1, r.s2, r.s3, r.s4, r.s5)) != 0ull;
         const bool inR = __builtin_amdgcn_ballot_w64(casts && may_reach(ls, r.s8, r.s9, r.sa, r.sb, r.sc, r.sd)) != 0ull;
-        if (sp + 2u > 64u) { whole = false; break; }
-        if (inR) stackv = lane == sp++ ? __float_as_int(r.se) : stackv;
-        if (inL) stackv = lane == sp++ ? __float_as_int(r.s6) : stackv;
+        if (sp + 2u > 64u) { finished = false; break; }
+        if (inR) { stackv = lane == sp ? __float_as_int(r.se) : stackv; stackFrom = lane == sp ? (int)(2u * v + 1u) : stackFrom; sp++; }
+        if (inL) { stackv = lane == sp ? __float_as_int(r.s6) : stackv; stackFrom = lane == sp ? (int)(2u * v) : stackFrom; sp++; }
       } else {
         const bool may = casts && own != __float_as_int(r.sf) && may_reach(ls, r.s9, r.sa, r.sb, r.sc, r.sd, r.se) &&
                          may_accept(ls, r.s0, r.s1, r.s2, r.s3, r.s4, r.s5, r.s6, r.s7, r.s8);
         if (__builtin_amdgcn_ballot_w64(may) != 0ull) {
-          if (kept >= limit || kept >= (uint32_t)kCut) { whole = false; break; }
-          keepv = lane == 1u + kept++ ? (int)cur : keepv;
+          if (kept < cap && lane == 0u) leaves[kept] = cur;
+          if (v < (uint32_t)kPruneRecords && lane == 0u) pruned_mark(seenParent, seenMark, v);
+          kept++;   // (beyond cap: counted, not kept -- the pass goes on to see the whole tree)
         }
       }
       if (sp == 0u) break;
-      cur = (uint32_t)__builtin_amdgcn_readlane(stackv, (int)--sp);
+      --sp;
+      cur = (uint32_t)__builtin_amdgcn_readlane(stackv, (int)sp);
+      from = (uint32_t)__builtin_amdgcn_readlane(stackFrom, (int)sp);
     }
-    if (whole) {
-      word0 = kept == 0u ? kClearMark : kept;
-      listv = lane >= 1u && lane <= kept ? keepv : 0;
-      if (lane == 0u && stats != nullptr) {
-        if (kept == 0u) atomicAdd(&stats[2], 1ull);
-        else { atomicAdd(&stats[3], 1ull); atomicAdd(&stats[4], (unsigned long long)kept); }
-      }
+    whole = finished && kept <= cap;
+    pruned = finished && kept > cap && visited <= (uint32_t)kPruneRecords && cap >= 2u;
+    if (pruned) {
+      __syncthreads();
+      uint32_t count = 0u;
+      if (lane == 0u) count = pruned_cut_select(seenRef, seenKid, seenMark, cap, cutEntry, cutDepth, leaves);
+      prunedEntries = (uint32_t)__builtin_amdgcn_readfirstlane((int)count);
     }
   }
-  if (lane < (uint32_t)kListWords) cuts[(size_t)pos * kListWords + lane] = lane == 0u ? word0 : (uint32_t)listv;
+  __syncthreads();
+  // The square's list -- the surviving leaves, the cut over the pruned tree, else the node cut -- in chunks of `limit`: chunk c in
+  // plane c, a count and that many references.  Every plane's record is written, whatever the list: a count of 0 where it has
+  // ended (or never began).
+  const uint32_t* const list = whole || pruned ? leaves : refs;
+  const uint32_t entries = whole ? kept : pruned ? prunedEntries : n;
+  for (uint32_t c = 0; c < chunks; c++) {
+    const uint32_t count = chunk_entries(entries, limit, c);
+    const uint32_t word0 = c == 0u && whole && kept == 0u ? kClearMark : count;
+    if (lane < (uint32_t)kListWords)
+      cuts[((size_t)c * fp.totalSquares + pos) * kListWords + lane] = lane == 0u ? word0 : lane <= count ? list[c * limit + lane - 1u] : 0u;
+  }
+  if (lane == 0u && stats != nullptr) {
+    const uint32_t used = chunk_count(entries, limit);
+    if (whole && kept == 0u) atomicAdd(&stats[2], 1ull);
+    else if (whole && used == 1u) { atomicAdd(&stats[3], 1ull); atomicAdd(&stats[4], (unsigned long long)kept); }
+    else if (whole) { atomicAdd(&stats[5], 1ull); atomicAdd(&stats[6], (unsigned long long)kept); }
+    else if (pruned) { atomicAdd(&stats[kEntryCutStatsPruned], 1ull); atomicAdd(&stats[kEntryCutStatsPruned + 1u], (unsigned long long)prunedEntries); }
+    else if (used > 1u) { atomicAdd(&stats[7], 1ull); atomicAdd(&stats[8], (unsigned long long)n); }
+    if (used != 0u) atomicAdd(&stats[kEntryCutStatsChunks + used - 1u], 1ull);
+  }
 }
 
 // =====================================================================================================================

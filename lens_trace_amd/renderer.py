@@ -500,6 +500,17 @@ class RendererHIP:
         self._check(self._L.lt_hip_entry_cut_leaf_counts(self._ctx, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def entry_cut_chunk_counts(self):
+        """lt_hip_entry_cut_chunk_counts, of the cuts the context holds now: a dict of `chunks` (the records a list may take,
+        LT_ENTRY_CUT_CHUNKS), `leaf` and `plain` ((squares, entries) of the lists of leaves and of the node cuts that take more
+        than one record), `pruned` ((squares, entries) of the cuts over the pruned tree) and `squares_by_chunks` (k -> the squares
+        whose list takes k records, k = 1 .. 16).  Waits for the context's last render.  All zero while the context holds no
+        cuts."""
+        out = (ctypes.c_uint64 * 23)()
+        self._check(self._L.lt_hip_entry_cut_chunk_counts(self._ctx, out))
+        return {"chunks": int(out[0]), "leaf": (int(out[1]), int(out[2])), "pruned": (int(out[3]), int(out[4])),
+                "plain": (int(out[5]), int(out[6])), "squares_by_chunks": {k: int(out[6 + k]) for k in range(1, 17)}}
+
     def scene_structure(self, what):
         """lt_hip_read_scene_structure: 0 own tree (NODE_DTYPE array), 1 leaf order table (n_prims x 8 uint32), 2 the per-lane walks'
         array (bytes), 3 (own height, group-tree height, groups, prepared on the device), 4 the packet walks' records (bytes, 64 per
