@@ -852,6 +852,29 @@ int lt_hip_entry_cut_chunks_test_host(const int32_t* heights, const uint32_t* ch
  * lane is one the cut is not built for.  No GPU. */
 int lt_hip_entry_cut_triangle_test_host(const float* origins, const float* light_boxes, const float* triangles, uint64_t n, uint8_t* out);
 
+/* Clear squares handed out whole.  A call that reuses a camera's entry cuts hands its squares out from an item
+ * table built behind the cuts, on the device: a square marked clear is one work item for all frames of the launch instead of one
+ * per frame group, and where the launch is a fused one of a depth-3 image whose tile width is a multiple of 8, without padded
+ * tiles and with a 16-byte aligned output, that item folds its samples into the running mean itself, frame by frame: they are neither
+ * stored nor read back by the fold.  Same pixels.  LT_CLEAR_ITEMS=0: the hand-out and the fold as they were without it.
+ * The table is taken only where it thins the hand-out: the build's counters come back to the host asynchronously, and once they are
+ * there a set of cuts with fewer than a third of its squares clear is rendered without the table, as before there was one (the
+ * Cornell box at 4K lost 0.15 ms to it).  LT_CLEAR_ITEMS=1: the table however few squares are clear; =2: likewise, and whole squares
+ * store their samples (the hand-out alone, for measurements).
+ * Of the table ctx holds now: out5[0] its entries and out5[1] the squares it hands out whole, as the build counted them; out5[2] those
+ * of them that the host told some launch of the context's last render call to fold that way (all or none: the host's decision, not a
+ * count by the render kernel); out5[3] the tables built so far; out5[4] 1 if some launch of the last render call took the table.
+ * Waits for the context's last render. */
+int lt_hip_clear_item_counts(lt_hip_context* ctx, uint64_t* out5);
+
+/* The item table and its fold map on the host, for tests: marks[p] is word 0 of the list of the square at hand-out position p < n
+ * (0xffffffff: clear), order[p] that square's index (NULL: p), groups the frame groups of the launch.  table: 16 + n * groups
+ * words -- words 0 .. 7 the entry counts of the eight shares, the entries of share x from word 16 + (start of x) * groups, an entry
+ * (place in the share) * groups + group, bit 31 set for a whole square.  map (NULL: none): one byte per 8-pixel row segment of
+ * tiles_in_call stacked tiles of tile_w x tile_h pixels (tile_w a multiple of 8; n their 8x8 squares), 1 in a whole square.  No GPU. */
+int lt_hip_clear_items_test_host(const uint32_t* marks, const uint32_t* order, uint32_t n, uint32_t groups, uint32_t tile_w, uint32_t tile_h,
+                                 uint32_t tiles_in_call, uint32_t* table, uint8_t* map);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,16 +155,8 @@ __global__ void lt_running_mean_kernel(const float* __restrict__ samples, uint32
     if ((tile % fp.tilesX) * fp.tileW + lx >= fp.width || (tile / fp.tilesX) * fp.tileH + ly >= fp.height) return;
   }
   float acc = base > 0 ? out[i] : 0.0f;
-  for (uint32_t f = 0; f < n; f++) {
-    const float c = samples[(uint64_t)f * stride + i];
-    const int32_t N = base + (int32_t)f;
-    if (N <= 0) {
-      acc = c;
-    } else {
-      const float nf = (float)N, n1 = (float)(N + 1);
-      acc = (c + (acc * nf)) / n1;
-    }
-  }
+  for (uint32_t f = 0; f < n; f++)
+    acc = running_mean_step(acc, samples[(uint64_t)f * stride + i], base + (int32_t)f);
   out[i] = acc;
 }
 
@@ -174,16 +166,16 @@ __global__ void lt_running_mean_kernel(const float* __restrict__ samples, uint32
 // the floats' own alignment) and has four frames' loads in flight before the first divide that depends on them; per float the
 // expression and the order of the frames are lt_running_mean_kernel's.  The thread whose four floats would pass `floats` folds what
 // is left of them one by one.
+// map: the fold map of the launch's item table (lt_entry_cut.hpp: fold_segment), or null.  A quad lies in one 24-float segment; where
+// the segment's byte is set the wave that rendered the square has folded these samples into `out` itself (render_square), and
+// the sample images hold nothing for them: the thread leaves at once.
 struct __attribute__((packed, aligned(4))) MeanQuad { float v[4]; };
 __global__ __launch_bounds__(256) void lt_running_mean4_kernel(const float* __restrict__ samples, uint32_t n, uint64_t stride, float* __restrict__ out,
-                                                               uint64_t first, uint64_t floats, int32_t base) {
+                                                               uint64_t first, uint64_t floats, int32_t base, const unsigned char* __restrict__ map) {
   const uint64_t i = first + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4u;
   if (i >= floats) return;
-  auto fold = [&](float acc, float c, int32_t N) {
-    if (N <= 0) return c;
-    const float nf = (float)N, n1 = (float)(N + 1);
-    return (c + (acc * nf)) / n1;
-  };
+  if (map != nullptr && map[lt_entry_cut::fold_segment_of_float(i)] != 0) return;
+  auto fold = [&](float acc, float c, int32_t N) { return running_mean_step(acc, c, N); };
   if (i + 4u > floats) {
     for (uint64_t j = i; j < floats; j++) {
       float acc = base > 0 ? out[j] : 0.0f;
@@ -210,6 +202,58 @@ __global__ __launch_bounds__(256) void lt_running_mean4_kernel(const float* __re
     acc.x = fold(acc.x, c.v[0], N); acc.y = fold(acc.y, c.v[1], N); acc.z = fold(acc.z, c.v[2], N); acc.w = fold(acc.w, c.v[3], N);
   }
   *(float4*)(out + i) = acc;
+}
+
+// The item table and the fold map of a set of entry cuts (lt_entry_cut.hpp: kItemWhole, fold_segment; FrameParams::itemTable), for
+// launches of `groups` frame groups per square: workgroup x compacts the share of XCD x in the share's order -- per square its
+// entries (item_entries: one where word 0 of the square's list is the clear mark), an exclusive scan of those counts 1024 squares
+// at a time, item_write at the scanned place -- and leaves the share's length in word x of the table.  map, where not null: the
+// byte of every segment of every square, 1 for a square handed out whole.  stats: [0] entries, [1] squares handed out whole.
+constexpr uint32_t kItemThreads = 1024u;
+__global__ __launch_bounds__(kItemThreads) void lt_clear_items_kernel(const uint32_t* __restrict__ cuts, FrameParams fp, uint32_t groups,
+                                                                      uint32_t* __restrict__ items, unsigned char* __restrict__ map,
+                                                                      unsigned long long* __restrict__ stats) {
+  using namespace lt_entry_cut;
+  __shared__ uint32_t waveSum[kItemThreads / kBlock], wholeSquares;
+  const uint32_t xcd = blockIdx.x, tid = threadIdx.x, lane = tid % kBlock, wave = tid / kBlock;
+  const uint32_t share = xcd_share_size(fp.totalSquares, xcd), start = xcd_share_start(fp.totalSquares, xcd);
+  uint32_t* const dst = items + kItemHeader + (size_t)start * groups;
+  if (tid == 0u) wholeSquares = 0u;
+  uint32_t base = 0u;
+  for (uint32_t chunk = 0u; chunk < share; chunk += kItemThreads) {
+    const uint32_t local = chunk + tid;
+    const bool in = local < share;
+    const uint32_t word0 = in ? cuts[(size_t)(start + local) * kListWords] : 0u;
+    const uint32_t count = in ? item_entries(word0, groups) : 0u;
+    uint32_t incl = count;
+    for (uint32_t d = 1u; d < (uint32_t)kBlock; d <<= 1) {
+      const uint32_t v = (uint32_t)__shfl_up((int)incl, d);
+      if (lane >= d) incl += v;
+    }
+    __syncthreads();   // (the sums of the chunk before have been read)
+    if (lane == (uint32_t)kBlock - 1u) waveSum[wave] = incl;
+    const unsigned long long wholeLanes = __builtin_amdgcn_ballot_w64(in && item_whole(word0));
+    if (lane == 0u && wholeLanes != 0ull) atomicAdd(&wholeSquares, (uint32_t)__popcll(wholeLanes));
+    __syncthreads();
+    uint32_t before = 0u, total = 0u;
+    for (uint32_t w = 0u; w < kItemThreads / kBlock; w++) {
+      before += w < wave ? waveSum[w] : 0u;
+      total += waveSum[w];
+    }
+    if (in) {
+      item_write(dst + base + before + incl - count, word0, local, groups);
+      if (map != nullptr)
+        fold_mark_square(map, fp.order ? fp.order[start + local] : start + local, fp.blocksPerTileX, fp.blocksPerTile, fp.tileW, fp.tileH,
+                         item_whole(word0) ? 1 : 0);
+    }
+    base += total;
+  }
+  __syncthreads();
+  if (tid == 0u) {
+    items[xcd] = base;
+    atomicAdd(&stats[0], (unsigned long long)base);
+    atomicAdd(&stats[1], (unsigned long long)wholeSquares);
+  }
 }
 
 // The walks' slab tests compare against the smallest positive float (`tExit >= max(tEnter, 0x00000001)`: "tExit > 0" in one
@@ -350,6 +394,24 @@ struct lt_hip_context {
   uint32_t cuts_chunks = 0;          // RenderKnobs::entry_cut_chunks of that build, likewise: the planes of d_cuts that it wrote
   uint32_t cuts_node_chunks = 0;     // RenderKnobs::entry_cut_node_chunks of that build, likewise
   uint64_t cut_builds = 0;          // launches of lt_entry_cut_kernel so far (lt_hip_entry_cut_counts)
+  // The item table of those cuts and its fold map (lt_clear_items_kernel; ensure_clear_items): valid while cuts_valid is and for the
+  // launches they were built for -- items_groups frame groups per square (0: none built since the cuts were), items_folds: with a map.
+  uint32_t* d_items = nullptr;
+  uint64_t items_words = 0;
+  uint32_t* d_foldmap = nullptr;     // (bytes, four to a word: render_kernel_body reads words, lt_running_mean4_kernel bytes)
+  uint64_t foldmap_words = 0;
+  uint32_t items_groups = 0;
+  bool items_folds = false;
+  unsigned long long* d_item_stats = nullptr;   // [0] the table's entries, [1] the squares it hands out whole
+  uint64_t item_builds = 0;          // launches of lt_clear_items_kernel so far
+  bool last_folded = false;          // some launch of the context's last render call was told to have the whole squares fold their own samples
+  bool last_tabled = false;          // ... and some launch of it took the table (lt_hip_clear_item_counts)
+  // Whether the table is worth taking is a matter of how many squares are clear, which only the device knows: the build's counters
+  // come back by an asynchronous copy into pinned memory with an event behind it, and a later launch that finds the event done reads
+  // them (ensure_clear_items).  -1: not known yet; dropped with the cuts.
+  unsigned long long* h_item_stats = nullptr;
+  hipEvent_t items_ev = nullptr;
+  int items_worth = -1;
   uint64_t scene_generation = 0;     // goes up whenever a resident scene buffer or an array derived from one is written or given back
   hipEvent_t render_ev = nullptr;    // behind the last launch of the last render call, on render_stream: a render on another stream waits for it
   hipStream_t render_stream = nullptr;
@@ -500,6 +562,11 @@ extern "C" int lt_hip_destroy(lt_hip_context* ctx) {
   if (ctx->d_camhits) (void)hipFree(ctx->d_camhits);
   if (ctx->d_cuts) (void)hipFree(ctx->d_cuts);
   if (ctx->d_cut_stats) (void)hipFree(ctx->d_cut_stats);
+  if (ctx->d_items) (void)hipFree(ctx->d_items);
+  if (ctx->d_foldmap) (void)hipFree(ctx->d_foldmap);
+  if (ctx->d_item_stats) (void)hipFree(ctx->d_item_stats);
+  if (ctx->h_item_stats) (void)hipHostFree(ctx->h_item_stats);
+  if (ctx->items_ev) (void)hipEventDestroy(ctx->items_ev);
   if (ctx->render_ev) (void)hipEventDestroy(ctx->render_ev);
   if (ctx->d_groupWalks) (void)hipFree(ctx->d_groupWalks);
   if (ctx->d_shadowq) (void)hipFree(ctx->d_shadowq);
@@ -1163,6 +1230,9 @@ struct RenderKnobs {
                                         // leaf pass may visit per square, for measurements (1, or unset: 512)
   uint32_t entry_cut_chunks = (uint32_t)lt_entry_cut::kDefaultChunks;   // LT_ENTRY_CUT_CHUNKS=1..16: the 64-byte records a square's list may take (lt_entry_cut.hpp: Chunks)
   uint32_t entry_cut_node_chunks = (uint32_t)lt_entry_cut::kDefaultNodeChunks;   // LT_ENTRY_CUT_NODE_CHUNKS=1..16: the records of a list of nodes at most
+  bool clear_items = !env_off("LT_CLEAR_ITEMS");   // off: no item table -- a clear square is `groups` claims and stores its samples (ensure_clear_items)
+  bool clear_items_fold = true;         // LT_CLEAR_ITEMS=2: the table's hand-out alone -- whole squares store their samples, the fold reads them
+  bool clear_items_force = false;       // LT_CLEAR_ITEMS=1 or 2: the table however few squares are clear (unset: only where a third of them are)
   uint32_t shadow_frames = 2;           // LT_SHADOW_FRAMES=1..2: frames per work item whose shadow rays walk together (launch_walk)
   bool debug_shadow_frames = getenv("LT_DEBUG_SHADOW_FRAMES") != nullptr;   // launch_walk prints the frame groups of every render launch
                                                                             // and, where there are groups, how many waves walked them together
@@ -1180,6 +1250,10 @@ struct RenderKnobs {
     if (const char* e = getenv("LT_ENTRY_CUT_CHUNKS")) entry_cut_chunks = (uint32_t)std::max(1, std::min(lt_entry_cut::kMaxChunks, atoi(e)));
     if (const char* e = getenv("LT_ENTRY_CUT_NODE_CHUNKS")) entry_cut_node_chunks = (uint32_t)std::max(1, std::min(lt_entry_cut::kMaxChunks, atoi(e)));
     entry_cut_node_chunks = std::min(entry_cut_node_chunks, entry_cut_chunks);   // (a list of nodes takes no more records than a list may)
+    if (const char* e = getenv("LT_CLEAR_ITEMS")) {
+      clear_items_fold = atoi(e) != 2;
+      clear_items_force = atoi(e) != 0;
+    }
     if (const char* e = getenv("LT_SHADOW_FRAMES")) shadow_frames = (uint32_t)std::max(1, std::min(2, atoi(e)));
   }
 };
@@ -1322,7 +1396,8 @@ static void launch_program(const RenderCall& c, const SceneDev& sc, const FrameP
     else if (c.stats && c.deep) launch(Config<true, true, M>{});
     else if (c.stats) launch(Config<false, true, M>{});
     else if constexpr (PROGRAM == kAccumulator) {
-      if (fp.shadowFrames > 1u) launch(Config<false, false, M, false, true>{});   // (frame groups: a kernel of their own)
+      if (fp.shadowFrames > 1u && fp.itemTable != nullptr) launch(Config<false, false, M, false, true, true>{});   // (... from an item table: likewise)
+      else if (fp.shadowFrames > 1u) launch(Config<false, false, M, false, true>{});   // (frame groups: a kernel of their own)
       else launch(Config<false, false, M>{});
     } else launch(Config<false, false, M>{});
   });
@@ -1565,17 +1640,23 @@ struct ReadBack {
   bool foldPieced = false;        // the call's last fold came in the pieces, an event behind each (launch_running_mean)
 };
 
+// The fold of a fused launch runs four floats per thread (lt_running_mean4_kernel) where every float of the range is folded and `out`
+// takes 16-byte stores.  (Every range launch_running_mean cuts begins at a multiple of four floats: the pieces' bounds are multiples
+// of 4096 bytes.)
+static bool mean_in_quads(uint32_t depth, bool paddedTiles, const float* out) { return depth == 3u && !paddedTiles && (uintptr_t)out % 16u == 0u; }
+
 // Folds the nf sample images a fused launch left in ctx->d_samples into `out` (timed by its own event pair, so that
-// lt_hip_stats::render_ms can leave it out).
+// lt_hip_stats::render_ms can leave it out).  map: the fold map the launch folded its whole squares by (ensure_clear_items: only
+// where the quads run), or null.
 static int launch_running_mean(lt_hip_context* ctx, hipStream_t s, const FrameParams& fp, uint64_t floats, uint32_t nf, int32_t base,
-                               bool paddedTiles, float* out, ReadBack* rb) {
+                               bool paddedTiles, float* out, ReadBack* rb, const unsigned char* map) {
   const uint32_t threads = 256;
-  // four floats per thread (lt_running_mean4_kernel) where every float of the range is folded and `out` takes 16-byte stores; the
-  // pieces' bounds are multiples of 4096 bytes, so a piece that starts aligned is followed by aligned ones
-  const bool quads = fp.depth == 3u && !paddedTiles && (uintptr_t)out % 16u == 0u;
+  const bool quads = mean_in_quads(fp.depth, paddedTiles, out);
+  // (what the render launch folded is skipped by the quads alone: every range below then begins at a multiple of four floats)
+  if (map != nullptr && (!quads || (rb && rb->piece % 16u != 0u))) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "a fold map without the four-float fold");
   auto launch = [&](uint64_t lo, uint64_t hi) {
     if (quads && lo % 4u == 0u)
-      lt_running_mean4_kernel<<<dim3((uint32_t)((hi - lo + 4u * threads - 1) / (4u * threads))), dim3(threads), 0, s>>>(ctx->d_samples, nf, floats, out, lo, hi, base);
+      lt_running_mean4_kernel<<<dim3((uint32_t)((hi - lo + 4u * threads - 1) / (4u * threads))), dim3(threads), 0, s>>>(ctx->d_samples, nf, floats, out, lo, hi, base, map);
     else
       lt_running_mean_kernel<<<dim3((uint32_t)((hi - lo + threads - 1) / threads)), dim3(threads), 0, s>>>(ctx->d_samples, nf, floats, out, lo, hi, base, fp,
                                                                                                        paddedTiles ? 1 : 0);
@@ -1810,10 +1891,14 @@ static int calibrate_shadow_walk(lt_hip_context* ctx, RenderCall& c, SceneDev& s
 // FrameParams, field by field: camx .. yaw, width, height (camera_ray), tileW .. totalSquares (square_pixel), order, orderHead and
 // persistent (the hand-out), ldsRows (the walk's stack) are in the key; depth, clampOutput, giMaxDepth, pixelCounters and squareMajor do
 // not reach a camera hit and are in it all the same; frameCount, accumulateN, fusedFrames, frameStride, shadowFrames, storeHeadHits,
-// the cameraHits and entryCuts pointers and entryCutPlane and entryCutChunks, which say how to read entryCuts, are cleared.  (The
+// the cameraHits and entryCuts pointers and entryCutPlane and entryCutChunks, which say how to read entryCuts, and the item table's and the
+// fold's fields (itemTable .. itemGroups), which are set per launch, are cleared.  (The
 // entry cuts kept with the hits are a function of the hits, of the scene's primitives, lights and own tree -- the scene generation
 // -- and of the knobs of their build, which launch_camera_hits compares by themselves.)
-static_assert(sizeof(FrameParams) == 200 && offsetof(FrameParams, entryCutChunks) + sizeof(uint32_t) == sizeof(FrameParams) &&
+static_assert(sizeof(FrameParams) == 232 && offsetof(FrameParams, entryCutChunks) + sizeof(uint32_t) == offsetof(FrameParams, itemTable) &&
+                  offsetof(FrameParams, itemTable) + 8 == offsetof(FrameParams, foldMap) && offsetof(FrameParams, foldMap) + 8 == offsetof(FrameParams, foldOut) &&
+                  offsetof(FrameParams, foldOut) + 8 == offsetof(FrameParams, foldBase) && offsetof(FrameParams, foldBase) + 4 == offsetof(FrameParams, itemGroups) &&
+                  offsetof(FrameParams, itemGroups) + sizeof(uint32_t) == sizeof(FrameParams) &&
                   offsetof(FrameParams, entryCuts) + sizeof(const uint32_t*) == offsetof(FrameParams, entryCutPlane) &&
                   offsetof(FrameParams, entryCutPlane) + sizeof(uint32_t) == offsetof(FrameParams, entryCutChunks) &&
                   offsetof(FrameParams, storeHeadHits) + sizeof(uint32_t) == offsetof(FrameParams, entryCuts),
@@ -1822,6 +1907,7 @@ static std::vector<unsigned char> camera_hits_key(const lt_hip_context* ctx, con
   FrameParams f = pass;
   f.frameCount = 0; f.accumulateN = 0; f.fusedFrames = 0; f.frameStride = 0; f.shadowFrames = 0; f.storeHeadHits = 0; f.cameraHits = nullptr;
   f.entryCuts = nullptr; f.entryCutPlane = 0; f.entryCutChunks = 0;
+  f.itemTable = nullptr; f.foldMap = nullptr; f.foldOut = nullptr; f.foldBase = 0; f.itemGroups = 0;
   std::vector<unsigned char> key;
   auto put = [&](const void* p, size_t n) { key.insert(key.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
   put(&f, sizeof(f));   // (no padding inside: the assertion above and the fields' natural alignment)
@@ -1872,6 +1958,8 @@ static void set_entry_cuts(const lt_hip_context* ctx, FrameParams& fp, uint32_t 
 }
 static int launch_entry_cuts(lt_hip_context* ctx, const RenderCall& c, const SceneDev& sc, const FrameParams& fh, bool all) {
   ctx->cuts_valid = false;
+  ctx->items_groups = 0;   // (the item table is of the cuts that were: ensure_clear_items builds it again behind this launch)
+  ctx->items_worth = -1;
   // (the timing call builds lists of nodes alone: its planes are those a list of nodes may take)
   const uint32_t chunks = all ? c.k.entry_cut_chunks : c.k.entry_cut_node_chunks;
   const uint64_t lists = c.nblocks * chunks;   // (cuts_squares counts records: squares times planes)
@@ -1889,6 +1977,55 @@ static int launch_entry_cuts(lt_hip_context* ctx, const RenderCall& c, const Sce
   ctx->cuts_chunks = chunks;
   ctx->cuts_node_chunks = c.k.entry_cut_node_chunks;
   ctx->cut_builds++;
+  return LT_OK;
+}
+
+// The item table of the cuts a reusing call reads (lt_entry_cut.hpp: kItemWhole; lt_clear_items_kernel), for a launch of `groups`
+// frame groups per square: built on the render's stream behind the cuts -- by the first launch that reads them, which is where the
+// number of groups is known, and again by a launch of another number (a call's last, shorter chunk; a call of other frames) -- and
+// kept with them: launch_entry_cuts drops it with the cuts it was made from, and a launch takes it only while cuts_valid holds.  No
+// host synchronisation: the queues' lengths stay in device memory.  fold: the launch is a fused one whose fold runs in quads over a
+// map that is exact for it (render_on_stream); the map is then built with the table and the launch's whole squares fold their
+// own samples into `out` from n = base on.  LT_CLEAR_ITEMS=0: never called.
+// Worth taking only where enough squares are clear.  Where few are -- the Cornell box at 4K -- nearly every entry is a single frame
+// group, as without a table, and each pays the entry's scalar load behind its claim, which items that short cannot hide, and the
+// table kernel's larger code: 0.15 ms on that launch of 1.9.  The count is the device's: the first build's counters
+// are copied back asynchronously, and from the first launch that finds them there a set of cuts with fewer than a third of its
+// squares clear is rendered without the table -- the kernel and the hand-out it had before there was one.  Until then, and under
+// LT_CLEAR_ITEMS=1, the table is taken.  (The pixels are the same either way.)
+static int ensure_clear_items(lt_hip_context* ctx, const RenderCall& c, FrameParams& fp, uint32_t groups, bool fold, uint64_t floats, float* out, int32_t base) {
+  const uint64_t words = lt_entry_cut::kItemHeader + c.nblocks * groups;
+  const uint64_t mapWords = (lt_entry_cut::fold_segment_of_float(floats) + 3u) / 4u;
+  if (ctx->items_worth < 0 && ctx->items_groups != 0u && ctx->items_ev && hipEventQuery(ctx->items_ev) == hipSuccess)
+    ctx->items_worth = 3ull * ctx->h_item_stats[1] >= c.nblocks ? 1 : 0;
+  (void)hipGetLastError();   // (hipErrorNotReady of the query is no error)
+  if (ctx->items_worth == 0 && !c.k.clear_items_force) return LT_OK;
+  if (ctx->items_groups != groups || (fold && !ctx->items_folds)) {
+    ctx->items_groups = 0;
+    LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_items, ctx->items_words, words, words * sizeof(uint32_t)));
+    if (fold) LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_foldmap, ctx->foldmap_words, mapWords, mapWords * sizeof(uint32_t)));
+    if (!ctx->d_item_stats) LT_HIP_CHECK(ctx, hipMalloc(&ctx->d_item_stats, 2 * sizeof(unsigned long long)));
+    LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_item_stats, 0, 2 * sizeof(unsigned long long), c.s));
+    hipLaunchKernelGGL(lt_clear_items_kernel, dim3(8), dim3(kItemThreads), 0, c.s, (const uint32_t*)ctx->d_cuts, fp, groups, ctx->d_items,
+                       fold ? (unsigned char*)ctx->d_foldmap : nullptr, ctx->d_item_stats);
+    LT_HIP_CHECK(ctx, hipGetLastError());
+    if (ctx->items_worth < 0) {
+      if (!ctx->h_item_stats) LT_HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->h_item_stats, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+      if (!ctx->items_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->items_ev, hipEventDisableTiming));
+      LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_item_stats, ctx->d_item_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.s));
+      LT_HIP_CHECK(ctx, hipEventRecord(ctx->items_ev, c.s));
+    }
+    ctx->items_groups = groups;
+    ctx->items_folds = fold;
+    ctx->item_builds++;
+  }
+  fp.itemTable = ctx->d_items;
+  fp.itemGroups = groups;
+  if (fold) {
+    fp.foldMap = ctx->d_foldmap;
+    fp.foldOut = out;
+    fp.foldBase = base;
+  }
   return LT_OK;
 }
 
@@ -2023,6 +2160,8 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
     float* const out = fused ? ctx->d_samples : out_device;
     const dim3 grid(k.persistent ? (uint32_t)std::min<uint64_t>(nblocks * nf, resident) : (uint32_t)nblocks);
     uint32_t* queues = k.persistent ? ctx->d_queues + (size_t)launchIndex * 8 * kQueueStride : nullptr;
+    const unsigned char* foldMap = nullptr;   // the map this launch folds its whole squares by, and its fold skips them by
+    bool tabled = false;                      // this launch hands out from the item table
     if (fu.giWavefront) {
       SceneDev scGi = sc;
       scGi.shadowPackets = k.shadow_packets >= 0 ? sc.shadowPackets : 0u;   // the pipeline's bounce stages cast incoherent shadow rays: per lane
@@ -2036,9 +2175,23 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
       const hipFunction_t fn = devlibm == 2 ? up.lds : devlibm == 1 ? up.ldsStrict : up.ldsPortable;
       LT_HIP_CHECK(ctx, hipModuleLaunchKernel(fn, grid.x, 1, 1, kBlock, 1, 1, lds, s, args, nullptr));
     } else {
+      // The item table (ensure_clear_items): for a launch of frame groups over the kept cuts of a reusing call -- every square stored
+      // (launch_camera_hits has cleared orderHead), square-major, walk 1 or 2 as forced or remembered (not the launch that times the
+      // walks: its candidates run one after the other into the same output) -- whose entries fit 31 bits.  Folding by the items themselves on
+      // top of it: a fused launch whose fold runs in quads over whole 8-pixel segments.
+      FrameParams fl = fp;
+      const uint32_t groups = (nf + 1u) / 2u;
+      if (k.clear_items && k.persistent && !stats && d->program == LT_PROGRAM_ACCUMULATOR && (shadowMode == 1 || shadowMode == 2) && fp.entryCuts != nullptr && ctx->cuts_valid && fp.cameraHits != nullptr &&
+          std::all_of(fp.orderHead, fp.orderHead + 8, [](uint32_t h) { return h == 0u; }) && std::min(shadowGroup, k.shadow_frames) >= 2u &&
+          nf >= 2u && fp.squareMajor != 0u && nblocks * groups < 0x80000000ull) {
+        const bool fold = k.clear_items_fold && fused && mean_in_quads(fp.depth, paddedTiles, out_device) && p.tileW % 8u == 0u;
+        if (const int rc = ensure_clear_items(ctx, call, fl, groups, fold, p.floats, out_device, (int32_t)(d->accumulate_base + f))) return rc;
+      }
+      foldMap = (const unsigned char*)fl.foldMap;
+      tabled = fl.itemTable != nullptr;
       if (shadowMode < 0 && calibrate)
         if (const int rc = calibrate_shadow_walk(ctx, call, sc, fp, grid, out, queues, queueOk, shadowKey, shadowMode, shadowGroup)) return rc;
-      if (const int rc = launch_walk(ctx, call, sc, (uint32_t)std::max(0, shadowMode), shadowGroup, fp, grid, out, queues)) return rc;
+      if (const int rc = launch_walk(ctx, call, sc, (uint32_t)std::max(0, shadowMode), shadowGroup, fl, grid, out, queues)) return rc;
     }
     LT_HIP_CHECK(ctx, hipGetLastError());
     call.launches++;
@@ -2047,8 +2200,10 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
       fp.storeHeadHits = 0u;
     }
     if (fused)
-      if (const int rc = launch_running_mean(ctx, s, fp, p.floats, nf, (int32_t)(d->accumulate_base + f), paddedTiles, out_device, f + nf >= frames ? rb : nullptr))
+      if (const int rc = launch_running_mean(ctx, s, fp, p.floats, nf, (int32_t)(d->accumulate_base + f), paddedTiles, out_device, f + nf >= frames ? rb : nullptr, foldMap))
         return rc;
+    ctx->last_folded = (launchIndex != 0 && ctx->last_folded) || foldMap != nullptr;
+    ctx->last_tabled = (launchIndex != 0 && ctx->last_tabled) || tabled;
     f += nf;
   }
   LT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, s));
@@ -3599,6 +3754,56 @@ extern "C" int lt_hip_entry_cut_pruned_test_host(const uint32_t* refs, const uin
   for (uint32_t v = 0; v < n; v++)
     if ((int)refs[v] < 0 && survives[v]) lt_entry_cut::pruned_mark(parents, mark.data(), v);
   *count = lt_entry_cut::pruned_cut_select(refs, kids, mark.data(), cap, entry.data(), depth.data(), out);
+  return LT_OK;
+}
+
+// Of the item table the context holds now (ensure_clear_items): out5[0] its entries and out5[1] the squares it hands out whole, as
+// lt_clear_items_kernel counted them; out5[2] those of them that the host told some launch of the context's last render call to fold
+// by their own wave (all or none: the host's decision, not a count by the render kernel -- that a launch did as told is what the
+// pixels show); out5[3] the tables built so far; out5[4] 1 if some launch of the last render call took the table.
+extern "C" int lt_hip_clear_item_counts(lt_hip_context* ctx, uint64_t* out5) {
+  uint64_t* const out4 = out5;
+  if (!ctx || !out5) return LT_ERR_INVALID_ARGUMENT;
+  out4[0] = out4[1] = out4[2] = 0;
+  out5[4] = ctx->last_tabled ? 1 : 0;
+  out4[3] = ctx->item_builds;
+  if (ctx->cuts_valid && ctx->items_groups != 0u && ctx->d_item_stats) {
+    LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (ctx->render_ev_recorded) LT_HIP_CHECK(ctx, hipEventSynchronize(ctx->render_ev));
+    unsigned long long h[2];
+    LT_HIP_CHECK(ctx, hipMemcpy(h, ctx->d_item_stats, sizeof(h), hipMemcpyDeviceToHost));
+    out4[0] = h[0];
+    out4[1] = h[1];
+    out4[2] = ctx->last_folded ? h[1] : 0;
+  }
+  return LT_OK;
+}
+
+// lt_entry_cut.hpp's item table and fold map as the host compiles them (item_entries, item_write, fold_mark_square), share by share
+// as lt_clear_items_kernel lays them out: marks[p] is word 0 of the list of the square at hand-out position p < n, order[p] its
+// square index (null: p).  table: room for 16 + n * groups words; map (null: none): a byte per segment of tiles_in_call stacked
+// tiles of tile_w x tile_h pixels, tile_w a multiple of 8.
+extern "C" int lt_hip_clear_items_test_host(const uint32_t* marks, const uint32_t* order, uint32_t n, uint32_t groups, uint32_t tile_w, uint32_t tile_h,
+                                            uint32_t tiles_in_call, uint32_t* table, uint8_t* map) {
+  if (!marks || !table || groups == 0 || (uint64_t)n * groups >= 0x80000000ull) return LT_ERR_INVALID_ARGUMENT;
+  const uint32_t bptx = (tile_w + 7u) / 8u, bpty = (tile_h + 7u) / 8u;
+  if (map && (tile_w == 0 || tile_w % 8u != 0 || tile_h == 0 || (uint64_t)tiles_in_call * bptx * bpty != n)) return LT_ERR_INVALID_ARGUMENT;
+  for (uint32_t xcd = 0; xcd < 8u; xcd++) {
+    const uint32_t share = xcd_share_size(n, xcd), start = xcd_share_start(n, xcd);
+    uint32_t* const dst = table + lt_entry_cut::kItemHeader + (size_t)start * groups;
+    uint32_t at = 0;
+    for (uint32_t local = 0; local < share; local++) {
+      const uint32_t word0 = marks[start + local];
+      lt_entry_cut::item_write(dst + at, word0, local, groups);
+      at += lt_entry_cut::item_entries(word0, groups);
+      if (map) {
+        const uint32_t b = order ? order[start + local] : start + local;
+        if (b >= n) return LT_ERR_INVALID_ARGUMENT;
+        lt_entry_cut::fold_mark_square(map, b, bptx, bptx * bpty, tile_w, tile_h, lt_entry_cut::item_whole(word0) ? 1 : 0);
+      }
+    }
+    table[xcd] = at;
+  }
   return LT_OK;
 }
 

@@ -770,7 +770,7 @@ __device__ __forceinline__ bool own_walk_step_all(const SceneDev& sc, const Ray&
 }
 
 // Compile-time configuration of one kernel instantiation.
-template <bool DEEP_, bool STATS_, int DEVLIBM_, bool LDSSCENE_ = false, bool GROUPS_ = false>
+template <bool DEEP_, bool STATS_, int DEVLIBM_, bool LDSSCENE_ = false, bool GROUPS_ = false, bool ITEMS_ = false>
 struct Config {
   static constexpr bool kDeep = DEEP_;       // BVH deeper than the LDS stack: spill entries >= kLdsStack to scratch
   static constexpr bool kStats = STATS_;     // count rays / node visits / triangle tests
@@ -779,6 +779,10 @@ struct Config {
   // accumulator's launches with frame groups (FrameParams::shadowFrames > 1) only: the two-frame shading and walk live in a kernel of
   // their own, so that the one-frame kernel keeps its registers and code (with them it spilled more, and colonnade lost 4 %)
   static constexpr bool kGroups = GROUPS_;
+  // ... and of those the launches that hand out from an item table (FrameParams::itemTable): again a kernel of their own, so that
+  // the kernel without a table keeps its registers and code (with the table's state in it, it ran 0.04 ms slower on the flagship
+  // with the table switched off)
+  static constexpr bool kItems = ITEMS_;
 };
 
 template <int PROGRAM, bool DEEP, bool STATS, bool SHADOW, bool LDSSCENE = false>
@@ -1698,7 +1702,26 @@ struct FrameParams {
   // builder's values (LT_ENTRY_CUT_CHUNKS), set with entryCuts: the same for every frame of every call that reads those cuts.
   uint32_t entryCutPlane;    // words between the planes, totalSquares * 16
   uint32_t entryCutChunks;   // >= 1 where entryCuts is set
+  // The item table of those cuts (lt_entry_cut.hpp: kItemWhole; lt_clear_items_kernel), built for itemGroups frame groups per
+  // square: a queue's claims index its share of the table instead of the square-major arithmetic, and a square marked clear is ONE
+  // entry, whose wave runs all its frame groups.  Null: no table (render_kernel_body hands out as it always did).
+  const uint32_t* itemTable;
+  // ... and where the wave that renders such a square folds its samples into the running mean itself instead of storing them: the fold map (lt_entry_cut.hpp:
+  // fold_segment; four bytes to a word), the running mean the launch's samples are folded into (the caller's output, depth 3) and
+  // the n of the launch's first frame (accumulate_base + its index in the call).  foldMap null: every item stores its samples.
+  const uint32_t* foldMap;
+  float* foldOut;
+  int32_t foldBase;
+  uint32_t itemGroups;
 };
+
+// One step of the running mean, accumulator.frag:10-20: the mean of n + 1 samples from the mean of n and sample c (n <= 0: c is
+// the first).  The one expression of lt_running_mean_kernel, lt_running_mean4_kernel and render_square's fold of a whole square.
+__host__ __device__ inline float running_mean_step(float acc, float c, int32_t n) {
+  if (n <= 0) return c;
+  const float nf = (float)n, n1 = (float)(n + 1);
+  return (c + (acc * nf)) / n1;
+}
 
 // Camera ray of pixel (x,y): acc.cl:304-312.
 template <int DEVLIBM>

@@ -376,4 +376,39 @@ LT_EC_HD inline unsigned pruned_cut_select(const unsigned* ref, const unsigned s
   return n;
 }
 
+// The item table of a kept set of cuts (lt_clear_items_kernel; render_kernel_body).  A launch of `groups` frame groups per stored
+// square hands out, per XCD share and in the share's order, ONE entry for a square marked clear -- the wave that takes it runs the
+// square's frame groups one after the other -- and `groups` entries for any other square, one per frame group.  An entry is the
+// index the square-major hand-out without a table gives that item, local * groups + group (local: the square's place in its
+// share), with kItemWhole set for a whole square; a share's entries lie from word kItemHeader + share start * groups of the table,
+// and words 0 .. 7 hold the eight shares' entry counts.
+constexpr unsigned kItemWhole = 0x80000000u;
+constexpr unsigned kItemHeader = 16u;
+LT_EC_HD inline bool item_whole(unsigned word0) { return word0 == kClearMark; }
+LT_EC_HD inline unsigned item_entries(unsigned word0, unsigned groups) { return item_whole(word0) ? 1u : groups; }
+// Writes a square's entries at dst (item_entries of them).
+LT_EC_HD inline void item_write(unsigned* dst, unsigned word0, unsigned local, unsigned groups) {
+  if (item_whole(word0)) {
+    dst[0] = (local * groups) | kItemWhole;
+    return;
+  }
+  for (unsigned g = 0; g < groups; g++) dst[g] = local * groups + g;
+}
+
+// The fold map that goes with a table: one byte per 8-pixel row segment of the tile-stacked output (tileW a multiple of 8, three
+// floats per pixel: a segment is 24 floats, six whole quads of lt_running_mean4_kernel), 1 where the segment's square is handed
+// out whole -- its samples are then folded into the running mean by the wave that renders it and never stored -- else 0.  Row ly of the
+// stacked tile k, square column sbx; and the segment a float of the output lies in.
+constexpr unsigned kFoldSegmentFloats = 24u;
+LT_EC_HD inline unsigned long long fold_segment(unsigned k, unsigned tileH, unsigned tileW, unsigned ly, unsigned sbx) {
+  return ((unsigned long long)k * tileH + ly) * (tileW / 8u) + sbx;
+}
+LT_EC_HD inline unsigned long long fold_segment_of_float(unsigned long long i) { return i / kFoldSegmentFloats; }
+// Marks the (up to eight) segments of square b = (tile k, square sb of the tile) with `mark`.
+LT_EC_HD inline void fold_mark_square(unsigned char* map, unsigned b, unsigned blocksPerTileX, unsigned blocksPerTile, unsigned tileW,
+                                      unsigned tileH, unsigned char mark) {
+  const unsigned k = b / blocksPerTile, sb = b % blocksPerTile, sbx = sb % blocksPerTileX, sby = sb / blocksPerTileX;
+  for (unsigned r = 0; r < 8u && sby * 8u + r < tileH; r++) map[fold_segment(k, tileH, tileW, sby * 8u + r, sbx)] = mark;
+}
+
 }  // namespace lt_entry_cut

@@ -51,12 +51,15 @@ __device__ __forceinline__ bool square_pixel(const FrameParams& fp, uint32_t b, 
 // (pos: the square's position in the hand-out order -- what a queued shadow ray's slot is made of, SceneDev::shadowPackets == 3;
 // hitRow: the square's stored camera hits, FrameParams::cameraHits, or null; frames: 2 for a work item of two frames, frame and
 // frame + 1, of accumulator over stored hits -- FrameParams::shadowFrames -- else 1; cut: the square's entry cut, FrameParams::entryCuts,
-// or null)
+// or null; folding: the item is a frame group of a square handed out whole whose samples are not stored -- FrameParams::foldMap -- but
+// folded by the wave itself, frame by frame in frame order, into the running mean at fp.foldOut: the wave runs the square's groups
+// one after the other, so between them the mean waits in the words it ends up in, which no one else touches during the launch)
 template <int PROGRAM, class CFG>
 __device__ __forceinline__ void render_square(const SceneDev& sc, const FrameParams& fp, float* __restrict__ out, uint32_t b,
                                               uint32_t frame, uint32_t frames, Stack<CFG::kDeep>& st, Counters& c, uint32_t pos,
-                                              const uint4* hitRow, const uint32_t* cut) {
+                                              const uint4* hitRow, const uint32_t* cut, bool folding) {
   constexpr bool STATS = CFG::kStats;
+  const bool fold = PROGRAM == kAccumulator && CFG::kGroups && CFG::kItems && !STATS && folding;
   const uint32_t k = b / fp.blocksPerTile, sb = b % fp.blocksPerTile;
   const uint32_t sbx = sb % fp.blocksPerTileX, sby = sb / fp.blocksPerTileX;
   const uint32_t tile = fp.tileFirst + k * fp.tileStride;
@@ -78,15 +81,18 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
   if (valid) {
     Counters pc{};   // this pixel's own counters (diagnostic output), folded into the lane's totals below
     const uint32_t pixel = (k * fp.tileH + ly) * fp.tileW + lx;
-    float* o = out + (size_t)frame * fp.frameStride + (((size_t)k * fp.tileH + ly) * fp.tileW + lx) * fp.depth;
-    auto store = [&](float* d, const V3& color) {
-      if (fp.accumulateN <= 0) {   // overwrite, or first frame of a running mean (`if (frameCount > 0)` guard)
+    const size_t first = (((size_t)k * fp.tileH + ly) * fp.tileW + lx) * fp.depth;
+    float* o = out + (size_t)frame * fp.frameStride + first;
+    auto store = [&](uint32_t f, const V3& color) {   // the colour of frame f of the launch
+      // (a folded frame: lt_running_mean4_kernel's step on the mean itself, n = foldBase + f)
+      float* d = fold ? fp.foldOut + first : o + (size_t)(f - frame) * fp.frameStride;
+      const int32_t n = fold ? fp.foldBase + (int32_t)f : fp.accumulateN;
+      if (n <= 0) {   // overwrite, or first frame of a running mean (`if (frameCount > 0)` guard)
         d[0] = color.x; d[1] = color.y; d[2] = color.z;
-      } else {                     // accumulator.frag:12-18: (c + acc*n) / (n+1)
-        const float n = (float)fp.accumulateN, n1 = (float)(fp.accumulateN + 1);
-        d[0] = (color.x + (d[0] * n)) / n1;
-        d[1] = (color.y + (d[1] * n)) / n1;
-        d[2] = (color.z + (d[2] * n)) / n1;
+      } else {        // accumulator.frag:12-18: (c + acc*n) / (n+1)
+        d[0] = running_mean_step(d[0], color.x, n);
+        d[1] = running_mean_step(d[1], color.y, n);
+        d[2] = running_mean_step(d[2], color.z, n);
       }
     };
     bool grouped = false;
@@ -95,8 +101,8 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
         V3 color[2];
         grouped = shade_pixel2<CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, c, hitRow, color, cut);
         if (grouped) {
-          store(o, color[0]);
-          store(o + fp.frameStride, color[1]);
+          store(frame, color[0]);
+          store(frame + 1u, color[1]);
         }
       }
     }
@@ -105,13 +111,13 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
       // compiler keeps: one inlined copy of shade_pixel and its walks)
 #pragma unroll 1
       for (uint32_t f = frame; !grouped && f < frame + frames; f++)
-        store(o + (size_t)(f - frame) * fp.frameStride, shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + f, (int)x, (int)y, st, c, qslot, pixel, f, queued, hitRow, storeRow));
+        store(f, shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + f, (int)x, (int)y, st, c, qslot, pixel, f, queued, hitRow, storeRow));
     } else {
       const V3 color = shade_pixel<PROGRAM, CFG>(sc, fp, fp.frameCount + frame, (int)x, (int)y, st, STATS ? pc : c, qslot, pixel, frame, queued, hitRow, storeRow);
       if (STATS && fp.pixelCounters) {
         o[0] = (float)pc.rays; o[1] = (float)pc.shadow; o[2] = (float)pc.nodes; o[3] = (float)pc.tris;
       } else {
-        store(o, color);
+        store(frame, color);
       }
     }
     if (STATS) {
@@ -179,10 +185,18 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
   const uint32_t home = fp.persistent ? (__builtin_amdgcn_s_getreg((3u << 11) | 20u) & 7u) : 0u;   // HW_REG_XCC_ID
   uint32_t sweep = 0;
   uint32_t claimed = 0, claimedLeft = 0;   // a claim of two indices: the next one, and how many of the claim are left (below)
+  // An entry of the item table that stands for a whole square (FrameParams::itemTable): the wave runs the square's frame groups one
+  // after the other, through this same loop.  One word of state, so that the walks keep their registers: the index of the square's
+  // next group (never 0; a multiple of the groups per square when none is left), and in bit 31 whether its samples are folded
+  // (render_square: fold).  0: no whole square in hand.
+  uint32_t wholeNext = 0u;
+  uint32_t tableLimit = 0u, tableSweep = 8u;   // the length of the queue's share of the table, loaded once per sweep (8: none yet)
+  auto sload = [](const uint32_t* p) { return *(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)p; };
   bool done = false;
   while (!done) {
     uint32_t b, frame = 0, frames = 1, pos = 0;
     bool stored = false;   // the item's camera hits are in fp.cameraHits
+    bool folding = false;  // the item's samples are folded into the running mean by the item itself (render_square)
     if (!fp.persistent) {
       b = xcd_remap(blockIdx.x, gridDim.x);
       pos = b;
@@ -195,8 +209,17 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
       // of a square shorter when the launch's frames are not a multiple of it: `groups` items per square
       const uint32_t group = PROGRAM == kAccumulator && CFG::kGroups && !STATS && !HITS && fp.cameraHits != nullptr && fp.shadowFrames >= 2u ? 2u : 1u;
       const uint32_t groups = (fp.fusedFrames + group - 1u) / group;
+      // With an item table (FrameParams::itemTable; the host sets it for launches whose every square is stored, in square-major order,
+      // and built for this many groups) a claim indexes the queue's share of the table, whose length is in device memory: one scalar
+      // load per sweep.
+      const bool table = PROGRAM == kAccumulator && CFG::kGroups && CFG::kItems && !STATS && !HITS && group == 2u && fp.itemTable != nullptr &&
+                         fp.itemGroups == groups && fp.squareMajor != 0u && head == 0u;
+      if (table && tableSweep != sweep) {
+        tableLimit = sload(fp.itemTable + xcd);
+        tableSweep = sweep;
+      }
       // (head * fusedFrames + (share - head) * groups <= share * fusedFrames < 2^32: checked by the host)
-      const uint32_t limit = HITS ? camera_hit_squares(fp, xcd) : head * fp.fusedFrames + (share - head) * groups;
+      const uint32_t limit = table ? tableLimit : HITS ? camera_hit_squares(fp, xcd) : head * fp.fusedFrames + (share - head) * groups;
       // A claim is an atomic on one of eight addresses, and those complete one after the other, some 15 ns apart: the flagship
       // launch's 129 600 claims per queue are 1.9 ms of that, which the items' work only partly hides.  So a claim
       // takes TWO consecutive indices where the queue has more than four items per wave of the launch (kClaimPair), and the wave
@@ -206,18 +229,43 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
       // (one frame at 4K, 16 items per wave: 1.97 ms with one index per claim, 2.11 with two).  (A counter ends at most two per
       // wave and queue above `limit`, which the host keeps below 2^30 or so: no wrap.)
       uint32_t t = 0;
-      if (claimedLeft == 0u) {
-        const uint32_t take = limit / 4u > gridDim.x ? kClaimPair : 1u;
-        if (threadIdx.x == 0) t = atomicAdd(&queues[xcd * kQueueStride], take);
-        claimed = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-        claimedLeft = take;
-      }
-      t = claimed++;
-      claimedLeft--;
-      if (t >= limit) {
-        claimedLeft = 0u;
-        done = ++sweep >= 8u;
-        continue;
+      if (table && wholeNext != 0u) {   // the next frame group of a whole square: no claim
+        folding = (wholeNext & lt_entry_cut::kItemWhole) != 0u;
+        t = wholeNext & ~lt_entry_cut::kItemWhole;
+        wholeNext = (t + 1u) % groups == 0u ? 0u : wholeNext + 1u;
+      } else {
+        if (claimedLeft == 0u) {
+          // (A table's queue goes out in pairs only while more than half of what it could hold is in it: a queue that whole squares have
+          // thinned out -- the flagship's hold 3 entries per square of 8, 0.7 ms of atomics under a launch of 4 ms -- ran 0.35 ms
+          // slower in pairs, and one that is mostly single frame groups, as without a table, is as claim-bound as without one: the
+          // Cornell box at 4K ran 0.5 ms slower with one entry per claim)
+          const uint32_t take = limit / 4u > gridDim.x && (!table || limit / share > groups / 2u) ? kClaimPair : 1u;
+          if (threadIdx.x == 0) t = atomicAdd(&queues[xcd * kQueueStride], take);
+          claimed = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+          claimedLeft = take;
+        }
+        t = claimed++;
+        claimedLeft--;
+        if (t >= limit) {
+          claimedLeft = 0u;
+          done = ++sweep >= 8u;
+          continue;
+        }
+        if (table) {   // the entry: the index the arithmetic below takes apart, and whether it stands for the whole square
+          const uint32_t entry = sload(fp.itemTable + lt_entry_cut::kItemHeader + (size_t)start * groups + t);
+          t = entry & ~lt_entry_cut::kItemWhole;
+          if ((entry & lt_entry_cut::kItemWhole) != 0u) {
+            // Folded where the fold map says so: the word lt_running_mean4_kernel skips the square's floats by (the byte of the square's
+            // first row; its rows are marked alike).
+            if (fp.foldMap != nullptr) {
+              const uint32_t sq = fp.order ? sload(fp.order + start + t / groups) : start + t / groups;
+              const uint32_t k = sq / fp.blocksPerTile, sb = sq % fp.blocksPerTile;
+              const unsigned long long seg = lt_entry_cut::fold_segment(k, fp.tileH, fp.tileW, sb / fp.blocksPerTileX * 8u, sb % fp.blocksPerTileX);
+              folding = (sload(fp.foldMap + (seg >> 2)) >> (8u * (uint32_t)(seg & 3ull)) & 0xffu) != 0u;
+            }
+            wholeNext = groups == 1u ? 0u : (t + 1u) | (folding ? lt_entry_cut::kItemWhole : 0u);
+          }
+        }
       }
       stored = fp.cameraHits != nullptr && t >= head * fp.fusedFrames;
       // frame-major inside the XCD's share (every frame of a square stays on its XCD), the head squares of all frames first
@@ -243,9 +291,12 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
       pos = b;
       if (fp.order) b = (uint32_t)__builtin_amdgcn_readfirstlane((int)fp.order[b]);
     }
-    if (HITS) camera_hit_square<CFG>(sc, fp, b, pos, st, c);
-    else render_square<PROGRAM, CFG>(sc, fp, out, b, frame, frames, st, c, pos, stored ? fp.cameraHits + (size_t)pos * kBlock : nullptr,
-                                     stored && fp.entryCuts != nullptr ? fp.entryCuts + (size_t)pos * lt_entry_cut::kListWords : nullptr);
+    if (HITS) {
+      camera_hit_square<CFG>(sc, fp, b, pos, st, c);
+    } else {
+      render_square<PROGRAM, CFG>(sc, fp, out, b, frame, frames, st, c, pos, stored ? fp.cameraHits + (size_t)pos * kBlock : nullptr,
+                                  stored && fp.entryCuts != nullptr ? fp.entryCuts + (size_t)pos * lt_entry_cut::kListWords : nullptr, folding);
+    }
   }
   if (STATS) {
     atomicAdd(&stats[0], (unsigned long long)c.rays);

@@ -511,6 +511,15 @@ class RendererHIP:
         return {"chunks": int(out[0]), "leaf": (int(out[1]), int(out[2])), "pruned": (int(out[3]), int(out[4])),
                 "plain": (int(out[5]), int(out[6])), "squares_by_chunks": {k: int(out[6 + k]) for k in range(1, 17)}}
 
+    def clear_item_counts(self):
+        """lt_hip_clear_item_counts, of the item table the context holds now: a dict of `entries` (the table's work items),
+        `whole` (the clear squares it hands out as one item each), `folded` (those of them whose samples the context's last
+        render launch folded by their own wave: all or none) and `builds` (tables built so far).  Waits for the context's last
+        render.  LT_CLEAR_ITEMS=0, or no cuts kept: all but `builds` zero."""
+        out = (ctypes.c_uint64 * 5)()
+        self._check(self._L.lt_hip_clear_item_counts(self._ctx, out))
+        return {"entries": int(out[0]), "whole": int(out[1]), "folded": int(out[2]), "builds": int(out[3]), "used": bool(out[4])}
+
     def scene_structure(self, what):
         """lt_hip_read_scene_structure: 0 own tree (NODE_DTYPE array), 1 leaf order table (n_prims x 8 uint32), 2 the per-lane walks'
         array (bytes), 3 (own height, group-tree height, groups, prepared on the device), 4 the packet walks' records (bytes, 64 per
