@@ -834,6 +834,15 @@ int lt_hip_entry_cut_leaf_counts(lt_hip_context* ctx, uint64_t* out3);
  * squares whose list, of any kind, takes k records.  Waits for the context's last render. */
 int lt_hip_entry_cut_chunk_counts(lt_hip_context* ctx, uint64_t* out23);
 
+/* Diagnostics: copies the entry cuts ctx holds now back to the host, as the two-frame shadow walks read them (tests say from them
+ * what their walks ran through): one plane per record a square's list may take (out23[0] above), each plane 16 uint32 per 8x8 square
+ * of the image the cuts were built for, in hand-out order -- a count, 0 .. 15, or 0xffffffff for a square marked clear, then that many
+ * references in the walk's stack encoding (bit 31 set: a leaf's record among lt_hip_read_scene_structure's kind 4).  A record after the
+ * first with a count of 0 ends its square's list.  out == NULL: only *out_bytes (the size) is set.  *out_bytes = 0 while the context
+ * holds no cuts: no call has reused a set of camera hits yet, or they were dropped since (another scene, camera or image).  Waits for
+ * the device. */
+int lt_hip_read_entry_cuts(lt_hip_context* ctx, void* out, uint64_t capacity, uint64_t* out_bytes);
+
 /* The cut over the pruned tree on the host, for tests: a tree of n <= 512 records as the leaf pass writes it down (record 0 the root;
  * refs[v] negative: a leaf; parents[v], kids[2 v], kids[2 v + 1]: record indices, 0xffff none) and survives[v] != 0 for the leaves that
  * survive.  out: the references of the cut, at most cap (2 .. 240) of them; *count: their number.  No GPU. */

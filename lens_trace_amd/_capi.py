@@ -49,7 +49,7 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_overlap_tris_list", "lt_hip_overlap_tris_list_device", "lt_hip_overlap_tris_list_host",
            "lt_hip_entry_cut_counts", "lt_hip_entry_cut_test_host",
            "lt_hip_entry_cut_leaf_counts", "lt_hip_entry_cut_triangle_test_host",
-           "lt_hip_entry_cut_chunk_counts", "lt_hip_entry_cut_chunks_test_host",
+           "lt_hip_entry_cut_chunk_counts", "lt_hip_entry_cut_chunks_test_host", "lt_hip_read_entry_cuts",
            "lt_hip_entry_cut_pruned_test_host", "lt_hip_clear_item_counts", "lt_hip_clear_items_test_host"]
 # (lt_hip_camera_hit_passes returns a uint64_t count, not a status: bound in load() beside these)
 
@@ -313,6 +313,9 @@ def load():
         L.lt_hip_entry_cut_chunk_counts.restype = i32
         L.lt_hip_entry_cut_chunks_test_host.argtypes = [vp, vp, vp, vp, u64, vp]
         L.lt_hip_entry_cut_chunks_test_host.restype = i32
+    if hasattr(L, "lt_hip_read_entry_cuts"):
+        L.lt_hip_read_entry_cuts.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+        L.lt_hip_read_entry_cuts.restype = i32
     if hasattr(L, "lt_hip_entry_cut_pruned_test_host"):
         L.lt_hip_entry_cut_pruned_test_host.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
         L.lt_hip_entry_cut_pruned_test_host.restype = i32

@@ -393,6 +393,7 @@ struct lt_hip_context {
   uint32_t cuts_leaves = 0;          // RenderKnobs::entry_cut_leaves of the build that made them (another value: built again)
   uint32_t cuts_chunks = 0;          // RenderKnobs::entry_cut_chunks of that build, likewise: the planes of d_cuts that it wrote
   uint32_t cuts_node_chunks = 0;     // RenderKnobs::entry_cut_node_chunks of that build, likewise
+  uint32_t cuts_plane_squares = 0;   // FrameParams::totalSquares of that build: a plane of d_cuts is this many records
   uint64_t cut_builds = 0;          // launches of lt_entry_cut_kernel so far (lt_hip_entry_cut_counts)
   // The item table of those cuts and its fold map (lt_clear_items_kernel; ensure_clear_items): valid while cuts_valid is and for the
   // launches they were built for -- items_groups frame groups per square (0: none built since the cuts were), items_folds: with a map.
@@ -1976,6 +1977,7 @@ static int launch_entry_cuts(lt_hip_context* ctx, const RenderCall& c, const Sce
   ctx->cuts_leaves = c.k.entry_cut_leaves;
   ctx->cuts_chunks = chunks;
   ctx->cuts_node_chunks = c.k.entry_cut_node_chunks;
+  ctx->cuts_plane_squares = fh.totalSquares;
   ctx->cut_builds++;
   return LT_OK;
 }
@@ -3657,6 +3659,23 @@ extern "C" int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* 
   if (what == 3) { memcpy(out, info, sizeof(info)); return LT_OK; }
   LT_HIP_CHECK(ctx, hipDeviceSynchronize());
   LT_HIP_CHECK(ctx, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+// The entry cuts the context holds now, as the two-frame walk reads them: cuts_chunks planes of one record per square; none held:
+// 0 bytes.
+extern "C" int lt_hip_read_entry_cuts(lt_hip_context* ctx, void* out, uint64_t capacity, uint64_t* out_bytes) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  if (!out_bytes) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_read_entry_cuts: bad arguments");
+  uint64_t bytes = 0;
+  if (ctx->cuts_valid && ctx->d_cuts && (uint64_t)ctx->cuts_plane_squares * ctx->cuts_chunks <= ctx->cuts_squares)
+    bytes = (uint64_t)ctx->cuts_plane_squares * ctx->cuts_chunks * lt_entry_cut::kListWords * sizeof(uint32_t);
+  *out_bytes = bytes;
+  if (!out || bytes == 0) return LT_OK;
+  if (capacity < bytes) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_read_entry_cuts: buffer too small");
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  LT_HIP_CHECK(ctx, hipDeviceSynchronize());
+  LT_HIP_CHECK(ctx, hipMemcpy(out, ctx->d_cuts, bytes, hipMemcpyDeviceToHost));
   return LT_OK;
 }
 

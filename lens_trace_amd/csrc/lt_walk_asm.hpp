@@ -77,6 +77,29 @@ typedef unsigned long long lt_u64;
 #define LT_R_E2Y "s43"
 #define LT_R_E2Z "s44"
 #define LT_R_PRIM "s51"
+// ... and the two-frame walk's leaf records, which alternate between the two banks (LT_ASM_WALK2): LT_R2(name, bank).  Bank 0 is the
+// layout above; bank 1, record 1's registers, holds the triangle in s52 .. s60, the box in s61 .. s66, the primitive in s67.
+#define LT_R2(N, B) LT_R_##N##_##B
+#define LT_R_AX_0 LT_R_AX
+#define LT_R_AY_0 LT_R_AY
+#define LT_R_AZ_0 LT_R_AZ
+#define LT_R_E1X_0 LT_R_E1X
+#define LT_R_E1Y_0 LT_R_E1Y
+#define LT_R_E1Z_0 LT_R_E1Z
+#define LT_R_E2X_0 LT_R_E2X
+#define LT_R_E2Y_0 LT_R_E2Y
+#define LT_R_E2Z_0 LT_R_E2Z
+#define LT_R_PRIM_0 LT_R_PRIM
+#define LT_R_AX_1 "s52"
+#define LT_R_AY_1 "s53"
+#define LT_R_AZ_1 "s54"
+#define LT_R_E1X_1 "s55"
+#define LT_R_E1Y_1 "s56"
+#define LT_R_E1Z_1 "s57"
+#define LT_R_E2X_1 "s58"
+#define LT_R_E2Y_1 "s59"
+#define LT_R_E2Z_1 "s60"
+#define LT_R_PRIM_1 "s67"
 // (a kernel that keeps eight waves per SIMD owns s0 .. s71: everything below fits under that)
 #define LT_R_HML "s[68:69]"    /* lanes that hit the child just tested; in the leaf test: v_cmpx destination, tie masks */
 #define LT_R_HMR "s[70:71]"
@@ -177,6 +200,8 @@ typedef unsigned long long lt_u64;
 #define LT_LOHI_2 "s52", "s53", "s54", "s55", "s56", "s57"
 #define LT_LOHI_3 "s60", "s61", "s62", "s63", "s64", "s65"
 #define LT_LOHI_LEAF "s45", "s46", "s47", "s48", "s49", "s50"
+#define LT_LOHI_LEAF_0 LT_LOHI_LEAF
+#define LT_LOHI_LEAF_1 "s61", "s62", "s63", "s64", "s65", "s66"
 // ... and for a wave whose rays do not share an octant (shadow rays around a light overhead): the same two tests with each
 // axis' near / far plane picked per lane, min / max of the two products (fma and (bound - o) * inv are monotonic in the bound and
 // lo <= hi, so the smaller product is the near plane's): 17 and 22 instructions
@@ -515,6 +540,7 @@ typedef unsigned long long lt_u64;
   "s_mov_b64 exec, " LT_R_EXEC "\n"
 
 #define LT_ASM_IGNORE_ANYHIT "v_cmpx_ne_u32_e64 " LT_R_HML ", " LT_R_PRIM ", %[ign]\n"
+#define LT_ASM_IGNORE_ANYHIT2(B) "v_cmpx_ne_u32_e64 " LT_R_HML ", " LT_R2(PRIM, B) ", %[ign]\n"
 
 // ---- the any-hit walk of TWO frames' shadow rays at once (packet_anyhit_walk2).  Every lane carries two rays with one origin --
 // the shadow rays of one camera hit towards two samples of the light, frames s and s + 1 of a fused launch -- and the wave walks
@@ -539,6 +565,9 @@ typedef unsigned long long lt_u64;
 // behind each frame's u test: on the 1 M-triangle wall 0.93 of a leaf record's two frame tests get past it (measured, DESIGN
 // 5.1), so computing them up front for both costs what it saves, and four more registers; and the box's (bound - o) is reached by
 // fewer than one frame test in ten.  The walk ends when both masks are empty.
+// Runs of leaves -- a square's list of surviving leaves (lt_entry_cut.hpp), two children that are both leaves -- fetch the next
+// leaf's record while this one's two frame tests run (LT_ASM_LEAF2_RUN: the records alternate between the two register banks, the
+// leaf body is expanded once per bank): the same leaves meet the same tests in the same order.
 //
 // The two-frame leaf also drops the four instructions that restate dot4's `a.w * b.w` term in the one-frame leaf -- `x + 0`
 // after det, tvec . pvec and e2 . qvec, and `+ 0 * dw` in d . qvec.  They can change no accept HERE, term by term:
@@ -582,26 +611,26 @@ typedef unsigned long long lt_u64;
   "s_branch .Lt2second" S "%=\n"
 
 // tvec for the lanes open in either frame (a leaf is only popped while some lane is)
-#define LT_ASM_TRI2_TVEC                                                                                                        \
+#define LT_ASM_TRI2_TVEC(B)                                                                                                     \
   "s_or_b64 exec, %[open], %[open_1]\n"                                                                                         \
-  "v_subrev_f32_e32 %[tvx], " LT_R_AX ", %[ox]\n"   /* tvec = o - A */                                                          \
-  "v_subrev_f32_e32 %[tvy], " LT_R_AY ", %[oy]\n"                                                                               \
-  "v_subrev_f32_e32 %[tvz], " LT_R_AZ ", %[oz]\n"
+  "v_subrev_f32_e32 %[tvx], " LT_R2(AX, B) ", %[ox]\n"   /* tvec = o - A */                                                     \
+  "v_subrev_f32_e32 %[tvy], " LT_R2(AY, B) ", %[oy]\n"                                                                          \
+  "v_subrev_f32_e32 %[tvz], " LT_R2(AZ, B) ", %[oz]\n"
 
 // one frame's det, 1 / det, u (EXEC narrowed by the det and u tests); leaves: t0 = invDet, t1 = u.  tvec . pvec fills the wait
 // for v_rcp where LT_ASM_TRI_PART1 computes tvec, and pvec's registers then serve the division.
-#define LT_ASM_TRI2_PART1(S)                                                                                                    \
-  "v_mul_f32_e64 %[t4], %[dz" S "], -" LT_R_E2Y "\n"     /* pvec = cross(d, e2) */                                              \
-  "v_mul_f32_e64 %[t5], %[dx" S "], -" LT_R_E2Z "\n"                                                                            \
-  "v_fmac_f32_e32 %[t4], " LT_R_E2Z ", %[dy" S "]\n"                                                                            \
-  "v_fmac_f32_e32 %[t5], " LT_R_E2X ", %[dz" S "]\n"                                                                            \
-  "v_mul_f32_e64 %[t6], %[dy" S "], -" LT_R_E2X "\n"                                                                            \
-  "v_mul_f32_e32 %[t0], " LT_R_E1X ", %[t4]\n"                                                                                  \
-  "v_fmac_f32_e32 %[t6], " LT_R_E2Y ", %[dx" S "]\n"                                                                            \
-  "v_fmac_f32_e32 %[t0], " LT_R_E1Y ", %[t5]\n"                                                                                 \
-  "v_fmac_f32_e32 %[t0], " LT_R_E1Z ", %[t6]\n"     /* det */                                                                   \
+#define LT_ASM_TRI2_PART1(S, B)                                                                                                 \
+  "v_mul_f32_e64 %[t4], %[dz" S "], -" LT_R2(E2Y, B) "\n"     /* pvec = cross(d, e2) */                                         \
+  "v_mul_f32_e64 %[t5], %[dx" S "], -" LT_R2(E2Z, B) "\n"                                                                       \
+  "v_fmac_f32_e32 %[t4], " LT_R2(E2Z, B) ", %[dy" S "]\n"                                                                       \
+  "v_fmac_f32_e32 %[t5], " LT_R2(E2X, B) ", %[dz" S "]\n"                                                                       \
+  "v_mul_f32_e64 %[t6], %[dy" S "], -" LT_R2(E2X, B) "\n"                                                                       \
+  "v_mul_f32_e32 %[t0], " LT_R2(E1X, B) ", %[t4]\n"                                                                             \
+  "v_fmac_f32_e32 %[t6], " LT_R2(E2Y, B) ", %[dx" S "]\n"                                                                       \
+  "v_fmac_f32_e32 %[t0], " LT_R2(E1Y, B) ", %[t5]\n"                                                                            \
+  "v_fmac_f32_e32 %[t0], " LT_R2(E1Z, B) ", %[t6]\n"     /* det */                                                              \
   "s_cmp_lg_u32 %[fast], 0\n"                                                                                                   \
-  "s_cbranch_scc1 .LfastRcp" S "%=\n"                                                                                           \
+  "s_cbranch_scc1 .LfastRcp" S "b" #B "%=\n"                                                                                    \
   "v_div_scale_f32 %[t1], " LT_R_HML ", %[t0], %[t0], 1.0\n"                                                                    \
   "v_rcp_f32_e32 %[t2], %[t1]\n"                                                                                                \
   "v_cmpx_nlt_f32_e64 " LT_R_HML ", |%[t0]|, %[eps]\n" /* !(fabs(det) < epsilon) */                                             \
@@ -617,8 +646,8 @@ typedef unsigned long long lt_u64;
   "v_fma_f32 %[t1], -%[t1], %[t4], %[t3]\n"                                                                                     \
   "v_div_fmas_f32 %[t1], %[t1], %[t2], %[t4]\n"                                                                                 \
   "v_div_fixup_f32 %[t0], %[t1], %[t0], 1.0\n"      /* invDet = 1 / det, correctly rounded */                                   \
-  "s_branch .LrcpDone" S "%=\n"                                                                                                 \
-  ".LfastRcp" S "%=:\n"                             /* the as-shipped build's 1 / det: ldexp(rcp(frexp_mant), -frexp_exp) */    \
+  "s_branch .LrcpDone" S "b" #B "%=\n"                                                                                          \
+  ".LfastRcp" S "b" #B "%=:\n"                             /* the as-shipped build's 1 / det: ldexp(rcp(frexp_mant), -frexp_exp) */    \
   "v_frexp_mant_f32_e32 %[t1], %[t0]\n"                                                                                         \
   "v_rcp_f32_e32 %[t1], %[t1]\n"                                                                                                \
   "v_cmpx_nlt_f32_e64 " LT_R_HML ", |%[t0]|, %[eps]\n"                                                                          \
@@ -628,43 +657,80 @@ typedef unsigned long long lt_u64;
   "v_frexp_exp_i32_f32_e32 %[t2], %[t0]\n"                                                                                      \
   "v_sub_u32_e32 %[t2], 0, %[t2]\n"                                                                                             \
   "v_ldexp_f32 %[t0], %[t1], %[t2]\n"                                                                                           \
-  ".LrcpDone" S "%=:\n"                                                                                                         \
+  ".LrcpDone" S "b" #B "%=:\n"                                                                                                  \
   "v_mul_f32_e32 %[t1], %[t7], %[t0]\n"             /* u */                                                                     \
   "v_cmpx_ngt_f32_e64 " LT_R_HML ", 0, %[t1]\n"     /* !(u < 0) */                                                              \
   "v_cmpx_nlt_f32_e64 " LT_R_HML ", 1.0, %[t1]\n"   /* !(u > 1) */                                                              \
-  "s_cbranch_execz .LleafEnd" S "%=\n"
+  "s_cbranch_execz .LleafEnd" S "b" #B "%=\n"
 
 // one frame's qvec, v, u + v, t (EXEC narrowed by the v and u + v tests); leaves: t3 = t
-#define LT_ASM_TRI2_PART2(S)                                                                                                    \
-  "v_mul_f32_e64 %[t4], %[tvz], -" LT_R_E1Y "\n"    /* qvec = cross(tvec, e1) */                                                \
-  "v_fmac_f32_e32 %[t4], " LT_R_E1Z ", %[tvy]\n"                                                                                \
-  "v_mul_f32_e64 %[t5], %[tvx], -" LT_R_E1Z "\n"                                                                                \
-  "v_mul_f32_e64 %[t6], %[tvy], -" LT_R_E1X "\n"                                                                                \
-  "v_fmac_f32_e32 %[t5], " LT_R_E1X ", %[tvz]\n"                                                                                \
-  "v_fmac_f32_e32 %[t6], " LT_R_E1Y ", %[tvx]\n"                                                                                \
+#define LT_ASM_TRI2_PART2(S, B)                                                                                                 \
+  "v_mul_f32_e64 %[t4], %[tvz], -" LT_R2(E1Y, B) "\n"    /* qvec = cross(tvec, e1) */                                           \
+  "v_fmac_f32_e32 %[t4], " LT_R2(E1Z, B) ", %[tvy]\n"                                                                           \
+  "v_mul_f32_e64 %[t5], %[tvx], -" LT_R2(E1Z, B) "\n"                                                                           \
+  "v_mul_f32_e64 %[t6], %[tvy], -" LT_R2(E1X, B) "\n"                                                                           \
+  "v_fmac_f32_e32 %[t5], " LT_R2(E1X, B) ", %[tvz]\n"                                                                           \
+  "v_fmac_f32_e32 %[t6], " LT_R2(E1Y, B) ", %[tvx]\n"                                                                           \
   "v_mul_f32_e32 %[t2], %[dx" S "], %[t4]\n"                                                                                    \
   "v_fmac_f32_e32 %[t2], %[dy" S "], %[t5]\n"                                                                                   \
   "v_fmac_f32_e32 %[t2], %[dz" S "], %[t6]\n"                                                                                   \
   "v_mul_f32_e32 %[t2], %[t2], %[t0]\n"             /* v */                                                                     \
   "v_add_f32_e32 %[t7], %[t1], %[t2]\n"             /* u + v */                                                                 \
-  "v_mul_f32_e32 %[t3], " LT_R_E2X ", %[t4]\n"      /* the numerator of t */                                                    \
-  "v_fmac_f32_e32 %[t3], " LT_R_E2Y ", %[t5]\n"                                                                                 \
-  "v_fmac_f32_e32 %[t3], " LT_R_E2Z ", %[t6]\n"                                                                                 \
+  "v_mul_f32_e32 %[t3], " LT_R2(E2X, B) ", %[t4]\n"      /* the numerator of t */                                               \
+  "v_fmac_f32_e32 %[t3], " LT_R2(E2Y, B) ", %[t5]\n"                                                                            \
+  "v_fmac_f32_e32 %[t3], " LT_R2(E2Z, B) ", %[t6]\n"                                                                            \
   "v_cmpx_ngt_f32_e64 " LT_R_HML ", 0, %[t2]\n"     /* !(v < 0) */                                                              \
   "v_cmpx_nlt_f32_e64 " LT_R_HML ", 1.0, %[t7]\n"   /* !(u + v > 1) */                                                          \
   "v_mul_f32_e32 %[t3], %[t3], %[t0]\n"             /* t */
 
-#define LT_ASM_LEAF2(NF, S)                                                                                                     \
+#define LT_ASM_LEAF2(NF, S, B)                                                                                                  \
   "s_mov_b64 exec, %[open" S "]\n"                                                                                              \
-  "s_cbranch_execz .LleafEnd" S "%=\n"                                                                                          \
-  LT_ASM_IGNORE_ANYHIT                                                                                                          \
-  LT_ASM_TRI2_PART1(S)                                                                                                          \
-  LT_ASM_TRI2_PART2(S)                                                                                                          \
-  "s_cbranch_execz .LleafEnd" S "%=\n"                                                                                          \
-  LT_BXL(NF, LT_LOHI_LEAF, S)                                                                                                   \
+  "s_cbranch_execz .LleafEnd" S "b" #B "%=\n"                                                                                   \
+  LT_ASM_IGNORE_ANYHIT2(B)                                                                                                      \
+  LT_ASM_TRI2_PART1(S, B)                                                                                                       \
+  LT_ASM_TRI2_PART2(S, B)                                                                                                       \
+  "s_cbranch_execz .LleafEnd" S "b" #B "%=\n"                                                                                   \
+  LT_BXL(NF, LT_LOHI_LEAF_##B, S)                                                                                               \
   "v_cmpx_lt_f32_e64 " LT_R_HML ", %[t3], %[tmax" S "]\n" /* t < payload.t: accepted */                                         \
   "s_andn2_b64 %[open" S "], %[open" S "], exec\n"                                                                              \
-  ".LleafEnd" S "%=:\n"
+  ".LleafEnd" S "b" #B "%=:\n"
+
+// A run of leaves.  A leaf pushes nothing, so while a leaf's record is on its way the entry under it is the next one to pop whatever
+// the test finds: if that entry is a leaf too it is popped now and its record fetched into the OTHER bank, where it arrives behind
+// the two frame tests of this one.  Scalar loads return in any order, so the one wait there is is lgkmcnt(0): this bank's record is
+// waited for FIRST, the next one's load issued after.  The leaf body exists once per bank (B = 0: record 0's registers, 1: record
+// 1's) and the run alternates between the copies, NEXT = where a copy goes when it has fetched a leaf (SCC = 1) and when it has not.
+// Entry .Lrun<B>: bank B's load is in flight, M0 counts the entries under that leaf.  LT_R_CUR2 keeps what the peek found: negative
+// iff a leaf was popped and fetched ahead.  An interior node on top stays on the stack (LT_ASM_LEAF2_RUN_OUT puts it back) and is
+// popped by .Lpop with no load in flight: the interior path owns both banks.  The walk may end -- both `open` masks empty -- with a
+// fetch in flight: .Ldone drains it.
+#define LT_ASM_LEAF2_RUN(NF, B, OTHER, NEXT)                                                                                    \
+  ".Lrun" #B "%=:\n"                                                                                                            \
+  "s_sub_u32 m0, m0, 1\n"                           /* SCC = the borrow: M0 was 0 */                                            \
+  "s_cbranch_scc1 .LrunEmpty" #B "%=\n"                                                                                         \
+  "v_readlane_b32 " LT_R_CUR2 ", %[stk], m0\n"                                                                                  \
+  "s_lshl_b32 " LT_R_TMPHI ", " LT_R_CUR2 ", 6\n"                                                                               \
+  "s_cmp_lt_i32 " LT_R_CUR2 ", 0\n"                                                                                             \
+  "s_waitcnt lgkmcnt(0)\n"                          /* this leaf's record has arrived */                                        \
+  "s_cbranch_scc0 .LrunNode" #B "%=\n"                                                                                          \
+  "s_load_dwordx16 " OTHER ", %[pairs], " LT_R_TMPHI "\n"                                                                       \
+  ".LrunTest" #B "%=:\n"                                                                                                        \
+  LT_ASM_TRI2_TVEC(B)                                                                                                           \
+  LT_ASM_LEAF2(NF, "", B)                                                                                                       \
+  LT_ASM_LEAF2(NF, "_1", B)                                                                                                     \
+  "s_or_b64 " LT_R_TMPM ", %[open], %[open_1]\n"    /* SCC = some lane of some frame still looking */                           \
+  "s_cbranch_scc0 .Ldone%=\n"                                                                                                   \
+  "s_cmp_lt_i32 " LT_R_CUR2 ", 0\n"                 /* the next leaf is on its way into the other bank? */                      \
+  NEXT
+#define LT_ASM_LEAF2_RUN_OUT(B)                                                                                                 \
+  ".LrunEmpty" #B "%=:\n"                           /* nothing under this leaf */                                               \
+  "s_mov_b32 m0, 0\n"                                                                                                           \
+  "s_mov_b32 " LT_R_CUR2 ", 0\n"                                                                                              \
+  "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
+  "s_branch .LrunTest" #B "%=\n"                                                                                                \
+  ".LrunNode" #B "%=:\n"                            /* an interior node under this leaf: it stays */                            \
+  "s_add_u32 m0, m0, 1\n"                                                                                                       \
+  "s_branch .LrunTest" #B "%=\n"
 
 #define LT_ASM_WALK2(NF)                                                                                                        \
   "s_mov_b64 " LT_R_EXEC ", exec\n"                                                                                             \
@@ -680,8 +746,8 @@ typedef unsigned long long lt_u64;
   "s_mov_b32 m0, 0\n"                                                                                                           \
   "s_mov_b32 " LT_R_CUR ", 0\n"                                                                                                 \
   /* The square's entry cut (lt_entry_cut.hpp), or null: [count][references, in the stack's own encoding].  The stack register is  \
-     the walk's from here on (parked above, or every lane is this path's), so it serves as its own address: lane i of the first    \
-     fifteen takes entry i, M0 the count, and the walk enters at the pop; count 0: at the root, as without a list. */             \
+     the walk's from here on (parked above, or every lane is this path's), so it serves as its own address: lane i of the first \
+     fifteen takes entry i, M0 the count, and the walk enters at the pop; count 0: at the root, as without a list. */           \
   "s_cmp_eq_u64 %[cut], 0\n"                                                                                                    \
   "s_cbranch_scc1 .Lnode%=\n"                                                                                                   \
   "s_load_dword " LT_R_LEAF ", %[cut], 0x0\n"                                                                                   \
@@ -712,7 +778,7 @@ typedef unsigned long long lt_u64;
   "s_lshl_b32 " LT_R_TMPHI ", " LT_R_CUR2 ", 6\n"                                                                               \
   "s_load_dwordx16 " LT_R_REC1 ", %[pairs], " LT_R_TMPHI "\n"                                                                   \
   "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
-  LT_ASM_TESTS2(NF, 0, 1, "a")                                                                                            \
+  LT_ASM_TESTS2(NF, 0, 1, "a")                                                                                                  \
   LT_ASM_PUSH(LT_R_REF0L, LT_R_HML)                                                                                             \
   LT_ASM_PUSH(LT_R_REF0R, LT_R_HMR)                                                                                             \
   LT_ASM_TESTS2(NF, 2, 3, "b")                                                                                                  \
@@ -733,13 +799,12 @@ typedef unsigned long long lt_u64;
   ".Lleaf%=:\n"                                                                                                                 \
   "s_lshl_b32 " LT_R_TMPLO ", " LT_R_CUR ", 6\n"                                                                                \
   "s_load_dwordx16 " LT_R_REC0 ", %[pairs], " LT_R_TMPLO "\n"                                                                   \
-  "s_waitcnt lgkmcnt(0)\n"                                                                                                      \
-  LT_ASM_TRI2_TVEC                                                                                                              \
-  LT_ASM_LEAF2(NF, "")                                                                                                          \
-  LT_ASM_LEAF2(NF, "_1")                                                                                                        \
-  "s_or_b64 " LT_R_TMPM ", %[open], %[open_1]\n"    /* SCC = some lane of some frame still looking */                           \
-  "s_cbranch_scc1 .Lpop%=\n"                                                                                                    \
+  LT_ASM_LEAF2_RUN(NF, 0, LT_R_REC1, "s_cbranch_scc0 .Lpop%=\n")   /* falls into bank 1's copy when it has fetched a leaf for it */ \
+  LT_ASM_LEAF2_RUN(NF, 1, LT_R_REC0, "s_cbranch_scc1 .Lrun0%=\ns_branch .Lpop%=\n")                                             \
+  LT_ASM_LEAF2_RUN_OUT(0)                                                                                                       \
+  LT_ASM_LEAF2_RUN_OUT(1)                                                                                                       \
   ".Ldone%=:\n"                                                                                                                 \
+  "s_waitcnt lgkmcnt(0)\n"                          /* a leaf fetched ahead and never tested may still be on its way: s[36:67] are the compiler's again after this block */ \
   "s_cmp_eq_u64 " LT_R_EXEC ", -1\n"                                                                                            \
   "s_cbranch_scc1 .Lrestored%=\n"                                                                                               \
   "s_mov_b32 m0, %[ldsrow]\n"                                                                                                   \

@@ -511,6 +511,18 @@ class RendererHIP:
         return {"chunks": int(out[0]), "leaf": (int(out[1]), int(out[2])), "pruned": (int(out[3]), int(out[4])),
                 "plain": (int(out[5]), int(out[6])), "squares_by_chunks": {k: int(out[6 + k]) for k in range(1, 17)}}
 
+    def entry_cuts(self):
+        """lt_hip_read_entry_cuts: the entry cuts the context holds now as the two-frame shadow walks read them, a (planes x squares,
+        16) uint32 array -- plane c holds record c of every square's list in hand-out order: a count (0xffffffff: marked clear), then
+        that many references -- or None while it holds none.  Waits for the device."""
+        n = ctypes.c_uint64(0)
+        self._check(self._L.lt_hip_read_entry_cuts(self._ctx, None, ctypes.c_uint64(0), ctypes.byref(n)))
+        if n.value == 0:
+            return None
+        buf = np.zeros(n.value // 4, dtype=np.uint32)
+        self._check(self._L.lt_hip_read_entry_cuts(self._ctx, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(buf.nbytes), ctypes.byref(n)))
+        return buf.reshape(-1, 16)
+
     def clear_item_counts(self):
         """lt_hip_clear_item_counts, of the item table the context holds now: a dict of `entries` (the table's work items),
         `whole` (the clear squares it hands out as one item each), `folded` (those of them whose samples the context's last
