@@ -352,6 +352,53 @@ int lt_hip_trace_hits(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, con
 int lt_hip_trace_hits_device(lt_hip_context* ctx, const lt_hip_multihit_desc* desc, const lt_hip_ray* rays, uint64_t n,
                              void* out, uint64_t out_bytes, void* hip_stream);
 
+/* Hit lists: the WHOLE hit sequence of every ray, as CSR -- every surface of a transparency or lens stack, every crossing for
+ * thickness, penetration depth and parity, where LT_TRACE_FIRST_K stops at eight and LT_TRACE_COUNT only says that there are
+ * more.  The hit sequence is lt_hip_trace_hits', word for word, without the limit: the peeling definition above, t ascending by the
+ * float `<`, bit-equal t (-0 == +0) in the reference's traversal order for that ray, no t > 0 test, tmax as given, the `ignore`
+ * leaf never entered; in a scene that gets no own hierarchy (boxes that do not nest, a primitive named by two leaves) it is what
+ * the walk in the reference's order reports, once per leaf, equal t in traversal order.
+ *   offsets   n + 1 uint64: offsets[i] is the sum of the sequence lengths of rays 0 .. i-1 (an exclusive scan: offsets[0] = 0,
+ *             offsets[n] the total).
+ *   items     offsets[n] lt_hip_hit records of 16 bytes, {t, prim, u, v}: items[offsets[i] .. offsets[i + 1]) is the whole
+ *             sequence of ray i, nearest first.  Every record feeds lt_hip_surface_at as it is.  A ray that hits nothing has an
+ *             empty segment: there are no miss records.
+ * So the differences of offsets are LT_TRACE_COUNT's words, and the first min(8, length) records of a segment are
+ * LT_TRACE_FIRST_K's real records at max_hits = 8, bit for bit in all four fields, in every math flavour.
+ * program: a built-in LT_PROGRAM_* (it selects the triangle epsilon), as in lt_hip_multihit_desc.
+ * flags: LT_RENDER_FLAG_STRICT_MATH or LT_RENDER_FLAG_PORTABLE_MATH, with the render path's meaning; LT_TRACE_FLAG_COHERENT is
+ * accepted and has no effect (there is no multi-hit packet walk); LT_TRACE_LIST_FLAG_FILL_ONLY.  reserved must be 0.
+ * Sizing, items that are too small, FILL_ONLY, n == 0 and the statistics are lt_hip_overlap_boxes_list's (below) with 4 bytes per
+ * item replaced by 16: items == NULL with items_bytes == 0 writes the offsets only; with items_bytes < 16 offsets[n] nothing is
+ * written to items, offsets is written in full, the host-memory form returns LT_ERR_BUFFER_TOO_SMALL and the device form LT_OK;
+ * with FILL_ONLY offsets is input and, whatever it holds, ray i writes only into items[offsets[i] .. min(offsets[i + 1],
+ * items_bytes / 16)), a length that would be negative being 0; the device entry point takes pointers that are 16-byte aligned;
+ * lt_hip_get_stats reports rays = n, kernel_ms and 4 / 2 / 6 kernels launched (one fewer with a fill in a scene without an own
+ * hierarchy: nothing is left to order there).
+ * Errors, in order: LT_ERR_INVALID_ARGUMENT for a null ctx / desc, struct_size too small, a user program (LT_ERR_UNKNOWN_PROGRAM
+ * for an id that is neither), any other flag, STRICT with PORTABLE, reserved != 0, n >= 2^32, null rays or offsets with n > 0,
+ * items == NULL with items_bytes != 0, FILL_ONLY with items == NULL (device entry point: pointers that are not 16-byte aligned);
+ * LT_ERR_NO_SCENE; LT_ERR_BUFFER_TOO_SMALL when offsets_bytes < 8 (n + 1).  Such a call writes nothing.
+ * Cost: the count is LT_TRACE_COUNT's walk, the fill that walk again.  The segments of the rays the backend's own hierarchy takes
+ * are then sorted by one wavefront each, up to 1024 records in LDS and longer ones in place in device memory.  A ray that walks
+ * in the reference's order (a scene without an own hierarchy, a non-finite ray, magnitudes beyond the own walks') keeps its
+ * segment sorted while it fills it, which is quadratic in the segment's length.  Batches whose items pass 4 GiB are untested.
+ * There is no _host form: the CPU definition of this family is the peeling itself (tests/multihit.py runs it on the oracle).
+ * (lens_trace_amd/csrc/lt_query.hip, lt_overlist.hip) */
+#define LT_TRACE_LIST_FLAG_FILL_ONLY 0x200u
+typedef struct lt_hip_hits_list_desc {
+  uint32_t struct_size;         /* >= sizeof(lt_hip_hits_list_desc) */
+  int32_t program;              /* a built-in LT_PROGRAM_* (selects the epsilon) */
+  uint32_t flags;
+  uint32_t reserved;            /* 0 */
+} lt_hip_hits_list_desc;        /* 16 B */
+
+int lt_hip_trace_hits_list(lt_hip_context* ctx, const lt_hip_hits_list_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                           uint64_t* offsets, uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes);
+/* Device memory of the context's GPU, enqueued on hip_stream (a hipStream_t, NULL = default stream), not waited for. */
+int lt_hip_trace_hits_list_device(lt_hip_context* ctx, const lt_hip_hits_list_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                                  uint64_t* offsets, uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes, void* hip_stream);
+
 /* Shading of caller-supplied rays: a picture through any camera model (pitched, orthographic, fisheye, a calibrated lens, a light
  * probe, a tensor of rays).  For each ray the result is the colour the named program's `shade` returns for it -- what linearKernel /
  * tileKernel would have stored had this ray been a pixel's camera ray at film position (film_x, film_y) and frame frameCount:

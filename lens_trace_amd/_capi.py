@@ -24,6 +24,7 @@ TRACE_CLOSEST, TRACE_ANY = 0, 1      # lt_hip_trace_desc::kind
 TRACE_FLAG_COHERENT = 0x100          # runs of 64 consecutive rays are coherent: walked as packets
 TRACE_FIRST_K, TRACE_COUNT = 0, 1    # lt_hip_multihit_desc::kind (lt_hip_trace_hits only)
 TRACE_MAX_HITS = 8                   # LT_TRACE_MAX_HITS
+TRACE_LIST_FLAG_FILL_ONLY = 0x200    # lt_hip_hits_list_desc::flags: offsets is input, only items is written
 NEAREST_FIRST_K, NEAREST_COUNT = 0, 1   # lt_hip_nearest_k_desc::kind
 NEAREST_MAX_K = 8                    # LT_NEAREST_MAX_K
 OVERLAP_FIRST_K, OVERLAP_COUNT, OVERLAP_ANY = 0, 1, 2   # lt_hip_overlap_desc::kind
@@ -38,6 +39,7 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_set_scene", "lt_hip_output_floats", "lt_hip_render", "lt_hip_render_scene", "lt_hip_render_device", "lt_hip_untile",
            "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure",
            "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device",
+           "lt_hip_trace_hits_list", "lt_hip_trace_hits_list_device",
            "lt_hip_shade_rays", "lt_hip_shade_rays_device", "lt_hip_shade_paths", "lt_hip_shade_paths_device",
            "lt_hip_trace_surface", "lt_hip_trace_surface_device", "lt_hip_surface_at", "lt_hip_surface_at_device",
            "lt_hip_nearest_points", "lt_hip_nearest_points_device", "lt_hip_nearest_points_host",
@@ -153,6 +155,10 @@ class OverlapListDesc(ctypes.Structure):   # lt_hip_overlap_list_desc
 
 class NearestListDesc(ctypes.Structure):   # lt_hip_nearest_list_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class HitsListDesc(ctypes.Structure):   # lt_hip_hits_list_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("program", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 def _np_dtypes():
@@ -291,6 +297,9 @@ def load():
             getattr(L, lists).argtypes = [vp, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64]
             getattr(L, lists + "_device").argtypes = [vp, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64, vp]
             getattr(L, lists + "_host").argtypes = [vp, u64, vp, u64, ctypes.POINTER(OverlapListDesc), vp, u64, vp, u64, vp, u64]
+    if hasattr(L, "lt_hip_trace_hits_list"):
+        L.lt_hip_trace_hits_list.argtypes = [vp, ctypes.POINTER(HitsListDesc), vp, u64, vp, u64, vp, u64]
+        L.lt_hip_trace_hits_list_device.argtypes = [vp, ctypes.POINTER(HitsListDesc), vp, u64, vp, u64, vp, u64, vp]
     if hasattr(L, "lt_hip_nearest_list"):
         L.lt_hip_nearest_list.argtypes = [vp, ctypes.POINTER(NearestListDesc), vp, u64, vp, u64, vp, u64]
         L.lt_hip_nearest_list_device.argtypes = [vp, ctypes.POINTER(NearestListDesc), vp, u64, vp, u64, vp, u64, vp]

@@ -2419,8 +2419,8 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
 // Ten families of entry points take caller-supplied records against the resident scene, each in a host and a _device form:
 // lt_hip_trace_rays, lt_hip_trace_hits, lt_hip_trace_surface, lt_hip_surface_at (lt_query.hip), lt_hip_shade_rays (lt_shade.hip),
 // lt_hip_shade_paths (lt_paths.hip), lt_hip_nearest_points and lt_hip_nearest_k (lt_nearest.hip), lt_hip_overlap_boxes
-// (lt_overlap.hip), lt_hip_overlap_tris (lt_tritri.hip).  (The lists, lt_hip_overlap_boxes_list, lt_hip_overlap_tris_list and
-// lt_hip_nearest_list -- lt_overlist.hip --, have two result buffers and a course of their own: run_list_call, behind the triangle queries.)  Every argument error is found before anything is enqueued, so that a failed call writes nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
+// (lt_overlap.hip), lt_hip_overlap_tris (lt_tritri.hip).  (The lists, lt_hip_overlap_boxes_list, lt_hip_overlap_tris_list,
+// lt_hip_nearest_list and lt_hip_trace_hits_list -- lt_overlist.hip --, have two result buffers and a course of their own: run_list_call, behind the triangle queries.)  Every argument error is found before anything is enqueued, so that a failed call writes nothing to `out`.  What the families share is written once: the rules about flags and buffers (check_ray_flags,
 // check_ray_buffers), the course of an entry point with the host form's staging (run_ray_call) and the events and statistics
 // around the launches (begin_ray_launches, end_ray_launches).  A family has its check (the rules about its descriptor, at their
 // place in the order), its launches (enqueue_*) and two one-line entry points.
@@ -2655,6 +2655,7 @@ static int enqueue_hits(lt_hip_context* ctx, const HitsCall& hc, const void* ray
   qp.counts = hc.maxHits ? nullptr : (uint32_t*)out;
   qp.n = (uint32_t)n;
   qp.maxHits = hc.maxHits;
+  qp.kind = hc.maxHits ? lt_query::kFirstK : lt_query::kCount;
   qp.next = ctx->d_query_ctl;
   qp.refill = k.trace_refill;
   const SceneDev sc = scene_dev(ctx, k, hc.devlibm);
@@ -3066,16 +3067,27 @@ extern "C" int lt_hip_overlap_tris_host(const void* nodes, uint64_t node_bytes, 
 }
 
 // ---------------------------------------------------------------------------------- lists
-// lt_hip_overlap_boxes_list*, lt_hip_overlap_tris_list* and lt_hip_nearest_list*: the whole sequence of every query as CSR
+// lt_hip_overlap_boxes_list*, lt_hip_overlap_tris_list*, lt_hip_nearest_list* and lt_hip_trace_hits_list*: the whole sequence of every query as CSR
 // (lt_overlist.hpp) -- the family's walk with its kCountWide into offsets, the scan, the walk again with its kList into items, the
 // ordering.  A sibling of run_ray_call: the results are two buffers and the second one's size is known only after the scan, so
 // the host form runs in two halves with a look at offsets[n] between them.  The work counters are the ray queries'
-// (ctx->query_ev).  What the three families share is written once -- the descriptor's and the buffers' rules, the course, the
-// staging; a family is a ListFamily: its nouns, the bytes of an item and its two walks.
+// (ctx->query_ev).  What the four families share is written once -- the buffers' rules, the course, the staging; a family is a
+// ListFamily -- its nouns, the bytes of an item and its two walks -- and the check of its descriptor, which leaves a ListCall.
 static_assert(sizeof(lt_hip_overlap_list_desc) == 8, "overlap-list descriptor (include/lenstrace_hip.h)");
 static_assert(sizeof(lt_hip_nearest_list_desc) == 8 && LT_NEAREST_LIST_FLAG_FILL_ONLY == LT_OVERLAP_LIST_FLAG_FILL_ONLY,
               "radius-list descriptor (include/lenstrace_hip.h)");
+static_assert(sizeof(lt_hip_hits_list_desc) == 16 &&
+                  (LT_TRACE_LIST_FLAG_FILL_ONLY & (LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT)) == 0,
+              "hit-list descriptor (include/lenstrace_hip.h)");
 constexpr uint32_t kListFillOnly = LT_OVERLAP_LIST_FLAG_FILL_ONLY;
+
+// What the check of a family's descriptor leaves for the course and the launches: FILL_ONLY, and -- the hit lists -- the math
+// flavour (SceneDev's) and the triangle epsilon.  The overlap and radius lists have neither choice.
+struct ListCall {
+  bool fillOnly = false;
+  int devlibm = 2;
+  lt_query::Epsilon eps = lt_query::kEpsDouble4;
+};
 
 // One walk of a list call over device memory: the count into `offsets` (fill == false), or the fill of `items` and its ordering.
 struct ListPass {
@@ -3087,6 +3099,7 @@ struct ListPass {
   unsigned long long* offsets;
   void* items;
   unsigned long long capacity;   // items
+  lt_query::Epsilon eps;         // the hit lists' triangle epsilon
 };
 using ListWalk = hipError_t (*)(const SceneDev&, const ListPass&, uint32_t, hipStream_t);
 
@@ -3097,6 +3110,7 @@ struct ListFamily {
   const char* items;                     // what items holds: "words", "records"
   uint64_t itemBytes;
   ListWalk walk;
+  bool rankOrder = false;                // the ordering is a launch only in a scene with an own tree (lt_overlist::order_ray_hits)
 };
 
 using OverlapLaunch = hipError_t (*)(const SceneDev&, const lt_overlap::Params&, uint32_t, hipStream_t);
@@ -3140,12 +3154,33 @@ static hipError_t nearest_list_walk(const SceneDev& sc, const ListPass& p, uint3
   return e != hipSuccess ? e : lt_overlist::order_hits(p.offsets, p.n, qp.items, p.capacity, p.oneShot, cuCount, s);
 }
 
+static hipError_t hits_list_walk(const SceneDev& sc, const ListPass& p, uint32_t cuCount, hipStream_t s) {
+  lt_query::HitsParams qp{};
+  qp.rays = (const float4*)p.records;
+  qp.n = p.n;
+  qp.next = p.next;
+  qp.refill = p.refill;
+  qp.offsets = p.offsets;
+  if (!p.fill) {
+    qp.kind = lt_query::kCountWide;
+    return lt_query::launch_hits(sc, qp, p.eps, cuCount, s);
+  }
+  qp.kind = lt_query::kList;
+  qp.items = (uint4*)p.items;
+  qp.capacity = p.capacity;
+  qp.oneShot = p.oneShot ? 1u : 0u;
+  const hipError_t e = lt_query::launch_hits(sc, qp, p.eps, cuCount, s);
+  return e != hipSuccess ? e : lt_overlist::order_ray_hits(p.offsets, p.n, qp.items, p.capacity, p.oneShot, qp.rays, sc.rank8, sc.n_prims, cuCount, s);
+}
+
 constexpr ListFamily kOverlapBoxesList{"overlap lists", "lt_hip_overlap_list_desc", "LT_OVERLAP_LIST_FLAG_FILL_ONLY", "lt_hip_overlap_boxes_list",
                                        "boxes", "words", sizeof(int32_t), overlap_list_walk<lt_overlap::launch>};
 constexpr ListFamily kOverlapTrisList{"overlap lists", "lt_hip_overlap_list_desc", "LT_OVERLAP_LIST_FLAG_FILL_ONLY", "lt_hip_overlap_tris_list",
                                       "tris", "words", sizeof(int32_t), overlap_list_walk<lt_tritri::launch>};
 constexpr ListFamily kNearestList{"radius lists", "lt_hip_nearest_list_desc", "LT_NEAREST_LIST_FLAG_FILL_ONLY", "lt_hip_nearest_list",
                                   "points", "records", sizeof(lt_hip_hit), nearest_list_walk};
+constexpr ListFamily kHitsList{"hit lists", "lt_hip_hits_list_desc", "LT_TRACE_LIST_FLAG_FILL_ONLY", "lt_hip_trace_hits_list",
+                               "rays", "records", sizeof(lt_hip_hit), hits_list_walk, true};
 
 // The descriptor's rules -- the two descriptors are the same two words --; empty when it passes.
 template <class Desc>
@@ -3154,6 +3189,31 @@ static std::string list_desc_error(const ListFamily& f, const Desc* d) {
   if (d->struct_size < sizeof(Desc)) return std::string("bad ") + f.desc + " (struct_size)";
   if (d->flags & ~kListFillOnly) return std::string(f.lists) + " take " + f.fillOnly + " only";
   return std::string();
+}
+
+// The check of the overlap and radius lists' descriptors.
+template <class Desc>
+static int check_list_desc(lt_hip_context* ctx, const ListFamily& f, const Desc* d, ListCall& lc) {
+  const std::string why = list_desc_error(f, d);
+  if (!why.empty()) return fail(ctx, LT_ERR_INVALID_ARGUMENT, why);
+  lc.fillOnly = (d->flags & kListFillOnly) != 0;
+  return LT_OK;
+}
+
+// ... and of the hit lists': the program and the flags by lt_hip_trace_hits' rules (check_hits), FILL_ONLY beside them.
+static int check_hits_list_desc(lt_hip_context* ctx, const ListFamily& f, const lt_hip_hits_list_desc* d, ListCall& lc) {
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(f.lists) + ": desc is NULL");
+  if (d->struct_size < sizeof(lt_hip_hits_list_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("bad ") + f.desc + " (struct_size)");
+  if (const int rc = query_epsilon(ctx, d->program, lc.eps)) return rc;
+  RayCall rc{};
+  if (d->flags & ~(LT_RENDER_FLAG_STRICT_MATH | LT_RENDER_FLAG_PORTABLE_MATH | LT_TRACE_FLAG_COHERENT | LT_TRACE_LIST_FLAG_FILL_ONLY))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT,
+                std::string(f.lists) + " take LT_RENDER_FLAG_STRICT_MATH, LT_RENDER_FLAG_PORTABLE_MATH, LT_TRACE_FLAG_COHERENT and " + f.fillOnly + " only");
+  if (const int e = check_ray_flags(ctx, d->flags & ~LT_TRACE_LIST_FLAG_FILL_ONLY, true, "hit lists take", rc)) return e;
+  if (d->reserved != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(f.desc) + "::reserved must be 0");
+  lc.devlibm = rc.devlibm;
+  lc.fillOnly = (d->flags & LT_TRACE_LIST_FLAG_FILL_ONLY) != 0;
+  return LT_OK;
 }
 
 // The rules about the records and the two buffers that the context's entry points and the host forms share, in their order.
@@ -3168,7 +3228,7 @@ static std::string list_buffers_error(const ListFamily& f, uint32_t flags, const
 
 // One half of a call, or both, on `s`, over device memory: `sized` runs the count and the scan, `fill` the fill and the ordering
 // over `capacity` items (`oneShot`: behind this stream's own scan, and nothing is written when its total is larger).
-static int enqueue_list(lt_hip_context* ctx, const ListFamily& f, const void* records, uint64_t n, uint64_t* offsets, void* items,
+static int enqueue_list(lt_hip_context* ctx, const ListFamily& f, const ListCall& lc, const void* records, uint64_t n, uint64_t* offsets, void* items,
                         uint64_t capacity, bool sized, bool fill, bool oneShot, hipStream_t s) {
   const RenderKnobs k;
   LT_HIP_CHECK(ctx, ensure_ray_counters(ctx->d_query_ctl));
@@ -3176,8 +3236,8 @@ static int enqueue_list(lt_hip_context* ctx, const ListFamily& f, const void* re
     const uint64_t words = lt_overlist::scan_partials(n);
     LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_list_partials, ctx->list_partials_words, words, words * sizeof(uint64_t)));
   }
-  ListPass p{records, (uint32_t)n, ctx->d_query_ctl, k.trace_refill, false, oneShot, (unsigned long long*)offsets, items, capacity};
-  const SceneDev sc = scene_dev(ctx, k, 2);
+  ListPass p{records, (uint32_t)n, ctx->d_query_ctl, k.trace_refill, false, oneShot, (unsigned long long*)offsets, items, capacity, lc.eps};
+  const SceneDev sc = scene_dev(ctx, k, lc.devlibm);
   if (const int rc = begin_ray_launches(ctx, &ctx->query_ev, s)) return rc;
   uint32_t launches = 0;
   if (sized) {
@@ -3188,28 +3248,27 @@ static int enqueue_list(lt_hip_context* ctx, const ListFamily& f, const void* re
   if (fill) {
     p.fill = true;
     LT_HIP_CHECK(ctx, f.walk(sc, p, (uint32_t)ctx->cu_count, s));
-    launches += 1 + lt_overlist::kOrderLaunches;
+    launches += 1 + (f.rankOrder && sc.rank8 == nullptr ? 0u : lt_overlist::kOrderLaunches);
   }
   return end_ray_launches(ctx, ctx->query_ev, s, launches, n, 0);
 }
 
 template <class Desc, class Record>
 static int run_list_call(lt_hip_context* ctx, const ListFamily& f, const Desc* desc, const Record* in, uint64_t n, uint64_t* offsets,
-                         uint64_t offsets_bytes, void* items, uint64_t items_bytes, bool device, void* hip_stream) {
+                         uint64_t offsets_bytes, void* items, uint64_t items_bytes, bool device, void* hip_stream,
+                         int (*check)(lt_hip_context*, const ListFamily&, const Desc*, ListCall&) = check_list_desc<Desc>) {
   if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  ListCall lc{};
+  if (const int rc = check(ctx, f, desc, lc)) return rc;
   {
-    const std::string why = list_desc_error(f, desc);
-    if (!why.empty()) return fail(ctx, LT_ERR_INVALID_ARGUMENT, why);
-  }
-  {
-    const std::string why = list_buffers_error(f, desc->flags, in, n, offsets, items, items_bytes);
+    const std::string why = list_buffers_error(f, lc.fillOnly ? kListFillOnly : 0u, in, n, offsets, items, items_bytes);
     if (!why.empty()) return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string(f.call) + ": " + why);
   }
   if (device && n > 0 && (((uintptr_t)in | (uintptr_t)offsets | (uintptr_t)items) & 15u))
     return fail(ctx, LT_ERR_INVALID_ARGUMENT, std::string("device ") + f.in + ", offsets and items must be 16-byte aligned");
   if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, std::string(f.call) + " before lt_hip_set_scene");
   if (offsets_bytes < (n + 1) * sizeof(uint64_t)) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "offsets is smaller than n + 1 words");
-  const bool fillOnly = (desc->flags & kListFillOnly) != 0;
+  const bool fillOnly = lc.fillOnly;
   const uint64_t capacity = items_bytes / f.itemBytes;
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (n == 0) {
@@ -3218,7 +3277,7 @@ static int run_list_call(lt_hip_context* ctx, const ListFamily& f, const Desc* d
     else offsets[0] = 0;
     return LT_OK;
   }
-  if (device) return enqueue_list(ctx, f, in, n, offsets, items, capacity, !fillOnly, items != nullptr, !fillOnly, (hipStream_t)hip_stream);
+  if (device) return enqueue_list(ctx, f, lc, in, n, offsets, items, capacity, !fillOnly, items != nullptr, !fillOnly, (hipStream_t)hip_stream);
   // The host form: the records and the offsets in the two staging buffers of the ray families, the items in a buffer of their own
   // -- growing a buffer frees what it held, and the offsets have to outlive the growth of the items.
   const uint64_t inBytes = n * sizeof(Record), offBytes = (n + 1) * sizeof(uint64_t);
@@ -3233,7 +3292,7 @@ static int run_list_call(lt_hip_context* ctx, const ListFamily& f, const Desc* d
     LT_HIP_CHECK(ctx, hipMemcpyAsync(dOffsets, offsets, offBytes, hipMemcpyHostToDevice, ctx->stream));
     total = offsets[n] < capacity ? offsets[n] : capacity;   // the items that can be written at all
   } else {
-    if (const int rc = enqueue_list(ctx, f, ctx->d_query_rays, n, dOffsets, nullptr, 0, true, false, false, ctx->stream)) return rc;
+    if (const int rc = enqueue_list(ctx, f, lc, ctx->d_query_rays, n, dOffsets, nullptr, 0, true, false, false, ctx->stream)) return rc;
     LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (const int rc = finish_pending(ctx)) return rc;
     sizedMs = ctx->last.kernel_ms;
@@ -3246,7 +3305,7 @@ static int run_list_call(lt_hip_context* ctx, const ListFamily& f, const Desc* d
   if (total == 0) return LT_OK;
   const uint64_t itemBytes = total * f.itemBytes;
   LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_list_items, ctx->list_items_bytes, itemBytes, itemBytes));
-  if (const int rc = enqueue_list(ctx, f, ctx->d_query_rays, n, dOffsets, ctx->d_list_items, total, false, true, false, ctx->stream)) return rc;
+  if (const int rc = enqueue_list(ctx, f, lc, ctx->d_query_rays, n, dOffsets, ctx->d_list_items, total, false, true, false, ctx->stream)) return rc;
   LT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   if (const int rc = finish_pending(ctx)) return rc;
   ctx->last.kernel_ms += sizedMs;
@@ -3283,6 +3342,16 @@ extern "C" int lt_hip_nearest_list(lt_hip_context* ctx, const lt_hip_nearest_lis
 extern "C" int lt_hip_nearest_list_device(lt_hip_context* ctx, const lt_hip_nearest_list_desc* desc, const lt_hip_point* points, uint64_t n,
                                           uint64_t* offsets, uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes, void* hip_stream) {
   return run_list_call(ctx, kNearestList, desc, points, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream);
+}
+
+extern "C" int lt_hip_trace_hits_list(lt_hip_context* ctx, const lt_hip_hits_list_desc* desc, const lt_hip_ray* rays, uint64_t n, uint64_t* offsets,
+                                      uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes) {
+  return run_list_call(ctx, kHitsList, desc, rays, n, offsets, offsets_bytes, items, items_bytes, false, nullptr, check_hits_list_desc);
+}
+
+extern "C" int lt_hip_trace_hits_list_device(lt_hip_context* ctx, const lt_hip_hits_list_desc* desc, const lt_hip_ray* rays, uint64_t n,
+                                             uint64_t* offsets, uint64_t offsets_bytes, lt_hip_hit* items, uint64_t items_bytes, void* hip_stream) {
+  return run_list_call(ctx, kHitsList, desc, rays, n, offsets, offsets_bytes, items, items_bytes, true, hip_stream, check_hits_list_desc);
 }
 
 // The same lists without a context or a GPU.  `sequence(nd, n_nodes, prims, record, seq)` fills `seq` with the whole sequence of

@@ -739,7 +739,7 @@ __device__ inline void traverse_own_lane(const SceneDev& sc, const Ray& ray, flo
 // group step and the same stack, another leaf action.  The walk never prunes by t, so it meets every leaf the reference's box
 // tests reach; here each leaf's triangle is tested from a payload of constant t = tmax -- accepted iff intersectTriangle accepts
 // it with t < tmax, whatever was found before -- and an accepted one that also passes the reference's test of the leaf's own
-// box goes to sink(t, primitive).  Returns true when the stack is empty.
+// box goes to sink(t, primitive, u, v).  Returns true when the stack is empty.
 template <int PROGRAM, int ROWS, class SINK>
 __device__ __forceinline__ bool own_walk_step_all(const SceneDev& sc, const Ray& ray, float ix, float iy, float iz, const OwnRay& w, float tmax,
                                                   SINK& sink, int* col, int* deep, uint32_t& e, int& sp) {
@@ -752,7 +752,7 @@ __device__ __forceinline__ bool own_walk_step_all(const SceneDev& sc, const Ray&
     if (intersect_triangle_data<PROGRAM>(t0, t1, make_float4(__uint_as_float(s2.x), 0.0f, 0.0f, 0.0f), ray, trial, sc.fastRcp != 0u) &&
         box_test_finite(__uint_as_float(s2.y), __uint_as_float(s2.z), __uint_as_float(s2.w), __uint_as_float(s3.x), __uint_as_float(s3.y),
                         __uint_as_float(s3.z), ray, ix, iy, iz))
-      sink(trial.t, (int)s3.w);
+      sink(trial.t, (int)s3.w, trial.u, trial.v);
   } else {
     const uint4 slot[4] = {s0, s1, s2, s3};
 #pragma unroll

@@ -2,12 +2,14 @@
 // queries' counts into the segments' bounds, and the ordering of each segment.  The count and the fill are lt_overlap.hip's and
 // lt_tritri.hip's kernels with the sinks kCountWide and kList (lt_overlap.hpp).  The radius lists (lt_hip_nearest_list) share both
 // steps: their count and fill are lt_nearest.hip's kernel with its kCountWide and kList, and their segments are 16-byte records.
+// So do the hit lists (lt_hip_trace_hits_list), with lt_query_hits_kernel's kinds of the same names; their order needs the rays.
 //
 // Neither step waits for another workgroup.  The scan is three launches -- per-tile sums, one workgroup over those sums, per-tile
 // scans plus the tile's base -- and the stream orders them.  A segment is sorted by one wave alone.
 #include "lt_overlist.hpp"
 #include "lt_device.hpp"
 #include "lt_nearest.hpp"
+#include "lt_query.hpp"
 
 using namespace lt;
 
@@ -104,10 +106,47 @@ template <class T> struct Span;
 template <> struct Span<int32_t> { static constexpr uint32_t kWords = lt_overlist::kListSortSpan; };
 template <> struct Span<uint4> { static constexpr uint32_t kWords = lt_overlist::kListSortSpanHits; };
 
+// An order, as the ordering kernel asks for it: take(q, key) -- is query q's segment this kernel's to sort, and the word its
+// comparator wants to know about the query --, and before(a, b, key).  The overlap and the radius lists: every segment, by
+// `smaller`, no word.
 template <class T>
-__device__ __forceinline__ void put_smaller_first(T* w, u64 lo, u64 hi) {
+struct PlainOrder {
+  __device__ __forceinline__ bool take(u64, uint32_t&) const { return true; }
+  __device__ __forceinline__ bool before(const T& a, const T& b, uint32_t) const { return smaller(a, b); }
+};
+
+// The hit lists' records {t, prim, u, v} of the rays the own tree takes (lt_query::own_tree_takes: the kernel's own predicate on
+// the same ray), which fill their segments in the own hierarchy's order: t by the float `<`, bit-equal t (-0 == +0) by the
+// reference's leaf order for the ray's octant -- rank8, read on ties only; the octant is the word, from the signs of 1 / direction
+// as own_ray computes it.  In a scene with an own tree a primitive has one leaf, so this is a strict total order over the distinct
+// records of a segment, and the network's result is the sequence although the network is not stable.  The other rays' segments
+// are sorted when they are filled (lt_query.hip, HitInsert) and are left as they are.  (A segment the caller's offsets made longer
+// than the ray's sequence ends in whatever the caller's buffer held: a primitive that is none of the scene's has no row in the
+// table and goes behind those that have, by its own bits.)
+struct RayHitOrder {
+  const float4* rays;
+  const uint32_t* rank8;
+  uint32_t nPrims;
+  __device__ __forceinline__ u64 rank(uint32_t prim, uint32_t octant) const {
+    return prim < nPrims ? (u64)rank8[8 * (size_t)prim + octant] : (1ull << 32) | prim;
+  }
+  __device__ __forceinline__ bool take(u64 q, uint32_t& octant) const {
+    const float4 a = rays[2 * q], b = rays[2 * q + 1];
+    const Ray ray{mk4(a.x, a.y, a.z, 1.0f), mk4(b.x, b.y, b.z, 0.0f)};
+    const float ix = 1.0f / ray.d.x, iy = 1.0f / ray.d.y, iz = 1.0f / ray.d.z;
+    octant = (ix < 0.0f ? 1u : 0u) | (iy < 0.0f ? 2u : 0u) | (iz < 0.0f ? 4u : 0u);
+    return lt_query::own_tree_takes(ray, ix, iy, iz);
+  }
+  __device__ __forceinline__ bool before(const uint4& a, const uint4& b, uint32_t octant) const {
+    const float ta = __uint_as_float(a.x), tb = __uint_as_float(b.x);
+    return ta < tb || (ta == tb && rank(a.y, octant) < rank(b.y, octant));
+  }
+};
+
+template <class T, class ORDER>
+__device__ __forceinline__ void put_smaller_first(T* w, u64 lo, u64 hi, const ORDER& order, uint32_t key) {
   const T a = w[lo], b = w[hi];
-  if (smaller(b, a)) { w[lo] = b; w[hi] = a; }
+  if (order.before(b, a, key)) { w[lo] = b; w[hi] = a; }
 }
 
 // Sorts w[0 .. L) ascending, L >= 2, by the normalised bitonic network over P = the power of two at or above L: every comparator
@@ -118,8 +157,8 @@ __device__ __forceinline__ void put_smaller_first(T* w, u64 lo, u64 hi) {
 // ends in __syncthreads(): the workgroup is this one wave, and the call carries the workgroup-scope release and acquire fences
 // that order one lane's stores before another's loads.  A comparator's lower index grows with its number t, so a lane stops
 // at the first one that starts at or behind L.
-template <class T>
-__device__ __forceinline__ void sort_segment(T* w, u64 L) {
+template <class T, class ORDER>
+__device__ __forceinline__ void sort_segment(T* w, u64 L, const ORDER& order, uint32_t key) {
   const u64 lane = threadIdx.x;
   for (uint32_t lk = 1; (1ull << (lk - 1)) < L; lk++) {     // k = 1 << lk
     const u64 half = 1ull << (lk - 1);
@@ -127,7 +166,7 @@ __device__ __forceinline__ void sort_segment(T* w, u64 L) {
       const u64 block = (t >> (lk - 1)) << lk, r = t & (half - 1);
       const u64 lo = block + r, hi = block + (2 * half - 1 - r);
       if (lo >= L) break;
-      if (hi < L) put_smaller_first(w, lo, hi);
+      if (hi < L) put_smaller_first(w, lo, hi, order, key);
     }
     __syncthreads();
     for (uint32_t lj = lk - 1; lj-- > 0;) {                  // j = 1 << lj = k / 4 .. 1
@@ -135,7 +174,7 @@ __device__ __forceinline__ void sort_segment(T* w, u64 L) {
       for (u64 t = lane;; t += kBlock) {
         const u64 lo = ((t >> lj) << (lj + 1)) | (t & (j - 1)), hi = lo + j;
         if (lo >= L) break;
-        if (hi < L) put_smaller_first(w, lo, hi);
+        if (hi < L) put_smaller_first(w, lo, hi, order, key);
       }
       __syncthreads();
     }
@@ -152,9 +191,10 @@ __device__ __forceinline__ u64 lane_word(u64 v, uint32_t lane) {
 
 // Order: a wave takes 64 consecutive queries, each lane reads one's clamped bounds (lt_overlap::Sink's), and the wave sorts the
 // segments longer than one element one after another: up to Span<T> elements in LDS (16 KB either way), longer ones where they
-// lie.  T: int32_t, an overlap list's offsets, or uint4, a radius list's records.
-template <class T>
-__global__ __launch_bounds__(kBlock) void lt_list_order_kernel(const u64* offsets, uint32_t n, T* items, u64 capacity, uint32_t oneShot) {
+// lie.  T: int32_t, an overlap list's offsets, or uint4, a radius list's records -- or, ORDER = RayHitOrder, a hit list's, where
+// the order leaves out the segments it does not take and every comparator knows the segment's ray's octant.
+template <class T, class ORDER = PlainOrder<T>>
+__global__ __launch_bounds__(kBlock) void lt_list_order_kernel(const u64* offsets, uint32_t n, T* items, u64 capacity, uint32_t oneShot, ORDER order) {
   __shared__ T seg[Span<T>::kWords];
   if (oneShot != 0u && offsets[n] > capacity) return;
   const uint32_t lane = threadIdx.x;
@@ -162,26 +202,29 @@ __global__ __launch_bounds__(kBlock) void lt_list_order_kernel(const u64* offset
   for (uint32_t c = blockIdx.x; c < chunks; c += gridDim.x) {
     const u64 q = (u64)c * kBlock + lane;
     u64 begin = 0, length = 0;
+    uint32_t key = 0u;
     if (q < n) {
       const u64 to = offsets[q + 1];
       const u64 end = to < capacity ? to : capacity;
       begin = offsets[q];
       length = end > begin ? end - begin : 0ull;
+      if (length > 1ull && !order.take(q, key)) length = 0ull;
     }
     u64 todo = __builtin_amdgcn_ballot_w64(length > 1ull);
     while (todo != 0ull) {
       const uint32_t j = (uint32_t)__builtin_ctzll(todo);
       todo &= todo - 1ull;
       const u64 L = lane_word(length, j);
+      const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)j);
       T* const w = items + lane_word(begin, j);
       if (L <= Span<T>::kWords) {
         for (u64 i = lane; i < L; i += kBlock) seg[i] = w[i];
         __syncthreads();
-        sort_segment(seg, L);
+        sort_segment(seg, L, order, k);
         for (u64 i = lane; i < L; i += kBlock) w[i] = seg[i];
         __syncthreads();   // (the next segment's words overwrite these)
       } else {
-        sort_segment(w, L);
+        sort_segment(w, L, order, k);
       }
     }
   }
@@ -199,15 +242,15 @@ hipError_t scan(unsigned long long* offsets, uint32_t n, unsigned long long* par
 
 namespace {
 
-template <class T>
+template <class T, class ORDER = PlainOrder<T>>
 hipError_t order_elements(const unsigned long long* offsets, uint32_t n, T* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
-                          hipStream_t s) {
+                          hipStream_t s, ORDER order = ORDER{}) {
   if (n == 0) return hipSuccess;
   const uint32_t chunks = (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock);
   // 16 KB of LDS per wave: ten waves per CU
   const uint32_t resident = cuCount * 10u;
-  hipLaunchKernelGGL(lt_list_order_kernel<T>, dim3(chunks < resident ? chunks : resident), dim3(kBlock), 0, s, offsets, n, items, capacity,
-                     oneShot ? 1u : 0u);
+  hipLaunchKernelGGL((lt_list_order_kernel<T, ORDER>), dim3(chunks < resident ? chunks : resident), dim3(kBlock), 0, s, offsets, n, items,
+                     capacity, oneShot ? 1u : 0u, order);
   return hipGetLastError();
 }
 
@@ -221,6 +264,12 @@ hipError_t order(const unsigned long long* offsets, uint32_t n, int32_t* items, 
 hipError_t order_hits(const unsigned long long* offsets, uint32_t n, uint4* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
                       hipStream_t s) {
   return order_elements(offsets, n, items, capacity, oneShot, cuCount, s);
+}
+
+hipError_t order_ray_hits(const unsigned long long* offsets, uint32_t n, uint4* items, unsigned long long capacity, bool oneShot,
+                          const float4* rays, const uint32_t* rank8, uint32_t nPrims, uint32_t cuCount, hipStream_t s) {
+  if (rank8 == nullptr) return hipSuccess;   // every ray walked in the reference's order and filled its segment sorted
+  return order_elements(offsets, n, items, capacity, oneShot, cuCount, s, RayHitOrder{rays, rank8, nPrims});
 }
 
 }  // namespace lt_overlist

@@ -9,6 +9,9 @@
 // No kernel waits for another workgroup: the scan is three launches, and a segment is sorted by the one wave that took it.
 // The radius lists (lt_hip_nearest_list) are the same four steps with lt_nearest.hip's walk and its kinds of the same names; their
 // items are 16-byte records {d2, prim, u, v}, ordered by (d2, prim).
+// The hit lists (lt_hip_trace_hits_list) are the four steps once more with lt_query.hip's walks: 16-byte records {t, prim, u, v},
+// ordered by t and, among bit-equal t, by the reference's traversal order -- for the rays the own tree takes through the scene's
+// rank table in the ordering kernel, for the others by a stable insertion during the fill.
 #pragma once
 #include <stdint.h>
 
@@ -18,7 +21,7 @@ namespace lt_overlist {
 constexpr uint32_t kListScanTile = 2048;
 // The longest segment that is sorted in LDS: 16 KB per wave.  Longer ones are sorted in place in global memory.
 constexpr uint32_t kListSortSpan = 4096;
-// The same for a radius list's 16-byte records (lt_hip_nearest_list): 16 KB per wave again, ten waves per CU.
+// The same for 16-byte records (lt_hip_nearest_list, lt_hip_trace_hits_list): 16 KB per wave again, ten waves per CU.
 constexpr uint32_t kListSortSpanHits = 1024;
 
 // Partial sums the scan of n queries needs (one uint64 per tile of the n + 1 words).
@@ -46,6 +49,12 @@ hipError_t order(const unsigned long long* offsets, uint32_t n, int32_t* items, 
 // both are bit-identical, so the order among them is no one's to see.  One launch on `s`.
 hipError_t order_hits(const unsigned long long* offsets, uint32_t n, uint4* items, unsigned long long capacity, bool oneShot, uint32_t cuCount,
                       hipStream_t s);
+
+// The same over a hit list's records {t, prim, u, v}, for the rays the own tree takes (lt_query::own_tree_takes on rays[i]; the
+// other rays' segments are sorted already and stay untouched): ascending t by the float `<`, bit-equal t by rank8[8 prim + octant],
+// the octant ray i's (nPrims: the table's rows).  rank8 null -- a scene without an own tree -- launches nothing.  One launch on `s`, or none.
+hipError_t order_ray_hits(const unsigned long long* offsets, uint32_t n, uint4* items, unsigned long long capacity, bool oneShot,
+                          const float4* rays, const uint32_t* rank8, uint32_t nPrims, uint32_t cuCount, hipStream_t s);
 
 }  // namespace lt_overlist
 #endif

@@ -15,7 +15,9 @@
 //   lt_query_packet_kernel  LT_TRACE_FLAG_COHERENT: one wave per 64 consecutive rays, walked as one packet (packet_walk) when
 //                           the 64 qualify, per lane otherwise.
 // And the multi-hit queries (lt_hip_trace_hits): lt_query_hits_kernel, lt_query_kernel's loop with another leaf action -- every
-// accepted primitive goes into a per-lane list sorted by t (the first K hits), or is counted.
+// accepted primitive goes into a per-lane list sorted by t (the first K hits), or is counted.  The hit lists
+// (lt_hip_trace_hits_list; lt_overlist.hpp has the four steps) are that kernel with two more sinks: the count as one uint64 per
+// ray, and every accepted hit stored into the ray's segment of the CSR items.
 // And the surface queries (lt_hip_surface_at; lt_hip_trace_surface is a closest-hit query and this): lt_surface_at_kernel turns hit
 // records into what every `shade` of the reference computes first at a hit.  Nothing is walked.
 #include "lt_query.hpp"
@@ -33,10 +35,7 @@ __device__ __forceinline__ void put_result(const lt_query::Params& qp, uint32_t 
   else qp.hits[idx] = make_uint4(__float_as_uint(pl.t), pl.hitType != 0 ? (uint32_t)pl.prim : 0xffffffffu, __float_as_uint(pl.u), __float_as_uint(pl.v));
 }
 
-__device__ __forceinline__ bool finite_ray(const Ray& ray, float ix, float iy, float iz) {
-  return __builtin_fabsf(ix) < __builtin_inff() && __builtin_fabsf(iy) < __builtin_inff() && __builtin_fabsf(iz) < __builtin_inff() &&
-         __builtin_fabsf(ray.o.x) < __builtin_inff() && __builtin_fabsf(ray.o.y) < __builtin_inff() && __builtin_fabsf(ray.o.z) < __builtin_inff();
-}
+using lt_query::finite_ray;
 
 // A ray the own tree does not take, or any ray of a scene without one: the reference's order over the caller's tree.
 template <int PROGRAM, bool ANYHIT>
@@ -111,7 +110,39 @@ struct HitList {
 
 struct HitCount {
   uint32_t n;
-  __device__ __forceinline__ void operator()(float, int) { n++; }
+  __device__ __forceinline__ void operator()(float, int, float, float) { n++; }
+};
+
+// The hit lists (lt_hip_trace_hits_list): the clamped end of ray i's segment, and the records it has room for -- a length that
+// would be negative is 0, so with any offsets at all no store falls outside items[0 .. capacity).
+__device__ __forceinline__ unsigned long long segment_end(const lt_query::HitsParams& qp, uint32_t i) {
+  const unsigned long long to = qp.offsets[(size_t)i + 1];
+  return to < qp.capacity ? to : qp.capacity;
+}
+__device__ __forceinline__ uint32_t segment_room(const lt_query::HitsParams& qp, uint32_t i) {
+  const unsigned long long begin = qp.offsets[i], to = segment_end(qp, i);
+  const unsigned long long room = to > begin ? to - begin : 0ull;
+  return room > 0xffffffffull ? 0xffffffffu : (uint32_t)room;
+}
+
+// The fill of a ray that walks in the reference's order: that order is the sequence's among bit-equal t, and no sort that comes
+// later could know it, so the lane keeps its segment sorted while it fills it -- a stable insertion in device memory over the
+// lane's own loads and stores, a hit of equal t going behind what is there, one pushed past the segment's end dropped.  Quadratic
+// in the segment's length, on the path that is the slow one already.
+struct HitInsert {
+  uint4* seg;
+  uint32_t room, filled;
+  __device__ __forceinline__ void operator()(float t, int prim, float u, float v) {
+    uint32_t j = filled;
+    while (j > 0u) {
+      const uint4 r = seg[j - 1u];
+      if (!(t < __uint_as_float(r.x))) break;
+      if (j < room) seg[j] = r;
+      j--;
+    }
+    if (j < room) seg[j] = make_uint4(__float_as_uint(t), (uint32_t)prim, __float_as_uint(u), __float_as_uint(v));
+    if (filled < room) filled++;
+  }
 };
 
 // walk_reference for these queries: the caller's tree in the reference's order (acc.cl:132-217: near child first by
@@ -137,12 +168,18 @@ __device__ __forceinline__ void walk_reference_all(const SceneDev& sc, const Ray
       }
       if (off != ign) {
         Hit trial{0, 0, tmax, 0.0f, 0.0f};
-        if (intersect_triangle<PROGRAM>(sc.tris, off, ray, trial, sc.fastRcp != 0u)) sink(trial.t, off);
+        if (intersect_triangle<PROGRAM>(sc.tris, off, ray, trial, sc.fastRcp != 0u)) sink(trial.t, off, trial.u, trial.v);
       }
     }
     if (sp == 0) break;
     cur = todo[--sp];
   }
+}
+
+// A ray's count: one uint32 (LT_TRACE_COUNT) or, kCountWide, one uint64 into the list's offsets.
+template <int KIND>
+__device__ __forceinline__ void put_hit_count(const lt_query::HitsParams& qp, uint32_t idx, uint32_t n) {
+  if (KIND == lt_query::kCountWide) qp.offsets[idx] = n; else qp.counts[idx] = n;
 }
 
 }  // namespace
@@ -267,12 +304,18 @@ __global__ __launch_bounds__(kBlock, 8) void lt_query_packet_kernel(SceneDev sc,
 }
 
 // lt_query_kernel's claim, stage and refill loop with the multi-hit leaf action (own_walk_step_all): COUNT counts a ray's accepted
-// primitives in a register; otherwise they go into the lane's HitList of qp.maxHits entries, 2 maxHits LDS rows behind the stage,
+// primitives in a register; kFirstK puts them into the lane's HitList of qp.maxHits entries, 2 maxHits LDS rows behind the stage,
 // which the lane resets when it takes a new ray -- its neighbours' lists stay as they are -- and writes out when its walk is done.
-template <int PROGRAM, bool COUNT>
+// The hit lists (lt_hip_trace_hits_list) are two more sinks, neither with LDS list rows, so their layout and occupancy are the
+// count's: kCountWide is the count stored as one uint64 into offsets[idx]; kList stores each accepted hit {t, prim, u, v} -- u and v
+// arrive with it -- behind the last in the ray's segment while records are left of it (`left`; the segment's end is read again
+// beside the store, lt_nearest.hip's ListSink says why), or, for a ray that walks in the reference's order, by HitInsert.
+template <int PROGRAM, int KIND>
 __global__ __launch_bounds__(kBlock, 8) void lt_query_hits_kernel(SceneDev sc, lt_query::HitsParams qp) {
   using u64 = unsigned long long;
+  constexpr bool COUNT = KIND == lt_query::kCount || KIND == lt_query::kCountWide, LIST = KIND == lt_query::kList;
   extern __shared__ int lds_stack[];   // [kTraceRows stack rows][kTraceStage rows of staged rays][2 maxHits list rows], 64 lanes each
+  if (LIST && qp.oneShot != 0u && qp.offsets[qp.n] > qp.capacity) return;   // (every lane reads the same word)
   int* const col = lds_stack + threadIdx.x;
   int* const stage = lds_stack + kTraceRows * kBlock;
   const uint32_t total = qp.n;
@@ -288,11 +331,19 @@ __global__ __launch_bounds__(kBlock, 8) void lt_query_hits_kernel(SceneDev sc, l
   Ray ray{};
   float ix = 0.0f, iy = 0.0f, iz = 0.0f, tmax = 0.0f;
   OwnRay w{};
-  HitList list{lds_stack + (kTraceRows + kTraceStage) * kBlock + threadIdx.x, COUNT ? 0u : qp.maxHits};
+  HitList list{lds_stack + (kTraceRows + kTraceStage) * kBlock + threadIdx.x, COUNT || LIST ? 0u : qp.maxHits};
   HitCount count{0u};
-  auto ranked = [&](float t, int prim) { list.insert(t, prim, sc.rank8, w.octant); };   // the own tree's order is not the reference's
-  auto inOrder = [&](float t, int prim) { list.insert(t, prim, nullptr, 0u); };
-  uint32_t idx = 0u, e = 0u;
+  uint32_t idx = 0u, e = 0u, left = 0u;
+  auto ranked = [&](float t, int prim, float, float) { list.insert(t, prim, sc.rank8, w.octant); };   // the own tree's order is not the reference's
+  auto inOrder = [&](float t, int prim, float, float) { list.insert(t, prim, nullptr, 0u); };
+  auto behind = [&](float t, int prim, float u, float v) {   // kList, the own walk: its order is left to the ordering kernel
+    if (left != 0u) {
+      const u64 to = segment_end(qp, idx);
+      // (left <= to holds while the offsets are what the lane read when it took the ray; were they changed under the launch, the store is dropped)
+      if (left <= to) qp.items[to - left] = make_uint4(__float_as_uint(t), (uint32_t)prim, __float_as_uint(u), __float_as_uint(v));
+      left--;
+    }
+  };
   int sp = 0;
   int deep[kOwnRows + kOwnDeep - kTraceRows];
   for (;;) {
@@ -336,7 +387,7 @@ __global__ __launch_bounds__(kBlock, 8) void lt_query_hits_kernel(SceneDev sc, l
         const int ign = ignRaw >= 0 ? ignRaw : -1;
         ix = 1.0f / ray.d.x; iy = 1.0f / ray.d.y; iz = 1.0f / ray.d.z;
         tmax = __int_as_float(stage[7 * kBlock + s]);
-        if (COUNT) count.n = 0u; else list.reset(tmax);
+        if (COUNT) count.n = 0u; else if (LIST) left = segment_room(qp, idx); else list.reset(tmax);
         if (ownTree && finite_ray(ray, ix, iy, iz) && packet_ray_ok(ray, ix, iy, iz)) {
           w = own_ray(sc, ray, ix, iy, iz, ign);
           e = 0u;
@@ -345,7 +396,10 @@ __global__ __launch_bounds__(kBlock, 8) void lt_query_hits_kernel(SceneDev sc, l
         } else {
           if (COUNT) {
             walk_reference_all<PROGRAM>(sc, ray, ix, iy, iz, ign, tmax, count);
-            qp.counts[idx] = count.n;
+            put_hit_count<KIND>(qp, idx, count.n);
+          } else if (LIST) {
+            HitInsert sorted{qp.items + qp.offsets[idx], left, 0u};
+            walk_reference_all<PROGRAM>(sc, ray, ix, iy, iz, ign, tmax, sorted);
           } else {
             walk_reference_all<PROGRAM>(sc, ray, ix, iy, iz, ign, tmax, inOrder);
             list.template finish<PROGRAM>(sc, ray, tmax, qp.hits + (size_t)idx * qp.maxHits);
@@ -359,11 +413,12 @@ __global__ __launch_bounds__(kBlock, 8) void lt_query_hits_kernel(SceneDev sc, l
       continue;
     }
     if (active) {
-      const bool done = COUNT ? own_walk_step_all<PROGRAM, kTraceRows>(sc, ray, ix, iy, iz, w, tmax, count, col, deep, e, sp)
-                              : own_walk_step_all<PROGRAM, kTraceRows>(sc, ray, ix, iy, iz, w, tmax, ranked, col, deep, e, sp);
+      const bool done = COUNT  ? own_walk_step_all<PROGRAM, kTraceRows>(sc, ray, ix, iy, iz, w, tmax, count, col, deep, e, sp)
+                        : LIST ? own_walk_step_all<PROGRAM, kTraceRows>(sc, ray, ix, iy, iz, w, tmax, behind, col, deep, e, sp)
+                               : own_walk_step_all<PROGRAM, kTraceRows>(sc, ray, ix, iy, iz, w, tmax, ranked, col, deep, e, sp);
       if (done) {
-        if (COUNT) qp.counts[idx] = count.n;
-        else list.template finish<PROGRAM>(sc, ray, tmax, qp.hits + (size_t)idx * qp.maxHits);
+        if (COUNT) put_hit_count<KIND>(qp, idx, count.n);
+        else if (!LIST) list.template finish<PROGRAM>(sc, ray, tmax, qp.hits + (size_t)idx * qp.maxHits);
         active = false;
       }
     }
@@ -449,13 +504,16 @@ static void launch_hits_one(const SceneDev& sc, const HitsParams& p, uint32_t cu
   const uint32_t fit = 160u * 1024u / (rows * kBlock * (uint32_t)sizeof(int)), perCu = fit < 32u ? fit : 32u;
   const uint32_t resident = cuCount * perCu;
   const dim3 grid(chunks < resident ? chunks : resident);
-  if (p.maxHits == 0u) hipLaunchKernelGGL((lt_query_hits_kernel<PROGRAM, true>), grid, dim3(kBlock), rows * kBlock * (uint32_t)sizeof(int), s, sc, p);
-  else hipLaunchKernelGGL((lt_query_hits_kernel<PROGRAM, false>), grid, dim3(kBlock), rows * kBlock * (uint32_t)sizeof(int), s, sc, p);
+  const uint32_t bytes = rows * kBlock * (uint32_t)sizeof(int);
+  if (p.kind == (uint32_t)kCount) hipLaunchKernelGGL((lt_query_hits_kernel<PROGRAM, kCount>), grid, dim3(kBlock), bytes, s, sc, p);
+  else if (p.kind == (uint32_t)kCountWide) hipLaunchKernelGGL((lt_query_hits_kernel<PROGRAM, kCountWide>), grid, dim3(kBlock), bytes, s, sc, p);
+  else if (p.kind == (uint32_t)kList) hipLaunchKernelGGL((lt_query_hits_kernel<PROGRAM, kList>), grid, dim3(kBlock), bytes, s, sc, p);
+  else hipLaunchKernelGGL((lt_query_hits_kernel<PROGRAM, kFirstK>), grid, dim3(kBlock), bytes, s, sc, p);
 }
 
 hipError_t launch_hits(const SceneDev& sc, const HitsParams& p, Epsilon eps, uint32_t cuCount, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  if (p.maxHits > kMaxHits) return hipErrorInvalidValue;
+  if (p.kind > (uint32_t)kList || p.maxHits > kMaxHits || (p.kind == (uint32_t)kFirstK) != (p.maxHits != 0u)) return hipErrorInvalidValue;
   const hipError_t e = hipMemsetAsync(p.next, 0, 8 * kQueueStride * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   switch (eps) {

@@ -27,17 +27,40 @@ hipError_t launch(const lt::SceneDev& sc, const Params& p, Epsilon eps, bool any
 // t < tmax, in ascending t (bit-equal t: the reference's traversal order).  Results: the first maxHits of them as maxHits
 // lt_hip_hit records per ray, ray-major, unused slots {tmax, -1, 0, 0}; or, maxHits == 0, their number as one word per ray.
 constexpr uint32_t kMaxHits = 8;   // LT_TRACE_MAX_HITS
+// The sinks of lt_query_hits_kernel.  kFirstK and kCount are the descriptor's kinds.  The hit lists (lt_hip_trace_hits_list) are
+// the other two: kCountWide, kCount as one uint64 per ray into offsets[i]; kList, the whole sequence of ray i as lt_hip_hit records
+// into items[offsets[i] .. min(offsets[i + 1], capacity)) -- a length that would be negative is 0, so that with any offsets at all
+// no store falls outside items[0 .. capacity).  A ray the own tree takes fills its segment in the own walk's order
+// (lt_overlist::order_ray_hits sorts it then); every other ray keeps its segment sorted as it fills it (own_tree_takes).
+enum HitsKind { kFirstK = 0, kCount = 1, kCountWide = 2, kList = 3 };
 struct HitsParams {
   const float4* rays;
   uint4* hits;          // first K: record i * maxHits + j
   uint32_t* counts;     // count
   uint32_t n;
-  uint32_t maxHits;     // 1..kMaxHits; 0 = count
+  uint32_t maxHits;     // 1..kMaxHits; 0 = every other kind
   uint32_t* next;       // as Params::next
   uint32_t refill;      // as Params::refill
+  uint32_t kind;        // HitsKind
+  uint32_t oneShot;     // kList: the offsets are this stream's own scan -- when offsets[n] > capacity the launch writes nothing
+  unsigned long long* offsets;   // kCountWide: written, n words; kList: read, n + 1 words
+  uint4* items;                  // kList: `capacity` records
+  unsigned long long capacity;
 };
 
-// Enqueues lt_query_hits_kernel on `s`.  Returns the first HIP error.
+// Which walk a ray of the query kernels takes: the own tree's, when the scene has one (SceneDev::rank8), every component of the
+// origin and of the inverse direction is finite and the magnitudes are packet_ray_ok's; the reference's order over the caller's
+// tree otherwise.  ix = 1.0f / direction.x and so on, as the kernels compute them.  The hit lists' ordering asks the same
+// question about the same ray (lt_overlist.hip).
+__device__ __forceinline__ bool finite_ray(const lt::Ray& ray, float ix, float iy, float iz) {
+  return __builtin_fabsf(ix) < __builtin_inff() && __builtin_fabsf(iy) < __builtin_inff() && __builtin_fabsf(iz) < __builtin_inff() &&
+         __builtin_fabsf(ray.o.x) < __builtin_inff() && __builtin_fabsf(ray.o.y) < __builtin_inff() && __builtin_fabsf(ray.o.z) < __builtin_inff();
+}
+__device__ __forceinline__ bool own_tree_takes(const lt::Ray& ray, float ix, float iy, float iz) {
+  return finite_ray(ray, ix, iy, iz) && lt::packet_ray_ok(ray, ix, iy, iz);
+}
+
+// Enqueues lt_query_hits_kernel on `s`, the instantiation of p.kind.  Returns the first HIP error.
 hipError_t launch_hits(const lt::SceneDev& sc, const HitsParams& p, Epsilon eps, uint32_t cuCount, hipStream_t s);
 
 // Surface queries (lt_hip_surface_at, and lt_hip_trace_surface behind its closest-hit query): lt_surface_at_kernel over n hit

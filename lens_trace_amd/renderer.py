@@ -330,6 +330,8 @@ def overlap_tris_host(scene: Scene, tris, k=None, count=False, any=False):
 # The list families: (the descriptor, its FILL_ONLY flag, the numpy dtype of an item, the torch dtype and trailing shape of one).
 _OVERLAP_LIST = (C.OverlapListDesc, C.OVERLAP_LIST_FLAG_FILL_ONLY, np.int32, ("int32", ()))
 _NEAREST_LIST = (C.NearestListDesc, C.NEAREST_LIST_FLAG_FILL_ONLY, HIT_DTYPE, ("float32", (4,)))
+# (the hit lists' descriptor also names a program and carries math flags: _list_call's `describe`)
+_HITS_LIST = (C.HitsListDesc, C.TRACE_LIST_FLAG_FILL_ONLY, HIT_DTYPE, ("float32", (4,)))
 
 
 def _list_host(name, scene, rec, family=_OVERLAP_LIST):
@@ -619,6 +621,21 @@ class RendererHIP:
         return self._ray_call("trace_hits", d, rays, _QUERY_RAYS, (np.uint32, ()) if count else (HIT_DTYPE, (k,)),
                               ("int32", ()) if count else ("float32", (k, 4)), stream)
 
+    def trace_hits_list(self, rays, program="accumulator", portable_math=False, strict_math=False, coherent=False, stream=None):
+        """Every hit of each ray, nearest first, as CSR (lt_hip_trace_hits_list): (offsets, items) with items[offsets[i] :
+        offsets[i + 1]] the whole hit sequence of ray i -- trace_hits' records (t, prim, u, v) without the limit of eight and
+        without miss records; surface_at takes them as they are.  Rays, program and the math flags as trace_hits takes them:
+        numpy in gives numpy, offsets uint64 (n + 1,) and items HIT_DTYPE (total,); a torch tensor on this context's GPU gives
+        tensors, offsets as int64 and items float32 (total, 4) (column 1: int32 bits), after the sizing call, one read of the
+        total and the fill call on `stream` (default: the current torch stream).  coherent is accepted and changes nothing."""
+        prog, flags = _program_id(program), _ray_flags(coherent, portable_math, strict_math)
+
+        def describe(list_flags):
+            return C.HitsListDesc(ctypes.sizeof(C.HitsListDesc), prog, flags | list_flags, 0)
+        if isinstance(rays, np.ndarray):
+            return self._list_call("trace_hits", rays, lambda r: ray_records(r, *_QUERY_RAYS), "rays", 8, stream, _HITS_LIST, describe)
+        return self._list_call("trace_hits", rays, None, "rays", 8, stream, _HITS_LIST, describe)
+
     # -- surface queries -------------------------------------------------------------------------------
     def trace_surface(self, rays, program="accumulator", coherent=False, portable_math=False, strict_math=False, stream=None):
         """Closest hits with the surface behind them (lt_hip_trace_surface): for each ray trace_rays' record (t, prim, u, v), the
@@ -739,13 +756,16 @@ class RendererHIP:
         return self._device_call("overlap_tris", d, tris, "tris", "n", 12, ("int32", (d.max_k,) if d.max_k else ()), stream)
 
     # -- overlap lists ----------------------------------------------------------------------------------
-    def _list_call(self, name, records, numpy_records, what, width, stream, family=_OVERLAP_LIST):
+    def _list_call(self, name, records, numpy_records, what, width, stream, family=_OVERLAP_LIST, describe=None):
         """lt_hip_<name>_list: numpy in, the host entry point sized and then filled; a torch tensor in, the device entry point --
-        the sizing call, one .item() for the total, the items allocated, the family's FILL_ONLY call."""
+        the sizing call, one .item() for the total, the items allocated, the family's FILL_ONLY call.  describe(flags): the
+        family's descriptor with these list flags, where it holds more than its size and flags (a program, math flags)."""
         vp = ctypes.c_void_p
         Desc, fill_only, item, (tdtype, tshape) = family
         size = ctypes.sizeof(Desc)
-        sizing, fill = Desc(size, 0), Desc(size, fill_only)
+        if describe is None:
+            describe = lambda flags: Desc(size, flags)  # noqa: E731
+        sizing, fill = describe(0), describe(fill_only)
         if isinstance(records, np.ndarray):
             rec = numpy_records(records)
             f = getattr(self._L, "lt_hip_%s_list" % name)
