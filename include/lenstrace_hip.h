@@ -923,6 +923,15 @@ int lt_hip_entry_cut_triangle_test_host(const float* origins, const float* light
  * Waits for the context's last render. */
 int lt_hip_clear_item_counts(lt_hip_context* ctx, uint64_t* out5);
 
+/* A clear square handed out whole renders its two-frame groups in one pass over the square: the per-pixel set-up once, two new
+ * randoms per group (a group shares two seeds with the next), the running mean in registers where the square folds.  A group whose
+ * frames would not walk together, or with a light sample off the light list, and a trailing group of one frame go back to the
+ * per-group path.  Same pixels.  LT_CLEAR_SQUARE=0: every group through the per-group path.
+ * Of the context's last render launch, as its waves counted: out3[0] the squares that entered the pass, out3[1] those of them that left
+ * it before their last group, out3[2] the frame groups rendered in it.  All zero where the launch took no such pass.  Waits for the
+ * context's last render. */
+int lt_hip_clear_square_counts(lt_hip_context* ctx, uint64_t* out3);
+
 /* The item table and its fold map on the host, for tests: marks[p] is word 0 of the list of the square at hand-out position p < n
  * (0xffffffff: clear), order[p] that square's index (NULL: p), groups the frame groups of the launch.  table: 16 + n * groups
  * words -- words 0 .. 7 the entry counts of the eight shares, the entries of share x from word 16 + (start of x) * groups, an entry

@@ -405,6 +405,9 @@ struct lt_hip_context {
   bool items_folds = false;
   unsigned long long* d_item_stats = nullptr;   // [0] the table's entries, [1] the squares it hands out whole
   uint64_t item_builds = 0;          // launches of lt_clear_items_kernel so far
+  // the work counters of the context's last render launch if it rendered whole squares in one pass (render_clear_square), whose
+  // counters lie in the same lines (kClearCountAt), else null: lt_hip_clear_square_counts
+  const uint32_t* last_clear_queues = nullptr;
   bool last_folded = false;          // some launch of the context's last render call was told to have the whole squares fold their own samples
   bool last_tabled = false;          // ... and some launch of it took the table (lt_hip_clear_item_counts)
   // Whether the table is worth taking is a matter of how many squares are clear, which only the device knows: the build's counters
@@ -1234,6 +1237,7 @@ struct RenderKnobs {
   bool clear_items = !env_off("LT_CLEAR_ITEMS");   // off: no item table -- a clear square is `groups` claims and stores its samples (ensure_clear_items)
   bool clear_items_fold = true;         // LT_CLEAR_ITEMS=2: the table's hand-out alone -- whole squares store their samples, the fold reads them
   bool clear_items_force = false;       // LT_CLEAR_ITEMS=1 or 2: the table however few squares are clear (unset: only where a third of them are)
+  bool clear_square = !env_off("LT_CLEAR_SQUARE");   // off: a clear square handed out whole renders its frame groups one by one (render_clear_square)
   uint32_t shadow_frames = 2;           // LT_SHADOW_FRAMES=1..2: frames per work item whose shadow rays walk together (launch_walk)
   bool debug_shadow_frames = getenv("LT_DEBUG_SHADOW_FRAMES") != nullptr;   // launch_walk prints the frame groups of every render launch
                                                                             // and, where there are groups, how many waves walked them together
@@ -2103,6 +2107,7 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
   if (!ctx->render_ev) LT_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->render_ev, hipEventDisableTiming));
   if (ctx->render_ev_recorded && s != ctx->render_stream) LT_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->render_ev, 0));
   if (stats) LT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_stats, 0, 8 * sizeof(unsigned long long), s));
+  ctx->last_clear_queues = nullptr;   // (it points into d_queues, which may move below)
   if (k.persistent) {   // (persistent wavefronts by default; LT_PERSISTENT=0 selects one-square-per-workgroup dispatch: A/B measurements)
     const uint64_t queueBytes = ((uint64_t)frames + 1) * 8 * kQueueStride * sizeof(uint32_t);   // (the last eight: the camera-hit pass's)
     LT_HIP_CHECK(ctx, grow_scratch(ctx, ctx->d_queues, ctx->queue_frames, (uint64_t)frames + 1, queueBytes));
@@ -2191,6 +2196,10 @@ static int render_on_stream(lt_hip_context* ctx, const lt_hip_render_desc* d, co
       }
       foldMap = (const unsigned char*)fl.foldMap;
       tabled = fl.itemTable != nullptr;
+      // (a whole square's frame groups in one pass, render_clear_square; not where the launch counts its groups' walks, launch_walk)
+      const bool onePass = tabled && k.clear_square && !k.debug_shadow_frames;
+      if (onePass) fl.itemGroups |= kItemGroupsOnePass;
+      ctx->last_clear_queues = onePass ? queues : nullptr;
       if (shadowMode < 0 && calibrate)
         if (const int rc = calibrate_shadow_walk(ctx, call, sc, fp, grid, out, queues, queueOk, shadowKey, shadowMode, shadowGroup)) return rc;
       if (const int rc = launch_walk(ctx, call, sc, (uint32_t)std::max(0, shadowMode), shadowGroup, fl, grid, out, queues)) return rc;
@@ -3864,6 +3873,27 @@ extern "C" int lt_hip_clear_item_counts(lt_hip_context* ctx, uint64_t* out5) {
     out4[1] = h[1];
     out4[2] = ctx->last_folded ? h[1] : 0;
   }
+  return LT_OK;
+}
+
+// Of the context's last render launch, what its waves counted in render_clear_square (lt_kernel.hpp): out3[0] the clear squares that
+// entered the one-pass path, out3[1] those of them that left it before their last frame group (the general path rendered the rest),
+// out3[2] the frame groups rendered inside it.  All zero where the launch had no such path: no item table, LT_CLEAR_SQUARE=0,
+// LT_DEBUG_SHADOW_FRAMES.  Waits for the context's last render.
+extern "C" int lt_hip_clear_square_counts(lt_hip_context* ctx, uint64_t* out3) {
+  if (!ctx || !out3) return LT_ERR_INVALID_ARGUMENT;
+  out3[0] = out3[1] = out3[2] = 0;
+  if (ctx->last_clear_queues == nullptr) return LT_OK;
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (ctx->render_ev_recorded) LT_HIP_CHECK(ctx, hipEventSynchronize(ctx->render_ev));
+  uint32_t h[8 * kQueueStride];
+  LT_HIP_CHECK(ctx, hipMemcpy(h, ctx->last_clear_queues, sizeof(h), hipMemcpyDeviceToHost));
+  for (uint32_t xcd = 0; xcd < 8u; xcd++)
+    for (uint32_t i = 0; i < 3u; i++) {
+      uint64_t v;
+      memcpy(&v, h + xcd * kQueueStride + kClearCountAt + 2u * i, sizeof(v));
+      out3[i] += v;
+    }
   return LT_OK;
 }
 

@@ -34,6 +34,8 @@ constexpr int kQueueStride = 64;   // dwords between work counters: one 256-byte
                                    // cache line serialise every wave of the chip on one memory channel, 12 ns per work
                                    // item: 25 ms of a 2-million-item launch, whatever the items cost.  Taking several
                                    // items per atomic on top of the padding does not pay: -1 % at 4, -2.4 % at 8.)
+constexpr int kClearCountAt = 32;  // the dword of a render launch's work counter line where its three 64-bit clear-square counters
+                                   // start (render_kernel_body; lt_hip_clear_square_counts): zeroed with the work counters, one set per XCD
 constexpr int kPacketEntry = 4;    // dwords per entry of a packet walk's wave-uniform stack (node reference + 64-bit lane mask, one spare)
 constexpr int kPacketRows = 2;     // ... which therefore fits 32 entries -- kLdsStack levels -- in two 256-byte rows of the wave's LDS
 constexpr int kMaxStack = 64;      // the reference's nodesToVisit[64] (acc.cl:137)
@@ -1195,45 +1197,58 @@ __device__ inline void traverse(const SceneDev& sc, const Ray& ray, bool useIgno
 // cut: the entry cut of the square whose stored camera hits these rays leave (lt_entry_cut.hpp; wave-uniform), or null; cutPlane,
 // cutChunks: where its further chunks are (FrameParams::entryCutPlane, entryCutChunks).
 constexpr uint32_t kEntryCutClear = 0xffffffffu;   // lt_entry_cut::kClearMark (lt_kernel.hpp holds the two together)
+
+// Whether two frames' shadow rays of a square walk together (traverse_shadow2; render_clear_square, lt_kernel.hpp, which asks the
+// same of a clear square's frame groups without walking any): called by the lanes that cast the rays, tmax[j] frame j's ray length.
+// `all`: those lanes' ballot.   Also the rays' reciprocal directions and the form of the walk, for the caller that walks.
+__device__ __forceinline__ bool shadow_frames_walk_together(const SceneDev& sc, const Ray (&ray)[2], const float (&tmax)[2], unsigned long long& all,
+                                                            float (&inv)[2][3], uint32_t& form) {
+  bool ok = sc.shadowPackets == 1u || sc.shadowPackets == 2u;
+  unsigned long long sign[2][3];
+  all = __builtin_amdgcn_ballot_w64(true);
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    inv[j][0] = 1.0f / ray[j].d.x; inv[j][1] = 1.0f / ray[j].d.y; inv[j][2] = 1.0f / ray[j].d.z;
+    const bool finite = __builtin_fabsf(inv[j][0]) < __builtin_inff() && __builtin_fabsf(inv[j][1]) < __builtin_inff() &&
+                        __builtin_fabsf(inv[j][2]) < __builtin_inff() && __builtin_fabsf(ray[j].o.x) < __builtin_inff() &&
+                        __builtin_fabsf(ray[j].o.y) < __builtin_inff() && __builtin_fabsf(ray[j].o.z) < __builtin_inff();
+    ok = ok && __all(finite) && sc.rank8 != nullptr && __all(packet_ray_ok(ray[j], inv[j][0], inv[j][1], inv[j][2]));
+    if (ok && sc.shadowPackets == 2u) {   // traverse's per-wavefront test, with this frame's ray length
+      auto first = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+      const float rx = first(ray[j].o.x), ry = first(ray[j].o.y), rz = first(ray[j].o.z);
+      const float ex = ray[j].o.x - rx, ey = ray[j].o.y - ry, ez = ray[j].o.z - rz;
+      ok = __builtin_amdgcn_ballot_w64(ex * ex + ey * ey + ez * ez > sc.shadowSpread * (tmax[j] * tmax[j])) == 0ull;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) sign[j][a] = __builtin_amdgcn_ballot_w64(inv[j][a] < 0.0f);
+  }
+  // The form of the walk: 0 .. 7 = all 128 rays in one octant; 8 + 4 * a + k = axis a mixed (some frame's ballot neither empty nor
+  // full, or the two frames' ballots different) and the other two axes of one sign each, k as in packet_neg_mode; two or three
+  // mixed axes: apart.
+  uint32_t neg = 0u, mixed = 0u;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    neg |= sign[0][a] != 0ull ? 1u << a : 0u;
+    mixed |= (sign[0][a] == 0ull || sign[0][a] == all) && sign[1][a] == sign[0][a] ? 0u : 1u << a;
+  }
+  ok = ok && (mixed & (mixed - 1u)) == 0u;
+  form = neg;
+  if (mixed == 1u) form = 8u + (neg >> 1);
+  else if (mixed == 2u) form = 12u + ((neg & 1u) | (neg >> 1 & 2u));
+  else if (mixed == 4u) form = 16u + (neg & 3u);
+  return ok;
+}
+
 template <int PROGRAM, class CFG>
 __device__ inline bool traverse_shadow2(const SceneDev& sc, const Ray (&ray)[2], int ignore, Hit (&pl)[2], Stack<CFG::kDeep>& st, Counters& c,
                                         const uint32_t* cut, uint32_t cutPlane, uint32_t cutChunks) {
   bool ok = false;
   if constexpr (!CFG::kStats && !CFG::kDeep && !CFG::kLdsScene) {
     float inv[2][3];
-    ok = sc.shadowPackets == 1u || sc.shadowPackets == 2u;
-    unsigned long long sign[2][3];
-    const unsigned long long all = __builtin_amdgcn_ballot_w64(true);
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      inv[j][0] = 1.0f / ray[j].d.x; inv[j][1] = 1.0f / ray[j].d.y; inv[j][2] = 1.0f / ray[j].d.z;
-      const bool finite = __builtin_fabsf(inv[j][0]) < __builtin_inff() && __builtin_fabsf(inv[j][1]) < __builtin_inff() &&
-                          __builtin_fabsf(inv[j][2]) < __builtin_inff() && __builtin_fabsf(ray[j].o.x) < __builtin_inff() &&
-                          __builtin_fabsf(ray[j].o.y) < __builtin_inff() && __builtin_fabsf(ray[j].o.z) < __builtin_inff();
-      ok = ok && __all(finite) && sc.rank8 != nullptr && __all(packet_ray_ok(ray[j], inv[j][0], inv[j][1], inv[j][2]));
-      if (ok && sc.shadowPackets == 2u) {   // traverse's per-wavefront test, with this frame's ray length
-        auto first = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-        const float rx = first(ray[j].o.x), ry = first(ray[j].o.y), rz = first(ray[j].o.z);
-        const float ex = ray[j].o.x - rx, ey = ray[j].o.y - ry, ez = ray[j].o.z - rz;
-        ok = __builtin_amdgcn_ballot_w64(ex * ex + ey * ey + ez * ez > sc.shadowSpread * (pl[j].t * pl[j].t)) == 0ull;
-      }
-#pragma unroll
-      for (int a = 0; a < 3; a++) sign[j][a] = __builtin_amdgcn_ballot_w64(inv[j][a] < 0.0f);
-    }
-    // The form of the walk: 0 .. 7 = all 128 rays in one octant; 8 + 4 * a + k = axis a mixed (some frame's ballot neither empty nor
-    // full, or the two frames' ballots different) and the other two axes of one sign each, k as in packet_neg_mode; two or three
-    // mixed axes: apart.
-    uint32_t neg = 0u, mixed = 0u;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      neg |= sign[0][a] != 0ull ? 1u << a : 0u;
-      mixed |= (sign[0][a] == 0ull || sign[0][a] == all) && sign[1][a] == sign[0][a] ? 0u : 1u << a;
-    }
-    ok = ok && (mixed & (mixed - 1u)) == 0u;
-    uint32_t form = neg;
-    if (mixed == 1u) form = 8u + (neg >> 1);
-    else if (mixed == 2u) form = 12u + ((neg & 1u) | (neg >> 1 & 2u));
-    else if (mixed == 4u) form = 16u + (neg & 3u);
+    unsigned long long all;
+    const float tmax[2] = {pl[0].t, pl[1].t};
+    uint32_t form;
+    ok = shadow_frames_walk_together(sc, ray, tmax, all, inv, form);
     if (sc.groupWalks != nullptr && (int)__lane_id() == __ffsll((long long)all) - 1) {
       atomicAdd(&sc.groupWalks[ok ? 0 : 1], 1ull);
       if (ok && form >= 8u) atomicAdd(&sc.groupWalks[form - 6u], 1ull);
@@ -1712,8 +1727,15 @@ struct FrameParams {
   const uint32_t* foldMap;
   float* foldOut;
   int32_t foldBase;
+  // (bit 31, kItemGroupsOnePass: a clear square handed out whole renders its two-frame groups in one pass -- render_clear_square,
+  // lt_kernel.hpp; LT_CLEAR_SQUARE=0 leaves it clear.  A bit of a word that only the table's kernel reads: the struct and every
+  // other kernel's arguments stay as they are.  The groups themselves are fewer than 2^31: the host's check on the table's entries.)
   uint32_t itemGroups;
 };
+constexpr uint32_t kItemGroupsOnePass = 0x80000000u;
+// ... so itemGroups is read through these two and nowhere by itself
+__host__ __device__ inline uint32_t item_groups(const FrameParams& fp) { return fp.itemGroups & ~kItemGroupsOnePass; }
+__host__ __device__ inline bool item_one_pass(const FrameParams& fp) { return (fp.itemGroups & kItemGroupsOnePass) != 0u; }
 
 // One step of the running mean, accumulator.frag:10-20: the mean of n + 1 samples from the mean of n and sample c (n <= 0: c is
 // the first).  The one expression of lt_running_mean_kernel, lt_running_mean4_kernel and render_square's fold of a whole square.

@@ -132,6 +132,162 @@ __device__ __forceinline__ void render_square(const SceneDev& sc, const FramePar
   if (queueing && !queued) ((uint4*)sc.shadowQueue)[2 * (size_t)sc.shadowCap + qslot] = make_uint4(kDeadSlot, 0u, 0u, 0u);
 }
 
+// A clear square handed out whole (lt_entry_cut.hpp: kItemWhole; the square b at hand-out position pos, its hits stored), all its
+// two-frame groups in one pass: what render_square -> shade_pixel2 -> shade_lighting2 -> traverse_shadow2 evaluate for each group
+// over again is evaluated once per square -- the pixel, fx / fy, the stored hit, what kind of lane it is, position, normal and
+// diffuse colour, the cut's word 0 -- and a group draws two new randoms, its other two being the group before's last two (frame s
+// draws seeds s, s + 1, s + 2: a launch of 16 frames has 18 seeds per pixel, not 32).  With `fold` the running mean waits in three
+// registers from the first group to the last instead of going through fp.foldOut twice per group.  Every value is the expression
+// the per-group path evaluates, in its flavour and order; no walk is called here, so nothing of this is live across one.
+// Returns the first frame group it did NOT render, `groups` when none is left: a group whose frames would not have walked together
+// (shadow_frames_walk_together: render_square then renders them apart), one with a light sample off the light list, a trailing group
+// of one frame, all of them where the cut's word 0 is no clear mark.  render_kernel_body goes on from that group as it always did.
+// count: [0] squares that got past the mark, [1] those of them that left before their last group, [2] groups rendered here.
+template <class CFG>
+__device__ __forceinline__ uint32_t render_clear_square(const SceneDev& sc, const FrameParams& fp, float* __restrict__ out, uint32_t b, uint32_t pos,
+                                                        uint32_t groups, bool fold, uint32_t (&count)[3]) {
+  if (*(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)(fp.entryCuts + (size_t)pos * lt_entry_cut::kListWords) != kEntryCutClear) return 0u;
+  count[0]++;
+  const uint32_t k = b / fp.blocksPerTile, sb = b % fp.blocksPerTile;
+  const uint32_t sbx = sb % fp.blocksPerTileX, sby = sb / fp.blocksPerTileX;
+  const uint32_t tile = fp.tileFirst + k * fp.tileStride;
+  const uint32_t tx = tile % fp.tilesX, ty = tile / fp.tilesX;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t lx = sbx * 8u + (lane & 7u);
+  const uint32_t ly = sby * 8u + (lane >> 3);
+  const uint32_t x = tx * fp.tileW + lx, y = ty * fp.tileH + ly;
+  const bool valid = k < fp.tilesInCall && lx < fp.tileW && ly < fp.tileH && x < fp.width && y < fp.height;
+  const size_t first = (((size_t)k * fp.tileH + ly) * fp.tileW + lx) * fp.depth;   // (the pixel's first float, as render_square makes it)
+  // once per square: the lane's kind (a light: (1, 1, 1) in every frame; no surface: black; else shaded), and a shaded lane's
+  // position, normal and diffuse colour (shade_lighting2's expressions on the same stored hit)
+  bool shaded = false;
+  float flat = 0.0f;   // the colour of a lane that is not shaded, every channel of every frame
+  float fx = 0.0f, fy = 0.0f;
+  V4 position = mk4(0.0f, 0.0f, 0.0f, 1.0f), normal = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+  V3 diffuse{0.0f, 0.0f, 0.0f};
+  if (valid) {
+    (void)camera_ray<CFG::kDevLibm>(fp, (int)x, (int)y, fx, fy);
+    const uint4 h = (fp.cameraHits + (size_t)pos * kBlock)[__lane_id()];
+    const int prim = (int)h.x;
+    if (is_light(sc.lights, prim)) flat = 1.0f;
+    else shaded = (int)h.y == 1;
+    if (shaded) {
+      const float* pr = prim_ptr(sc, prim);
+      const V3 bc = barycentrics(__uint_as_float(h.z), __uint_as_float(h.w));
+      const V3 p3 = bary3<CFG::kDevLibm>(pr + 0, pr + 3, pr + 6, bc);
+      position = mk4(p3.x, p3.y, p3.z, 1.0f);
+      const V3 n3 = bary3<CFG::kDevLibm>(pr + 9, pr + 12, pr + 15, bc);
+      normal = mk4(n3.x, n3.y, n3.z, 0.0f);
+      const Material* m = sc.mats + prim_material(pr);
+      diffuse = V3{m->diffuse[0], m->diffuse[1], m->diffuse[2]};
+    }
+  }
+  const bool anyShaded = __builtin_amdgcn_ballot_w64(shaded) != 0ull;
+  float mean[3] = {0.0f, 0.0f, 0.0f};
+  if (fold && valid) {
+    const float* d = fp.foldOut + first;
+    mean[0] = d[0]; mean[1] = d[1]; mean[2] = d[2];
+  }
+  // (the sample of frame f of the launch: render_square's store, with the mean in `mean` where it folds)
+  auto store = [&](uint32_t f, const V3& color) {
+    if (fold) {
+      const int32_t n = fp.foldBase + (int32_t)f;
+      mean[0] = running_mean_step(mean[0], color.x, n);
+      mean[1] = running_mean_step(mean[1], color.y, n);
+      mean[2] = running_mean_step(mean[2], color.z, n);
+    } else {
+      float* d = out + (size_t)f * fp.frameStride + first;
+      const int32_t n = fp.accumulateN;
+      if (n <= 0) {
+        d[0] = color.x; d[1] = color.y; d[2] = color.z;
+      } else {
+        d[0] = running_mean_step(d[0], color.x, n);
+        d[1] = running_mean_step(d[1], color.y, n);
+        d[2] = running_mean_step(d[2], color.z, n);
+      }
+    }
+  };
+  const uint32_t full = fp.fusedFrames / 2u;   // the groups of two frames; one frame left over is the general path's
+  float carried[2] = {0.0f, 0.0f};             // the randoms of the two seeds a group shares with the next
+  uint32_t g = 0u;
+  // pass `it` draws seeds 2 * it and 2 * it + 1 past the launch's first -- pass 0 nothing else -- and renders group it - 1 with them and
+  // the two of the pass before: one copy of random()'s code
+#pragma unroll 1
+  for (uint32_t it = 0u; it <= full; it++) {
+    bool together = false;
+    float ndotl[2] = {0.0f, 0.0f};
+    if (shaded) {
+      float rnd[4];
+      rnd[0] = carried[0];
+      rnd[1] = carried[1];
+      // (behind the opaque wave-uniform branch of shade_lighting2, for its reason: the sine's coefficients are made where they are used)
+      uint32_t opaque = sc.shadowPackets;
+      asm volatile("" : "+s"(opaque));
+      const uint32_t s = fp.frameCount + 2u * it;
+      if (opaque == 0xffffffffu) {
+#pragma unroll
+        for (int i = 0; i < 2; i++) rnd[2 + i] = __uint_as_float(opaque + (uint32_t)i);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 2; i++) rnd[2 + i] = random_<CFG::kDevLibm>(fx, fy, (float)(s + (uint32_t)i));
+      }
+      carried[0] = rnd[2];
+      carried[1] = rnd[3];
+      if (it != 0u) {
+        V4 lightPosition[2];
+        bool listed = true;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          const float* lp = light_prim(sc, rnd[j]);
+          // (off the list only where random() returns exactly 1.0 -- index == count -- or the list is empty: no pixel and frame of
+          // the tests draws that, so the term of `together` below that reads `listed` is the one line here no test reaches)
+          listed = listed && light_index_listed(sc, rnd[j]);
+          float uvx = rnd[j + 1], uvy = rnd[j + 2];
+          if (uvx + uvy > 1.0f) {
+            uvx = 1.0f - uvx;
+            uvy = 1.0f - uvy;
+          }
+          const V3 l3 = bary3<CFG::kDevLibm>(lp + 0, lp + 3, lp + 6, barycentrics(uvx, uvy));
+          lightPosition[j] = mk4(l3.x, l3.y, l3.z, 1.0f);
+        }
+        asm volatile("" ::: "memory");
+        Ray ray[2];
+        float tmax[2];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          const V4 toLight = normalize4<CFG::kDevLibm>(sub4(lightPosition[j], position));
+          tmax[j] = (float)((double)distance4<CFG::kDevLibm>(position, lightPosition[j]) - 0.01);
+          ndotl[j] = dot4(toLight, normal);
+          ray[j] = Ray{position, toLight};
+        }
+        asm volatile("" : "+v"(ndotl[0]), "+v"(ndotl[1]));
+        float inv[2][3];
+        uint32_t form;
+        unsigned long long all;
+        together = shadow_frames_walk_together(sc, ray, tmax, all, inv, form) && __builtin_amdgcn_ballot_w64(!listed) == 0ull;
+      }
+    }
+    if (it == 0u) continue;
+    if (anyShaded && __builtin_amdgcn_ballot_w64(together) == 0ull) break;
+    if (valid) {
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        V3 color = shaded ? V3{diffuse.x * ndotl[j], diffuse.y * ndotl[j], diffuse.z * ndotl[j]} : V3{flat, flat, flat};
+        if (fp.clampOutput) color = V3{Math<CFG::kDevLibm>::clamp01(color.x), Math<CFG::kDevLibm>::clamp01(color.y), Math<CFG::kDevLibm>::clamp01(color.z)};
+        store(2u * (it - 1u) + (uint32_t)j, color);
+      }
+    }
+    g = it;
+    count[2]++;
+  }
+  if (fold && valid && g != 0u) {
+    float* d = fp.foldOut + first;
+    d[0] = mean[0]; d[1] = mean[1]; d[2] = mean[2];
+  }
+  if (g != groups) count[1]++;
+  return g;
+}
+
 // The camera-hit pass's work on one square: the walk of render_square's camera rays (same lanes, same walk: kAccumulator's and
 // kAccumulatorQueue's are one), the hits stored for every frame's render_square.  All 64 slots are written: four whole lines.
 template <class CFG>
@@ -190,6 +346,10 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
   // next group (never 0; a multiple of the groups per square when none is left), and in bit 31 whether its samples are folded
   // (render_square: fold).  0: no whole square in hand.
   uint32_t wholeNext = 0u;
+  // ... and the kernel of the item table renders such a square's two-frame groups in one pass (render_clear_square): what this wave
+  // saw of that, in three scalars, added to the launch's counters when the wave ends (kClearCountAt)
+  constexpr bool kClearSquare = PROGRAM == kAccumulator && CFG::kGroups && CFG::kItems && !STATS && !HITS;
+  uint32_t clearCount[3] = {0u, 0u, 0u};
   uint32_t tableLimit = 0u, tableSweep = 8u;   // the length of the queue's share of the table, loaded once per sweep (8: none yet)
   auto sload = [](const uint32_t* p) { return *(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)p; };
   bool done = false;
@@ -213,7 +373,7 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
       // and built for this many groups) a claim indexes the queue's share of the table, whose length is in device memory: one scalar
       // load per sweep.
       const bool table = PROGRAM == kAccumulator && CFG::kGroups && CFG::kItems && !STATS && !HITS && group == 2u && fp.itemTable != nullptr &&
-                         fp.itemGroups == groups && fp.squareMajor != 0u && head == 0u;
+                         item_groups(fp) == groups && fp.squareMajor != 0u && head == 0u;
       if (table && tableSweep != sweep) {
         tableLimit = sload(fp.itemTable + xcd);
         tableSweep = sweep;
@@ -263,7 +423,17 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
               const unsigned long long seg = lt_entry_cut::fold_segment(k, fp.tileH, fp.tileW, sb / fp.blocksPerTileX * 8u, sb % fp.blocksPerTileX);
               folding = (sload(fp.foldMap + (seg >> 2)) >> (8u * (uint32_t)(seg & 3ull)) & 0xffu) != 0u;
             }
-            wholeNext = groups == 1u ? 0u : (t + 1u) | (folding ? lt_entry_cut::kItemWhole : 0u);
+            // The square's groups of two frames in one pass (render_clear_square), as far as they go: the loop takes the square up at
+            // the first group that is left, as if it had rendered the ones before it.
+            if constexpr (kClearSquare) {
+              if (item_one_pass(fp) && sc.groupWalks == nullptr && fp.entryCuts != nullptr) {
+                const uint32_t at = start + t / groups;
+                const uint32_t rendered = render_clear_square<CFG>(sc, fp, out, fp.order ? sload(fp.order + at) : at, at, groups, folding, clearCount);
+                if (rendered == groups) continue;
+                t += rendered;
+              }
+            }
+            wholeNext = (t + 1u) % groups == 0u ? 0u : (t + 1u) | (folding ? lt_entry_cut::kItemWhole : 0u);
           }
         }
       }
@@ -296,6 +466,13 @@ __device__ __forceinline__ void render_kernel_body(const SceneDev& sc, const Fra
     } else {
       render_square<PROGRAM, CFG>(sc, fp, out, b, frame, frames, st, c, pos, stored ? fp.cameraHits + (size_t)pos * kBlock : nullptr,
                                   stored && fp.entryCuts != nullptr ? fp.entryCuts + (size_t)pos * lt_entry_cut::kListWords : nullptr, folding);
+    }
+  }
+  if constexpr (kClearSquare) {
+    if (clearCount[0] != 0u && threadIdx.x == 0u) {   // (only a persistent launch has a table: `queues` is set)
+      unsigned long long* const at = (unsigned long long*)(queues + home * kQueueStride + kClearCountAt);
+#pragma unroll
+      for (int i = 0; i < 3; i++) atomicAdd(&at[i], (unsigned long long)clearCount[i]);
     }
   }
   if (STATS) {

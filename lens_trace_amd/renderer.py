@@ -534,6 +534,15 @@ class RendererHIP:
         self._check(self._L.lt_hip_clear_item_counts(self._ctx, out))
         return {"entries": int(out[0]), "whole": int(out[1]), "folded": int(out[2]), "builds": int(out[3]), "used": bool(out[4])}
 
+    def clear_square_counts(self):
+        """lt_hip_clear_square_counts, of the context's last render launch: a dict of `entered` (clear squares whose frame groups
+        one pass over the square began to render), `left` (those of them that went back to the per-group path before their last
+        group) and `groups` (frame groups rendered in that pass).  Waits for the context's last render.  LT_CLEAR_SQUARE=0, or no
+        item table: all zero."""
+        out = (ctypes.c_uint64 * 3)()
+        self._check(self._L.lt_hip_clear_square_counts(self._ctx, out))
+        return {"entered": int(out[0]), "left": int(out[1]), "groups": int(out[2])}
+
     def scene_structure(self, what):
         """lt_hip_read_scene_structure: 0 own tree (NODE_DTYPE array), 1 leaf order table (n_prims x 8 uint32), 2 the per-lane walks'
         array (bytes), 3 (own height, group-tree height, groups, prepared on the device), 4 the packet walks' records (bytes, 64 per
