@@ -908,6 +908,15 @@ int lt_hip_entry_cut_chunks_test_host(const int32_t* heights, const uint32_t* ch
  * lane is one the cut is not built for.  No GPU. */
 int lt_hip_entry_cut_triangle_test_host(const float* origins, const float* light_boxes, const float* triangles, uint64_t n, uint8_t* out);
 
+/* random()'s short sine on the host, for tests (lt_device.hpp: random_fast_r, the same operation sequence as the kernels').  n
+ * cases, either of (uvx, uvy, seed) in args3 -- the argument formed as math flavour `flavour` (0 portable, 1 device libm, 2 as
+ * shipped) forms it and reduced by fmod_pi -- or, where r is not null, of that reduced argument itself.  params10, where not
+ * null, replaces the eight coefficients, pi_lo and delta (tests of mutated copies).  Out, each nullable: r_out the reduced
+ * argument, p the fast value of sin(r) * 43758.5453, determined 1 where the float is proved to be the library's, a that float
+ * (before the fract).  No GPU. */
+int lt_hip_random_fast_test_host(int flavour, const float* args3, const double* r, uint64_t n, const double* params10, double* r_out,
+                                 double* p, uint8_t* determined, float* a);
+
 /* Clear squares handed out whole.  A call that reuses a camera's entry cuts hands its squares out from an item
  * table built behind the cuts, on the device: a square marked clear is one work item for all frames of the launch instead of one
  * per frame group, and where the launch is a fused one of a depth-3 image whose tile width is a multiple of 8, without padded

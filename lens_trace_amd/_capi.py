@@ -53,7 +53,7 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_entry_cut_leaf_counts", "lt_hip_entry_cut_triangle_test_host",
            "lt_hip_entry_cut_chunk_counts", "lt_hip_entry_cut_chunks_test_host", "lt_hip_read_entry_cuts",
            "lt_hip_entry_cut_pruned_test_host", "lt_hip_clear_item_counts", "lt_hip_clear_items_test_host",
-           "lt_hip_clear_square_counts"]
+           "lt_hip_clear_square_counts", "lt_hip_random_fast_test_host"]
 # (lt_hip_camera_hit_passes returns a uint64_t count, not a status: bound in load() beside these)
 
 
@@ -337,6 +337,9 @@ def load():
     if hasattr(L, "lt_hip_clear_square_counts"):
         L.lt_hip_clear_square_counts.argtypes = [vp, ctypes.POINTER(u64)]
         L.lt_hip_clear_square_counts.restype = i32
+    if hasattr(L, "lt_hip_random_fast_test_host"):
+        L.lt_hip_random_fast_test_host.argtypes = [i32, vp, vp, u64, vp, vp, vp, vp, vp]
+        L.lt_hip_random_fast_test_host.restype = i32
     for name in EXPORTS:
         if not hasattr(L, name) and os.environ.get("LT_HIP_LIBRARY"):
             continue      # (an older build of the library loaded for an A/B measurement, tests/tools/ab_libs.sh)

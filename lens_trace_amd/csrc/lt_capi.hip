@@ -3789,6 +3789,35 @@ extern "C" int lt_hip_entry_cut_triangle_test_host(const float* origins, const f
   return LT_OK;
 }
 
+// lt_device.hpp's random_fast_r as the host compiles it (the same operations: every fma spelled out, no contraction).
+extern "C" int lt_hip_random_fast_test_host(int flavour, const float* args3, const double* r, uint64_t n, const double* params10, double* r_out,
+                                            double* p, uint8_t* determined, float* a) {
+  if ((!args3 && !r && n) || flavour < 0 || flavour > 2) return LT_ERR_INVALID_ARGUMENT;
+  lt::RandomFastParams k;
+  if (params10) {
+    for (int i = 0; i < 8; i++) k.c[i] = params10[i];
+    k.pi_lo = params10[8];
+    k.delta = params10[9];
+  }
+  for (uint64_t i = 0; i < n; i++) {
+    double ri;
+    if (r) ri = r[i];
+    else {
+      const float* q = args3 + 3 * i;
+      const double x = flavour == 2 ? lt::random_arg_<2>(q[0], q[1], q[2]) : lt::random_arg_<0>(q[0], q[1], q[2]);
+      ri = lt::fmod_pi(x);
+    }
+    double pi;
+    float ai;
+    const bool det = params10 ? lt::random_fast_r_with(ri, k, pi, ai) : lt::random_fast_r(ri, pi, ai);
+    if (r_out) r_out[i] = ri;
+    if (p) p[i] = pi;
+    if (determined) determined[i] = det ? 1 : 0;
+    if (a) a[i] = ai;
+  }
+  return LT_OK;
+}
+
 extern "C" int lt_hip_entry_cut_leaf_counts(lt_hip_context* ctx, uint64_t* out3) {
   if (!ctx || !out3) return LT_ERR_INVALID_ARGUMENT;
   out3[0] = out3[1] = out3[2] = 0;

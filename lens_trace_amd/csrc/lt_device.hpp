@@ -150,7 +150,7 @@ __device__ __forceinline__ V4 neg4(V4 a) { return mk4(-a.x, -a.y, -a.z, -a.w); }
 __device__ __forceinline__ float dot4(V4 a, V4 b) {
   return __builtin_fmaf(a.w, b.w, __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x)));
 }
-__device__ __forceinline__ float dot2(float ax, float ay, float bx, float by) { return __builtin_fmaf(ay, by, ax * bx); }
+__host__ __device__ __forceinline__ float dot2(float ax, float ay, float bx, float by) { return __builtin_fmaf(ay, by, ax * bx); }
 __device__ __forceinline__ V4 cross4(V4 a, V4 b) {
   return mk4(__builtin_fmaf(a.y, b.z, -(a.z * b.y)), __builtin_fmaf(a.z, b.x, -(a.x * b.z)),
              __builtin_fmaf(a.x, b.y, -(a.y * b.x)), 0.0f);
@@ -254,7 +254,7 @@ __device__ inline float distance4(V4 a, V4 b) {
 // fused multiply-add (no rounding: the exact value is a double), a second one when n was off by one (the sign, resp. r >= y,
 // of the rounded remainder tells: rounding never crosses 0 or the double y).  The library's fmod is a long-division loop.
 // (tests/test_gpu_parity.py holds it against fmod() over the arguments random() makes and over edge cases.)
-__device__ __forceinline__ double fmod_pi(double x) {
+__host__ __device__ __forceinline__ double fmod_pi(double x) {
   const double ax = __builtin_fabs(x);
   if (!(ax < 0x1p+40)) return fmod(x, M_PI);   // (huge, infinite or NaN: the library's own)
   double n = __builtin_floor(ax * 0.31830988618379067);
@@ -264,13 +264,126 @@ __device__ __forceinline__ double fmod_pi(double x) {
   return __builtin_copysign(r, x);
 }
 
-// acc.cl:63-66: float dot, then double add / fmod / sin / mul, then float fract
+// ---------------------------------------------------------------- random()
+// acc.cl:63-66: float dot, then double add / fmod / sin / mul, then float fract.  The argument of the fmod, in the flavour's form:
 template <int M = 0>
-__device__ inline float random_(float uvx, float uvy, float seed) {
-  float d = dot2(uvx, uvy, 12.9898f, 78.233f);
-  double x = Math<M>::kShipped ? __builtin_fma(1113.1, (double)seed, (double)d) : (double)d + 1113.1 * (double)seed;
-  float a = (float)(sin(fmod_pi(x)) * 43758.5453);
+__host__ __device__ __forceinline__ double random_arg_(float uvx, float uvy, float seed) {
+  const float d = dot2(uvx, uvy, 12.9898f, 78.233f);
+  return M == 2 ? __builtin_fma(1113.1, (double)seed, (double)d) : (double)d + 1113.1 * (double)seed;
+}
+// THE DEFINITION of random(): the float a = fl32(fl64(sin(r) * 43758.5453)) with the library's sine, r = fmod(x, pi), and
+// a - floor(a) of it.  Everything below returns these bits; every test compares against them.
+__device__ inline float random_library_a(double x) { return (float)(sin(fmod_pi(x)) * 43758.5453); }
+template <int M = 0>
+__device__ inline float random_library_(float uvx, float uvy, float seed) {
+  const float a = random_library_a(random_arg_<M>(uvx, uvy, seed));
   return a - __builtin_floorf(a);
+}
+
+// The float `a` without the library's sine, where it can be PROVED to be the library's (tools/random_sine_fit.py derives the
+// coefficients and prints every figure used here; u = 2^-53).  The operation sequence, each operation rounded once:
+//     m = |r| <= pi/2 ? r : copysign((pi_hi - |r|) + pi_lo, r)          (pi_hi = M_PI, pi_lo = the double nearest pi - pi_hi)
+//     z = m m;  q = c7;  q = fma(q, z, c_k), k = 6 .. 0;  t = q z;  s = fma(t, m, m);  p~ = s K                (K = 43758.5453)
+//     lo = fl32(p~ (1 - delta)),  hi = fl32(p~ (1 + delta)),  delta = 2^-46;  determined = (lo == hi),  a = lo
+//
+// CLAIM.  Let r be a double with |r| < pi_hi (every result of fmod_pi) and L = fl64(S K) the library's product, S its sine of r, off
+// by at most 4 ulp (OpenCL's bound; ocml's own is tighter).  If `determined`, then fl32(L) == lo.
+//
+// PROOF.  Write P = sin(r) K, the real number.
+//   (reflect) sin(r) = sign(r) sin(m*) with m* = |r| where |r| <= pi/2, else m* = pi - |r| = (pi_hi - |r|) + (pi - pi_hi): the
+//       difference is exact (Sterbenz: pi_hi / 2 <= |r| <= pi_hi), pi_lo is off by u |pi_lo| <= 0.23 u m* (m* >= pi - (pi_hi -
+//       2^-51) > 4.4 pi_lo) and the sum rounds once: |m| = m* (1 + e), |e| <= 1.23 u, and sin moves by no more in relative
+//       terms (x cos x <= sin x on [0, pi/2]).  0 <= |m| <= fl(pi/2) (1 + 2u), z = m^2 < 2.4675 = ZMAX.
+//   (polynomial) q_exact interpolates g(z) = (sin(sqrt z) / sqrt z - 1) / z in the 8 Chebyshev points of [0, ZMAX]: |g - q_exact| <=
+//       max |g^(8)| / 8! * 2 (ZMAX / 4)^8 and g^(8) is an alternating series of decreasing terms, the first 8! / 19!.  Relative to
+//       sin(m) that is times z m / sin(m) <= 3.88: 0.012 u.  The coefficients' rounding: u sum |c_k| ZMAX^k * 3.88 = 0.731 u.
+//   (evaluation) the running error bound of the Horner steps with z off by u z: |q^ - q| <= 0.235 u; t = q z, |t| <= 0.364: |t^ - t| <=
+//       1.509 u; s = m (1 + t^) rounded once and 1 + t >= 2 / pi: s is off by 3.371 u of sin(m); the product by K one more u.
+//       Underflow: z, t or their steps below 2^-1022 are off by 2^-1075 in absolute terms instead, which t <= 0.364 u-terms absorb.
+//   In all |p~ - P| <= (0.743 + 3.371 + 1.23 + 1) u |P| = 6.343 u |P|.
+//   (library) an ulp of S is at most 2 u |S|: |S - sin(r)| <= 8 u |sin r|, its product rounds once: |L - P| <= 9.001 u |P|.
+//   So |L - p~| <= 15.35 u |P| <= 15.36 u |p~| = delta' |p~|.  fl64(p~ (1 +- delta)) lies within u (1 + delta) |p~| of p~ (1 +- delta), and
+//   delta' (1 + delta) + u (1 + delta) < 16.35 u < 128 u = delta: L lies between the two doubles whose floats are lo and hi.  Rounding to float
+//   is monotone: lo == hi is fl32(L).  Where p~ or L is below 2^-1022 in magnitude the relative bounds fail, but then |P| < 2^-1020,
+//   and lo, hi and fl32(L) are all zeros, equal as floats, and a - floor(a) is +0 for either sign of zero.  QED.
+// A NaN r (x infinite or NaN) makes p~ NaN and lo == hi false.  The rate of `determined` false: the bracket is 2 delta |p~| wide, floats'
+// rounding boundaries are 2^-24 |p~| apart at the closest: at most 2 delta 2^24 = 2^-21 per lane, 2^-15 per wave of 64.
+struct RandomFastParams { double c[8], pi_lo, delta; };
+__host__ __device__ __forceinline__ bool random_fast_r_with(double r, const RandomFastParams& k, double& p, float& a) {
+  const double ar = __builtin_fabs(r);
+  const double m = ar <= 0x1.921fb54442d18p+0 ? r : __builtin_copysign((0x1.921fb54442d18p+1 - ar) + k.pi_lo, r);
+  const double z = m * m;
+  double q = k.c[7];
+#pragma unroll
+  for (int i = 6; i >= 0; i--) q = __builtin_fma(q, z, k.c[i]);
+  const double t = q * z;
+  const double s = __builtin_fma(t, m, m);
+  p = s * 43758.5453;
+  const float lo = (float)(p * (1.0 - k.delta)), hi = (float)(p * (1.0 + k.delta));
+  a = lo;
+  return lo == hi;
+}
+__host__ __device__ __forceinline__ bool random_fast_r(double r, double& p, float& a) {
+  // (tools/random_sine_fit.py)
+  RandomFastParams k{{-0x1.5555555555555p-3, 0x1.1111111111107p-7, -0x1.a01a01a018aacp-13, 0x1.71de3a5456633p-19,
+                      -0x1.ae6455a1cdfddp-26, 0x1.61240158708f1p-33, -0x1.ae5137d193396p-41, 0x1.89a46890c7ff8p-49},
+                     0x1.1a62633145c07p-53, 0x1p-46};
+#if defined(__HIP_DEVICE_COMPILE__)
+  // The coefficients are pinned to scalar registers HERE.  Left to itself the compiler makes each a vector-register pair, hoists
+  // the eight pairs out of the kernel's work loop, spills them in a 64-VGPR kernel, and every step of the polynomial then waits for
+  // a scratch load.  A scalar pair is two s_mov_b32 where it is used, and each fma has room for one scalar operand.
+#pragma unroll
+  for (int i = 0; i < 8; i++) asm volatile("" : "+s"(k.c[i]));
+#endif
+  return random_fast_r_with(r, k, p, a);
+}
+// ... from the fmod's argument: |x| >= 2^40, infinite or NaN is "not determined" without a look (fmod_pi's own library call is
+// then dead code here: the one copy of it is random_library_a's)
+__device__ __forceinline__ bool random_fast_a(double x, float& a) {
+  a = 0.0f;
+  if (!(__builtin_fabs(x) < 0x1p+40)) return false;
+  double p;
+  return random_fast_r(fmod_pi(x), p, a);
+}
+
+// N randoms of one film position, seeds seed[0 .. N): the fast value of each, and ONE copy of the library's sine behind a branch
+// that a wave takes once in 2^15 / N visits, for the lanes and seeds whose float is not determined.  fallbacks, where given,
+// counts them.
+template <int M, int N>
+__device__ __forceinline__ void randoms_(float uvx, float uvy, const float (&seed)[N], float (&rnd)[N], uint32_t* fallbacks = nullptr) {
+  uint32_t pending = 0u;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    float a;
+    if (!random_fast_a(random_arg_<M>(uvx, uvy, seed[i]), a)) pending |= 1u << i;
+    rnd[i] = a - __builtin_floorf(a);
+  }
+  if (pending != 0u) {
+    if (fallbacks) *fallbacks += (uint32_t)__builtin_popcount(pending);
+#pragma unroll 1
+    for (int i = 0; i < N; i++) {
+      if (!((pending >> i) & 1u)) continue;
+      float sd = seed[0];
+#pragma unroll
+      for (int j = 1; j < N; j++) sd = i == j ? seed[j] : sd;
+      const float v = random_library_<M>(uvx, uvy, sd);
+#pragma unroll
+      for (int j = 0; j < N; j++) rnd[j] = i == j ? v : rnd[j];
+    }
+  }
+}
+// one random, from the fmod's argument and from (uv, seed)
+__device__ inline float random_x_(double x, uint32_t* fallbacks = nullptr) {
+  float a;
+  if (!random_fast_a(x, a)) {
+    if (fallbacks) ++*fallbacks;
+    a = random_library_a(x);
+  }
+  return a - __builtin_floorf(a);
+}
+template <int M = 0>
+__device__ inline float random_(float uvx, float uvy, float seed, uint32_t* fallbacks = nullptr) {
+  return random_x_(random_arg_<M>(uvx, uvy, seed), fallbacks);
 }
 
 // ---------------------------------------------------------------- traversal
@@ -1332,9 +1445,12 @@ __device__ __forceinline__ void light_sample(const SceneDev& sc, const float* pr
   // i.e. three double-precision sin / fmod evaluations that want every register -- and only then the hit primitive's own
   // positions and normals, fenced so that the compiler does not issue those loads ahead of the randoms and carry 19 floats
   // through them in scratch memory.
-  const float* lp = light_prim(sc, random_<CFG::kDevLibm>(fx, fy, seedIndex));
-  float uvx = random_<CFG::kDevLibm>(fx, fy, seedU);
-  float uvy = random_<CFG::kDevLibm>(fx, fy, seedV);
+  const float seed[3] = {seedIndex, seedU, seedV};
+  float rnd[3];
+  randoms_<CFG::kDevLibm, 3>(fx, fy, seed, rnd);
+  const float* lp = light_prim(sc, rnd[0]);
+  float uvx = rnd[1];
+  float uvy = rnd[2];
   if (uvx + uvy > 1.0f) {
     uvx = 1.0f - uvx;
     uvy = 1.0f - uvy;
@@ -1530,8 +1646,8 @@ __device__ inline bool shade_lighting2(const SceneDev& sc, const Hit& pl, float 
 #pragma unroll
     for (int i = 0; i < 4; i++) rnd[i] = __uint_as_float(opaque + (uint32_t)i);
   } else {
-#pragma unroll
-    for (int i = 0; i < 4; i++) rnd[i] = random_<CFG::kDevLibm>(fx, fy, (float)(s + (uint32_t)i));
+    const float seed[4] = {(float)s, (float)(s + 1u), (float)(s + 2u), (float)(s + 3u)};
+    randoms_<CFG::kDevLibm, 4>(fx, fy, seed, rnd);
   }
   V4 lightPosition[2];
   bool listed = true;   // both samples are points of the light list's primitives: what the square's entry cut was made for
@@ -1589,6 +1705,14 @@ __device__ inline V4 uniform_sample_hemisphere(float uvx, float uvy) {
   const float phi = (float)(2.0 * M_PI * (double)uvy);
   return mk4(r * Math<DEVLIBM>::cos(phi), z, r * Math<DEVLIBM>::sin(phi), 0.0f);
 }
+// ... of the randoms of two seeds (gi.cl:300 and :352: one copy of random()'s fallback for the pair)
+template <int DEVLIBM>
+__device__ inline V4 random_hemisphere(float fx, float fy, float seedX, float seedY) {
+  const float seed[2] = {seedX, seedY};
+  float rnd[2];
+  randoms_<DEVLIBM, 2>(fx, fy, seed, rnd);
+  return uniform_sample_hemisphere<DEVLIBM>(rnd[0], rnd[1]);
+}
 // gi.cl:76-81
 template <int DEVLIBM>
 __device__ inline V4 align_hemisphere(V4 h, V4 up) {
@@ -1618,7 +1742,7 @@ __device__ inline V3 shade_gi(const SceneDev& sc, const Ray& cameraRay, float fx
                                        position, normal, ndotl, st, c)) {
       direct = V3{m->diffuse[0] * ndotl, m->diffuse[1] * ndotl, m->diffuse[2] * ndotl};
     }
-    V4 hemi = uniform_sample_hemisphere<CFG::kDevLibm>(random_<CFG::kDevLibm>(fx, fy, (float)(s + 3u)), random_<CFG::kDevLibm>(fx, fy, (float)(s + 4u)));
+    V4 hemi = random_hemisphere<CFG::kDevLibm>(fx, fy, (float)(s + 3u), (float)(s + 4u));
     Ray ext{position, align_hemisphere<CFG::kDevLibm>(hemi, normal)};
     V4 previousNormal = normal;
     int previousPrimitive = pl.prim;
@@ -1644,7 +1768,7 @@ __device__ inline V3 shade_gi(const SceneDev& sc, const Ray& cameraRay, float fx
           indirect.x = Math<CFG::kDevLibm>::mad(w * em->diffuse[0], endotl, indirect.x);
           indirect.y = Math<CFG::kDevLibm>::mad(w * em->diffuse[1], endotl, indirect.y);
           indirect.z = Math<CFG::kDevLibm>::mad(w * em->diffuse[2], endotl, indirect.z);
-          hemi = uniform_sample_hemisphere<CFG::kDevLibm>(random_<CFG::kDevLibm>(fx, fy, (float)(sd + 8u)), random_<CFG::kDevLibm>(fx, fy, (float)(sd + 9u)));
+          hemi = random_hemisphere<CFG::kDevLibm>(fx, fy, (float)(sd + 8u), (float)(sd + 9u));
           ext.o = epos;
           ext.d = align_hemisphere<CFG::kDevLibm>(hemi, enorm);
           previousNormal = enorm;

@@ -228,8 +228,11 @@ __device__ __forceinline__ uint32_t render_clear_square(const SceneDev& sc, cons
 #pragma unroll
         for (int i = 0; i < 2; i++) rnd[2 + i] = __uint_as_float(opaque + (uint32_t)i);
       } else {
-#pragma unroll
-        for (int i = 0; i < 2; i++) rnd[2 + i] = random_<CFG::kDevLibm>(fx, fy, (float)(s + (uint32_t)i));
+        const float seed[2] = {(float)s, (float)(s + 1u)};
+        float drawn[2];
+        randoms_<CFG::kDevLibm, 2>(fx, fy, seed, drawn);
+        rnd[2] = drawn[0];
+        rnd[3] = drawn[1];
       }
       carried[0] = rnd[2];
       carried[1] = rnd[3];
@@ -807,7 +810,7 @@ __global__ __launch_bounds__(kBlock, LT_GI_STAGE_WAVES) void lt_gi_primary_kerne
                                           normal, ndotl, st, c)) {
           direct = V3{m->diffuse[0] * ndotl, m->diffuse[1] * ndotl, m->diffuse[2] * ndotl};
         }
-        const V4 hemi = uniform_sample_hemisphere<CFG::kDevLibm>(random_<CFG::kDevLibm>(fx, fy, (float)(s + 3u)), random_<CFG::kDevLibm>(fx, fy, (float)(s + 4u)));
+        const V4 hemi = random_hemisphere<CFG::kDevLibm>(fx, fy, (float)(s + 3u), (float)(s + 4u));
         dir = align_hemisphere<CFG::kDevLibm>(hemi, normal);
         prim = pl.prim;
         alive = fp.giMaxDepth > 0;
@@ -914,7 +917,7 @@ void lt_gi_bounce_kernel(SceneDev sc, FrameParams fp, GiParams gp, uint32_t dept
           ind.y = Math<CFG::kDevLibm>::mad(w * em->diffuse[1], endotl, ind.y);
           ind.z = Math<CFG::kDevLibm>::mad(w * em->diffuse[2], endotl, ind.z);
           gp.indirect[pix] = ind;
-          const V4 hemi = uniform_sample_hemisphere<CFG::kDevLibm>(random_<CFG::kDevLibm>(fx, fy, (float)(sd + 8u)), random_<CFG::kDevLibm>(fx, fy, (float)(sd + 9u)));
+          const V4 hemi = random_hemisphere<CFG::kDevLibm>(fx, fy, (float)(sd + 8u), (float)(sd + 9u));
           ndir = align_hemisphere<CFG::kDevLibm>(hemi, enorm);
           hitPrim = epl.prim;
           alive = d + 1 < fp.giMaxDepth;
@@ -1040,7 +1043,7 @@ __global__ __launch_bounds__(256) void lt_gi_finish_kernel(SceneDev sc, FramePar
       ind.y = Math<CFG::kDevLibm>::mad(w * em->diffuse[1], endotl, ind.y);
       ind.z = Math<CFG::kDevLibm>::mad(w * em->diffuse[2], endotl, ind.z);
       gp.indirect[pix] = ind;
-      const V4 hemi = uniform_sample_hemisphere<CFG::kDevLibm>(random_<CFG::kDevLibm>(fx, fy, (float)(sd + 8u)), random_<CFG::kDevLibm>(fx, fy, (float)(sd + 9u)));
+      const V4 hemi = random_hemisphere<CFG::kDevLibm>(fx, fy, (float)(sd + 8u), (float)(sd + 9u));
       ndir = align_hemisphere<CFG::kDevLibm>(hemi, mk4(sn.x, sn.y, sn.z, sn.w));
       alive = d + 1 < fp.giMaxDepth;
     }

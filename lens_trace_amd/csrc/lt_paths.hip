@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kBlock, LT_PATHS_WAVES) void lt_paths_primary_kerne
       if (direct_light<kGI, CFG>(sc, pr, pl.prim, pl.u, pl.v, fx, fy, (float)s, (float)(s + 1u), (float)(s + 2u), 1.0f, position, normal, ndotl, st, c)) {
         direct = V3{m->diffuse[0] * ndotl, m->diffuse[1] * ndotl, m->diffuse[2] * ndotl};
       }
-      const V4 hemi = uniform_sample_hemisphere<CFG::kDevLibm>(random_<CFG::kDevLibm>(fx, fy, (float)(s + 3u)), random_<CFG::kDevLibm>(fx, fy, (float)(s + 4u)));
+      const V4 hemi = random_hemisphere<CFG::kDevLibm>(fx, fy, (float)(s + 3u), (float)(s + 4u));
       dir = align_hemisphere<CFG::kDevLibm>(hemi, normal);
       prim = pl.prim;
       alive = p.giMaxDepth > 0;
