@@ -268,6 +268,65 @@ int lt_hip_own_wide(const void* own_nodes, uint64_t node_bytes, uint32_t n_prims
  * primitive offsets that no leaf names are written by nobody. */
 int lt_hip_read_scene_structure(lt_hip_context* ctx, int what, void* out, uint64_t capacity, uint64_t* out_bytes);
 
+/* The scene from bare triangles: the four buffers lt_hip_set_scene wants -- the pre-order LinearBVHNode tree, the ordered 76-byte
+ * primitives, the light container; the materials pass through -- built by the CANONICAL MEDIAN BUILD, the rule of the reference's
+ * AccelerationStructureExplicit (median split, ACCELERATION_STRUCTURE_TYPE_BVH) with the two places it leaves to the
+ * implementation fixed: the order of triangles whose centres coincide, and the sign of a zero bound.
+ *
+ * Per triangle i (its index in the input), for each axis:
+ *   lo, hi   the IEEE 754-2019 minimum / maximum of the three vertices (minimum(-0, +0) = -0, maximum(-0, +0) = +0);
+ *   c        0.5f * lo + 0.5f * hi: two rounded products, one rounded sum, never a fused multiply-add.
+ * A range of count >= 2 triangles (the root's range is all of them), for node number `node`:
+ *   d[a]     max c[a] - min c[a] over the range, one rounded subtraction;
+ *   dim      (d[0] > d[1] && d[0] > d[2]) ? 0 : (d[1] > d[2] ? 1 : 2);
+ *   order    the range by (c[dim], i): floats compared by value (-0 == +0), equal values by the lower input index.  The first
+ *            floor(count / 2) go left, the others right.  (d[dim] == 0 is no special case: the range then splits by input index.)
+ *   node     axis = dim, primitiveCount = 0, pad = 0, secondChildOffset = node + 2 * floor(count / 2); the left child is node + 1.
+ * A range of one triangle is a leaf: primitivesOffset = its position in the ordered buffer (leaves are numbered left to right),
+ * primitiveCount = 1, axis = 0, pad = 0.  So the shape -- node numbers, offsets, every node's range, the height ceil(log2 n) --
+ * depends on n alone; the data decide the permutation, the axes and the boxes.
+ * Boxes: a leaf's is its triangle's lo / hi, an interior node's the IEEE minimum / maximum of its children's: no bound depends on
+ * the order it was folded in.
+ * Primitives: the input permuted into leaf order, in the 76-byte layout (positions, normals, materialIndex; material_indices ==
+ * NULL: every index 0).  Lights: the first 64 positions of the ordered buffer, ascending, whose material has any emission
+ * component > 0; count is capped at 64 and the unused slots are 0.  Materials: unchanged.
+ * Whenever no two triangles share their centre on all three axes this is the output of the reference's builder with the median
+ * rule: every field byte for byte, the box floats by value (a zero bound may differ in sign).
+ *
+ * Errors, in order: LT_ERR_INVALID_ARGUMENT for a null ctx / desc, struct_size too small, flags != 0, n == 0, null positions,
+ * normals or materials, material_bytes == 0 (device form: a pointer that is not 4-byte aligned); LT_ERR_BAD_SCENE for
+ * material_bytes that is no multiple of 32 and for lt_hip_set_scene's size limits (4 GiB of nodes, 2 GiB of traversal triangles);
+ * then, from the data, LT_ERR_BAD_SCENE for a vertex coordinate that is NaN or infinite ("non-finite vertex position") and for a
+ * materialIndex outside [0, material_bytes / 32).  A failed call leaves the resident scene as it was. */
+typedef struct lt_hip_triangles_desc {
+  uint32_t struct_size;             /* >= sizeof(lt_hip_triangles_desc) */
+  uint32_t flags;                   /* 0 */
+  uint64_t n;                       /* triangles */
+  const float* positions;           /* 9 floats per triangle: A, B, C */
+  const float* normals;             /* 9 floats per triangle: the normals at A, B, C */
+  const int32_t* material_indices;  /* one per triangle, or NULL: all 0 */
+  const void* materials;            /* 32-byte Material records */
+  uint64_t material_bytes;
+} lt_hip_triangles_desc;            /* 56 B */
+
+/* Host pointers, synchronous: the arrays are uploaded as they are and the four buffers built by kernels (lens_trace_amd/csrc/
+ * lt_build.hip), for every n >= 1; what lt_hip_set_scene derives from its buffers is then derived from these, by the same rule
+ * (on the device from 8192 nodes on, LT_DEVICE_BUILD=0 / 1 forces; a tree the device preparation declines -- a bound of 2^40 or
+ * more -- and small scenes go through a copy on the host).  The scene counts as uploaded (lt_hip_stats::scene_uploads); it has no
+ * host image, so a later lt_hip_set_scene / lt_hip_render_scene never finds its buffers "unchanged", whatever their sizes. */
+int lt_hip_set_triangles(lt_hip_context* ctx, const lt_hip_triangles_desc* desc);
+/* Device pointers of the context's GPU (every pointer of desc).  Waits for the earlier work of hip_stream (a hipStream_t, NULL =
+ * default stream) and returns when the scene is resident: the caller's arrays are free to reuse, the context keeps its own
+ * 76-byte copy. */
+int lt_hip_set_triangles_device(lt_hip_context* ctx, const lt_hip_triangles_desc* desc, void* hip_stream);
+/* The same rule in plain C++: host only, no context, no GPU (errors through lt_hip_last_error(NULL)).  nodes receives 32 (2 n - 1)
+ * bytes, prims 76 n bytes, lights 260 bytes; LT_ERR_BUFFER_TOO_SMALL when node_bytes or prim_bytes is less. */
+int lt_hip_build_scene_host(const lt_hip_triangles_desc* desc, void* nodes, uint64_t node_bytes, void* prims, uint64_t prim_bytes, void* lights);
+/* Copies one of the four resident scene buffers back to the host, whichever call made them resident: which 0 = nodes, 1 =
+ * primitives, 2 = materials, 3 = lights.  out == NULL: only *out_bytes (the size) is set.  LT_ERR_NO_SCENE without a scene,
+ * LT_ERR_BUFFER_TOO_SMALL when capacity is less than the size. */
+int lt_hip_read_scene_buffer(lt_hip_context* ctx, int which, void* out, uint64_t capacity, uint64_t* out_bytes);
+
 /* Ray queries over the resident scene (the scene of the last lt_hip_set_scene).  Each ray is traced as the reference traces
  * one of its own -- `intersect`, or `intersectIgnorePrimitiveIndex` when ignore >= 0 (accumulator.cl:132-217) -- from the
  * payload {t = tmax, primitiveIndex = hitType = 0}, over the caller's LinearBVHNode tree in the reference's order, with the

@@ -38,6 +38,7 @@ EXPORTS = ["lt_hip_abi_version", "lt_hip_create", "lt_hip_destroy", "lt_hip_last
            "lt_hip_resolve_program",
            "lt_hip_set_scene", "lt_hip_output_floats", "lt_hip_render", "lt_hip_render_scene", "lt_hip_render_device", "lt_hip_untile",
            "lt_hip_synchronize", "lt_hip_get_stats", "lt_hip_own_hierarchy", "lt_hip_own_wide", "lt_hip_read_scene_structure",
+           "lt_hip_set_triangles", "lt_hip_set_triangles_device", "lt_hip_build_scene_host", "lt_hip_read_scene_buffer",
            "lt_hip_trace_rays", "lt_hip_trace_rays_device", "lt_hip_trace_hits", "lt_hip_trace_hits_device",
            "lt_hip_trace_hits_list", "lt_hip_trace_hits_list_device",
            "lt_hip_shade_rays", "lt_hip_shade_rays_device", "lt_hip_shade_paths", "lt_hip_shade_paths_device",
@@ -160,6 +161,12 @@ class NearestListDesc(ctypes.Structure):   # lt_hip_nearest_list_desc
 
 class HitsListDesc(ctypes.Structure):   # lt_hip_hits_list_desc
     _fields_ = [("struct_size", ctypes.c_uint32), ("program", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class TrianglesDesc(ctypes.Structure):   # lt_hip_triangles_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n", ctypes.c_uint64),
+                ("positions", ctypes.c_void_p), ("normals", ctypes.c_void_p), ("material_indices", ctypes.c_void_p),
+                ("materials", ctypes.c_void_p), ("material_bytes", ctypes.c_uint64)]
 
 
 def _np_dtypes():
@@ -305,6 +312,11 @@ def load():
         L.lt_hip_nearest_list.argtypes = [vp, ctypes.POINTER(NearestListDesc), vp, u64, vp, u64, vp, u64]
         L.lt_hip_nearest_list_device.argtypes = [vp, ctypes.POINTER(NearestListDesc), vp, u64, vp, u64, vp, u64, vp]
         L.lt_hip_nearest_list_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(NearestListDesc), vp, u64, vp, u64, vp, u64]
+    if hasattr(L, "lt_hip_set_triangles"):
+        L.lt_hip_set_triangles.argtypes = [vp, ctypes.POINTER(TrianglesDesc)]
+        L.lt_hip_set_triangles_device.argtypes = [vp, ctypes.POINTER(TrianglesDesc), vp]
+        L.lt_hip_build_scene_host.argtypes = [ctypes.POINTER(TrianglesDesc), vp, u64, vp, u64, vp]
+        L.lt_hip_read_scene_buffer.argtypes = [vp, i32, vp, u64, ctypes.POINTER(u64)]
     if hasattr(L, "lt_hip_camera_hit_passes"):
         L.lt_hip_camera_hit_passes.argtypes = [vp]
         L.lt_hip_camera_hit_passes.restype = u64

@@ -4,6 +4,7 @@
 #include "lt_retree.hpp"
 #include "lt_own16.hpp"
 #include "lt_prep.hpp"
+#include "lt_build.hpp"
 #include "lt_query.hpp"
 #include "lt_nearest.hpp"
 #include "lt_overlap.hpp"
@@ -356,6 +357,7 @@ struct lt_hip_context {
   bool verdict_sizes_valid = false;
   bool speculate_next = true;        // lt_hip_render_scene: the last scene handed over with a frame was the resident one (render while hashing)
   SceneHash scene_hash{};                                    // content hashes (one per buffer) ...
+  bool scene_hash_valid = false;     // ... of the resident scene: false for one built on the device (lt_hip_set_triangles), which no host buffers can equal
   uint64_t scene_sizes[4] = {0, 0, 0, 0};                   // ... and sizes of the resident scene (lt_hip_set_scene)
   uint32_t scene_uploads = 0, scene_reused = 0;
   float* d_out = nullptr;            // staging output for lt_hip_render
@@ -1000,6 +1002,7 @@ static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const Scen
   ctx->has_scene = true;
   ctx->device_prepared = device_prepared;
   ctx->scene_hash = hash;
+  ctx->scene_hash_valid = true;
   memcpy(ctx->scene_sizes, sizes, sizeof(ctx->scene_sizes));
   ctx->scene_uploads++;
   ctx->scene_generation++;   // (every path that wrote a scene buffer ends here; those that write without it -- a failed edit -- count below)
@@ -1016,18 +1019,20 @@ static void adopt_scene(lt_hip_context* ctx, const uint64_t sizes[4], const Scen
 
 // The device path of lt_hip_set_scene.  kDeviceDeclined: nothing of ctx was touched, the host path decides.
 constexpr int kDeviceDeclined = -1000;
+template <class Arrived>
+static int prepare_resident(lt_hip_context* ctx, void*& d_nodes, void*& d_prims, const void* materials, const void* lights, hipMemcpyKind kind,
+                            const uint64_t sizes[4], const SceneHash& hash, const SceneKnobs& k, SceneLaps& laps, Arrived primsArrived);
+
 static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const void* prims, const void* materials, const void* lights,
                                const uint64_t sizes[4], const SceneHash& hash, const SceneKnobs& k, SceneLaps& laps) {
-  const uint32_t n_nodes = (uint32_t)(sizes[0] / 32), n_prims = (uint32_t)(sizes[1] / 76), n_mats = (uint32_t)(sizes[2] / 32);
+  const uint32_t n_prims = (uint32_t)(sizes[1] / 76);
   if (check_lights((const uint8_t*)lights, n_prims)) return kDeviceDeclined;   // (the light list is 260 bytes: checked here; the host words the error)
   void *d_nodes = nullptr, *d_prims = nullptr;
-  const lt_prep::Allocator al{&ctx->pool, &ScenePool::get_cb, &ScenePool::put_cb};
   struct Guard {   // (whatever is still set when this returns goes back)
-    ScenePool& pool; const lt_prep::Allocator& al; void** a; void** b; lt_prep::Out* o;
-    ~Guard() { pool.put(*a); pool.put(*b); lt_prep::release(*o, al); }
+    ScenePool& pool; void** a; void** b;
+    ~Guard() { pool.put(*a); pool.put(*b); }
   };
-  lt_prep::Out prep;
-  Guard guard{ctx->pool, al, &d_nodes, &d_prims, &prep};
+  Guard guard{ctx->pool, &d_nodes, &d_prims};
   LT_HIP_CHECK(ctx, ctx->pool.upload(&d_nodes, nodes, sizes[0]));
   LT_HIP_CHECK(ctx, ctx->pool.get(&d_prims, sizes[1]));
   laps.lap("upload nodes");
@@ -1044,6 +1049,23 @@ static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const voi
     primError = hipMemcpy(d_prims, prims, sizes[1], hipMemcpyHostToDevice);
   }
   struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{primThread};   // (every exit below waits for it)
+  return prepare_resident(ctx, d_nodes, d_prims, materials, lights, hipMemcpyHostToDevice, sizes, hash, k, laps, [&]() {
+    if (primThread.joinable()) primThread.join();
+    return primError;
+  });
+}
+
+// The second half of the device path: d_nodes and d_prims are pool buffers on the device (the primitives may still be on their
+// way: primsArrived waits for them), materials and lights are copied from wherever `kind` says they are.  On success the two
+// buffers are the context's and the pointers null; kDeviceDeclined: nothing of ctx was touched and they are still the caller's.
+template <class Arrived>
+static int prepare_resident(lt_hip_context* ctx, void*& d_nodes, void*& d_prims, const void* materials, const void* lights, hipMemcpyKind kind,
+                            const uint64_t sizes[4], const SceneHash& hash, const SceneKnobs& k, SceneLaps& laps, Arrived primsArrived) {
+  const uint32_t n_nodes = (uint32_t)(sizes[0] / 32), n_prims = (uint32_t)(sizes[1] / 76), n_mats = (uint32_t)(sizes[2] / 32);
+  const lt_prep::Allocator al{&ctx->pool, &ScenePool::get_cb, &ScenePool::put_cb};
+  struct Guard { const lt_prep::Allocator& al; lt_prep::Out* o; ~Guard() { lt_prep::release(*o, al); } };
+  lt_prep::Out prep;
+  Guard guard{al, &prep};
   const auto t0 = std::chrono::steady_clock::now();
   // (height <= 30: the packet walks' stack, one VGPR, holds 2 * height + 2 entries at most; LT_RETREE=0: the caller's splits)
   LT_HIP_CHECK(ctx, lt_prep::run(d_nodes, n_nodes, nullptr, n_prims, n_mats, 30, k.slack, k.own_splits, ctx->stream, al, prep));
@@ -1051,8 +1073,7 @@ static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const voi
                         prep.ms_check, prep.ms_build, prep.levels, prep.ms_wide, prep.flags);
   if (prep.flags != 0 || prep.bvh_height > kMaxStack) return kDeviceDeclined;
   laps.lap("device preparation");
-  if (primThread.joinable()) primThread.join();
-  LT_HIP_CHECK(ctx, primError);
+  LT_HIP_CHECK(ctx, primsArrived());
   bool primsOk = false;
   LT_HIP_CHECK(ctx, lt_prep::check_primitives(d_prims, n_prims, n_mats, ctx->stream, ctx->d_prep_flag, primsOk));
   if (!primsOk) return kDeviceDeclined;
@@ -1065,8 +1086,8 @@ static int set_scene_on_device(lt_hip_context* ctx, const void* nodes, const voi
   LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_tris, (size_t)n_prims * 48));
   LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_mats, sizes[2]));
   LT_HIP_CHECK(ctx, ctx->pool.get(&ctx->d_lights, sizes[3]));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_mats, materials, sizes[2], hipMemcpyHostToDevice, ctx->stream));
-  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_lights, lights, sizes[3], hipMemcpyHostToDevice, ctx->stream));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_mats, materials, sizes[2], kind, ctx->stream));
+  LT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_lights, lights, sizes[3], kind, ctx->stream));
   const OwnBuild own{prep.d_nodes2, prep.d_rank8, prep.d_children, prep.d_groupOf, prep.n_own, prep.groups, prep.own_height, prep.wide_height,
                      prep.root_lo, prep.root_hi};
   prep.d_nodes2 = prep.d_rank8 = nullptr;   // (the context's from here on; the guard gives back the rest)
@@ -1098,7 +1119,7 @@ static int set_scene_impl(lt_hip_context* ctx, const void* nodes, uint64_t node_
   const SceneHash hash = known_hash ? *known_hash : hash_scene(bufs, sizes);
   laps.lap(known_hash ? "hash (known)" : "hash");
   LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->has_scene && memcmp(sizes, ctx->scene_sizes, sizeof(sizes)) == 0 && !k.always_upload) {
+  if (ctx->has_scene && ctx->scene_hash_valid && memcmp(sizes, ctx->scene_sizes, sizeof(sizes)) == 0 && !k.always_upload) {
     if (hash == ctx->scene_hash) {
       ctx->scene_reused++;
       return LT_OK;
@@ -1206,6 +1227,133 @@ extern "C" int lt_hip_set_scene(lt_hip_context* ctx, const void* nodes, uint64_t
   } catch (const std::exception& e) {   // (std::bad_alloc, std::system_error of a thread: nothing may cross the C ABI)
     return fail(ctx, LT_ERR_HIP, std::string("lt_hip_set_scene: ") + e.what());
   }
+}
+
+// ---------------------------------------------------------------------------------- scenes from bare triangles
+// lt_hip_set_triangles / _device: the caller's tree, the ordered primitives and the light container are built on the device by the
+// canonical median rule (lt_build.hip) and handed to the second half of the device path; lt_hip_build_scene_host is the same rule
+// on the host, lt_hip_read_scene_buffer reads the four resident buffers back.
+static_assert(sizeof(lt_hip_triangles_desc) == 56, "triangle descriptor (include/lenstrace_hip.h)");
+
+// The argument rules of the three forms, in the header's order.
+static int check_triangles_desc(lt_hip_context* ctx, const lt_hip_triangles_desc* d, bool device, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  if (!d) return fail(ctx, LT_ERR_INVALID_ARGUMENT, w + "NULL desc");
+  if (d->struct_size < sizeof(lt_hip_triangles_desc)) return fail(ctx, LT_ERR_INVALID_ARGUMENT, w + "struct_size too small");
+  if (d->flags != 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, w + "unknown flags");
+  if (d->n == 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, w + "no triangles");
+  if (!d->positions || !d->normals || !d->materials) return fail(ctx, LT_ERR_INVALID_ARGUMENT, w + "NULL positions, normals or materials");
+  if (d->material_bytes == 0) return fail(ctx, LT_ERR_INVALID_ARGUMENT, w + "zero materials");
+  if (device && (((uintptr_t)d->positions | (uintptr_t)d->normals | (uintptr_t)d->material_indices | (uintptr_t)d->materials) & 3u))
+    return fail(ctx, LT_ERR_INVALID_ARGUMENT, w + "device pointers must be 4-byte aligned");
+  if (d->material_bytes % 32 || d->material_bytes / 32 > 0x7fffffffull)
+    return fail(ctx, LT_ERR_BAD_SCENE, "scene buffer sizes are not whole multiples of LinearBVHNode(32) / Primitive(76) / Material(32) / LightContainer(260)");
+  if (d->n > 0x7fffffffull / 48 || 32 * (2 * d->n - 1) > 0xffffffffull)
+    return fail(ctx, LT_ERR_BAD_SCENE, "scene too large for 32-bit byte offsets (4 GiB of nodes / 2 GiB of traversal triangles)");
+  return LT_OK;
+}
+
+static int triangles_flags_error(lt_hip_context* ctx, uint32_t flags) {
+  return fail(ctx, LT_ERR_BAD_SCENE, (flags & lt_build::kFlagNonFinite) ? "non-finite vertex position" : "materialIndex out of range");
+}
+
+static int set_triangles_impl(lt_hip_context* ctx, const lt_hip_triangles_desc* d, bool device, void* hip_stream) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  const char* who = device ? "lt_hip_set_triangles_device" : "lt_hip_set_triangles";
+  if (const int rc = check_triangles_desc(ctx, d, device, who)) return rc;
+  const SceneKnobs k;
+  SceneLaps laps{k.timing};
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = (uint32_t)d->n, n_nodes = 2 * n - 1, n_mats = (uint32_t)(d->material_bytes / 32);
+  const uint64_t sizes[4] = {32ull * n_nodes, 76ull * n, d->material_bytes, 260};
+  const lt_prep::Allocator al{&ctx->pool, &ScenePool::get_cb, &ScenePool::put_cb};
+  struct Staged {   // (the host form's device copies of the caller's arrays, and what the build made: back to the pool on every exit)
+    ScenePool& pool; const lt_prep::Allocator& al; void* p[4] = {nullptr, nullptr, nullptr, nullptr}; lt_build::Out built;
+    ~Staged() { for (void* q : p) pool.put(q); lt_build::release(built, al); }
+  } st{ctx->pool, al};
+  const void* src[4] = {d->positions, d->normals, d->material_indices, d->materials};
+  if (device) {
+    LT_HIP_CHECK(ctx, hipStreamSynchronize((hipStream_t)hip_stream));   // (what wrote the caller's tensors is done)
+  } else {
+    const uint64_t bytes[4] = {36ull * n, 36ull * n, 4ull * n, d->material_bytes};
+    for (int i = 0; i < 4; i++) {
+      if (!src[i]) continue;
+      LT_HIP_CHECK(ctx, ctx->pool.upload(&st.p[i], src[i], bytes[i]));
+      src[i] = st.p[i];
+    }
+  }
+  laps.lap("triangles on the device");
+  LT_HIP_CHECK(ctx, lt_build::run((const float*)src[0], (const float*)src[1], (const int32_t*)src[2], src[3], n_mats, n, ctx->stream, ctx->d_prep_flag,
+                                  k.timing, al, st.built));
+  if (st.built.flags) return triangles_flags_error(ctx, st.built.flags);
+  if (k.timing) fprintf(stderr, "[lt set_scene] build: checks + sorts %.2f ms, %d levels %.2f ms, gather + boxes + lights %.2f ms\n", st.built.ms_sort,
+                        st.built.height, st.built.ms_levels, st.built.ms_finish);
+  laps.lap("canonical median build");
+  // What follows is lt_hip_set_scene's from its uploaded buffers on, by the same size rule.
+  int rc = kDeviceDeclined;
+  if (k.device < 0 ? n_nodes >= 8192u : k.device != 0)
+    rc = prepare_resident(ctx, st.built.d_nodes, st.built.d_prims, src[3], st.built.d_lights, hipMemcpyDeviceToDevice, sizes, SceneHash(), k, laps,
+                          []() { return hipSuccess; });
+  if (rc == kDeviceDeclined) {   // (a small scene, or a tree lt_prep declines -- a bound beyond 2^40: the host path, from a copy of the four buffers)
+    std::vector<uint8_t> host[4];
+    const void* from[4] = {st.built.d_nodes, st.built.d_prims, src[3], st.built.d_lights};
+    for (int i = 0; i < 4; i++) {
+      host[i].resize(sizes[i]);
+      if (i == 2 && !device) memcpy(host[i].data(), d->materials, sizes[i]);
+      else LT_HIP_CHECK(ctx, hipMemcpy(host[i].data(), from[i], sizes[i], hipMemcpyDeviceToHost));
+    }
+    laps.lap("read back for the host path");
+    SceneKnobs hk = k;
+    hk.device = 0;
+    hk.always_upload = true;   // (whatever is resident, this is a new scene)
+    rc = set_scene_impl(ctx, host[0].data(), sizes[0], host[1].data(), sizes[1], host[2].data(), sizes[2], host[3].data(), sizes[3], hk, nullptr);
+  }
+  if (rc == LT_OK) ctx->scene_hash_valid = false;   // (no host image: host buffers handed over later are never "the resident scene")
+  return rc;
+}
+
+extern "C" int lt_hip_set_triangles(lt_hip_context* ctx, const lt_hip_triangles_desc* desc) {
+  try {
+    return set_triangles_impl(ctx, desc, false, nullptr);
+  } catch (const std::exception& e) {
+    return fail(ctx, LT_ERR_HIP, std::string("lt_hip_set_triangles: ") + e.what());
+  }
+}
+
+extern "C" int lt_hip_set_triangles_device(lt_hip_context* ctx, const lt_hip_triangles_desc* desc, void* hip_stream) {
+  try {
+    return set_triangles_impl(ctx, desc, true, hip_stream);
+  } catch (const std::exception& e) {
+    return fail(ctx, LT_ERR_HIP, std::string("lt_hip_set_triangles_device: ") + e.what());
+  }
+}
+
+extern "C" int lt_hip_build_scene_host(const lt_hip_triangles_desc* desc, void* nodes, uint64_t node_bytes, void* prims, uint64_t prim_bytes, void* lights) {
+  if (const int rc = check_triangles_desc(nullptr, desc, false, "lt_hip_build_scene_host")) return rc;
+  if (!nodes || !prims || !lights) return fail(nullptr, LT_ERR_INVALID_ARGUMENT, "lt_hip_build_scene_host: NULL output buffer");
+  if (node_bytes < 32 * (2 * desc->n - 1) || prim_bytes < 76 * desc->n) return fail(nullptr, LT_ERR_BUFFER_TOO_SMALL, "lt_hip_build_scene_host: output buffer too small");
+  try {
+    const uint32_t flags = lt_build::build_host(desc->positions, desc->normals, desc->material_indices, desc->materials, (uint32_t)(desc->material_bytes / 32),
+                                                (uint32_t)desc->n, nodes, prims, lights);
+    return flags ? triangles_flags_error(nullptr, flags) : LT_OK;
+  } catch (const std::exception& e) {
+    return fail(nullptr, LT_ERR_HIP, std::string("lt_hip_build_scene_host: ") + e.what());
+  }
+}
+
+extern "C" int lt_hip_read_scene_buffer(lt_hip_context* ctx, int which, void* out, uint64_t capacity, uint64_t* out_bytes) {
+  if (!ctx) return LT_ERR_INVALID_ARGUMENT;
+  if (!out_bytes || which < 0 || which > 3) return fail(ctx, LT_ERR_INVALID_ARGUMENT, "lt_hip_read_scene_buffer: bad arguments");
+  if (!ctx->has_scene) return fail(ctx, LT_ERR_NO_SCENE, "no scene uploaded");
+  const void* const src[4] = {ctx->d_nodes, ctx->d_prims, ctx->d_mats, ctx->d_lights};
+  const uint64_t bytes = ctx->scene_sizes[which];
+  *out_bytes = bytes;
+  if (!out) return LT_OK;
+  if (capacity < bytes) return fail(ctx, LT_ERR_BUFFER_TOO_SMALL, "lt_hip_read_scene_buffer: buffer too small");
+  LT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  LT_HIP_CHECK(ctx, hipDeviceSynchronize());
+  LT_HIP_CHECK(ctx, hipMemcpy(out, src[which], bytes, hipMemcpyDeviceToHost));
+  return LT_OK;
 }
 
 // ---------------------------------------------------------------------------------- render
@@ -2394,7 +2542,7 @@ extern "C" int lt_hip_render_scene(lt_hip_context* ctx, const void* nodes, uint6
     // Rendering from the resident copy while the host hashes what came with the frame pays when the scene is the resident one --
     // a still scene, every call but the first.  A caller whose scene changed last time (an animation) gets the hash first: a
     // millisecond in front of the frame instead of a whole frame rendered for nothing.
-    const bool speculate = ctx->has_scene && ctx->speculate_next && memcmp(sizes, ctx->scene_sizes, sizeof(sizes)) == 0 &&
+    const bool speculate = ctx->has_scene && ctx->scene_hash_valid && ctx->speculate_next && memcmp(sizes, ctx->scene_sizes, sizeof(sizes)) == 0 &&
                            !sk.always_upload && !continues;
     int rc;
     if (speculate) {

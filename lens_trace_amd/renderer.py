@@ -431,6 +431,57 @@ class RendererHIP:
         self._scene_key = None
         self._scene_refs = None
 
+    def set_triangles(self, positions, normals, material_indices, materials, stream=None):
+        """Makes a scene resident from bare triangles (lt_hip_set_triangles; include/lenstrace_hip.h defines the canonical median
+        build): the tree, the ordered primitives and the light list are built on the GPU -- what
+        scene.build_from_triangles_canonical builds on the host, byte for byte.  positions, normals: float32, 9 values per
+        triangle ((n, 3, 3) or (n, 9)); material_indices: int32 (n,) or None (all 0); materials: MATERIAL_DTYPE records (or their
+        bytes).  numpy arrays go to the host entry point; contiguous torch tensors on this context's GPU (materials then a uint8
+        or float32 tensor of the records' bytes) go to the device one, which waits for the earlier work of `stream` (default: the
+        current torch stream) and returns when the scene is resident."""
+        vp = ctypes.c_void_p
+        if isinstance(positions, np.ndarray):
+            from .scene import _triangle_arrays
+            pos, nrm, mi, mats = _triangle_arrays(positions, normals, material_indices, materials)
+            d = C.TrianglesDesc(ctypes.sizeof(C.TrianglesDesc), 0, pos.shape[0], pos.ctypes.data_as(vp), nrm.ctypes.data_as(vp),
+                                None if mi is None else mi.ctypes.data_as(vp), mats.ctypes.data_as(vp) if mats.size else None, mats.nbytes)
+            rc = self._L.lt_hip_set_triangles(self._ctx, ctypes.byref(d))
+        else:
+            import torch
+            dev = torch.device("cuda", self.device)
+            wanted = (("positions", positions, torch.float32), ("normals", normals, torch.float32), ("material_indices", material_indices, torch.int32),
+                      ("materials", materials, None))
+            for what, t, dtype in wanted:
+                if t is None and what == "material_indices":
+                    continue
+                if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() or (dtype is not None and t.dtype != dtype):
+                    raise ValueError("%s must be a contiguous %s tensor on %s" % (what, dtype or "uint8 or float32", dev))
+            if positions.numel() % 9 or normals.numel() != positions.numel() or \
+                    (material_indices is not None and material_indices.numel() * 9 != positions.numel()):
+                raise ValueError("triangle arrays disagree in length")
+            if stream is None:
+                stream = torch.cuda.current_stream(dev)
+            handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+            d = C.TrianglesDesc(ctypes.sizeof(C.TrianglesDesc), 0, positions.numel() // 9, positions.data_ptr(), normals.data_ptr(),
+                                None if material_indices is None else material_indices.data_ptr(),
+                                materials.data_ptr() if materials.numel() else None, materials.numel() * materials.element_size())
+            rc = self._L.lt_hip_set_triangles_device(self._ctx, ctypes.byref(d), vp(handle))
+        self._check(rc)
+        self.invalidate_scene()   # (render() hands its scene over again: the resident one is no Scene object's)
+
+    def scene_buffers(self, camera=None):
+        """lt_hip_read_scene_buffer: the four resident buffers -- nodes, primitives, materials, lights -- as a Scene, whichever
+        call made them resident; `camera`: its 28-byte camera buffer (default: Scene's own)."""
+        bufs = []
+        for which in range(4):
+            n = ctypes.c_uint64(0)
+            self._check(self._L.lt_hip_read_scene_buffer(self._ctx, which, None, ctypes.c_uint64(0), ctypes.byref(n)))
+            buf = np.zeros(n.value, dtype=np.uint8)
+            self._check(self._L.lt_hip_read_scene_buffer(self._ctx, which, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(buf.nbytes),
+                                                         ctypes.byref(n)))
+            bufs.append(buf)
+        return Scene(*bufs) if camera is None else Scene(*bufs, camera=bytes(camera))
+
     def resolve_program(self, kernel_file_path):
         """Built-in program by basename, or a user .hip file compiled with hipRTC at first use and cached by path."""
         out = ctypes.c_int(0)

@@ -195,3 +195,37 @@ def build_from_triangles(positions, normals, material_indices, materials, camera
     h = L.lt_host_scene_from_triangles_ex(pos.ctypes.data_as(vp), nrm.ctypes.data_as(vp), mi.ctypes.data_as(vp), pos.shape[0],
                                           mats.ctypes.data_as(vp), mats.size // 32, default_bvh if bvh is None else bvh)
     return _scene_from_handle(L, h, camera)
+
+
+def _triangle_arrays(positions, normals, material_indices, materials):
+    """The four arrays of lt_hip_triangles_desc from numpy input: positions, normals float32 (n, 9); material_indices int32 (n,) or
+    None; materials as bytes."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 9)
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 9)
+    mi = None if material_indices is None else np.ascontiguousarray(material_indices, dtype=np.int32).reshape(-1)
+    mats = np.ascontiguousarray(materials).view(np.uint8).reshape(-1)
+    if pos.shape != nrm.shape or (mi is not None and mi.shape[0] != pos.shape[0]):
+        raise ValueError("triangle arrays disagree in length")
+    return pos, nrm, mi, mats
+
+
+def build_from_triangles_canonical(positions, normals, material_indices, materials, camera=None):
+    """lt_hip_build_scene_host: the canonical median build (include/lenstrace_hip.h) on the host -- no context, no GPU.  The
+    buffers RendererHIP.set_triangles makes resident from the same arrays, byte for byte.  positions, normals: float32 [N,3,3];
+    material_indices: int32 [N] or None (all 0); materials: MATERIAL_DTYPE [K]."""
+    import ctypes
+    from . import _capi as C
+    pos, nrm, mi, mats = _triangle_arrays(positions, normals, material_indices, materials)
+    n = pos.shape[0]
+    vp = ctypes.c_void_p
+    d = C.TrianglesDesc(ctypes.sizeof(C.TrianglesDesc), 0, n, pos.ctypes.data_as(vp), nrm.ctypes.data_as(vp),
+                        None if mi is None else mi.ctypes.data_as(vp), mats.ctypes.data_as(vp) if mats.size else None, mats.nbytes)
+    nodes = np.zeros(32 * max(1, 2 * n - 1), dtype=np.uint8)
+    prims = np.zeros(76 * max(1, n), dtype=np.uint8)
+    lights = np.zeros(260, dtype=np.uint8)
+    L = C.load()
+    rc = L.lt_hip_build_scene_host(ctypes.byref(d), nodes.ctypes.data_as(vp), nodes.nbytes, prims.ctypes.data_as(vp), prims.nbytes,
+                                   lights.ctypes.data_as(vp))
+    if rc:
+        raise C.LensTraceError(rc, L.lt_hip_last_error(None).decode())
+    return Scene(nodes, prims, mats.copy(), lights, camera or camera_bytes(0.0, 2.5, -50.0))
